@@ -8,8 +8,17 @@ One "step" = the hot path of BASELINE.json configs[1] over one batch:
   embeddings over the library's RCCL communicator]  ->  float64 all-pairs cosine
   ranking of this GPU's 1000 queries against all N*1000 candidates (integer ranks).
 Weak scaling: per-GPU work is fixed; value = N*1000*K / max-over-ranks time.
-Successive steps rotate through --batches (8) distinct resident batches, the K timed steps are repeated
---repeats (5) times and the MEDIAN repeat is reported (min / max next to it).
+Successive steps rotate through --batches (8) distinct resident batches.  The K timed steps are split into --repeats (5)
+consecutive repeats (fewer when K is smaller), each timed on its own, and the MEDIAN repeat's time per step is reported
+(min / max next to it).  Every repeat ends with a full synchronisation, so the drain of the queue is spread over K / 5
+steps instead of K: on the MI355X, K = 20 split 5 ways and timed as one window gave the same ms_per_step within
+run-to-run noise.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
+
+Run length beyond the K timed steps and the W warm-up steps: N > 1 runs K more steps with the exchange timed (comm_ms);
+N = 1 runs the untimed-for-the-headline side legs - the host-buffer leg (--repeats windows of K batches each: its
+double-buffered copies are timed over whole K-batch windows, so the pipeline's fill is not counted once per few steps),
+the trained-weights recall leg (K + 1 steps), and the fixed-size secondary and reference-API legs.  The CPU baseline
+leg depends on --cpu-pairs only.
 
     python bench.py --gpus N --steps K --warmup W
         N > 1: this process (which never touches a GPU) starts one child per GPU
@@ -63,9 +72,9 @@ PROFILE_ROUND = "r06"              # profiles/<round>_hbm_traffic_by_symbol.json
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps in all (split over --repeats)")
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5, help="the K timed steps are repeated this often; median reported")
+    ap.add_argument("--repeats", type=int, default=5, help="the K timed steps are split into this many separately timed runs; median reported")
     ap.add_argument("--batches", type=int, default=8, help="distinct resident input batches the steps rotate through")
     ap.add_argument("--pairs", type=int, default=PAIRS_PER_GPU, help="pairs per GPU per step")
     ap.add_argument("--chunk", type=int, default=0, help="samples per internal launch (0 = library default)")
@@ -95,7 +104,43 @@ def parse_args(argv=None):
     ap.add_argument("--no-secondary", action="store_true", help="skip the configs[2]/[3]/[4] measurements")
     ap.add_argument("--no-dropin", action="store_true", help="skip the reference-API legs (RetrievalWrapper, refine_cca)")
     ap.add_argument("--refine-pairs", type=int, default=25000, help="host pairs of the refine_cca leg")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="pairs workload: write what the last timed step computed (embeddings of both views, ranks, d*, "
+                         "ties) as DIR/<name>.npy, float32 / float64, at most 64 MB (a seeded sample of rows beyond)")
+    args = ap.parse_args(argv)
+    if args.dump_outputs and args.workload != "pairs":
+        ap.error("--dump-outputs: only the pairs workload (the headline step) writes its outputs")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, rank=0, world=1):
+    """Writes the outputs of one step as <path>/<name>.npy (float32 stays float32, everything else becomes float64:
+    the integer ranks and tie counts are exact there).  All arrays share their first axis (one row per query / pair);
+    when they would exceed DUMP_LIMIT_BYTES together, the same fixed, seeded sample of rows is taken from each and
+    its indices are written as sample_rows.npy.  With several ranks every file name carries _rank<r>."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, np.float32 if np.asarray(v).dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a.nbytes // max(1, len(a)) for a in arrays.values())
+    keep = max(1, DUMP_LIMIT_BYTES // max(1, row_bytes + 8))
+    if n > keep:
+        rows = np.sort(np.random.default_rng(20240917).choice(n, size=keep, replace=False))
+        arrays = dict({k: a[rows] for k, a in arrays.items()}, sample_rows=rows.astype(np.float64))
+    sfx = "_rank%d" % rank if world > 1 else ""
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + sfx + ".npy"), a)
+    return sorted(k + sfx for k in arrays)
+
+
+def _repeat_sizes(steps, repeats):
+    """--steps K is the number of timed steps in all: they are split into min(--repeats, K) consecutive repeats of
+    K // R or K // R + 1 steps, each timed on its own"""
+    steps = max(1, steps)
+    r = min(max(1, repeats), steps)
+    return [steps // r + (1 if i < steps % r else 0) for i in range(r)]
 
 
 CPU_THREADS = 16      # the oracle's OpenMP/BLAS loops scale to ~16 threads on the EPYC host, then degrade
@@ -391,17 +436,17 @@ def run_pool2m(args):
     fence()
     eng.profile_enable(False)
     survey = [p for p in eng.profile() if p["launches"] > 0]
-    times = []
-    for _ in range(max(1, args.repeats)):
+    times = []                                  # per repeat: its time per step, scaled to --steps steps
+    for k_rep in _repeat_sizes(args.steps, args.repeats):
         fence()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(k_rep):
             step()
         eng.sync()
         dt = time.perf_counter() - t0
         if hub:
             dt = hub.all_reduce_max(dt)
-        times.append(dt)
+        times.append(dt / k_rep * args.steps)
     dt = float(np.median(times))
     idx = d_idx.download((q_local, k), np.int32)
     ranks = d_ranks.download((q_local,), np.int32)
@@ -530,19 +575,19 @@ def run_train_dp(args):
         step()
     fence()
     eng.comm_stats(reset=True)
-    times = []
-    for _ in range(max(1, args.repeats)):
+    times = []                                  # per repeat: its time per step, scaled to --steps steps
+    for k_rep in _repeat_sizes(args.steps, args.repeats):
         fence()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(k_rep):
             step()                                  # returns with the loss on the host: one synchronisation per update
         dt = time.perf_counter() - t0
         if hub:
             dt = hub.all_reduce_max(dt)
-        times.append(dt)
+        times.append(dt / k_rep * args.steps)
     dt = float(np.median(times))
     cs = eng.comm_stats()
-    n_steps = args.steps * max(1, args.repeats)
+    n_steps = max(1, args.steps)
     # ---- what the collectives cost: the same steps once more with every collective bracketed by HIP events on the
     # stream it is enqueued on (asr_comm_timing).  In the data-parallel step both towers and all collectives share ONE
     # stream, so that time is exposed by construction; what the step loses beyond it (no tower overlap, no side stream
@@ -582,12 +627,12 @@ def run_train_dp(args):
         for _ in range(3):
             plain_step()
         plain.sync()
-        ptimes = []
-        for _ in range(max(1, args.repeats)):
+        ptimes = []                             # the same split of --steps as the timed region
+        for k_rep in _repeat_sizes(args.steps, args.repeats):
             t0 = time.perf_counter()
-            for _ in range(args.steps):
+            for _ in range(k_rep):
                 plain_step()
-            ptimes.append((time.perf_counter() - t0) / args.steps)
+            ptimes.append((time.perf_counter() - t0) / k_rep)
         plain_ms = float(np.median(ptimes)) * 1e3
         exposed = dt / args.steps * 1e3 - plain_ms
         plain.train_end()
@@ -730,22 +775,29 @@ def run_rank(args):
     eng.profile_reset()
     eng.profile_filter(None if args.profile_all else dom_symbol)
     eng.profile_enable(True)
-    times = []
-    for _ in range(max(1, args.repeats)):
+    times = []                                    # per repeat: its time per step, scaled to --steps steps
+    for k_rep in _repeat_sizes(args.steps, args.repeats):
         fence()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(k_rep):
             step(it)
             it += 1
         eng.sync()
         dt = time.perf_counter() - t0
         if hub:
             dt = hub.all_reduce_max(dt)          # the slowest rank defines the step
-        times.append(dt)
+        times.append(dt / k_rep * args.steps)
     eng.profile_enable(False)
     fence()
     eng.profile_filter(None)
     dt = float(np.median(times))
+    it_last_timed = it - 1                      # index of the last timed step (its batch: it_last_timed % --batches)
+    dumped = None
+    if args.dump_outputs:           # before anything else runs on these buffers: the results of the last timed step
+        dumped = dump_outputs(args.dump_outputs, dict(
+            lv1=d_lv1.download((n, 32), np.float32), lv2=d_lv2.download((n, 32), np.float32),
+            ranks=d_ranks.download((n,), np.int32), dstar=d_dstar.download((n,), np.float64),
+            ties=d_ties.download((n,), np.int32)), rank, world)
     comm_ms = comm_calls = None
     if use_dist:                                   # the all-gather of the candidate embeddings, per step (asr_comm_timing)
         eng.comm_timing(True)
@@ -944,6 +996,8 @@ def run_rank(args):
                 "frac": iso[dom_sym]["flops"] / (iso[dom_sym]["ms"] * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS,
                 "avg_launch_ms": iso[dom_sym]["ms"] / iso[dom_sym]["launches"], "launches": iso[dom_sym]["launches"]},
             "kernels": {p["name"]: round(p["total_ms"] / p["launches"], 4) for p in survey},
+            "dumped_outputs": None if dumped is None else {"dir": args.dump_outputs, "arrays": dumped,
+                                                           "step": it_last_timed},
         }
         # ---- Recall@k that means something: the timed region runs random-init weights (the contract's workload:
         # chance-level recall by construction); the same batch 0 - pairs the model never saw - embedded and ranked once
