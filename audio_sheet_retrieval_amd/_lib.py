@@ -34,7 +34,8 @@ EXPORTS = [
     "asr_profile_enable", "asr_profile_filter", "asr_profile_reset", "asr_profile_count", "asr_profile_get", "asr_profile_symbol",
     "asr_debug_activation",
     "asr_train_begin", "asr_train_end", "asr_train_set_global_batch", "asr_train_step", "asr_train_step_dev", "asr_valid_loss", "asr_set_objective", "asr_burn_in",
-    "asr_compute_gradients",
+    "asr_compute_gradients", "asr_train_step_in", "asr_train_step_in_dev", "asr_burn_in_in", "asr_compute_gradients_in",
+    "asr_valid_loss_in",
     "asr_comm_unique_id", "asr_comm_init", "asr_comm_init_custom", "asr_comm_destroy", "asr_comm_info", "asr_comm_stats", "asr_comm_timing", "asr_comm_library",
     "asr_comm_allreduce_dev", "asr_comm_allgather_dev",
     "asr_rank_sharded_dev", "asr_slice_windows_dev", "asr_piece_vote_dev", "asr_gather_windows_dev", "asr_dtw_dev", "asr_spectrogram_dev", "asr_debug_tune_report",
@@ -167,6 +168,13 @@ def load_library(path=None):
         "asr_set_objective": (c_int, [c_void_p, c_float, c_float, c_int]),
         "asr_burn_in": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
         "asr_compute_gradients": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, POINTER(c_float)]),
+        "asr_train_step_in": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_float, POINTER(c_float), c_void_p]),
+        "asr_train_step_in_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_float, POINTER(c_float),
+                                          c_void_p]),
+        "asr_burn_in_in": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
+        "asr_compute_gradients_in": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64,
+                                             POINTER(c_float)]),
+        "asr_valid_loss_in": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, POINTER(c_float)]),
         "asr_slice_windows_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_int,
                                           c_void_p]),
         "asr_piece_vote_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int, c_void_p, c_void_p,
@@ -785,51 +793,92 @@ class Engine(object):
         batch of n_global rows (0: equal shards of batch * world rows)."""
         self._check(self.lib.asr_train_set_global_batch(self.ctx, int(n_global)))
 
-    def train_step(self, x1_prepared, x2, lr):
-        """iter_funcs['train'](X1, X2) -> (loss, corr) (utils/train_dcca_pool.py:154)."""
-        x1, x2 = _f32c(x1_prepared), _f32c(x2)
-        if x1.shape[0] != x2.shape[0]:
-            raise ValueError("train_step: batch sizes differ")
-        if x1.shape[2:] != (self.net_h1, self.net_w1) or x2.shape[2:] != (self.cfg.h2, self.cfg.w2):
-            raise ValueError("train_step: input sizes %r / %r do not match the context (%d,%d)/(%d,%d); call "
-                             "set_input_size before train_begin" % (x1.shape, x2.shape, self.net_h1, self.net_w1,
+    def _train_inputs(self, x1, x2, prepared, who, check=True):
+        """(x1, in_mode, x2) for the training entry points.  prepared=True: x1 is model.prepare's output (float32 at
+        the network size); False: the raw window at the context's raw size (cfg.h1 x cfg.w1), uint8 -> ASR_IN_U8_RAW,
+        any other dtype -> float32 ASR_IN_F32_RAW - model.prepare then runs on the device."""
+        x2 = _f32c(x2)
+        if prepared:
+            x1, mode, want = _f32c(x1), IN_F32_PREPARED, (self.net_h1, self.net_w1)
+        else:
+            x1 = np.ascontiguousarray(x1) if x1.dtype == np.uint8 else _f32c(x1)
+            mode, want = (IN_U8_RAW if x1.dtype == np.uint8 else IN_F32_RAW), (self.cfg.h1, self.cfg.w1)
+        if check and x1.shape[0] != x2.shape[0]:
+            raise ValueError("%s: batch sizes differ" % who)
+        if check and x1.shape[2:] != want or x2.shape[2:] != (self.cfg.h2, self.cfg.w2):
+            raise ValueError("%s: input sizes %r / %r do not match the context's %s size (%d,%d)/(%d,%d); call "
+                             "set_input_size before train_begin" % (who, x1.shape, x2.shape,
+                                                                   "network" if prepared else "raw", want[0], want[1],
                                                                    self.cfg.h2, self.cfg.w2))
+        return x1, mode, x2
+
+    def train_step(self, x1_prepared, x2, lr, prepared=True):
+        """iter_funcs['train'](X1, X2) -> (loss, corr) (utils/train_dcca_pool.py:154).  prepared=False: x1 is the
+        pool's raw window (uint8 or float32 0..255) and model.prepare runs on the device (asr_train_step_in)."""
+        x1, mode, x2 = self._train_inputs(x1_prepared, x2, prepared, "train_step")
         loss = c_float()
         corr = np.empty(32, np.float32)
-        self._check(self.lib.asr_train_step(self.ctx, x1.ctypes.data, x2.ctypes.data, x1.shape[0], lr,
-                                            byref(loss), corr.ctypes.data))
+        if prepared:
+            self._check(self.lib.asr_train_step(self.ctx, x1.ctypes.data, x2.ctypes.data, x1.shape[0], lr,
+                                                byref(loss), corr.ctypes.data))
+        else:
+            self._check(self.lib.asr_train_step_in(self.ctx, x1.ctypes.data, mode, x2.ctypes.data, x1.shape[0], lr,
+                                                   byref(loss), corr.ctypes.data))
         return float(loss.value), corr
 
-    def burn_in(self, x1_prepared, x2):
+    def train_step_in_dev(self, x1_ptr, mode, x2_ptr, n, lr):
+        """asr_train_step_in_dev on device buffers (e.g. AudioScoreRetrievalPool.get_device: IN_F32_RAW)."""
+        loss = c_float()
+        corr = np.empty(32, np.float32)
+        self._check(self.lib.asr_train_step_in_dev(self.ctx, x1_ptr, mode, x2_ptr, n, lr, byref(loss), corr.ctypes.data))
+        return float(loss.value), corr
+
+    def burn_in(self, x1_prepared, x2, prepared=True):
         """iter_funcs['init_cca'](X1, X2) -> [v1 latent, v2 latent] of the train-mode graph
         (utils/train_dcca_pool.py:160-162): updates the BN / CCALayer running values only."""
-        x1, x2 = _f32c(x1_prepared), _f32c(x2)
+        x1, mode, x2 = self._train_inputs(x1_prepared, x2, prepared, "burn_in", check=not prepared)
         n = x1.shape[0]
         lv1, lv2 = np.empty((n, 32), np.float32), np.empty((n, 32), np.float32)
-        self._check(self.lib.asr_burn_in(self.ctx, x1.ctypes.data, x2.ctypes.data, n, lv1.ctypes.data, lv2.ctypes.data))
+        if prepared:
+            self._check(self.lib.asr_burn_in(self.ctx, x1.ctypes.data, x2.ctypes.data, n, lv1.ctypes.data,
+                                             lv2.ctypes.data))
+        else:
+            self._check(self.lib.asr_burn_in_in(self.ctx, x1.ctypes.data, mode, x2.ctypes.data, n, lv1.ctypes.data,
+                                                lv2.ctypes.data))
         return lv1, lv2
 
-    def compute_gradients(self, x1_prepared, x2):
+    def compute_gradients(self, x1_prepared, x2, prepared=True):
         """iter_funcs['compute_gradients'](X1, X2) (utils/train_dcca_pool.py:164): the gradients of the train loss
         wrt the trainable parameters as one flat array (order of get_params, other slots zero) and the loss."""
-        x1, x2 = _f32c(x1_prepared), _f32c(x2)
+        x1, mode, x2 = self._train_inputs(x1_prepared, x2, prepared, "compute_gradients", check=not prepared)
         n = c_int64()
         self._check(self.lib.asr_opt_state_size(self.ctx, byref(n)))
         g = np.empty(n.value, np.float32)
         loss = c_float()
-        self._check(self.lib.asr_compute_gradients(self.ctx, x1.ctypes.data, x2.ctypes.data, x1.shape[0],
-                                                   g.ctypes.data, n.value, byref(loss)))
+        if prepared:
+            self._check(self.lib.asr_compute_gradients(self.ctx, x1.ctypes.data, x2.ctypes.data, x1.shape[0],
+                                                       g.ctypes.data, n.value, byref(loss)))
+        else:
+            self._check(self.lib.asr_compute_gradients_in(self.ctx, x1.ctypes.data, mode, x2.ctypes.data, x1.shape[0],
+                                                          g.ctypes.data, n.value, byref(loss)))
         return g, float(loss.value)
 
     def set_objective(self, weight=1.0, gamma=0.7, symmetric=False):
         """objectives() = get_contrastive_cos_loss(weight, gamma, symmetric) (models/objectives.py:30-69)"""
         self._check(self.lib.asr_set_objective(self.ctx, float(weight), float(gamma), 1 if symmetric else 0))
 
-    def valid_loss(self, x1_prepared, x2):
+    def valid_loss(self, x1_prepared, x2, prepared=True):
         """iter_funcs['valid'](X1, X2) -> loss (utils/train_dcca_pool.py:155)."""
-        x1, x2 = _f32c(x1_prepared), _f32c(x2)
+        if prepared:
+            x1, x2 = _f32c(x1_prepared), _f32c(x2)
+            loss = c_float()
+            self._check(self.lib.asr_valid_loss(self.ctx, x1.ctypes.data, x2.ctypes.data, x1.shape[0], byref(loss)))
+            return float(loss.value)
+        x1, mode = self._view1_mode(x1_prepared, False)
+        x2 = _f32c(x2)
         loss = c_float()
-        self._check(self.lib.asr_valid_loss(self.ctx, x1.ctypes.data, x2.ctypes.data, x1.shape[0], byref(loss)))
+        self._check(self.lib.asr_valid_loss_in(self.ctx, x1.ctypes.data, mode, x2.ctypes.data, x1.shape[0],
+                                               byref(loss)))
         return float(loss.value)
 
     def get_opt_state(self):

@@ -128,6 +128,7 @@ void free_train(asr_ctx *ctx) {
                    T.Hg[0], T.Hg[1], T.dHg[0], T.dHg[1], T.lvg[0], T.lvg[1], T.Hpad[0], T.Hpad[1]};
     for (float *q : fp) if (q) hipFree(q);
     if (T.mask) hipFree(T.mask);
+    if (T.raw1) hipFree(T.raw1);
     if (T.repack_dev) hipFree(T.repack_dev);
     if (T.cca_ws) hipFree(T.cca_ws);
     if (T.l2_dev) hipFree(T.l2_dev);

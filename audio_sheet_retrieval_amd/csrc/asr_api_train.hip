@@ -474,6 +474,9 @@ int train_alloc(asr_ctx *ctx, int B) {
     ASR_HIP(ctx, hipMalloc((void **)&T.l2_dev, sizeof(double)));
     ASR_HIP(ctx, hipEventCreateWithFlags(&T.cca_done, hipEventDisableTiming));
     for (int v = 0; v < 2; ++v) ASR_HIP(ctx, hipMalloc((void **)&T.lvv[v], (size_t)B * 32 * sizeof(float)));
+    // raw sheets of the ASR_IN_*_RAW entry points, float32 at the raw size (uint8 batches use a quarter of it)
+    T.raw1_bytes = (size_t)B * ctx->cfg.h1 * ctx->cfg.w1 * sizeof(float);
+    ASR_HIP(ctx, hipMalloc(&T.raw1, T.raw1_bytes));
 
     for (int t = 0; t < 2; ++t) {
         Tower &tw = ctx->tw[t];
@@ -969,8 +972,8 @@ int train_backward_towers(asr_ctx *ctx, int B, int64_t row_lo) {
     return ASR_OK;
 }
 
-int train_step_common(asr_ctx *ctx, const float *x1, const float *x2, int64_t B, float lr, float *loss, float *corr,
-                      bool on_device, bool forward_only = false, float *lv1_out = nullptr, float *lv2_out = nullptr,
+int train_step_common(asr_ctx *ctx, const void *x1, int in_mode, const float *x2, int64_t B, float lr, float *loss,
+                      float *corr, bool on_device, bool forward_only = false, float *lv1_out = nullptr, float *lv2_out = nullptr,
                       float *grads_out = nullptr) {
     if (!ctx) return ASR_ERR_INVALID;
     const auto t_begin = std::chrono::steady_clock::now();
@@ -989,6 +992,8 @@ int train_step_common(asr_ctx *ctx, const float *x1, const float *x2, int64_t B,
     if (B < (dp ? 1 : 2) || B > T.B)
         return fail(ctx, ASR_ERR_INVALID, "train_step: batch %lld outside [%d, %d]", (long long)B, dp ? 1 : 2, T.B);
     if (!x1 || !x2) return fail(ctx, ASR_ERR_INVALID, "train_step: NULL input");
+    if (in_mode != ASR_IN_F32_PREPARED && in_mode != ASR_IN_F32_RAW && in_mode != ASR_IN_U8_RAW)
+        return fail(ctx, ASR_ERR_INVALID, "train_step: bad in_mode %d", in_mode);
     ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
     const int n = (int)B;
     const size_t b1 = (size_t)n * ctx->tw[0].in_h * ctx->tw[0].in_w * sizeof(float);
@@ -1021,7 +1026,29 @@ int train_step_common(asr_ctx *ctx, const float *x1, const float *x2, int64_t B,
     ctx->exch.n_global = (int)n_global;
     for (int t = 0; t < 2; ++t)
         if (ctx->main_pending) ASR_HIP(ctx, hipStreamWaitEvent(train_stream(ctx, t), ctx->main_done, 0));
-    ASR_HIP(ctx, hipMemcpyAsync(T.tw[0].x[0], x1, b1, kind, train_stream(ctx, 0)));
+    if (in_mode == ASR_IN_F32_PREPARED) {
+        ASR_HIP(ctx, hipMemcpyAsync(T.tw[0].x[0], x1, b1, kind, train_stream(ctx, 0)));
+    } else {
+        // a raw sheet batch (the pool's window at cfg.h1 x cfg.w1, like asr_embed_view1 takes it): to the device at its
+        // own size, then model.prepare on the sheet tower's stream into the tensor every block-1 reader takes
+        const asr_config &c = ctx->cfg;
+        const size_t rb = (size_t)n * c.h1 * c.w1 * (in_mode == ASR_IN_U8_RAW ? 1 : sizeof(float));
+        const int H = ctx->tw[0].in_h, W = ctx->tw[0].in_w;
+        if (c.resize_view1 ? (c.h1 / 2 != H || c.w1 / 2 != W) : (c.h1 != H || c.w1 != W))
+            return fail(ctx, ASR_ERR_STATE, "train_step: raw size %dx%d does not match the network input %dx%d", c.h1, c.w1,
+                        H, W);
+        if (rb > T.raw1_bytes)
+            return fail(ctx, ASR_ERR_STATE, "train_step: the raw staging buffer was sized for another input size");
+        const void *raw = x1;
+        if (!on_device) {
+            ASR_HIP(ctx, hipMemcpyAsync(T.raw1, x1, rb, hipMemcpyHostToDevice, train_stream(ctx, 0)));
+            raw = T.raw1;
+        }
+        ProfScope ps(ctx, "train_prepare1", 1, c.resize_view1 ? 4.0 * n * H * W : (double)n * H * W, (double)rb + b1,
+                     asr::prepare_view1_symbol(in_mode, c.resize_view1, W), train_stream(ctx, 0));
+        ASR_HIP(ctx, asr::launch_prepare_view1(train_stream(ctx, 0), raw, in_mode, c.resize_view1, n, c.h1, c.w1, H, W,
+                                               T.tw[0].x[0]));
+    }
     ASR_HIP(ctx, hipMemcpyAsync(T.tw[1].x[0], x2, b2, kind, train_stream(ctx, 1)));
     // weight decay term of the reported loss: sum p^2 over the trainable parameters BEFORE the update
     // (train_dcca_pool.py:141-142).  A one-workgroup reduction (0.15 ms): it runs on the main stream while the towers
@@ -1377,24 +1404,39 @@ int asr_train_end(asr_ctx *ctx) {
 }
 
 int asr_train_step(asr_ctx *ctx, const float *x1, const float *x2, int64_t batch, float lr, float *loss, float *corr) {
-    return train_step_common(ctx, x1, x2, batch, lr, loss, corr, false);
+    return train_step_common(ctx, x1, ASR_IN_F32_PREPARED, x2, batch, lr, loss, corr, false);
 }
 int asr_train_step_dev(asr_ctx *ctx, const float *x1_dev, const float *x2_dev, int64_t batch, float lr, float *loss,
                        float *corr) {
-    return train_step_common(ctx, x1_dev, x2_dev, batch, lr, loss, corr, true);
+    return train_step_common(ctx, x1_dev, ASR_IN_F32_PREPARED, x2_dev, batch, lr, loss, corr, true);
+}
+int asr_train_step_in(asr_ctx *ctx, const void *x1, int in_mode, const float *x2, int64_t batch, float lr, float *loss,
+                      float *corr) {
+    return train_step_common(ctx, x1, in_mode, x2, batch, lr, loss, corr, false);
+}
+int asr_train_step_in_dev(asr_ctx *ctx, const void *x1_dev, int in_mode, const float *x2_dev, int64_t batch, float lr,
+                          float *loss, float *corr) {
+    return train_step_common(ctx, x1_dev, in_mode, x2_dev, batch, lr, loss, corr, true);
 }
 
 int asr_burn_in(asr_ctx *ctx, const float *x1, const float *x2, int64_t batch, float *lv1, float *lv2) {
-    return train_step_common(ctx, x1, x2, batch, 0.0f, nullptr, nullptr, false, true, lv1, lv2);
+    return train_step_common(ctx, x1, ASR_IN_F32_PREPARED, x2, batch, 0.0f, nullptr, nullptr, false, true, lv1, lv2);
+}
+int asr_burn_in_in(asr_ctx *ctx, const void *x1, int in_mode, const float *x2, int64_t batch, float *lv1, float *lv2) {
+    return train_step_common(ctx, x1, in_mode, x2, batch, 0.0f, nullptr, nullptr, false, true, lv1, lv2);
 }
 
 int asr_compute_gradients(asr_ctx *ctx, const float *x1, const float *x2, int64_t batch, float *grads, int64_t n,
                           float *loss) {
+    return asr_compute_gradients_in(ctx, x1, ASR_IN_F32_PREPARED, x2, batch, grads, n, loss);
+}
+int asr_compute_gradients_in(asr_ctx *ctx, const void *x1, int in_mode, const float *x2, int64_t batch, float *grads,
+                             int64_t n, float *loss) {
     if (!ctx || !grads) return ASR_ERR_INVALID;
     if (!ctx->train) return fail(ctx, ASR_ERR_STATE, "compute_gradients: call asr_train_begin first");
     if (n != ctx->train->poff[90])
         return fail(ctx, ASR_ERR_INVALID, "compute_gradients: expected %lld values", (long long)ctx->train->poff[90]);
-    return train_step_common(ctx, x1, x2, batch, 0.0f, loss, nullptr, false, false, nullptr, nullptr, grads);
+    return train_step_common(ctx, x1, in_mode, x2, batch, 0.0f, loss, nullptr, false, false, nullptr, nullptr, grads);
 }
 
 int asr_set_objective(asr_ctx *ctx, float weight, float gamma, int symmetric) {
@@ -1408,10 +1450,13 @@ int asr_set_objective(asr_ctx *ctx, float weight, float gamma, int symmetric) {
 }
 
 int asr_valid_loss(asr_ctx *ctx, const float *x1, const float *x2, int64_t n, float *loss) {
+    return asr_valid_loss_in(ctx, x1, ASR_IN_F32_PREPARED, x2, n, loss);
+}
+int asr_valid_loss_in(asr_ctx *ctx, const void *x1, int in_mode, const float *x2, int64_t n, float *loss) {
     if (!ctx || !loss) return ASR_ERR_INVALID;
     if (n < 2) return fail(ctx, ASR_ERR_INVALID, "valid_loss: needs at least 2 pairs");
     std::vector<float> lv1((size_t)n * 32), lv2((size_t)n * 32);
-    int rc = asr_embed_view1(ctx, x1, ASR_IN_F32_PREPARED, n, ASR_OUT_LATENT, lv1.data());
+    int rc = asr_embed_view1(ctx, x1, in_mode, n, ASR_OUT_LATENT, lv1.data());
     if (rc != ASR_OK) return rc;
     rc = asr_embed_view2(ctx, x2, n, ASR_OUT_LATENT, lv2.data());
     if (rc != ASR_OK) return rc;

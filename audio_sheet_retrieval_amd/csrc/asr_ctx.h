@@ -96,6 +96,10 @@ struct TrainState {
     float *loss_dev = nullptr;      // [0] ranking loss, [1..32] corr
     double *l2_dev = nullptr;
     float *lvv[2] = {nullptr, nullptr};   // deterministic embeddings for asr_valid_loss
+    // raw sheet batch of the ASR_IN_*_RAW training entry points (asr_train_step_in, ...): the host batch is copied here
+    // at its own size (uint8 or float32, B x h1 x w1 at train_begin), then prepare_view1_kernel writes tw[0].x[0]
+    void *raw1 = nullptr;
+    size_t raw1_bytes = 0;
     hipEvent_t cca_done = nullptr;
     // block gates (single-GPU step, towers on their own streams): "the spectrogram tower has finished block b" of the
     // forward [0..8] and of the backward [9 + b, b = 8 (tail) .. 0] pass; the sheet tower's stream waits on them so that

@@ -236,6 +236,11 @@ struct Exchange {
 };
 
 // ---- training: forward with batch statistics --------------------------------
+// model.prepare of raw sheets for the training step (prepare_view1.h): in (N, Hraw, Wraw) ASR_IN_U8_RAW / _F32_RAW ->
+// out (N, H, W) float32 prepared; rsz: H, W = Hraw / 2, Wraw / 2 (2x2 blend), else H, W = Hraw, Wraw.
+hipError_t launch_prepare_view1(hipStream_t s, const void *in, int in_mode, int rsz, int N, int Hraw, int Wraw, int H,
+                                int W, float *out);
+const char *prepare_view1_symbol(int in_mode, int rsz, int W);      // as rocprofv3 --kernel-trace prints it
 // stats / stats_rows (may be null): partial table of the outputs' per-channel sums, [rows][2][cout] float64
 // mode 0: z + statistics; 1: statistics only (z unused); 2: BatchNorm (bn = [mu | inv_std], gamma, beta) + ELU of the
 // recomputed z written to `z` (block 1's output)

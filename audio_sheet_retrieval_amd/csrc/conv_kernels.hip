@@ -14,6 +14,7 @@
 // 4 accumulator registers of a lane are exactly one 2x2 window: max-pool is a
 // per-lane max with no cross-lane traffic.
 #include "asr_kernels.h"
+#include "prepare_view1.h"
 #include "../../include/asr_hip.h"
 #include <algorithm>
 #include <vector>
@@ -37,30 +38,7 @@ __device__ __forceinline__ int fdiv(int n, float rcp) { return (int)(((float)n +
 // ---------------------------------------------------------------------------
 // block 1
 // ---------------------------------------------------------------------------
-// tab (uint8 inputs only; may be null): 256-entry table of the correctly rounded quotients v / 255.0f.  The IEEE
-// division costs ~10 VALU instructions per tap - with nine taps per pixel about as much as block 1's 108 FMAs.
-template <int IN_MODE>
-__device__ __forceinline__ float load_prepared(const void *in, size_t img_off_raw, int Wraw,
-                                               int y, int x, int H, int W, int rsz, const float *tab = nullptr) {
-    // returns the prepared pixel (y,x) of the network-resolution image, 0 outside
-    if (y < 0 || y >= H || x < 0 || x >= W) return 0.0f;
-    if (IN_MODE == ASR_IN_F32_PREPARED) {
-        return ((const float *)in)[img_off_raw + (size_t)y * W + x];
-    }
-    auto rawn = [&](int yy, int xx) -> float {          // raw value / 255 (model.prepare)
-        if (IN_MODE == ASR_IN_U8_RAW) {
-            const unsigned char v = ((const unsigned char *)in)[img_off_raw + (size_t)yy * Wraw + xx];
-            return tab ? tab[v] : (float)v / 255.0f;
-        }
-        return ((const float *)in)[img_off_raw + (size_t)yy * Wraw + xx] / 255.0f;
-    };
-    if (!rsz) return rawn(y, x);
-    // rsz prepare: /255, then bilinear factor-2 = (.5,.5) horizontally, then vertically
-    const float a = rawn(2 * y, 2 * x), b = rawn(2 * y, 2 * x + 1);
-    const float c = rawn(2 * y + 1, 2 * x), d = rawn(2 * y + 1, 2 * x + 1);
-    const float top = a * 0.5f + b * 0.5f, bot = c * 0.5f + d * 0.5f;
-    return top * 0.5f + bot * 0.5f;
-}
+// load_prepared / fill_div255: prepare_view1.h (the one expression of model.prepare, shared with the training step)
 
 // PX pixels (along x) per thread.  PX = 1: a wave's float4 stores are 48 B apart (2.7 lanes per 128-B line) instead
 // of 192 B (one lane per line) - the store path, not the arithmetic, bounds this kernel.
@@ -71,7 +49,7 @@ __global__ __launch_bounds__(256) void conv1_kernel(const void *__restrict__ in,
     constexpr int COUTP = (COUT + 15) / 16 * 16;
     __shared__ float div255[256];
     if (IN_MODE == ASR_IN_U8_RAW) {
-        div255[threadIdx.x] = (float)threadIdx.x / 255.0f;          // 256 threads: one exact quotient each
+        fill_div255(div255);                                        // 256 threads: one exact quotient each
         __syncthreads();
     }
     const float *tab = (IN_MODE == ASR_IN_U8_RAW) ? div255 : nullptr;

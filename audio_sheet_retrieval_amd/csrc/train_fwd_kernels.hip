@@ -2,6 +2,7 @@
 // utils/train_dcca_pool.py:100-101): raw convolutions come from the MFMA kernel
 // (RAW epilogue); this file adds what batch statistics need.
 //
+//   prepare_view1_kernel    : model.prepare of a raw sheet batch (ASR_IN_*_RAW training inputs)
 //   conv1_raw_kernel        : block 1 (C_in = 1) without BN/ELU
 //   bn_stats_partial/final  : per-channel batch mean and biased variance over
 //                             (N,H,W), float64 accumulation, block-
@@ -11,7 +12,9 @@
 //   bn_apply_elu_pool_kernel: y = (z-mu)*(gamma*s)+beta, ELU, 2x2 max-pool
 //   conv1x1_raw_kernel, bn_gpool_kernel : block 9 + GlobalPoolLayer
 #include "asr_kernels.h"
+#include "prepare_view1.h"
 #include <algorithm>
+#include <cstdio>
 
 namespace asr {
 
@@ -136,6 +139,76 @@ hipError_t launch_conv1_raw(hipStream_t s, const float *x, const float *w, float
     else if (mode == 2) { if (cout == 12) ASR_C1R(12, 2); else ASR_C1R(24, 2); }
     else return hipErrorInvalidValue;
 #undef ASR_C1R
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// model.prepare of a raw sheet batch for the training step: in (N, Hraw, Wraw) uint8 or float32 0..255 -> out (N, H, W)
+// float32, the tensor every block-1 reader of the step takes (conv1_raw_kernel, the BatchNorm backward and the weight
+// gradient of block 1).  One load_prepared expression per pixel (prepare_view1.h, also conv1_kernel's), so the result
+// is prepare_plain / prepare_rsz bit for bit.  Memory-bound: VEC = 4 writes four neighbouring pixels with one 16-byte
+// store (W % 4 == 0), a wave's 64 stores covering 1 KB of a row; VEC = 1 is the scalar form for other widths.
+template <int IN_MODE, int RSZ, int VEC>
+__global__ __launch_bounds__(256) void prepare_view1_kernel(const void *__restrict__ in, float *__restrict__ out, int N,
+                                                            int Hraw, int Wraw, int H, int W) {
+    __shared__ float div255[256];
+    if (IN_MODE == ASR_IN_U8_RAW) {
+        fill_div255(div255);
+        __syncthreads();
+    }
+    const float *tab = (IN_MODE == ASR_IN_U8_RAW) ? div255 : nullptr;
+    const int gw = W / VEC;                                   // VEC-pixel groups per row
+    const int64_t total = (int64_t)N * H * gw;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < total; s += stride) {
+        const int64_t row = s / gw;                           // n * H + y
+        const int x0 = (int)(s - row * gw) * VEC;
+        const int n = (int)(row / H), y = (int)(row - (int64_t)n * H);
+        const size_t img = (size_t)n * Hraw * Wraw;
+        float v[VEC];
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) v[k] = load_prepared<IN_MODE>(in, img, Wraw, y, x0 + k, H, W, RSZ, tab);
+        float *dst = out + (size_t)row * W + x0;
+        if (VEC == 4) {
+            typedef float floatx4 __attribute__((ext_vector_type(4)));
+            floatx4 q;
+            q.x = v[0]; q.y = v[1]; q.z = v[2]; q.w = v[3];
+            *(floatx4 *)dst = q;
+        } else {
+            dst[0] = v[0];
+        }
+    }
+}
+
+const char *prepare_view1_symbol(int in_mode, int rsz, int W) {
+    static char names[2][2][2][128];
+    static bool init = false;
+    if (!init) {
+        for (int m = 0; m < 2; ++m)
+            for (int r = 0; r < 2; ++r)
+                for (int v = 0; v < 2; ++v)
+                    snprintf(names[m][r][v], sizeof names[m][r][v],
+                             "void asr::prepare_view1_kernel<%d, %d, %d>(void const*, float*, int, int, int, int, int)",
+                             m ? ASR_IN_U8_RAW : ASR_IN_F32_RAW, r, v ? 4 : 1);
+        init = true;
+    }
+    return names[in_mode == ASR_IN_U8_RAW ? 1 : 0][rsz ? 1 : 0][W % 4 == 0 ? 1 : 0];
+}
+
+hipError_t launch_prepare_view1(hipStream_t s, const void *in, int in_mode, int rsz, int N, int Hraw, int Wraw, int H,
+                                int W, float *out) {
+    if (in_mode != ASR_IN_U8_RAW && in_mode != ASR_IN_F32_RAW) return hipErrorInvalidValue;
+    if (rsz ? (2 * H > Hraw || 2 * W > Wraw) : (H != Hraw || W != Wraw)) return hipErrorInvalidValue;
+    const bool vec = W % 4 == 0;                              // (out rows then start 16-byte aligned: hipMalloc'd base)
+    const int64_t total = (int64_t)N * H * (vec ? W / 4 : W);
+    const int blocks = (int)std::min<int64_t>((total + 255) / 256, 256 * 32);
+    if (blocks == 0) return hipSuccess;
+#define ASR_PV1(M, R, V) prepare_view1_kernel<M, R, V><<<blocks, 256, 0, s>>>(in, out, N, Hraw, Wraw, H, W)
+#define ASR_PV1_M(R, V) do { if (in_mode == ASR_IN_U8_RAW) ASR_PV1(ASR_IN_U8_RAW, R, V); else ASR_PV1(ASR_IN_F32_RAW, R, V); } while (0)
+    if (rsz) { if (vec) ASR_PV1_M(1, 4); else ASR_PV1_M(1, 1); }
+    else { if (vec) ASR_PV1_M(0, 4); else ASR_PV1_M(0, 1); }
+#undef ASR_PV1_M
+#undef ASR_PV1
     return hipGetLastError();
 }
 

@@ -130,15 +130,38 @@ class MultiviewPoolIteratorUnsupervised(object):
         return self.prepare(xb, zb)
 
     def __iter__(self):
+        for xb, zb in self._batches(self.pool.__getitem__):
+            yield self.transform(xb, zb)
+
+    def raw(self):
+        """The batches of __iter__ WITHOUT `prepare`: same pass over the pool, same fill-up of a short last batch, same
+        reshuffle and epoch bookkeeping (one shared generator).  Sheets come as uint8 where the pool offers them
+        (SyntheticRetrievalPool.get_u8), otherwise as the pool returns them (float32 0..255).  What train() feeds to the
+        training entry points' raw input modes when `prepare` is the model's own."""
+        return self._batches(getattr(self.pool, "get_u8", self.pool.__getitem__))
+
+    def keys(self):
+        """The pool rows of every batch of __iter__ as one int64 index array each (rows of the window, then the fill-up
+        rows), same pass and bookkeeping: AudioScoreRetrievalPool.get_device(idx) assembles the batch on the device,
+        drawing its augmentation numbers in the order pool[...] would."""
+        n = self.pool.shape[0]
+
+        def fetch(key):
+            idx = np.arange(n, dtype=np.int64)[key]
+            return idx, idx
+        return (xb for xb, _ in self._batches(fetch))
+
+    def _batches(self, fetch):
+        """one pass (:195-218): fetch(slice) -> (x, z) rows of the pool"""
         window = int(self.epoch_counter % self.n_epochs)
         first = window * self.k_samples
         for lo in range(0, self.k_samples, self.batch_size):
-            xb, zb = self.pool[slice(first + lo, first + lo + self.batch_size)]
+            xb, zb = fetch(slice(first + lo, first + lo + self.batch_size))
             missing = self.batch_size - xb.shape[0]
             if missing > 0:
-                x_fill, z_fill = self.pool[0:missing]
+                x_fill, z_fill = fetch(slice(0, missing))
                 xb, zb = np.concatenate((xb, x_fill)), np.concatenate((zb, z_fill))
-            yield self.transform(xb, zb)
+            yield xb, zb
         self.epoch_counter += 1
         if self.shuffle and window + 1 == self.n_epochs:
             self.pool.reset_batch_generator()

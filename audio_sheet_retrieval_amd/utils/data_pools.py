@@ -5,8 +5,9 @@ stay resident on the device; `pool[key]` draws the augmentation random numbers o
 (NumPy global RNG: sheet_scaling -> system_translation per image, then onset_translation -> spec_padding per
 excerpt, sample after sample), reduces every sample to nine numbers and lets one gather kernel per view cut, rescale
 (nearest neighbour) and pad the windows (csrc/piece_vote_kernels.hip: gather_windows_kernel).  `pool.get_device(key)`
-returns device buffers that feed asr_train_step_dev / asr_embed_view*_dev directly (sheets un-normalised like the
-reference's pool: model.prepare / ASR_IN_F32_RAW divides by 255); `pool[key]` downloads them (reference behaviour).
+returns device buffers that feed asr_train_step_in_dev(..., ASR_IN_F32_RAW, ...) / asr_embed_view*_dev directly (sheets
+un-normalised like the reference's pool: model.prepare runs in the library's first kernel); train() assembles its
+batches this way (utils/train_dcca_pool.py); `pool[key]` downloads them (reference behaviour).
 
 MSMD loading (msmd package, absent) is out of scope: the pool takes the arrays the reference's loader would pass.
 """
@@ -151,13 +152,22 @@ class AudioScoreRetrievalPool(object):
             d2.append(self._audio_desc(i_sheet, i_spec, i_onset))
         return np.asarray(d1, np.float64).reshape(-1, 9), np.asarray(d2, np.float64).reshape(-1, 9)
 
-    def get_device(self, key):
-        """-> (sheet DeviceBuffer (n,1,160,200) float32 un-normalised, spec DeviceBuffer (n,1,bins,42), n)"""
+    def get_device(self, key, out=None):
+        """-> (sheet DeviceBuffer (n,1,160,200) float32 un-normalised, spec DeviceBuffer (n,1,bins,42), n).  `key`: int,
+        slice or index array into the (shuffled) entity list.  out=(sheet buffer, spec buffer): caller-owned buffers
+        large enough for n samples, filled and returned instead of two new allocations (a training loop then
+        allocates nothing per batch)."""
         d1, d2 = self._descriptors(key)
         n = d1.shape[0]
         eng = self.engine
-        b1 = eng.alloc(max(4, n * self.sheet_dim[0] * self.sheet_dim[1] * 4))
-        b2 = eng.alloc(max(4, n * self.spec_dim[0] * self.spec_dim[1] * 4))
+        nb1, nb2 = max(4, n * self.sheet_dim[0] * self.sheet_dim[1] * 4), max(4, n * self.spec_dim[0] * self.spec_dim[1] * 4)
+        if out is None:
+            b1, b2 = eng.alloc(nb1), eng.alloc(nb2)
+        else:
+            b1, b2 = out
+            if b1.nbytes < nb1 or b2.nbytes < nb2:
+                raise ValueError("get_device: buffers of %d / %d bytes for %d samples (%d / %d needed)"
+                                 % (b1.nbytes, b2.nbytes, n, nb1, nb2))
         eng.gather_windows_dev(self._d_img.ptr, self._img_floats, d1, self.sheet_dim[0], self.sheet_dim[1], b1.ptr)
         eng.gather_windows_dev(self._d_spec.ptr, self._spec_floats, d2, self.spec_dim[0], self.spec_dim[1], b2.ptr)
         return b1, b2, n

@@ -5,7 +5,14 @@ order, rank by counting); the training functions (create_iter_functions :85-167,
 train :185-315, fit :318-543) wrap the HIP training step."""
 from __future__ import annotations
 
+import collections
+
 import numpy as np
+
+#: training-function calls by input route since import (tests and tools read it): "prepared" = host-prepared float32
+#: (iter_funcs['train'] and friends), "raw" = the un-prepared batch (asr_*_in), "device" = batches assembled on the
+#: device by AudioScoreRetrievalPool.get_device (asr_train_step_in_dev)
+ROUTE_CALLS = collections.Counter()
 
 
 def atomic_pickle_dump(obj, path, protocol=2):
@@ -145,16 +152,20 @@ class IterFunctions(dict):
             self.batch_cap = 0
             self._global_batch = None
 
-    def _sizes(self, X1, X2):
+    def _sizes(self, shape1, shape2, raw=False):
+        """size the context for batches of these (n,1,H,W) shapes: view 1 prepared (network size; the raw size is
+        twice it for the _rsz model) or raw=True (the raw size itself)"""
         rsz = self.net.model_name.endswith("_rsz")
         eng = self.engine
-        if X1.shape[2:] != (eng.net_h1, eng.net_w1) or X2.shape[2:] != (eng.cfg.h2, eng.cfg.w2):
+        want1 = (eng.cfg.h1, eng.cfg.w1) if raw else (eng.net_h1, eng.net_w1)
+        if tuple(shape1[2:]) != want1 or tuple(shape2[2:]) != (eng.cfg.h2, eng.cfg.w2):
             if self.begun:
                 raise ValueError("input size changed after training started")
-            eng.set_input_size(1, X1.shape[2] * (2 if rsz else 1), X1.shape[3] * (2 if rsz else 1))
-            eng.set_input_size(2, X2.shape[2], X2.shape[3])
+            f = 1 if raw or not rsz else 2
+            eng.set_input_size(1, shape1[2] * f, shape1[3] * f)
+            eng.set_input_size(2, shape2[2], shape2[3])
 
-    def _shard(self, X1, X2):
+    def _shard(self, X1, X2, raw=False):
         """data parallel (engine.comm_init*): every rank iterates the same batches and trains on its contiguous share
         of the rows (distributed.shard_range - no row is dropped: a batch of 100 on 8 ranks is 4 x 13 + 4 x 12 rows
         and the library is told the size of the whole batch).  Allocates the training state on first use: every rank
@@ -164,7 +175,7 @@ class IterFunctions(dict):
         if world > 1:
             from ..distributed import shard_batch
             X1, X2 = shard_batch([X1, X2], rank, world)
-        self._sizes(X1, X2)
+        self._sizes(X1.shape, X2.shape, raw)
         self._ensure(-(-n // world))
         if world > 1 and getattr(self, "_global_batch", None) != n:
             self.engine.train_set_global_batch(n)
@@ -174,12 +185,40 @@ class IterFunctions(dict):
     def _train(self, X1, X2):
         X1, X2 = self._shard(X1, X2)
         loss, corr = self.engine.train_step(X1, X2, float(self.lr.get_value()))
+        ROUTE_CALLS["prepared"] += 1
+        return [np.float32(loss), corr]
+
+    def train_raw(self, X1, X2):
+        """iter_funcs['train'] on the batch BEFORE model.prepare (uint8 or float32 0..255 at the raw size): the library
+        prepares it on the device (asr_train_step_in) - the same update as the prepared batch gives, bit for bit."""
+        X1, X2 = self._shard(X1, X2, raw=True)
+        loss, corr = self.engine.train_step(X1, X2, float(self.lr.get_value()), prepared=False)
+        ROUTE_CALLS["raw"] += 1
+        return [np.float32(loss), corr]
+
+    def train_dev(self, b1, b2, n, shape1, shape2):
+        """iter_funcs['train'] on a batch already on the device (AudioScoreRetrievalPool.get_device: DeviceBuffers of
+        un-normalised float32 sheets (n,)+shape1 and spectrograms (n,)+shape2, asr_train_step_in_dev with
+        ASR_IN_F32_RAW).  One device only (device rows are not sharded over ranks)."""
+        from .. import _lib
+        if self.engine.comm_info()[1] > 1:
+            raise ValueError("train_dev: device-pool batches are not sharded over ranks")
+        self._sizes((n,) + tuple(shape1), (n,) + tuple(shape2), raw=True)
+        self._ensure(n)
+        loss, corr = self.engine.train_step_in_dev(b1.ptr, _lib.IN_F32_RAW, b2.ptr, n, float(self.lr.get_value()))
+        ROUTE_CALLS["device"] += 1
         return [np.float32(loss), corr]
 
     def _init_cca(self, X1, X2):
         """burn-in pass (:160-162): train-mode forward, only the running averages change."""
         X1, X2 = self._shard(X1, X2)
         return list(self.engine.burn_in(X1, X2))
+
+    def init_cca_raw(self, X1, X2):
+        """_init_cca on the un-prepared batch (asr_burn_in_in)"""
+        X1, X2 = self._shard(X1, X2, raw=True)
+        ROUTE_CALLS["raw"] += 1
+        return list(self.engine.burn_in(X1, X2, prepared=False))
 
     def _compute_gradients(self, X1, X2):
         """theano.function(input_vars, all_grads) (:164): one array per entry of all_params, no update applied."""
@@ -193,8 +232,16 @@ class IterFunctions(dict):
     def _valid(self, X1, X2):
         return [np.float32(self.engine.valid_loss(X1, X2))]
 
+    def valid_raw(self, X1, X2):
+        """_valid on the un-prepared batch (asr_valid_loss_in)"""
+        ROUTE_CALLS["raw"] += 1
+        return [np.float32(self.engine.valid_loss(X1, X2, prepared=False))]
+
     def _compute_output(self, X1, X2):
         return list(self.engine.embed_both(X1, X2, prepared=True))
+
+    def compute_output_raw(self, X1, X2):
+        return list(self.engine.embed_both(X1, X2, prepared=False))
 
 
 def create_iter_functions(layers, objectives, compute_updates, learning_rate, l_2, l_1, init_cca=False):
@@ -229,24 +276,46 @@ def pretrain(iter_funcs, dataset, train_batch_iter, epochs=3):
         return
     print("Pretraining for %d epochs..." % epochs)
     from .batch_iterators import threaded_generator_from_iterator
+    raw = _raw_route(iter_funcs, train_batch_iter)
     for _ in range(epochs):
         iterator = train_batch_iter(dataset["train"])
-        generator = threaded_generator_from_iterator(iterator)
+        generator = threaded_generator_from_iterator(iterator.raw() if raw else iterator)
         for X_b, Z_b in generator:
-            iter_funcs["init_cca"](X_b, Z_b)
+            if raw:
+                iter_funcs.init_cca_raw(X_b, Z_b)
+            else:
+                iter_funcs["init_cca"](X_b, Z_b)
+
+
+def _raw_route(iter_funcs, batch_iter):
+    """True when the batches can reach the library un-prepared: the iterator applies the model's own prepare, which
+    the training entry points' raw input modes evaluate on the device (network.is_fused_prepare)."""
+    from .. import network
+    return isinstance(iter_funcs, IterFunctions) and hasattr(batch_iter, "raw") and \
+        network.is_fused_prepare(iter_funcs.net, getattr(batch_iter, "prepare", None))
+
+
+def _device_pool(iter_funcs, pool):
+    """A pool whose batches are assembled on this context's device (utils/data_pools.py), on one device"""
+    from .data_pools import AudioScoreRetrievalPool
+    return isinstance(pool, AudioScoreRetrievalPool) and pool.engine is iter_funcs.engine and \
+        iter_funcs.engine.comm_info()[1] == 1
 
 
 # --------------------------------------------------------------------------
 # epoch generator and fit (:185-315, :318-543)
 # --------------------------------------------------------------------------
-def _collect_outputs(iter_funcs, generator, n_needed, with_loss=False):
-    """Run `compute_output` (and optionally `valid`) over a batch generator, keeping the first n_needed rows."""
+def _collect_outputs(iter_funcs, generator, n_needed, with_loss=False, raw=False):
+    """Run `compute_output` (and optionally `valid`) over a batch generator, keeping the first n_needed rows.
+    raw: the generator yields un-prepared batches (batch iterator's raw()), embedded with prepared=False."""
     V1, V2, losses = None, None, []
+    valid = iter_funcs.valid_raw if raw else iter_funcs["valid"]
+    compute_output = iter_funcs.compute_output_raw if raw else iter_funcs["compute_output"]
     for batch in generator:
         if with_loss:
-            losses.append(iter_funcs["valid"](*batch)[0])
+            losses.append(valid(*batch)[0])
         if V1 is None or V1.shape[0] < n_needed:
-            a, b = iter_funcs["compute_output"](*batch)
+            a, b = compute_output(*batch)
             V1 = a if V1 is None else np.vstack([V1, a])
             V2 = b if V2 is None else np.vstack([V2, b])
     return V1, V2, losses
@@ -267,9 +336,32 @@ def train(iter_funcs, dataset, train_batch_iter, valid_batch_iter, fit_cca):
         losses, evals = [], []
         recent = np.zeros(5, dtype=np.float32)
         t_start = t_last = time.time()
-        gen = threaded_generator_from_iterator(train_batch_iter(dataset["train"]))
+        # Feeds (all give the same updates, bit for bit): the model's own prepare -> the un-prepared batches go to the
+        # library, which prepares them on the device (uint8 sheets where the pool has them: a quarter of the bytes); a
+        # device-resident pool -> every batch is assembled on the device on THIS thread (the context is
+        # single-threaded) into two buffers reused for the whole sub-epoch; otherwise the reference's host-prepared
+        # batches from the producer thread.
+        iterator = train_batch_iter(dataset["train"])
+        raw = _raw_route(iter_funcs, train_batch_iter)
+        bufs = None
+        if raw and _device_pool(iter_funcs, dataset["train"]):
+            pool = dataset["train"]
+            bs = train_batch_iter.batch_size
+            eng = iter_funcs.engine
+            bufs = (eng.alloc(bs * int(np.prod(pool.sheet_dim)) * 4), eng.alloc(bs * int(np.prod(pool.spec_dim)) * 4))
+
+            def step(idx):
+                b1, b2, n = pool.get_device(idx, out=bufs)
+                return iter_funcs.train_dev(b1, b2, n, [1] + list(pool.sheet_dim), [1] + list(pool.spec_dim))
+            gen = ((idx,) for idx in iterator.keys())
+        elif raw:
+            step = iter_funcs.train_raw
+            gen = threaded_generator_from_iterator(iterator.raw())
+        else:
+            step = iter_funcs["train"]
+            gen = threaded_generator_from_iterator(iterator)
         for i_batch, batch in enumerate(gen):
-            res = iter_funcs["train"](*batch)
+            res = step(*batch)
             losses.append(res[0])
             if len(res) > 1:
                 evals.append(res[1])
@@ -283,12 +375,18 @@ def train(iter_funcs, dataset, train_batch_iter, valid_batch_iter, fit_cca):
             print(" (%d%%) %s time: %.2fs, ups: %.2f, loss: %.5f" % (perc, bar, now - t_start, ups, np.mean(losses)),
                   end="\r")
             sys.stdout.flush()
+        if bufs is not None:
+            for b in bufs:
+                b.free()
 
         n_valid_cca = int(np.min([1000, dataset["valid"].shape[0]]))
         it_copy = copy.copy(train_batch_iter)
         it_copy.epoch_counter = 0
-        V1_tr, V2_tr, _ = _collect_outputs(iter_funcs, threaded_generator_from_iterator(it_copy(dataset["train"])),
-                                           n_valid_cca)
+        it_copy = it_copy(dataset["train"])
+        batches = it_copy.raw() if raw else it_copy
+        # (a device pool's batches are drawn on this thread, as in the update loop: its context is the engine's)
+        V1_tr, V2_tr, _ = _collect_outputs(iter_funcs, batches if bufs is not None else
+                                           threaded_generator_from_iterator(batches), n_valid_cca, raw=raw)
         cca = None
         if fit_cca:
             cca = CCA(method="svd", engine=iter_funcs.engine)
@@ -299,8 +397,11 @@ def train(iter_funcs, dataset, train_batch_iter, valid_batch_iter, fit_cca):
 
         print("\x1b[K", end="\r")
         print(" ")
+        raw_va = _raw_route(iter_funcs, valid_batch_iter)
+        va_iter = valid_batch_iter(dataset["valid"])
         V1_va, V2_va, va_losses = _collect_outputs(
-            iter_funcs, threaded_generator_from_iterator(valid_batch_iter(dataset["valid"])), n_valid_cca, True)
+            iter_funcs, threaded_generator_from_iterator(va_iter.raw() if raw_va else va_iter), n_valid_cca, True,
+            raw=raw_va)
         if cca is not None:
             V1_va, V2_va = cca.transform_V1(V1_va), cca.transform_V2(V2_va)
         _, med_va, dist_va, hits_va, map_va = eval_retrieval(V1_va, V2_va, engine=iter_funcs.engine)

@@ -427,6 +427,29 @@ int asr_burn_in(asr_ctx *ctx, const float *x1, const float *x2, int64_t batch, f
  * CCALayer running values move exactly as in asr_burn_in); Adam's moments and t stay untouched.  loss may be NULL. */
 int asr_compute_gradients(asr_ctx *ctx, const float *x1, const float *x2, int64_t batch, float *grads, int64_t n,
                           float *loss);
+/* The same five functions on RAW sheet batches - what the reference's training loop produces before model.prepare:
+ * train() (utils/train_dcca_pool.py:154-162 via :185-231) iterates MultiviewPoolIteratorUnsupervised
+ * (utils/batch_iterators.py:114-141, 163-221), whose transform applies prepare_plain / prepare_rsz on the host
+ * (models/_common.py; x.astype(np.float32); x /= 255 on 512 x 160 x 200 pixels per batch).  Here the host passes the
+ * pool's window as it is:
+ *   in_mode  ASR_IN_F32_PREPARED: x1 exactly as asr_train_step & co. take it (these calls ARE those then);
+ *            ASR_IN_U8_RAW / ASR_IN_F32_RAW: x1 (batch,1,h1,w1) uint8 / float32 0..255 at the context's raw size
+ *            (asr_config.h1 x w1, as asr_embed_view1 takes it; for a resize_view1 model that is 2H x 2W of the network
+ *            input).  The training step copies the raw batch into a staging buffer of the training state (sized at
+ *            asr_train_begin) and one kernel writes the prepared float32 tensor the step reads - bit for bit what
+ *            prepare_plain / prepare_rsz give, so every result equals the prepared call's.  A uint8 batch moves a
+ *            quarter of the bytes.  asr_valid_loss_in embeds through asr_embed_view1 with the mode.
+ *   x2, batch, lr, outputs and data parallel (this rank's rows) as in the functions above.
+ * asr_train_step_in_dev takes device pointers (e.g. the window buffers of asr_gather_windows_dev, un-normalised
+ * float32 = ASR_IN_F32_RAW) and, like asr_train_step_dev, returns after the step. */
+int asr_train_step_in(asr_ctx *ctx, const void *x1, int in_mode, const float *x2, int64_t batch, float lr,
+                      float *loss, float *corr);
+int asr_train_step_in_dev(asr_ctx *ctx, const void *x1_dev, int in_mode, const float *x2_dev, int64_t batch,
+                          float lr, float *loss, float *corr);
+int asr_burn_in_in(asr_ctx *ctx, const void *x1, int in_mode, const float *x2, int64_t batch, float *lv1, float *lv2);
+int asr_compute_gradients_in(asr_ctx *ctx, const void *x1, int in_mode, const float *x2, int64_t batch,
+                             float *grads, int64_t n, float *loss);
+int asr_valid_loss_in(asr_ctx *ctx, const void *x1, int in_mode, const float *x2, int64_t n, float *loss);
 int asr_opt_state_size(asr_ctx *ctx, int64_t *n);
 int asr_get_opt_state(asr_ctx *ctx, float *m, float *v, int64_t n, int32_t *t);
 int asr_set_opt_state(asr_ctx *ctx, const float *m, const float *v, int64_t n, int32_t t);
