@@ -35,7 +35,7 @@ EXPORTS = [
     "asr_debug_activation",
     "asr_train_begin", "asr_train_end", "asr_train_set_global_batch", "asr_train_step", "asr_train_step_dev", "asr_valid_loss", "asr_set_objective", "asr_burn_in",
     "asr_compute_gradients", "asr_train_step_in", "asr_train_step_in_dev", "asr_burn_in_in", "asr_compute_gradients_in",
-    "asr_valid_loss_in",
+    "asr_valid_loss_in", "asr_valid_output_in", "asr_valid_output_in_dev",
     "asr_comm_unique_id", "asr_comm_init", "asr_comm_init_custom", "asr_comm_destroy", "asr_comm_info", "asr_comm_stats", "asr_comm_timing", "asr_comm_library",
     "asr_comm_allreduce_dev", "asr_comm_allgather_dev",
     "asr_rank_sharded_dev", "asr_slice_windows_dev", "asr_piece_vote_dev", "asr_gather_windows_dev", "asr_dtw_dev", "asr_spectrogram_dev", "asr_debug_tune_report",
@@ -175,6 +175,9 @@ def load_library(path=None):
         "asr_compute_gradients_in": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64,
                                              POINTER(c_float)]),
         "asr_valid_loss_in": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, POINTER(c_float)]),
+        "asr_valid_output_in": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, POINTER(c_float), c_void_p,
+                                        c_void_p]),
+        "asr_valid_output_in_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
         "asr_slice_windows_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_int,
                                           c_void_p]),
         "asr_piece_vote_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int, c_void_p, c_void_p,
@@ -880,6 +883,28 @@ class Engine(object):
         self._check(self.lib.asr_valid_loss_in(self.ctx, x1.ctypes.data, mode, x2.ctypes.data, x1.shape[0],
                                                byref(loss)))
         return float(loss.value)
+
+    def valid_output(self, x1, x2, prepared=True):
+        """iter_funcs['valid'] + iter_funcs['compute_output'] on the same batch (utils/train_dcca_pool.py:155,158) ->
+        (loss, v1 latent, v2 latent) from one forward of both towers (asr_valid_output_in): the loss of valid_loss and
+        the latents of embed_both, bit for bit.  prepared=False: x1 is the raw window, as embed_both takes it."""
+        x1, mode = self._view1_mode(x1, prepared)
+        x2 = _f32c(x2)
+        if x1.shape[0] != x2.shape[0]:
+            raise ValueError("valid_output: %d sheets but %d spectrograms" % (x1.shape[0], x2.shape[0]))
+        if x2.shape[2:] != (self.cfg.h2, self.cfg.w2):
+            self.set_input_size(2, x2.shape[2], x2.shape[3])
+        n = x1.shape[0]
+        loss = c_float()
+        o1, o2 = np.empty((n, 32), np.float32), np.empty((n, 32), np.float32)
+        self._check(self.lib.asr_valid_output_in(self.ctx, x1.ctypes.data, mode, x2.ctypes.data, n, byref(loss),
+                                                 o1.ctypes.data, o2.ctypes.data))
+        return float(loss.value), o1, o2
+
+    def valid_output_dev(self, x1_ptr, mode, x2_ptr, n, loss_ptr, lv1_ptr=None, lv2_ptr=None):
+        """asr_valid_output_in_dev: enqueue one batch on device buffers (loss_ptr: one float slot; latent pointers
+        (n,32) or None).  Ordered inside the context: a later gather into the same windows or a download waits for it."""
+        self._check(self.lib.asr_valid_output_in_dev(self.ctx, x1_ptr, mode, x2_ptr, n, loss_ptr, lv1_ptr, lv2_ptr))
 
     def get_opt_state(self):
         n = c_int64()

@@ -205,6 +205,7 @@ void free_ctx_buffers(asr_ctx *ctx) {
     if (ctx->topk_tickets) hipFree(ctx->topk_tickets);
     if (ctx->unit_ws) hipFree(ctx->unit_ws);
     if (ctx->rank_io) hipFree(ctx->rank_io);
+    if (ctx->valid_ws) hipFree(ctx->valid_ws);
     for (auto &r : ctx->prof) prof_fold(r.get());
     if (ctx->stream) hipStreamDestroy(ctx->stream);
 }
@@ -581,11 +582,6 @@ int embed_common(asr_ctx *ctx, int view, const void *x, int in_mode, int64_t n, 
     return ASR_OK;
 }
 
-// One host-buffer request: n samples of one view at x -> n x 32 floats at out.
-struct HostJob {
-    int view; const void *x; int in_mode; int64_t n; int out_kind; float *out;
-};
-
 bool host_pointer_is_pinned(const void *p) {
     hipPointerAttribute_t a;
     memset(&a, 0, sizeof a);
@@ -602,14 +598,19 @@ bool host_pointer_is_pinned(const void *p) {
 // samples) and the H2D of granule k+1 on the copy stream overlaps the tower of granule k (with ASR_HOST_STAGE=1 also
 // the staging copy of granule k+2, pageable -> page-locked; skipped when the caller's memory is page-locked already).
 // Every embedding lands in one device buffer and returns in a single D2H; one host synchronisation per call.
-int embed_host(asr_ctx *ctx, const HostJob *jobs, int njobs) {
+// With `loss` (asr_valid_output_in) the two jobs are the two views of the same pairs: the main stream joins both towers,
+// rank_loss_kernel reads the latents in place, and the loss returns with them.
+int embed_host(asr_ctx *ctx, const HostJob *jobs, int njobs, float *loss) {
     if (!ctx) return ASR_ERR_INVALID;
     if (!ctx->params_set) return fail(ctx, ASR_ERR_STATE, "embed: asr_set_params has not been called");
+    if (loss && (njobs != 2 || jobs[0].view != 1 || jobs[1].view != 2 || jobs[0].n != jobs[1].n || jobs[0].n < 2 ||
+                 jobs[0].out_kind != ASR_OUT_LATENT || jobs[1].out_kind != ASR_OUT_LATENT))
+        return fail(ctx, ASR_ERR_INVALID, "valid_output: two views of the same n >= 2 pairs, latents");
     int64_t total = 0;
     size_t max_bps = 0;
     for (int j = 0; j < njobs; ++j) {
         const HostJob &J = jobs[j];
-        if (J.n < 0 || (J.n > 0 && (!J.x || !J.out))) return fail(ctx, ASR_ERR_INVALID, "embed: NULL buffer or negative n");
+        if (J.n < 0 || (J.n > 0 && (!J.x || (!J.out && !loss)))) return fail(ctx, ASR_ERR_INVALID, "embed: NULL buffer or negative n");
         if (J.in_mode < 0 || J.in_mode > 2 || (J.view == 2 && J.in_mode != ASR_IN_F32_PREPARED))
             return fail(ctx, ASR_ERR_INVALID, "embed: bad in_mode %d for view %d", J.in_mode, J.view);
         if (J.out_kind != ASR_OUT_LATENT && J.out_kind != ASR_OUT_FEATURES)
@@ -692,6 +693,13 @@ int embed_host(asr_ctx *ctx, const HostJob *jobs, int njobs) {
         ASR_HIP(ctx, hipMalloc((void **)&H.out_dev, fl * sizeof(float)));
         H.out_floats = fl;
     }
+    if (loss && ctx->valid_ws_floats < 64) {
+        int rcs = sync_all(ctx);
+        if (rcs != ASR_OK) return rcs;
+        if (ctx->valid_ws) { ASR_HIP(ctx, hipFree(ctx->valid_ws)); ctx->valid_ws = nullptr; ctx->valid_ws_floats = 0; }
+        ASR_HIP(ctx, hipMalloc((void **)&ctx->valid_ws, 64 * sizeof(float)));
+        ctx->valid_ws_floats = 64;
+    }
     // results of an earlier "_dev" call may still be read by the main stream
     for (int v = 0; v < 2; ++v)
         if (ctx->main_pending) ASR_HIP(ctx, hipStreamWaitEvent(ctx->estream[v], ctx->main_done, 0));
@@ -733,15 +741,33 @@ int embed_host(asr_ctx *ctx, const HostJob *jobs, int njobs) {
         }
         out_row += J.n;
     }
+    if (loss) {      // enqueued before the copy-outs, which may block the host
+        const int64_t n = jobs[0].n;
+        hipError_t e = hipSuccess;
+        for (int v = 0; v < 2 && e == hipSuccess; ++v) {
+            e = hipEventRecord(ctx->vdone[v], ctx->estream[v]);
+            if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->vdone[v], 0);
+        }
+        if (e == hipSuccess)
+            e = asr::launch_rank_loss(ctx->stream, H.out_dev, H.out_dev + (size_t)n * 32, (int)n, ctx->cfg.gamma,
+                                      ctx->valid_ws, ctx->loss_weight, ctx->loss_symmetric);
+        if (e != hipSuccess) {
+            (void)sync_all(ctx);
+            (void)hipStreamSynchronize(H.h2d);
+            return fail(ctx, ASR_ERR_HIP, "valid_output: %s", hipGetErrorString(e));
+        }
+    }
     // copy-outs last: into pageable memory they block the host until the job's tower is through
     out_row = 0;
     for (int j = 0; j < njobs; ++j) {
         const HostJob &J = jobs[j];
         if (J.n == 0) continue;
-        ASR_HIP(ctx, hipMemcpyAsync(J.out, H.out_dev + (size_t)out_row * 32, (size_t)J.n * 32 * sizeof(float),
-                                    hipMemcpyDeviceToHost, ctx->estream[J.view - 1]));
+        if (J.out)
+            ASR_HIP(ctx, hipMemcpyAsync(J.out, H.out_dev + (size_t)out_row * 32, (size_t)J.n * 32 * sizeof(float),
+                                        hipMemcpyDeviceToHost, ctx->estream[J.view - 1]));
         out_row += J.n;
     }
+    if (loss) ASR_HIP(ctx, hipMemcpyAsync(loss, ctx->valid_ws, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     ASR_HIP(ctx, hipStreamSynchronize(H.h2d));
     return sync_all(ctx);
 }

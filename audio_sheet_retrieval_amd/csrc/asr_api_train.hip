@@ -1453,24 +1453,51 @@ int asr_valid_loss(asr_ctx *ctx, const float *x1, const float *x2, int64_t n, fl
     return asr_valid_loss_in(ctx, x1, ASR_IN_F32_PREPARED, x2, n, loss);
 }
 int asr_valid_loss_in(asr_ctx *ctx, const void *x1, int in_mode, const float *x2, int64_t n, float *loss) {
+    return asr_valid_output_in(ctx, x1, in_mode, x2, n, loss, nullptr, nullptr);
+}
+
+// One deterministic forward of both towers (the host pipeline's single pass over the two views), the loss of the
+// latents where they lie in the pipeline's output buffer, one copy-back and one host synchronisation.
+int asr_valid_output_in(asr_ctx *ctx, const void *x1, int in_mode, const float *x2, int64_t n, float *loss, float *lv1,
+                        float *lv2) {
     if (!ctx || !loss) return ASR_ERR_INVALID;
     if (n < 2) return fail(ctx, ASR_ERR_INVALID, "valid_loss: needs at least 2 pairs");
-    std::vector<float> lv1((size_t)n * 32), lv2((size_t)n * 32);
-    int rc = asr_embed_view1(ctx, x1, in_mode, n, ASR_OUT_LATENT, lv1.data());
+    const HostJob jobs[2] = {{1, x1, in_mode, n, ASR_OUT_LATENT, lv1}, {2, x2, ASR_IN_F32_PREPARED, n, ASR_OUT_LATENT, lv2}};
+    return embed_host(ctx, jobs, 2, loss);
+}
+
+// The towers on the caller's device buffers (asr_embed_view*_dev), then the loss on the main stream after both of them:
+// that join is what orders any later main-stream work - the next asr_gather_windows_dev into the same windows, a
+// download - behind this batch.  Latents the caller does not want go to the context's workspace.
+int asr_valid_output_in_dev(asr_ctx *ctx, const void *x1_dev, int in_mode, const float *x2_dev, int64_t n,
+                            float *loss_dev, float *lv1_dev, float *lv2_dev) {
+    if (!ctx || !loss_dev || !x1_dev || !x2_dev) return ASR_ERR_INVALID;
+    if (n < 2) return fail(ctx, ASR_ERR_INVALID, "valid_output_dev: needs at least 2 pairs");
+    if (!ctx->params_set) return fail(ctx, ASR_ERR_STATE, "valid_output_dev: asr_set_params has not been called");
+    if (!lv1_dev || !lv2_dev) {
+        const size_t need = 64 + (size_t)n * 64;
+        if (ctx->valid_ws_floats < need) {
+            int rcs = sync_all(ctx);      // a queued call may still read the workspace
+            if (rcs != ASR_OK) return rcs;
+            if (ctx->valid_ws) { ASR_HIP(ctx, hipFree(ctx->valid_ws)); ctx->valid_ws = nullptr; ctx->valid_ws_floats = 0; }
+            ASR_HIP(ctx, hipMalloc((void **)&ctx->valid_ws, need * sizeof(float)));
+            ctx->valid_ws_floats = need;
+        }
+        if (!lv1_dev) lv1_dev = ctx->valid_ws + 64;
+        if (!lv2_dev) lv2_dev = ctx->valid_ws + 64 + (size_t)n * 32;
+    }
+    int rc = embed_common(ctx, 1, x1_dev, in_mode, n, ASR_OUT_LATENT, lv1_dev, true);
     if (rc != ASR_OK) return rc;
-    rc = asr_embed_view2(ctx, x2, n, ASR_OUT_LATENT, lv2.data());
+    rc = embed_common(ctx, 2, x2_dev, ASR_IN_F32_PREPARED, n, ASR_OUT_LATENT, lv2_dev, true);
     if (rc != ASR_OK) return rc;
-    float *d = nullptr;
-    ASR_HIP(ctx, hipMalloc((void **)&d, ((size_t)n * 64 + 1) * sizeof(float)));
-    hipError_t e = hipMemcpyAsync(d, lv1.data(), (size_t)n * 32 * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d + (size_t)n * 32, lv2.data(), (size_t)n * 32 * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = asr::launch_rank_loss(ctx->stream, d, d + (size_t)n * 32, (int)n, ctx->cfg.gamma, d + (size_t)n * 64,
-                                                   ctx->loss_weight, ctx->loss_symmetric);
-    if (e == hipSuccess) e = hipMemcpyAsync(loss, d + (size_t)n * 64, sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "valid_loss: %s", hipGetErrorString(e));
-    return ASR_OK;
+    rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    {
+        ProfScope ps(ctx, "valid_loss", 0, 2.0 * 32 * (double)n * n * (ctx->loss_symmetric ? 2 : 1), 256.0 * n);
+        ASR_HIP(ctx, asr::launch_rank_loss(ctx->stream, lv1_dev, lv2_dev, (int)n, ctx->cfg.gamma, loss_dev,
+                                           ctx->loss_weight, ctx->loss_symmetric));
+    }
+    return mark_main(ctx);
 }
 
 int asr_opt_state_size(asr_ctx *ctx, int64_t *n) {

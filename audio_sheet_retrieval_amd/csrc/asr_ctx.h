@@ -262,6 +262,10 @@ struct asr_ctx {
     size_t unit_ws_floats = 0;                // pool, rebuilt per call (what an asr_db keeps)
     void *rank_io = nullptr;                  // asr_rank (host buffers): embeddings in, ranks / d* / ties out
     size_t rank_io_bytes = 0;
+    // asr_valid_output*: [0] the loss slot of the host entry point; from float 64 on, the latents of the device entry
+    // point when the caller passes no buffer for them (2 x n x 32)
+    float *valid_ws = nullptr;
+    size_t valid_ws_floats = 0;
     // asr_eval_batches: double-buffered host-to-host pipeline (inputs, embeddings, ranking outputs; copy streams)
     struct Pipe {
         hipStream_t h2d = nullptr, d2h = nullptr;
@@ -348,6 +352,16 @@ struct ProfScope {
 int join_views(asr_ctx *ctx);
 int mark_main(asr_ctx *ctx);
 int sync_all(asr_ctx *ctx);
+// the towers on caller-owned device memory (asr_embed_view*_dev) / on host arrays through the copy pipeline (asr_embed_*)
+int embed_common(asr_ctx *ctx, int view, const void *x, int in_mode, int64_t n, int out_kind, float *out,
+                 bool on_device);
+// One host-buffer request: n samples of one view at x -> n x 32 floats at out.
+struct HostJob {
+    int view; const void *x; int in_mode; int64_t n; int out_kind; float *out;
+};
+// loss != NULL (asr_valid_output_in): jobs = {view 1, view 2} of the same n pairs, latents; the contrastive loss of the
+// two is computed where they lie on the device and returned with them (a job's out may then be NULL: not copied back)
+int embed_host(asr_ctx *ctx, const HostJob *jobs, int njobs, float *loss = nullptr);
 // float64 row-norm scratch of the two sides of a ranking / top-k call
 int ensure_norms(asr_ctx *ctx, int64_t n1, int64_t n2);
 int rank_check(asr_ctx *ctx, int64_t n1, int64_t ld1, int64_t n2, int64_t ld2, int dim, int64_t query_offset,

@@ -152,6 +152,11 @@ class AudioScoreRetrievalPool(object):
             d2.append(self._audio_desc(i_sheet, i_spec, i_onset))
         return np.asarray(d1, np.float64).reshape(-1, 9), np.asarray(d2, np.float64).reshape(-1, 9)
 
+    def draw(self, key):
+        """Draw the augmentation random numbers pool[key] would draw, without assembling the batch (an evaluation pass
+        that skips a batch leaves the random stream where the reference's loop leaves it)."""
+        self._descriptors(key)
+
     def get_device(self, key, out=None):
         """-> (sheet DeviceBuffer (n,1,160,200) float32 un-normalised, spec DeviceBuffer (n,1,bins,42), n).  `key`: int,
         slice or index array into the (shuffled) entity list.  out=(sheet buffer, spec buffer): caller-owned buffers

@@ -11,7 +11,8 @@ import numpy as np
 
 #: training-function calls by input route since import (tests and tools read it): "prepared" = host-prepared float32
 #: (iter_funcs['train'] and friends), "raw" = the un-prepared batch (asr_*_in), "device" = batches assembled on the
-#: device by AudioScoreRetrievalPool.get_device (asr_train_step_in_dev)
+#: device by AudioScoreRetrievalPool.get_device (asr_train_step_in_dev); the evaluation passes of train() on such
+#: batches (asr_valid_output_in_dev): "valid_device" = validation batches, "eval_device" = train-metric batches embedded
 ROUTE_CALLS = collections.Counter()
 
 
@@ -243,6 +244,28 @@ class IterFunctions(dict):
     def compute_output_raw(self, X1, X2):
         return list(self.engine.embed_both(X1, X2, prepared=False))
 
+    def valid_output(self, X1, X2):
+        """iter_funcs['valid'](X1, X2)[0] and iter_funcs['compute_output'](X1, X2) from one forward of both towers
+        (asr_valid_output_in) -> (loss, v1 latent, v2 latent), bit for bit what the two calls return"""
+        loss, a, b = self.engine.valid_output(X1, X2, prepared=True)
+        return np.float32(loss), a, b
+
+    def valid_output_raw(self, X1, X2):
+        """valid_output on the un-prepared batch (counted like valid_raw)"""
+        ROUTE_CALLS["raw"] += 1
+        loss, a, b = self.engine.valid_output(X1, X2, prepared=False)
+        return np.float32(loss), a, b
+
+    def valid_output_dev(self, b1, b2, n, shape1, shape2, loss_ptr, lv1_ptr=None, lv2_ptr=None):
+        """valid_output on a batch already on the device (AudioScoreRetrievalPool.get_device, as train_dev takes it):
+        the loss goes to the float slot at loss_ptr, the latents to (n,32) device rows at lv1_ptr / lv2_ptr (None: not
+        kept).  Enqueued only: the results exist once a download (or engine.sync) returns.  One device only."""
+        from .. import _lib
+        if self.engine.comm_info()[1] > 1:
+            raise ValueError("valid_output_dev: device-pool batches are not sharded over ranks")
+        self._sizes((n,) + tuple(shape1), (n,) + tuple(shape2), raw=True)
+        self.engine.valid_output_dev(b1.ptr, _lib.IN_F32_RAW, b2.ptr, n, loss_ptr, lv1_ptr, lv2_ptr)
+
 
 def create_iter_functions(layers, objectives, compute_updates, learning_rate, l_2, l_1, init_cca=False):
     """Create functions for training, validation and testing (:85-167).  `objectives`, `compute_updates`,
@@ -302,22 +325,86 @@ def _device_pool(iter_funcs, pool):
         iter_funcs.engine.comm_info()[1] == 1
 
 
+def _fused(iter_funcs):
+    """iter_funcs['valid'] and iter_funcs['compute_output'] are still the instance's own methods: one library call
+    (asr_valid_output_in*) can serve both on a batch.  A caller who replaced either gets the reference's two calls."""
+    def own(name, method):
+        f = iter_funcs.get(name)
+        return getattr(f, "__self__", None) is iter_funcs and getattr(f, "__func__", None) is method
+    return isinstance(iter_funcs, IterFunctions) and own("valid", IterFunctions._valid) and \
+        own("compute_output", IterFunctions._compute_output)
+
+
 # --------------------------------------------------------------------------
 # epoch generator and fit (:185-315, :318-543)
 # --------------------------------------------------------------------------
 def _collect_outputs(iter_funcs, generator, n_needed, with_loss=False, raw=False):
     """Run `compute_output` (and optionally `valid`) over a batch generator, keeping the first n_needed rows.
-    raw: the generator yields un-prepared batches (batch iterator's raw()), embedded with prepared=False."""
+    raw: the generator yields un-prepared batches (batch iterator's raw()), embedded with prepared=False.
+    A batch that needs both goes through one forward (valid_output) when the two callables are the instance's own."""
     V1, V2, losses = None, None, []
     valid = iter_funcs.valid_raw if raw else iter_funcs["valid"]
     compute_output = iter_funcs.compute_output_raw if raw else iter_funcs["compute_output"]
+    both = (iter_funcs.valid_output_raw if raw else iter_funcs.valid_output) if _fused(iter_funcs) else None
     for batch in generator:
-        if with_loss:
-            losses.append(valid(*batch)[0])
-        if V1 is None or V1.shape[0] < n_needed:
-            a, b = compute_output(*batch)
+        need_out = V1 is None or V1.shape[0] < n_needed
+        if with_loss and need_out and both is not None:
+            loss, a, b = both(*batch)
+            losses.append(loss)
+        else:
+            if with_loss:
+                losses.append(valid(*batch)[0])
+            if need_out:
+                a, b = compute_output(*batch)
+        if need_out:
             V1 = a if V1 is None else np.vstack([V1, a])
             V2 = b if V2 is None else np.vstack([V2, b])
+    return V1, V2, losses
+
+
+def _collect_outputs_device(iter_funcs, pool, batch_iter, n_needed, with_loss, route):
+    """_collect_outputs on a device pool (AudioScoreRetrievalPool on this engine, the model's own prepare, fused
+    callables): the pass walks batch_iter.keys() on this thread, assembles every batch it evaluates on the device
+    (get_device into two window buffers reused for the pass) and queues it (asr_valid_output_in_dev; the library
+    orders the next gather behind it).  Latents go into one device buffer per pass, losses into one float slot per
+    batch; one download at the end.  A batch whose rows are not needed and whose loss is not asked for only draws its
+    augmentation numbers (pool.draw), so the random stream is the one pool[key] would leave.  Same rows, losses
+    (float32, batch order) and latents as _collect_outputs on the downloaded batches."""
+    eng = iter_funcs.engine
+    bs = batch_iter.batch_size
+    n_batches = -(-batch_iter.k_samples // bs)
+    # whole batches are kept until n_needed rows are in (at least one); a short batch can add one more
+    cap = min(n_batches, max(1, -(-n_needed // bs)) + 1) * bs
+    n_slots = n_batches if with_loss else cap // bs
+    shape1, shape2 = [1] + list(pool.sheet_dim), [1] + list(pool.spec_dim)
+    ws = eng.alloc(4 * (2 * cap * 32 + n_slots))
+    bufs = (eng.alloc(bs * int(np.prod(pool.sheet_dim)) * 4), eng.alloc(bs * int(np.prod(pool.spec_dim)) * 4))
+    rows = slot = 0
+    try:
+        for i, idx in enumerate(batch_iter.keys()):
+            need_out = i == 0 or rows < n_needed
+            if not (need_out or with_loss):
+                pool.draw(idx)
+                continue
+            b1, b2, n = pool.get_device(idx, out=bufs)
+            if slot >= n_slots or (need_out and rows + n > cap):
+                raise RuntimeError("device evaluation pass: batch %d (%d rows) outside the %d-row / %d-slot buffer"
+                                   % (i, n, cap, n_slots))
+            lv = (ws.offset(4 * rows * 32), ws.offset(4 * (cap + rows) * 32)) if need_out else (None, None)
+            iter_funcs.valid_output_dev(b1, b2, n, shape1, shape2, ws.offset(4 * (2 * cap * 32 + slot)), *lv)
+            ROUTE_CALLS[route] += 1
+            slot += 1
+            if need_out:
+                rows += n
+        out = ws.download((2 * cap * 32 + n_slots,), np.float32)
+    finally:
+        for b in (ws,) + bufs:
+            b.free()
+    if not slot:
+        return None, None, []
+    V1 = out[:rows * 32].reshape(rows, 32).copy()
+    V2 = out[cap * 32:(cap + rows) * 32].reshape(rows, 32).copy()
+    losses = list(out[2 * cap * 32:2 * cap * 32 + slot]) if with_loss else []
     return V1, V2, losses
 
 
@@ -383,10 +470,15 @@ def train(iter_funcs, dataset, train_batch_iter, valid_batch_iter, fit_cca):
         it_copy = copy.copy(train_batch_iter)
         it_copy.epoch_counter = 0
         it_copy = it_copy(dataset["train"])
-        batches = it_copy.raw() if raw else it_copy
-        # (a device pool's batches are drawn on this thread, as in the update loop: its context is the engine's)
-        V1_tr, V2_tr, _ = _collect_outputs(iter_funcs, batches if bufs is not None else
-                                           threaded_generator_from_iterator(batches), n_valid_cca, raw=raw)
+        fused = _fused(iter_funcs)
+        if bufs is not None and fused:
+            V1_tr, V2_tr, _ = _collect_outputs_device(iter_funcs, dataset["train"], it_copy, n_valid_cca, False,
+                                                      "eval_device")
+        else:
+            batches = it_copy.raw() if raw else it_copy
+            # (a device pool's batches are drawn on this thread, as in the update loop: its context is the engine's)
+            V1_tr, V2_tr, _ = _collect_outputs(iter_funcs, batches if bufs is not None else
+                                               threaded_generator_from_iterator(batches), n_valid_cca, raw=raw)
         cca = None
         if fit_cca:
             cca = CCA(method="svd", engine=iter_funcs.engine)
@@ -399,9 +491,15 @@ def train(iter_funcs, dataset, train_batch_iter, valid_batch_iter, fit_cca):
         print(" ")
         raw_va = _raw_route(iter_funcs, valid_batch_iter)
         va_iter = valid_batch_iter(dataset["valid"])
-        V1_va, V2_va, va_losses = _collect_outputs(
-            iter_funcs, threaded_generator_from_iterator(va_iter.raw() if raw_va else va_iter), n_valid_cca, True,
-            raw=raw_va)
+        if raw_va and fused and _device_pool(iter_funcs, dataset["valid"]):
+            V1_va, V2_va, va_losses = _collect_outputs_device(iter_funcs, dataset["valid"], va_iter, n_valid_cca, True,
+                                                              "valid_device")
+        else:
+            batches = va_iter.raw() if raw_va else va_iter
+            # (a pool on this engine is drawn on this thread: the context is single-threaded)
+            if not _device_pool(iter_funcs, dataset["valid"]):
+                batches = threaded_generator_from_iterator(batches)
+            V1_va, V2_va, va_losses = _collect_outputs(iter_funcs, batches, n_valid_cca, True, raw=raw_va)
         if cca is not None:
             V1_va, V2_va = cca.transform_V1(V1_va), cca.transform_V2(V2_va)
         _, med_va, dist_va, hits_va, map_va = eval_retrieval(V1_va, V2_va, engine=iter_funcs.engine)

@@ -450,6 +450,27 @@ int asr_burn_in_in(asr_ctx *ctx, const void *x1, int in_mode, const float *x2, i
 int asr_compute_gradients_in(asr_ctx *ctx, const void *x1, int in_mode, const float *x2, int64_t batch,
                              float *grads, int64_t n, float *loss);
 int asr_valid_loss_in(asr_ctx *ctx, const void *x1, int in_mode, const float *x2, int64_t n, float *loss);
+/* iter_funcs['valid'] + iter_funcs['compute_output'] on the same batch (utils/train_dcca_pool.py:155,158), which train()
+ * calls one after the other on every evaluation batch (:277-285; _collect_outputs here): ONE deterministic-mode forward of
+ * both towers, the contrastive loss of the objective set by asr_set_objective on the latents where they lie on the
+ * device, and both latents.  *loss equals asr_valid_loss_in's bit for bit, lv1 / lv2 (n,32) equal asr_embed_both's
+ * (ASR_OUT_LATENT) bit for bit.  in_mode as asr_valid_loss_in; n >= 2.  Eval mode: no BatchNorm, CCALayer or Adam
+ * state moves; works with a live training state, after asr_train_end and without one.
+ *   asr_valid_output_in: host buffers; lv1 / lv2 may be NULL (asr_valid_loss and asr_valid_loss_in are this call with
+ *     both NULL).  One pass of the host pipeline over the two views, the loss kernel on the pipeline's output buffer,
+ *     the copies back, one host synchronisation; no allocation per call.
+ *   asr_valid_output_in_dev: device pointers (e.g. the window buffers of asr_gather_windows_dev, ASR_IN_F32_RAW);
+ *     loss_dev is ONE float slot (a validation loop passes losses_dev + i), lv1_dev / lv2_dev (n,32) may be NULL (the
+ *     context's workspace then holds them).  Returns after enqueueing, without a host synchronisation.  Ordering,
+ *     by events inside the context - the caller needs no double buffering: the loss runs on the context's main
+ *     stream after both towers, so every later call of the context that touches the main stream or waits for it
+ *     (asr_gather_windows_dev into the same windows, asr_dev_download, asr_sync, asr_rank_dev, the next *_dev embed or
+ *     training step) runs after the towers have read x1_dev / x2_dev and sees loss_dev and lv*_dev complete.  Work the
+ *     caller enqueues on its own streams must wait for asr_sync first. */
+int asr_valid_output_in(asr_ctx *ctx, const void *x1, int in_mode, const float *x2, int64_t n, float *loss,
+                        float *lv1, float *lv2);
+int asr_valid_output_in_dev(asr_ctx *ctx, const void *x1_dev, int in_mode, const float *x2_dev, int64_t n,
+                            float *loss_dev, float *lv1_dev, float *lv2_dev);
 int asr_opt_state_size(asr_ctx *ctx, int64_t *n);
 int asr_get_opt_state(asr_ctx *ctx, float *m, float *v, int64_t n, int32_t *t);
 int asr_set_opt_state(asr_ctx *ctx, const float *m, const float *v, int64_t n, int32_t t);
