@@ -38,7 +38,7 @@ EXPORTS = [
     "asr_valid_loss_in", "asr_valid_output_in", "asr_valid_output_in_dev",
     "asr_comm_unique_id", "asr_comm_init", "asr_comm_init_custom", "asr_comm_destroy", "asr_comm_info", "asr_comm_stats", "asr_comm_timing", "asr_comm_library",
     "asr_comm_allreduce_dev", "asr_comm_allgather_dev",
-    "asr_rank_sharded_dev", "asr_slice_windows_dev", "asr_piece_vote_dev", "asr_gather_windows_dev", "asr_dtw_dev", "asr_spectrogram_dev", "asr_debug_tune_report",
+    "asr_rank_sharded_dev", "asr_slice_windows_dev", "asr_piece_vote_dev", "asr_gather_windows_dev", "asr_dtw_dev", "asr_dtw_batch_dev", "asr_spectrogram_dev", "asr_debug_tune_report",
     "asr_opt_state_size", "asr_get_opt_state", "asr_set_opt_state", "asr_debug_train_tensor", "asr_cca_train_debug",
 ]
 
@@ -185,6 +185,7 @@ def load_library(path=None):
         "asr_gather_windows_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p]),
         "asr_dtw_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                 POINTER(c_int32), POINTER(c_double)]),
+        "asr_dtw_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 7),
         "asr_spectrogram_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_int, c_float, c_float, c_int64, c_int, c_void_p]),
         "asr_debug_tune_report": (c_int, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_float)]),
@@ -428,6 +429,60 @@ class Engine(object):
             da.free()
             db.free()
         return float(md.value), dists, pa[:ln.value].copy(), pb[:ln.value].copy()
+
+    def dtw_batch(self, pairs, want_dists=False, first_of=None, want_path=True):
+        """Engine.dtw for a list of (a, b) code-sequence pairs in one library call (asr_dtw_batch_dev) -> one
+        (min_dist, dists or None, path_a, path_b) per pair, each bit-identical with dtw(a, b).  first_of "a" / "b"
+        (or one such value per pair) appends the first-entry projection of that side: per row of a the column of the
+        first path entry in it ("a"), per row of b the row of a of the first path entry at it ("b").  want_path=False
+        computes only the distances (min_dist / paths are None)."""
+        pairs = [(_f32c(a), _f32c(b)) for a, b in pairs]
+        if not pairs:
+            return []
+        dim = pairs[0][0].shape[1] if pairs[0][0].ndim == 2 else -1
+        for a, b in pairs:
+            if a.ndim != 2 or b.ndim != 2 or a.shape[1] != dim or b.shape[1] != dim:
+                raise ValueError("dtw_batch expects (n_a,d) and (n_b,d) arrays of one d")
+        sides = [first_of] * len(pairs) if first_of is None or isinstance(first_of, str) else list(first_of)
+        if len(sides) != len(pairs) or any(s not in (None, "a", "b") for s in sides):
+            raise ValueError("first_of must be None, 'a', 'b' or one of those per pair")
+        n_a = np.array([a.shape[0] for a, _ in pairs], np.int64)
+        n_b = np.array([b.shape[0] for _, b in pairs], np.int64)
+        cat_a, cat_b = np.concatenate([a for a, _ in pairs]), np.concatenate([b for _, b in pairs])
+        cells, paths = n_a * n_b, n_a + n_b
+        want_a, want_b = "a" in sides, "b" in sides
+        md = np.empty(len(pairs), np.float64) if want_path else None
+        ln = np.empty(len(pairs), np.int32) if want_path else None
+        pa = np.empty(int(paths.sum()), np.int32) if want_path else None
+        pb = np.empty(int(paths.sum()), np.int32) if want_path else None
+        dists = np.empty(int(cells.sum()), np.float64) if want_dists else None
+        fa = np.empty(int(n_a.sum()), np.int32) if want_a else None
+        fb = np.empty(int(n_b.sum()), np.int32) if want_b else None
+        ptr = lambda x: None if x is None else x.ctypes.data
+        da = self.alloc(max(cat_a.nbytes, 4)).upload(cat_a)
+        db = self.alloc(max(cat_b.nbytes, 4)).upload(cat_b)
+        try:
+            self._check(self.lib.asr_dtw_batch_dev(self.ctx, da.ptr, db.ptr, n_a.ctypes.data, n_b.ctypes.data,
+                                                   len(pairs), dim, ptr(md), ptr(ln), ptr(pa), ptr(pb), ptr(dists),
+                                                   ptr(fa), ptr(fb)))
+        finally:
+            da.free()
+            db.free()
+        out = []
+        o_cell = o_path = o_a = o_b = 0
+        for p, side in enumerate(sides):
+            R, C = int(n_a[p]), int(n_b[p])
+            d = dists[o_cell:o_cell + R * C].reshape(R, C) if want_dists else None
+            if want_path:
+                L = int(ln[p])
+                item = (float(md[p]), d, pa[o_path:o_path + L].copy(), pb[o_path:o_path + L].copy())
+            else:
+                item = (None, d, None, None)
+            if first_of is not None:
+                item += ((fa[o_a:o_a + R].copy() if side == "a" else fb[o_b:o_b + C].copy()) if side else None,)
+            out.append(item)
+            o_cell, o_path, o_a, o_b = o_cell + R * C, o_path + R + C, o_a + R, o_b + C
+        return out
 
     def spectrogram_dev(self, samples_ptr, n_samples, frame_size, hop, window, fb_start, fb_len, fb_weights, n_frames,
                         out_ptr, mul=1.0, add=1.0, transposed=True):

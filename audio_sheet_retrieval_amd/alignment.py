@@ -4,6 +4,8 @@ Mirror of audio_sheet_retrieval/utils/alignment.py:112-186 (align_baseline, alig
 estimate_alignment_error) with utils/dtw_by_dist.py:dtw_by_dist behind it.  The cosine distance matrix, the accumulated
 cost (anti-diagonal wavefront) and the traceback run in the library (asr_dtw_dev, float64, bit-exact with the
 reference's NumPy arithmetic); the O(n) path post-processing and the interpolation stay on the host as in the reference.
+The *_batch / compute_alignments variants align many pieces in one library call (asr_dtw_batch_dev: all pairs in one
+launch per stage, the first-entry projection of align_pydtw computed on the device) with identical results.
 """
 from __future__ import print_function
 
@@ -20,6 +22,32 @@ def dtw_by_dist_codes(engine, img_codes, spec_codes):
         return md, d.T, (p, q)
     md, d, p, q = engine.dtw(img_codes, spec_codes)
     return md, d, (q, p)
+
+
+def dtw_by_dist_codes_batch(engine, pairs, want_dists=True, first=False, path=True):
+    """dtw_by_dist_codes for a list of (img_codes, spec_codes) pairs in one call -> [(min_dist, dists, path)], with the
+    same per-pair transposition.  first=True appends, per pair, the sheet index of the first path entry of every audio
+    excerpt (align_pydtw's projection: path[1][first_entries(path[0], n_spec)]).  path=False: distances only
+    (min_dist and path None)."""
+    jobs, flipped = [], []
+    for img, spec in pairs:
+        wide = len(spec) > len(img)                      # rows = spec codes (transposed)
+        jobs.append((spec, img) if wide else (img, spec))
+        flipped.append(wide)
+    res = engine.dtw_batch(jobs, want_dists=want_dists, want_path=path,
+                           first_of=(["a" if w else "b" for w in flipped] if first else None))
+    out = []
+    for wide, r in zip(flipped, res):
+        md, d, p, q = r[:4]
+        item = (md, (d.T if wide else d) if d is not None else None, None if p is None else (p, q) if wide else (q, p))
+        out.append(item + (r[4],) if first else item)
+    return out
+
+
+def first_entries(path0, n):
+    """index of the first entry of every value 0..n-1 in a non-decreasing path row that visits each of them - the
+    `np.flatnonzero(path[0] == col)[0]` loop of align_pydtw (utils/alignment.py:131-138) in O(len + n)"""
+    return np.searchsorted(np.asarray(path0), np.arange(n), side="left")
 
 
 def align_baseline(dists):
@@ -44,6 +72,27 @@ def compute_alignment(engine, img_codes, spec_codes, sheet_idxs, spec_idxs, alig
         positions, dists = align_pydtw(engine, img_codes, spec_codes)
     else:
         raise ValueError("align_by must be 'baseline' or 'pydtw'")
+    return _interpolate(positions, dists, sheet_idxs, spec_idxs)
+
+
+def compute_alignments(engine, pieces, align_by):
+    """compute_alignment for a list of pieces (img_codes, spec_codes, sheet_idxs, spec_idxs) with one library call for
+    all of them -> [(mapping, details)], identical to calling compute_alignment per piece.  'baseline' computes only the
+    distance matrices."""
+    if align_by not in ("baseline", "pydtw"):
+        raise ValueError("align_by must be 'baseline' or 'pydtw'")
+    pydtw = align_by == "pydtw"
+    res = dtw_by_dist_codes_batch(engine, [(img, spec) for img, spec, _, _ in pieces], first=pydtw, path=pydtw)
+    out = []
+    for (_, _, sheet_idxs, spec_idxs), r in zip(pieces, res):
+        dists = r[1]
+        positions = r[3] if pydtw else align_baseline(dists)
+        out.append(_interpolate(positions, dists, sheet_idxs, spec_idxs))
+    return out
+
+
+def _interpolate(positions, dists, sheet_idxs, spec_idxs):
+    """:157-177 - rounded sheet positions -> coordinates -> interpolated frame -> x mapping"""
     positions = np.round(positions).astype(np.int64)
     coords = sheet_idxs[positions]
     # excerpts whose frame index did not advance carry no new information for the interpolation (:163)

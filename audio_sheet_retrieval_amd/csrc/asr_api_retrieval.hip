@@ -3,6 +3,45 @@
 // the reference interfaces each entry point replaces).  Context and shared helpers: asr_ctx.h.
 #include "asr_ctx.h"
 
+// workspace of one chunk of asr_dtw_batch_dev: byte offsets into ctx->dtw_ws (256-byte aligned sections)
+namespace {
+struct DtwChunk {
+    int p0 = 0, n = 0;                                    // pairs [p0, p0 + n)
+    int64_t cells = 0, diags = 0, paths = 0, rows_a = 0, rows_b = 0, ring = 0;
+    int lds_slots = 0;
+    bool any_ring = false;
+    size_t o_pairs = 0, o_cost = 0, o_rm = 0, o_dir = 0, o_ring = 0, o_md = 0, o_len = 0, o_pa = 0, o_pb = 0, o_fa = 0,
+           o_fb = 0, bytes = 0;
+};
+
+size_t dtw_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// section layout of a chunk; `wave`: accumulated cost + traceback are needed (not only the distances)
+void dtw_layout(DtwChunk &c, bool wave, bool rm, bool fa, bool fb) {
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += dtw_align(bytes); return at; };
+    c.o_pairs = take((size_t)c.n * sizeof(asr::DtwPair));
+    c.o_cost = take((size_t)c.cells * sizeof(double));
+    c.o_rm = rm ? take((size_t)c.cells * sizeof(double)) : 0;
+    if (wave) {
+        c.o_dir = take((size_t)c.cells);
+        c.o_ring = take((size_t)c.ring * sizeof(double));
+        c.o_md = take((size_t)c.n * sizeof(double));
+        c.o_len = take((size_t)c.n * sizeof(int32_t));
+        c.o_pa = take((size_t)c.paths * sizeof(int32_t));
+        c.o_pb = take((size_t)c.paths * sizeof(int32_t));
+        c.o_fa = fa ? take((size_t)c.rows_a * sizeof(int32_t)) : 0;
+        c.o_fb = fb ? take((size_t)c.rows_b * sizeof(int32_t)) : 0;
+    }
+    c.bytes = o;
+}
+
+int64_t dtw_env(const char *name, int64_t dflt) {
+    const char *v = getenv(name);
+    return v && *v ? atoll(v) : dflt;
+}
+}  // namespace
+
 extern "C" {
 
 int asr_rank_dev(asr_ctx *ctx, const float *lv1, int64_t n1, int64_t ld1, const float *lv2, int64_t n2, int64_t ld2,
@@ -497,6 +536,134 @@ int asr_dtw_dev(asr_ctx *ctx, const float *a_dev, int64_t n_a, const float *b_de
     if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "dtw: %s", hipGetErrorString(e));
     *path_len = len;
     if (min_dist) *min_dist = md;
+    return mark_main(ctx);
+}
+
+int asr_dtw_batch_dev(asr_ctx *ctx, const float *a_dev, const float *b_dev, const int64_t *n_a, const int64_t *n_b,
+                      int n_pairs, int dim, double *min_dist, int32_t *path_len, int32_t *path_a, int32_t *path_b,
+                      double *dists, int32_t *first_a, int32_t *first_b) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_pairs < 0 || dim < 1 || dim > 64)
+        return fail(ctx, ASR_ERR_INVALID, "dtw_batch: bad sizes n_pairs=%d dim=%d (1..64)", n_pairs, dim);
+    if (n_pairs == 0) return ASR_OK;
+    if (!a_dev || !b_dev || !n_a || !n_b) return fail(ctx, ASR_ERR_INVALID, "dtw_batch: NULL argument");
+    if ((path_a != nullptr) != (path_b != nullptr) || (path_a && !path_len))
+        return fail(ctx, ASR_ERR_INVALID, "dtw_batch: path_a, path_b and path_len go together");
+    int64_t tot_a = 0, tot_b = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        if (n_a[p] < 1 || n_b[p] < 1 || n_a[p] > 100000 || n_b[p] > 100000 || (n_a[p] + 1) * (n_b[p] + 1) > (1ll << 31))
+            return fail(ctx, ASR_ERR_INVALID, "dtw_batch: pair %d has bad sizes n_a=%lld n_b=%lld", p, (long long)n_a[p],
+                        (long long)n_b[p]);
+        tot_a += n_a[p];
+        tot_b += n_b[p];
+    }
+    const bool wave = min_dist || path_len || path_a || first_a || first_b;
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    int rc = ensure_norms(ctx, tot_a, tot_b);
+    if (rc != ASR_OK) return rc;
+    rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    // ASR_DTW_LDS_CAP=<slots>: pairs with min(n_a, n_b) + 1 above it take the global-ring wavefront (a debug switch
+    // that exercises the large-pair path at small sizes); ASR_DTW_BUDGET_MB: device workspace per chunk of pairs
+    const int lds_cap = (int)std::min<int64_t>(asr::dtw_batch_lds_slots(ctx->cfg.device), dtw_env("ASR_DTW_LDS_CAP", 1 << 30));
+    const size_t budget = (size_t)std::max<int64_t>(dtw_env("ASR_DTW_BUDGET_MB", 4096), 1) << 20;
+
+    // chunks of consecutive pairs whose workspace fits the budget (a pair larger than it gets a chunk of its own)
+    std::vector<DtwChunk> chunks;
+    DtwChunk c;
+    for (int p = 0; p < n_pairs; ++p) {
+        DtwChunk t = c;
+        const int64_t R = n_a[p], C = n_b[p], S = std::min(R, C) + 1;
+        t.n += 1;
+        t.cells += R * C;
+        t.diags += R + C - 1;
+        t.paths += R + C;
+        t.rows_a += R;
+        t.rows_b += C;
+        if (S > lds_cap) { t.ring += 3 * S; t.any_ring = true; }
+        else t.lds_slots = std::max<int>(t.lds_slots, (int)S);
+        dtw_layout(t, wave, dists != nullptr, first_a != nullptr, first_b != nullptr);
+        if (t.bytes > budget && c.n > 0) {
+            chunks.push_back(c);
+            DtwChunk f;
+            f.p0 = p;
+            c = f;
+            --p;
+            continue;
+        }
+        c = t;
+    }
+    chunks.push_back(c);
+    size_t need = 0;
+    for (const DtwChunk &k : chunks) need = std::max(need, k.bytes);
+    if (need > ctx->dtw_ws_bytes) {
+        rc = sync_all(ctx);
+        if (rc != ASR_OK) return rc;
+        if (ctx->dtw_ws) ASR_HIP(ctx, hipFree(ctx->dtw_ws));
+        ctx->dtw_ws = nullptr; ctx->dtw_ws_bytes = 0;
+        ASR_HIP(ctx, hipMalloc(&ctx->dtw_ws, need));
+        ctx->dtw_ws_bytes = need;
+    }
+
+    int64_t tot_cells = 0;
+    for (const DtwChunk &k : chunks) tot_cells += k.cells;
+    ProfScope ps(ctx, "dtw_batch", 0, 2.0 * dim * (double)tot_cells, (wave ? 17.0 : 8.0) * (double)tot_cells);
+    ASR_HIP(ctx, asr::launch_row_norms(ctx->stream, a_dev, tot_a, dim, dim, ctx->norm1));
+    ASR_HIP(ctx, asr::launch_row_norms(ctx->stream, b_dev, tot_b, dim, dim, ctx->norm2));
+    char *ws = (char *)ctx->dtw_ws;
+    int64_t row_a = 0, row_b = 0, host_cell = 0, host_path = 0;   // global offsets of the chunk's first pair
+    std::vector<asr::DtwPair> desc;
+    for (const DtwChunk &k : chunks) {
+        desc.assign(k.n, asr::DtwPair());
+        int64_t cell = 0, diag = 0, path = 0, ring = 0, ra = 0, rb = 0;
+        for (int q = 0; q < k.n; ++q) {
+            const int p = k.p0 + q;
+            asr::DtwPair &P = desc[q];
+            P.R = (int32_t)n_a[p]; P.C = (int32_t)n_b[p];
+            P.a_row = row_a + ra; P.b_row = row_b + rb;
+            P.cell = cell; P.diag = diag; P.rm = dists ? cell : -1; P.path = path;
+            P.fa = ra; P.fb = rb;
+            const int64_t S = std::min(n_a[p], n_b[p]) + 1;
+            P.ring = S > lds_cap ? ring : -1;
+            if (S > lds_cap) ring += 3 * S;
+            cell += n_a[p] * n_b[p]; diag += n_a[p] + n_b[p] - 1; path += n_a[p] + n_b[p]; ra += n_a[p]; rb += n_b[p];
+        }
+        asr::DtwPair *d_pairs = (asr::DtwPair *)(ws + k.o_pairs);
+        double *cost = (double *)(ws + k.o_cost), *rm = dists ? (double *)(ws + k.o_rm) : nullptr;
+        ASR_HIP(ctx, hipMemcpyAsync(d_pairs, desc.data(), desc.size() * sizeof(asr::DtwPair), hipMemcpyHostToDevice,
+                                    ctx->stream));
+        ASR_HIP(ctx, asr::launch_dtw_batch_dist(ctx->stream, d_pairs, k.n, k.diags, a_dev, ctx->norm1, b_dev, ctx->norm2,
+                                                dim, cost, rm));
+        if (wave) {
+            uint8_t *dir = (uint8_t *)(ws + k.o_dir);
+            double *md = (double *)(ws + k.o_md);
+            int32_t *len = (int32_t *)(ws + k.o_len), *pa = (int32_t *)(ws + k.o_pa), *pb = (int32_t *)(ws + k.o_pb);
+            int32_t *fa = first_a ? (int32_t *)(ws + k.o_fa) : nullptr, *fb = first_b ? (int32_t *)(ws + k.o_fb) : nullptr;
+            ASR_HIP(ctx, asr::launch_dtw_batch_wave(ctx->stream, d_pairs, k.n, k.lds_slots, k.any_ring, cost, dir,
+                                                    (double *)(ws + k.o_ring), md));
+            ASR_HIP(ctx, asr::launch_dtw_batch_traceback(ctx->stream, d_pairs, k.n, dir, pa, pb, len, fa, fb));
+            if (min_dist)
+                ASR_HIP(ctx, hipMemcpyAsync(min_dist + k.p0, md, k.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            if (path_len)
+                ASR_HIP(ctx, hipMemcpyAsync(path_len + k.p0, len, k.n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+            if (path_a) {
+                ASR_HIP(ctx, hipMemcpyAsync(path_a + host_path, pa, k.paths * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                            ctx->stream));
+                ASR_HIP(ctx, hipMemcpyAsync(path_b + host_path, pb, k.paths * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                            ctx->stream));
+            }
+            if (first_a)
+                ASR_HIP(ctx, hipMemcpyAsync(first_a + row_a, fa, k.rows_a * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                            ctx->stream));
+            if (first_b)
+                ASR_HIP(ctx, hipMemcpyAsync(first_b + row_b, fb, k.rows_b * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                            ctx->stream));
+        }
+        if (dists)
+            ASR_HIP(ctx, hipMemcpyAsync(dists + host_cell, rm, k.cells * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        ASR_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the next chunk reuses the workspace; `desc` is rebuilt
+        row_a += k.rows_a; row_b += k.rows_b; host_cell += k.cells; host_path += k.paths;
+    }
     return mark_main(ctx);
 }
 

@@ -193,6 +193,31 @@ hipError_t launch_dtw(hipStream_t s, const float *a, const double *na, int64_t R
                       const double *nb, int64_t C, int64_t ldb, int dim, double *D, double *dist_out, int32_t *path_i,
                       int32_t *path_j, int32_t *path_len, double *min_dist);
 
+// ---- batched alignment DTW (dtw_batch_kernels.hip): every pair of a batch in one launch per stage ----
+// one pair of a chunk; offsets count elements of the chunk's device arrays
+struct DtwPair {
+    int32_t R, C;          // rows (a) / columns (b) of the pair's cost matrix
+    int64_t a_row, b_row;  // first code row of the pair in a / b
+    int64_t cell;          // first cell in the anti-diagonal-major cost / direction arrays (R*C cells per pair)
+    int64_t diag;          // first anti-diagonal in the chunk's numbering (R+C-1 per pair)
+    int64_t rm;            // first element of the row-major distance copy, or -1
+    int64_t path;          // first path entry (capacity R+C)
+    int64_t ring;          // first double of the pair's global ring (3*(min(R,C)+1)), or -1: the ring is in LDS
+    int64_t fa, fb;        // first entry of the pair's first-entry projections (R / C entries)
+};
+// anti-diagonal slots (min(R,C)+1) one workgroup can keep in LDS: 3 buffers of doubles
+int dtw_batch_lds_slots(int device);
+hipError_t launch_dtw_batch_dist(hipStream_t s, const DtwPair *pairs, int n_pairs, int64_t n_diags, const float *a,
+                                 const double *na, const float *b, const double *nb, int dim, double *cost,
+                                 double *rm_out);
+// lds_slots: dynamic LDS of the LDS-ring pairs (0: none); any_ring: some pair has a global ring
+hipError_t launch_dtw_batch_wave(hipStream_t s, const DtwPair *pairs, int n_pairs, int lds_slots, bool any_ring,
+                                 const double *cost, uint8_t *dir, double *ring, double *min_dist);
+// first_a / first_b may be null
+hipError_t launch_dtw_batch_traceback(hipStream_t s, const DtwPair *pairs, int n_pairs, const uint8_t *dir,
+                                      int32_t *path_a, int32_t *path_b, int32_t *path_len, int32_t *first_a,
+                                      int32_t *first_b);
+
 // ---- piece-identification vote (audio_sheet_server.py:213-300) -----------------
 hipError_t launch_slice_windows(hipStream_t s, const float *src, int64_t T, int r0, int win_h, int win_w,
                                 const int32_t *starts_dev, int n, float *out);

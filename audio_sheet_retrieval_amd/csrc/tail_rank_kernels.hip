@@ -8,6 +8,7 @@
 //                 (utils/train_dcca_pool.py:28-82) as exact float64 distances
 //                 and rank-by-counting; bit-exact against oracle/retrieval.py.
 #include "asr_kernels.h"
+#include "dist64.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -89,35 +90,14 @@ hipError_t launch_tail(hipStream_t s, const float *a8, int N, int h, int w, int 
 }
 
 // ---------------------------------------------------------------------------
-// ranking: float64, scipy cdist_cosine operation order (two accumulators:
-// even k / odd k, summed at the end; odd tail element last).  Products of
-// float32 values are exact in float64, so fma vs mul+add cannot differ; the
-// explicit __dadd_rn/__dmul_rn only keep the compiler from re-associating.
+// ranking: float64, scipy cdist_cosine operation order (dot2acc / cos_dist in dist64.h)
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ double dot2acc(const float *__restrict__ u, const float *__restrict__ v, int dim) {
-    double a0 = 0.0, a1 = 0.0;
-    const int m = dim & ~1;
-    for (int k = 0; k < m; k += 2) {
-        a0 = __dadd_rn(a0, __dmul_rn((double)u[k], (double)v[k]));
-        a1 = __dadd_rn(a1, __dmul_rn((double)u[k + 1], (double)v[k + 1]));
-    }
-    double sacc = __dadd_rn(a0, a1);
-    if (dim & 1) sacc = __dadd_rn(sacc, __dmul_rn((double)u[dim - 1], (double)v[dim - 1]));
-    return sacc;
-}
-
 __global__ __launch_bounds__(256) void row_norms_kernel(const float *__restrict__ x, int64_t n, int64_t ld, int dim,
                                                         double *__restrict__ norms) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float *r = x + i * ld;
     norms[i] = __dsqrt_rn(dot2acc(r, r, dim));
-}
-
-__device__ __forceinline__ double cos_dist(double dot, double na, double nb) {
-    double c = __ddiv_rn(dot, __dmul_rn(na, nb));
-    if (fabs(c) > 1.0) c = copysign(1.0, c);
-    return __dsub_rn(1.0, c);
 }
 
 constexpr int RANK_THREADS = 256;

@@ -178,3 +178,63 @@ def synth_params(shapes, seed=1, trained_like=False):
                 a = (u - 0.5) * 0.01 + (np.eye(shp[0]) if j > 4 else 0)
         out.append(np.ascontiguousarray(a, dtype=np.float32))
     return out
+
+
+_STREAM_PIECE = np.uint64(0x5000000000000000)
+_STREAM_PIECE_SHEET = np.uint64(0x6000000000000000)
+_STREAM_PIECE_SPEC = np.uint64(0x7000000000000000)
+PIECE_HEIGHT = 180      # unrolled strip rows; the windows use the central SYSTEM_HEIGHT (r0 = H//2 - 80)
+
+
+def synth_piece(piece_idx, seed=23):
+    """One whole synthetic piece -> (sheet strip (PIECE_HEIGHT, W) float32 0..255, spectrogram (SPEC_BINS, T) float32,
+    o2c (n_notes, 2) int64 of (onset frame, sheet x)): the unrolled score, its performance and the onset -> coordinate
+    map that AudioScoreRetrievalPool takes (utils/data_pools.py:36-59).
+
+    Notes have synth_pairs' geometry: a dark 6x8 blob at (row, x - 4) in the strip, a 3x3 bump of +2.0 at
+    (bin, frame - 1) in the spectrogram, sheet row <-> bin as in synth_pairs, and (w - 8) = 192 px <-> (wf - 3) = 39
+    frames on average.  The time axis follows a monotone piecewise-linear tempo map (a segment every ~400 px, local
+    tempo 0.6x..1.6x), so a straight line (align_by baseline) and the DTW path disagree."""
+    h, hb, r0 = PIECE_HEIGHT, SPEC_BINS, PIECE_HEIGHT // 2 - SYSTEM_HEIGHT // 2
+    head = _draw(seed, _STREAM_PIECE, [piece_idx], 4)[0]
+    n_notes = 32 + int(head[0] % np.uint64(32))
+    draws = _draw(seed, _STREAM_PIECE, [piece_idx], 4 + 3 * n_notes + 64)[0, 4:]
+    gaps = 30 + (draws[:n_notes] % np.uint64(31)).astype(np.int64)            # 30..60 px between notes
+    xs = SHEET_CONTEXT // 2 + 20 + np.cumsum(gaps) - gaps[0]
+    rows = (draws[n_notes:2 * n_notes] % np.uint64(SYSTEM_HEIGHT - 6)).astype(np.int64)
+    width = int(xs[-1]) + SHEET_CONTEXT // 2 + 20
+    # tempo map: frames per pixel 39/192 scaled by a factor in [0.6, 1.6) per 400-px segment
+    n_seg = width // 400 + 1
+    rate = (39.0 / 192.0) * (0.6 + _unit(draws[3 * n_notes:3 * n_notes + n_seg]).astype(np.float64))
+    knots = np.concatenate(([0.0], np.cumsum(rate * 400.0)))
+    frame_of = lambda x: np.interp(x, np.arange(n_seg + 1) * 400.0, knots)
+    onsets = np.floor(frame_of(xs.astype(np.float64))).astype(np.int64) + SPEC_CONTEXT // 2
+    n_frames = int(onsets[-1]) + SPEC_CONTEXT // 2 + 10
+    # sheet: white, sparse dark speckle, staff lines, note blobs
+    u = _draw(seed, _STREAM_PIECE_SHEET, [piece_idx], h * width)[0]
+    dark = (u & np.uint64(0xFF)) >= np.uint64(230)
+    val = ((u >> np.uint64(8)) & np.uint64(0x7F)).astype(np.uint8)
+    sheet = np.where(dark, val, np.uint8(255)).astype(np.uint8).reshape(h, width)
+    sheet[r0 + _STAFF_ROWS, :] = 0
+    for x, r in zip(xs, rows):
+        sheet[r0 + r:r0 + r + 6, x - 4:x + 4] = 0
+    # spectrogram: long-tailed noise plus one bump per note onset
+    us = _unit(_draw(seed, _STREAM_PIECE_SPEC, [piece_idx], hb * n_frames)[0])
+    spec = (np.float32(3.0) * us * us).reshape(hb, n_frames).astype(np.float32)
+    bins = (rows * (hb - 3)) // (SYSTEM_HEIGHT - 6)
+    for o, b in zip(onsets, bins):
+        spec[b:b + 3, o - 1:o + 2] += np.float32(2.0)
+    o2c = np.stack((onsets, xs), axis=1).astype(np.int64)
+    return sheet.astype(np.float32), spec, o2c
+
+
+def synth_pieces(n_pieces, seed=23):
+    """(images, specs, o2c_maps) of n_pieces synthetic pieces, one performance each, in AudioScoreRetrievalPool's
+    argument layout: images[i] (H, W_i), specs[i] = [spec (bins, T_i)], o2c_maps[i] = [o2c (n, 2)]."""
+    images, specs, o2c_maps = [], [], []
+    for p in range(int(n_pieces)):
+        sheet, spec, o2c = synth_piece(p, seed)
+        images.append(sheet)
+        specs.append([spec])
+        o2c_maps.append([o2c])
+    return images, specs, o2c_maps

@@ -282,6 +282,28 @@ int asr_spectrogram_dev(asr_ctx *ctx, const float *samples_dev, int64_t n_sample
 int asr_dtw_dev(asr_ctx *ctx, const float *a_dev, int64_t n_a, const float *b_dev, int64_t n_b, int dim,
                 double *dists, int32_t *path_a, int32_t *path_b, int32_t *path_len, double *min_dist);
 
+/* ---- batched alignment DTW (audio2sheet_align.py over a whole test split) ---------------
+ * asr_dtw_dev for n_pairs independent pairs in one call, every result bit-identical with asr_dtw_dev on the pair alone
+ * (batch composition and order change nothing).  a_dev / b_dev: the pairs' code rows concatenated (pair p's rows
+ * start at sum_{q<p} n_a[q] / n_b[q]), float32, row length dim, on the device.  n_a / n_b: host arrays of n_pairs.
+ * Outputs (host, each may be NULL):
+ *   min_dist[p] = D1[-1,-1] / (n_a[p] + n_b[p]); path_len[p];
+ *   path_a / path_b: pair p's path (_traceback's (p, q), forward order) at offset sum_{q<p} (n_a[q] + n_b[q])
+ *     (capacity n_a + n_b; entries past path_len[p] unspecified) - path_a, path_b and path_len go together;
+ *   dists: pair p's n_a x n_b cosine distances, row-major, at offset sum_{q<p} n_a[q] * n_b[q];
+ *   first_a: per row i of pair p, the column of the first path entry in row i, at offset sum_{q<p} n_a[q];
+ *   first_b: per column j, the row of the first path entry in column j (align_pydtw's projection), at sum n_b[q].
+ * With min_dist, path_*, first_* all NULL only the distances are computed.
+ * Limits: 1 <= dim <= 64; per pair 1 <= n_a, n_b <= 100000 and (n_a+1)(n_b+1) <= 2^31 (asr_dtw_dev's).  The
+ * wavefront keeps three anti-diagonals of min(n_a,n_b) + 1 doubles in one workgroup's LDS (160 KiB on gfx950:
+ * min(n_a,n_b) <= 6825); a larger pair keeps them in a global ring instead, with the same results.  Device memory:
+ * ~17 bytes per cell of the pairs in flight (9 without dists), kept on the context between calls and freed by
+ * asr_destroy; a batch above ASR_DTW_BUDGET_MB (default 4096) runs in chunks of consecutive pairs.  ASR_DTW_LDS_CAP=<n>
+ * (debug) sends pairs with min(n_a,n_b) + 1 > n to the global-ring path. */
+int asr_dtw_batch_dev(asr_ctx *ctx, const float *a_dev, const float *b_dev, const int64_t *n_a, const int64_t *n_b,
+                      int n_pairs, int dim, double *min_dist, int32_t *path_len, int32_t *path_a, int32_t *path_b,
+                      double *dists, int32_t *first_a, int32_t *first_b);
+
 /* ---- training-pool batch assembly on the device ----------------------
  * AudioScoreRetrievalPool.__getitem__ (utils/data_pools.py:127-228): every sample is a window of one strip (unrolled
  * score image or spectrogram) of a pool that stays resident on the device, with the augmentations of
