@@ -38,7 +38,7 @@ EXPORTS = [
     "asr_valid_loss_in", "asr_valid_output_in", "asr_valid_output_in_dev",
     "asr_comm_unique_id", "asr_comm_init", "asr_comm_init_custom", "asr_comm_destroy", "asr_comm_info", "asr_comm_stats", "asr_comm_timing", "asr_comm_library",
     "asr_comm_allreduce_dev", "asr_comm_allgather_dev",
-    "asr_rank_sharded_dev", "asr_slice_windows_dev", "asr_piece_vote_dev", "asr_gather_windows_dev", "asr_dtw_dev", "asr_dtw_batch_dev", "asr_spectrogram_dev", "asr_debug_tune_report",
+    "asr_rank_sharded_dev", "asr_slice_windows_dev", "asr_piece_vote_dev", "asr_piece_vote_batch_dev", "asr_gather_windows_dev", "asr_dtw_dev", "asr_dtw_batch_dev", "asr_spectrogram_dev", "asr_debug_tune_report",
     "asr_opt_state_size", "asr_get_opt_state", "asr_set_opt_state", "asr_debug_train_tensor", "asr_cca_train_debug",
 ]
 
@@ -182,6 +182,8 @@ def load_library(path=None):
                                           c_void_p]),
         "asr_piece_vote_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int, c_void_p, c_void_p,
                                        POINTER(c_int32)]),
+        "asr_piece_vote_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int32, c_int]
+                                     + [c_void_p] * 6),
         "asr_gather_windows_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p]),
         "asr_dtw_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                 POINTER(c_int32), POINTER(c_double)]),
@@ -409,6 +411,28 @@ class Engine(object):
         self._check(self.lib.asr_piece_vote_dev(self.ctx, idx_ptr, n_idx, ids_ptr, n_db, n_pieces, top_k,
                                                 pieces.ctypes.data, counts.ctypes.data, byref(m)))
         return pieces[:m.value], counts[:m.value]
+
+    def piece_vote_batch_dev(self, idx_ptr, n_groups, per_group, ids_ptr, n_db, n_pieces, top_k, targets=None):
+        """piece_vote_dev for n_groups groups of per_group top-k indices in one call (asr_piece_vote_batch_dev) ->
+        (pieces (n_groups, top_k) int32, counts (n_groups, top_k) int32, n_out (n_groups,) int32, ranks, ratios);
+        row g holds piece_vote_dev's result on group g in its first n_out[g] slots (piece -1 / count 0 after them).
+        With targets (one piece id per group): ranks int32 / ratios float64 of the reference's full-eval rule, else
+        None."""
+        n_groups, top_k = int(n_groups), int(top_k)
+        pieces = np.empty((max(n_groups, 0), max(top_k, 0)), np.int32)
+        counts = np.empty_like(pieces)
+        n_out = np.empty(max(n_groups, 0), np.int32)
+        ranks = ratios = t = None
+        if targets is not None:
+            t = np.ascontiguousarray(targets, dtype=np.int32)
+            if t.shape != (n_groups,):
+                raise ValueError("piece_vote_batch_dev: %d targets for %d groups" % (t.size, n_groups))
+            ranks, ratios = np.empty(n_groups, np.int32), np.empty(n_groups, np.float64)
+        ptr = lambda x: None if x is None else x.ctypes.data
+        self._check(self.lib.asr_piece_vote_batch_dev(self.ctx, idx_ptr, n_groups, per_group, ids_ptr, n_db, n_pieces,
+                                                      top_k, ptr(t), ptr(pieces), ptr(counts), ptr(n_out), ptr(ranks),
+                                                      ptr(ratios)))
+        return pieces, counts, n_out, ranks, ratios
 
     def dtw(self, a, b, want_dists=True):
         """cosine distance matrix + DTW of two code sequences, rows = a (utils/dtw_by_dist.py:5-34 on

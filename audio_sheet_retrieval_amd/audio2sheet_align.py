@@ -135,17 +135,14 @@ def align_pieces(engine, pool, align_by, sheet_step=10, spec_step=2):
     return pieces, results, errors
 
 
-def main(argv=None):
-    args = _arguments(argv)
-    if args.plots:
-        raise SystemExit("--plots: plotting is not part of this implementation")
-    if args.real_audio:
-        raise SystemExit("--real_audio: audio decoding is not part of this implementation")
-    model, _ = select_model(args.model)
+def load_network(model_path, estimate_UV, train_split, config):
+    """the model's parameters from EXP_ROOT/<EXP_NAME>[_est_UV]/params[_<tag>].pkl on an engine -> (engine, param
+    file) - what the reference's drivers load (:55-66; audio_sheet_server.py:600-608)"""
+    model, _ = select_model(model_path)
     layers = model.build_model(show_model=False)
-    tag = compile_tag(args.train_split, args.config)
+    tag = compile_tag(train_split, config)
     print("Experimental Tag:", tag)
-    folder = model.EXP_NAME + ("_est_UV" if args.estimate_UV else "")
+    folder = model.EXP_NAME + ("_est_UV" if estimate_UV else "")
     param_file = os.path.join(EXP_ROOT, folder, "params.pkl" if tag is None else "params_%s.pkl" % tag)
     params = load_params(param_file)
     if isinstance(params[0], list):            # very old dumps hold one full list per layer handle
@@ -154,6 +151,16 @@ def main(argv=None):
     view1, view2, latent1, _ = layers
     engine = network.function([view1.input_var, view2.input_var],
                               network.get_output(latent1, deterministic=True)).engine
+    return engine, param_file
+
+
+def main(argv=None):
+    args = _arguments(argv)
+    if args.plots:
+        raise SystemExit("--plots: plotting is not part of this implementation")
+    if args.real_audio:
+        raise SystemExit("--real_audio: audio decoding is not part of this implementation")
+    engine, param_file = load_network(args.model, args.estimate_UV, args.train_split, args.config)
 
     data = select_pieces(args.data, args.seed)
     pool = AudioScoreRetrievalPool(engine, data["images"], data["specs"], data["o2c_maps"],

@@ -1,0 +1,124 @@
+#!/usr/bin/env python
+"""Piece identification over whole test pieces (the paper's second experiment), audio -> sheet ("A2S").  Command line
+of the reference's audio_sheet_server.py (:571-580):
+
+    python -m audio_sheet_retrieval_amd.audio_sheet_server --model models/mutopia_ccal_cont.py --data synthetic:16 \
+        --train_split splits/all_split.yaml --config exp_configs/mutopia_full_aug.yaml \
+        --init_sheet_db --full_eval --dump_results [--n_candidates 25] [--estimate_UV]
+
+--init_sheet_db embeds the sheet windows of every test piece (EmbeddingDB.from_pool: initialize_sheet_db, :309-354) and
+saves them to sheet_db_file.pkl in the working directory; without it that file is loaded.  --full_eval queries the
+data base with every piece's spectrogram: 100 windows per piece, n_candidates neighbours per window, the votes ranked
+per piece (detect_score, :213-251) with top_k = number of test pieces, and the target piece ranked by the reference's
+rule (:640-645).  --dump_results writes the ranks to retrieval_<tag>_A2S.yaml next to the parameters, the file
+scripts/eval_piece_retrieval.py reads.
+
+Here the windows of all pieces are cut on the device, embedded in one call per tower, and all pieces are voted on in one
+asr_piece_vote_batch_dev call (piece_identification.detect_scores).  The live server loop (microphone, GUI), audio
+decoding (--real_audio) and MSMD loading are not part of this implementation.  sheet_audio_server.py is the S2A
+direction (sheet -> audio) of the same driver.
+"""
+import argparse
+import os
+
+import numpy as np
+import yaml
+
+from . import audio2sheet_align
+from .piece_identification import EmbeddingDB, detect_performances, detect_scores, rank_summary
+from .utils.data_pools import NO_AUGMENT, AudioScoreRetrievalPool
+
+# per direction: data-base flag, data-base file, data-base view, what a query finds (the reference's summary line)
+DIRECTIONS = {
+    "A2S": dict(init_flag="--init_sheet_db", db_file="sheet_db_file.pkl", db_view=1, found="scores"),
+    "S2A": dict(init_flag="--init_audio_db", db_file="audio_db_file.pkl", db_view=2, found="performances"),
+}
+
+
+def _arguments(argv, direction):
+    d = DIRECTIONS[direction]
+    p = argparse.ArgumentParser(description="Identify every test piece: %s." %
+                                ("audio -> sheet music" if direction == "A2S" else "sheet music -> audio"))
+    p.add_argument("--model", help="model definition, e.g. models/mutopia_ccal_cont.py",
+                   default="models/mutopia_ccal_cont.py")
+    p.add_argument("--data", type=str, default="synthetic", help="test pieces ('synthetic[:n_pieces]')")
+    p.add_argument("--estimate_UV", action="store_true", help="use the parameters written by refine_cca")
+    p.add_argument(d["init_flag"], dest="init_db", action="store_true",
+                   help="build the data base from the test pieces and save it to %s" % d["db_file"])
+    p.add_argument("--full_eval", action="store_true", help="rank every test piece")
+    if direction == "A2S":
+        p.add_argument("--real_audio", action="store_true", help="(audio decoding is not part of this implementation)")
+    p.add_argument("--running_frames", type=int, default=100, help="(live server only; accepted)")
+    p.add_argument("--n_candidates", type=int, default=25, help="neighbours retrieved per query window")
+    p.add_argument("--train_split", type=str, default=None)
+    p.add_argument("--config", type=str, default=None)
+    p.add_argument("--dump_results", action="store_true", help="write the ranks to retrieval_<tag>_%s.yaml" % direction)
+    p.add_argument("--seed", type=int, default=23)
+    return p.parse_args(argv)
+
+
+def result_file(param_file, direction):
+    """the reference's dump name (:651-653): a tag-less params.pkl gives params_<direction>.yaml"""
+    return param_file.replace("params_", "retrieval_").replace(".pkl", "_%s.yaml") % direction
+
+
+def identify(engine, db, direction, pool, names, n_candidates):
+    """every piece of `pool` as a query against `db` (A2S: its spectrogram, S2A: its unrolled sheet), top_k = number of
+    pieces -> (ranks int32, ratios float64, per-piece (names, votes))"""
+    ids = {name: i for i, name in db.id_to_name.items()}
+    targets = np.array([ids.get(n, -1) for n in names], np.int32)     # a piece missing from the data base: rank n_out
+    if direction == "A2S":
+        queries = [spec[0] for spec in pool.specs]
+        res, ranks, ratios = detect_scores(engine, db, queries, top_k=len(names), n_candidates=n_candidates,
+                                           spec_shape=tuple(pool.spec_dim), targets=targets)
+    else:
+        res, ranks, ratios = detect_performances(engine, db, pool.images, top_k=len(names), n_candidates=n_candidates,
+                                                 sheet_shape=tuple(pool.sheet_dim), targets=targets)
+    return ranks, ratios, res
+
+
+def run(argv, direction):
+    d = DIRECTIONS[direction]
+    args = _arguments(argv, direction)
+    if getattr(args, "real_audio", False):
+        raise SystemExit("--real_audio: audio decoding is not part of this implementation")
+    data = audio2sheet_align.select_pieces(args.data, args.seed)
+    engine, param_file = audio2sheet_align.load_network(args.model, args.estimate_UV, args.train_split, args.config)
+    pool = AudioScoreRetrievalPool(engine, data["images"], data["specs"], data["o2c_maps"],
+                                   data_augmentation=dict(NO_AUGMENT), shuffle=False)
+    if args.init_db:
+        db = EmbeddingDB.from_pool(engine, pool, d["db_view"], names=data["names"])
+        print("%d %s codes of %d pieces collected" % (len(db), "sheet snippet" if d["db_view"] == 1 else "audio excerpt",
+                                                      len(data["names"])))
+        db.save(d["db_file"])
+    else:
+        db = EmbeddingDB.load(engine, d["db_file"])
+    if not args.full_eval:
+        raise SystemExit("the live server loop (microphone, GUI) is not part of this implementation; use --full_eval")
+
+    print("\nRunning full evaluation:")
+    ranks, ratios, _ = identify(engine, db, direction, pool, data["names"], args.n_candidates)
+    for name, rank, ratio in zip(data["names"], ranks, ratios):
+        print("rank: %02d (%.2f) %s" % (rank, ratio, name))
+    n_queries = len(ranks)
+    for r in range(1, n_queries + 1):
+        n_correct = int(np.sum(ranks == r))
+        if n_correct > 0:
+            print("%d of %d retrieved %s ranked at position %d." % (n_correct, n_queries, d["found"], r))
+    for key, (cnt, frac) in rank_summary(ranks).items():
+        print("rank %-4s %d (%.2f)" % (key, cnt, frac))
+    results = [int(r) for r in ranks]
+    if args.dump_results:
+        res_file = result_file(param_file, direction)
+        with open(res_file, "w") as fp:
+            yaml.dump(results, fp, default_flow_style=False)
+        print("ranks of %d pieces written to %s" % (n_queries, res_file))
+    return results
+
+
+def main(argv=None):
+    return run(argv, "A2S")
+
+
+if __name__ == "__main__":
+    main()

@@ -763,6 +763,85 @@ int asr_piece_vote_dev(asr_ctx *ctx, const int32_t *idx_dev, int64_t n_idx, cons
     return mark_main(ctx);
 }
 
+int asr_piece_vote_batch_dev(asr_ctx *ctx, const int32_t *idx_dev, int64_t n_groups, int64_t per_group,
+                             const int32_t *ids_dev, int64_t n_db, int32_t n_pieces, int top_k, const int32_t *targets,
+                             int32_t *pieces, int32_t *counts, int32_t *n_out, int32_t *ranks, double *ratios) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_groups < 0 || n_groups > INT32_MAX || per_group < 0 || n_db < 0 || n_db > INT32_MAX || n_pieces < 1 ||
+        n_pieces > (1 << 30) || top_k < 1 || (per_group > 0 && n_groups > (INT64_MAX / 8) / per_group))
+        return fail(ctx, ASR_ERR_INVALID,
+                    "piece_vote_batch: bad sizes n_groups=%lld per_group=%lld n_db=%lld n_pieces=%d top_k=%d",
+                    (long long)n_groups, (long long)per_group, (long long)n_db, n_pieces, top_k);
+    if (!pieces || !counts || !n_out || (targets && (!ranks || !ratios)))
+        return fail(ctx, ASR_ERR_INVALID, "piece_vote_batch: NULL output (pieces, counts, n_out; ranks, ratios with targets)");
+    if (n_groups > 0 && per_group > 0 && (!idx_dev || (n_db > 0 && !ids_dev)))
+        return fail(ctx, ASR_ERR_INVALID, "piece_vote_batch: NULL argument");
+    if (n_groups == 0) return ASR_OK;
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    int rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+
+    // ASR_VOTE_LDS_PIECES=<n> (debug): groups with n_pieces above it take the global-workspace path, which exercises
+    // it at small sizes; ASR_VOTE_BUDGET_MB: global-path counters + keys per launch (more groups run in chunks)
+    const int64_t lds_pieces = std::min<int64_t>(asr::VOTE_LDS_PIECES, dtw_env("ASR_VOTE_LDS_PIECES", 1 << 30));
+    const bool global_path = n_pieces > lds_pieces;
+    int64_t keys_cap = 1;
+    while (keys_cap < std::min<int64_t>(n_pieces, per_group)) keys_cap <<= 1;
+    const size_t per_group_ws = (size_t)n_pieces * sizeof(int32_t) + (size_t)keys_cap * sizeof(uint64_t);
+    const size_t budget = (size_t)std::max<int64_t>(dtw_env("ASR_VOTE_BUDGET_MB", 1024), 1) << 20;
+    const int64_t chunk = global_path ? std::max<int64_t>(1, std::min<int64_t>(n_groups, budget / per_group_ws)) : n_groups;
+
+    // results block (downloaded in one copy): pieces | counts (n_groups x top_k) | n_out | ranks | ratios
+    const size_t G = (size_t)n_groups, GK = G * (size_t)top_k;
+    const size_t o_counts = GK * 4, o_nout = 2 * GK * 4, o_ranks = o_nout + G * 4;
+    const size_t o_ratios = dtw_align(o_ranks + G * 4), res_bytes = o_ratios + G * 8;
+    const size_t o_targets = dtw_align(res_bytes), o_hist = dtw_align(o_targets + G * 4);
+    const size_t o_keys = dtw_align(o_hist + (global_path ? (size_t)chunk * n_pieces * 4 : 0));
+    const size_t need = o_keys + (global_path ? (size_t)chunk * keys_cap * 8 : 0);
+    if (need > ctx->vote_ws_bytes) {
+        rc = sync_all(ctx);
+        if (rc != ASR_OK) return rc;
+        if (ctx->vote_ws) ASR_HIP(ctx, hipFree(ctx->vote_ws));
+        ctx->vote_ws = nullptr; ctx->vote_ws_bytes = 0;
+        ASR_HIP(ctx, hipMalloc(&ctx->vote_ws, need));
+        ctx->vote_ws_bytes = need;
+    }
+    char *ws = (char *)ctx->vote_ws;
+    int32_t *d_targets = targets ? (int32_t *)(ws + o_targets) : nullptr;
+    if (targets) ASR_HIP(ctx, hipMemcpyAsync(d_targets, targets, G * 4, hipMemcpyHostToDevice, ctx->stream));
+    {
+        ProfScope ps(ctx, "piece_vote_batch", 0, 0.0, 8.0 * (double)n_groups * (double)per_group + 8.0 * (double)GK);
+        for (int64_t g0 = 0; g0 < n_groups; g0 += chunk) {
+            asr::VoteBatchArgs a;
+            a.n_groups = std::min<int64_t>(chunk, n_groups - g0);
+            a.per_group = per_group;
+            a.idx = idx_dev ? idx_dev + g0 * per_group : nullptr;
+            a.ids = ids_dev; a.n_db = n_db; a.n_pieces = n_pieces; a.top_k = top_k;
+            a.targets = d_targets ? d_targets + g0 : nullptr;
+            a.pieces = (int32_t *)ws + g0 * top_k;
+            a.counts = (int32_t *)(ws + o_counts) + g0 * top_k;
+            a.n_out = (int32_t *)(ws + o_nout) + g0;
+            a.ranks = (int32_t *)(ws + o_ranks) + g0;
+            a.ratios = (double *)(ws + o_ratios) + g0;
+            a.hist_ws = (int32_t *)(ws + o_hist);
+            a.keys_ws = (uint64_t *)(ws + o_keys);
+            a.keys_cap = keys_cap;
+            ASR_HIP(ctx, asr::launch_piece_vote_batch(ctx->stream, a, global_path));
+        }
+    }
+    std::vector<char> host(res_bytes);
+    ASR_HIP(ctx, hipMemcpyAsync(host.data(), ws, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    ASR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(pieces, host.data(), GK * 4);
+    memcpy(counts, host.data() + o_counts, GK * 4);
+    memcpy(n_out, host.data() + o_nout, G * 4);
+    if (targets) {
+        memcpy(ranks, host.data() + o_ranks, G * 4);
+        memcpy(ratios, host.data() + o_ratios, G * 8);
+    }
+    return mark_main(ctx);
+}
+
 int asr_topk(asr_ctx *ctx, const float *db, int64_t n_db, int64_t ld_db, const float *q, int64_t n_q, int64_t ld_q,
              int dim, int k, int64_t idx_offset, int32_t *idx, double *dist) {
     if (!ctx) return ASR_ERR_INVALID;

@@ -225,6 +225,20 @@ hipError_t launch_slice_windows(hipStream_t s, const float *src, int64_t T, int 
 hipError_t launch_piece_vote(hipStream_t s, const int32_t *idx, int64_t n_idx, const int32_t *ids, int64_t n_db,
                              int32_t n_pieces, int top_k, int32_t *counts_ws, int32_t *out_piece, int32_t *out_count);
 
+// ---- batched piece vote (piece_vote_batch_kernels.hip): n_groups query pieces in one launch ----
+// groups with n_pieces <= VOTE_LDS_PIECES keep counters and sort keys in LDS (48 KiB per workgroup); larger ones use
+// hist_ws (n_groups * n_pieces int32, zeroed by the launcher) and keys_ws (n_groups * keys_cap uint64, keys_cap a power
+// of two >= min(n_pieces, per_group)).  All pointers on the device; targets / ranks / ratios may be null together.
+constexpr int VOTE_LDS_PIECES = 4096;
+struct VoteBatchArgs {
+    const int32_t *idx; int64_t n_groups, per_group;
+    const int32_t *ids; int64_t n_db; int32_t n_pieces; int top_k;
+    const int32_t *targets;
+    int32_t *pieces, *counts, *n_out, *ranks; double *ratios;
+    int32_t *hist_ws; uint64_t *keys_ws; int64_t keys_cap;
+};
+hipError_t launch_piece_vote_batch(hipStream_t s, const VoteBatchArgs &a, bool global_path);
+
 // autotuner self-check (ASR_TUNE_VERIFY=1): deterministic input pattern, max |a - b| as float bits
 hipError_t launch_fill_pattern(hipStream_t s, float *p, int64_t n);
 hipError_t launch_max_abs_diff(hipStream_t s, const float *a, const float *b, int64_t n, uint32_t *out_bits);

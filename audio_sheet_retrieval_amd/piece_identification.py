@@ -8,6 +8,7 @@ the resident data base, vote histogram and selection (csrc/piece_vote_kernels.hi
 from __future__ import annotations
 
 import pickle
+from collections import OrderedDict
 
 import numpy as np
 
@@ -87,6 +88,44 @@ class EmbeddingDB(object):
                 codes, ids, id_to_name, snippets = pickle.load(fp, encoding="latin1")
         return cls(engine, codes, ids, id_to_name, snippets)
 
+    @classmethod
+    def from_pool(cls, engine, pool, view, names=None, max_windows=4096):
+        """initialize_sheet_db (view 1, :309-354) / initialize_audio_db (view 2, :356-394) for every piece of `pool` at
+        once.  `pool`: an AudioScoreRetrievalPool over all pieces with shuffle=False - its entities are listed piece
+        after piece in the order of the reference's per-piece pools, and pool.get_device draws the augmentation numbers
+        in the same order (NO_AUGMENT's sheet_scaling [1, 1] still draws one per sample).  The windows are cut on the
+        device `max_windows` at a time and embedded with one call per chunk; ids = the entity's piece index,
+        id_to_name = {piece index: names[index]} (default: the index), snippets = the empty array the reference keeps
+        with keep_snippets=False."""
+        if view not in (1, 2):
+            raise ValueError("view must be 1 (sheet data base) or 2 (audio data base), got %r" % (view,))
+        from . import _lib
+        n = int(pool.shape[0])
+        win_h, win_w = pool.sheet_dim if view == 1 else pool.spec_dim
+        if (getattr(engine.cfg, "h%d" % view), getattr(engine.cfg, "w%d" % view)) != (win_h, win_w):
+            engine.set_input_size(view, win_h, win_w)
+        chunk = max(1, min(n, int(max_windows)))
+        b1 = engine.alloc(chunk * pool.sheet_dim[0] * pool.sheet_dim[1] * 4)
+        b2 = engine.alloc(chunk * pool.spec_dim[0] * pool.spec_dim[1] * 4)
+        d_codes = engine.alloc(max(n * 32 * 4, 4))
+        try:
+            for s in range(0, n, chunk):
+                _, _, m = pool.get_device(slice(s, min(n, s + chunk)), out=(b1, b2))
+                if view == 1:
+                    engine.embed_view1_dev(b1.ptr, _lib.IN_F32_RAW, m, d_codes.offset(s * 32 * 4))
+                else:
+                    engine.embed_view2_dev(b2.ptr, m, d_codes.offset(s * 32 * 4))
+            codes = d_codes.download((n, 32), np.float32)
+        finally:
+            for b in (b1, b2, d_codes):
+                b.free()
+        n_pieces = len(pool.images)
+        if names is not None and len(names) != n_pieces:
+            raise ValueError("%d names for %d pieces" % (len(names), n_pieces))
+        id_to_name = {i: (names[i] if names is not None else i) for i in range(n_pieces)}
+        snippets = np.zeros((0, win_h // 2, win_w // 2), dtype=np.uint8)
+        return cls(engine, codes, pool.train_entities[:, 0], id_to_name, snippets)
+
     def save(self, path):
         with open(path, "wb") as fp:
             pickle.dump([self.codes, self.ids.astype(np.int64), self.id_to_name, self.snippets], fp, protocol=2)
@@ -139,3 +178,120 @@ def detect_performance(engine, audio_db, sheet, top_k=1, n_candidates=1, n_sampl
     r0 = sheet.shape[0] // 2 - sheet_shape[0] // 2
     names, votes, _, _ = _detect(engine, audio_db, sheet, 1, sheet_shape, r0, top_k, n_candidates, n_samples)
     return names, votes
+
+
+# ---- full evaluation: every test piece as a query (audio_sheet_server.py / sheet_audio_server.py --full_eval) --------
+def window_plan(inputs, win_shape, n_samples, centre_rows):
+    """-> (sources concatenated (float32, flat), per input its window starts, gather descriptors (n_inputs * n_samples,
+    9)).  starts: the reference's np.linspace(0, T - w, n_samples).astype(int) (:217-218, :273-274); rows: 0.. of a
+    spectrogram, the central win_h rows of a sheet (centre_rows, :269-271).  Every input is checked before anything
+    runs on the device."""
+    win_h, win_w = win_shape
+    srcs, starts, desc, off = [], [], [], 0
+    for i, x in enumerate(inputs):
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2:
+            raise ValueError("input %d: expected a 2-d array, got shape %r" % (i, x.shape))
+        rows, T = x.shape
+        r0 = rows // 2 - win_h // 2 if centre_rows else 0
+        if T < win_w:
+            raise ValueError("input %d has %d columns, a window needs %d" % (i, T, win_w))
+        if r0 < 0 or r0 + win_h > rows:
+            raise ValueError("input %d has %d rows, a window needs %d" % (i, rows, win_h))
+        st = np.linspace(start=0, stop=T - win_w, num=n_samples).astype(np.int32)
+        # identity gather: out[y, x] = src[off + (r0 + y) * T + start + x]
+        d = np.zeros((len(st), 9), np.float64)
+        d[:, 0], d[:, 1], d[:, 2], d[:, 3], d[:, 4] = off, T, r0, 1.0, rows - 1
+        d[:, 5], d[:, 6], d[:, 7] = st, 1.0, T - 1
+        srcs.append(x.ravel())
+        starts.append(st)
+        desc.append(d)
+        off += x.size
+    flat = np.concatenate(srcs) if srcs else np.zeros(0, np.float32)
+    return flat, starts, (np.concatenate(desc) if desc else np.zeros((0, 9), np.float64))
+
+
+def _detect_batch(engine, db, inputs, view, win_shape, centre_rows, top_k, n_candidates, n_samples, targets,
+                  max_windows):
+    from . import _lib
+    inputs = list(inputs)
+    if n_samples < 1 or n_candidates < 1 or top_k < 1 or max_windows < 1:
+        raise ValueError("n_samples, n_candidates, top_k and max_windows must be >= 1")
+    if targets is not None and len(targets) != len(inputs):
+        raise ValueError("%d targets for %d inputs" % (len(targets), len(inputs)))
+    flat, _, desc = window_plan(inputs, win_shape, n_samples, centre_rows)
+    n_in = len(inputs)
+    if n_in == 0:
+        return ([], np.zeros(0, np.int32), np.zeros(0, np.float64)) if targets is not None else []
+    win_h, win_w = win_shape
+    n_win = n_in * n_samples
+    chunk = min(n_win, int(max_windows))
+    if (getattr(engine.cfg, "h%d" % view), getattr(engine.cfg, "w%d" % view)) != (win_h, win_w):
+        engine.set_input_size(view, win_h, win_w)
+    d_src = engine.alloc(flat.nbytes).upload(flat)
+    d_win = engine.alloc(chunk * win_h * win_w * 4)
+    d_codes = engine.alloc(n_win * 32 * 4)
+    d_idx, d_dist = engine.alloc(n_win * n_candidates * 4), engine.alloc(n_win * n_candidates * 8)
+    try:
+        for s in range(0, n_win, chunk):
+            m = min(chunk, n_win - s)
+            engine.gather_windows_dev(d_src.ptr, flat.size, desc[s:s + m], win_h, win_w, d_win.ptr)
+            if view == 2:
+                engine.embed_view2_dev(d_win.ptr, m, d_codes.offset(s * 32 * 4))
+            else:
+                engine.embed_view1_dev(d_win.ptr, _lib.IN_F32_RAW, m, d_codes.offset(s * 32 * 4))
+            db.topk_dev(d_codes.offset(s * 32 * 4), m, n_candidates, d_idx.offset(s * n_candidates * 4),
+                        d_dist.offset(s * n_candidates * 8))
+        pieces, counts, n_out, ranks, ratios = engine.piece_vote_batch_dev(
+            d_idx.ptr, n_in, n_samples * n_candidates, db._d_ids.ptr, len(db), db.n_pieces, top_k, targets)
+    finally:
+        for b in (d_src, d_win, d_codes, d_idx, d_dist):
+            b.free()
+    results = []
+    for g in range(n_in):
+        c = counts[g, :n_out[g]]
+        names = [db.id_to_name[int(p)] for p in pieces[g, :n_out[g]]]
+        results.append((names, c.astype(np.float64) / c.sum() if c.size else c.astype(np.float64)))
+    return (results, ranks, ratios) if targets is not None else results
+
+
+def detect_scores(engine, sheet_db, spectrograms, top_k=1, n_candidates=1, n_samples=100, spec_shape=(92, 42),
+                  targets=None, max_windows=4096):
+    """detect_score for a list of spectrograms of any lengths: all windows cut on the device in one gather per chunk of
+    max_windows, one embedding and one top-k call per chunk, one asr_piece_vote_batch_dev call for all inputs.
+    -> [(piece names, normalised votes)] per input, each equal to detect_score's; with targets (one piece id per
+    input): (that list, ranks, ratios) of the reference's full-eval rule (see full_eval_rank)."""
+    return _detect_batch(engine, sheet_db, spectrograms, 2, spec_shape, False, top_k, n_candidates, n_samples, targets,
+                         max_windows)
+
+
+def detect_performances(engine, audio_db, sheets, top_k=1, n_candidates=1, n_samples=100, sheet_shape=(160, 200),
+                        targets=None, max_windows=4096):
+    """detect_performance for a list of unrolled score strips (central sheet_shape[0] rows), batched as
+    detect_scores."""
+    return _detect_batch(engine, audio_db, sheets, 1, sheet_shape, True, top_k, n_candidates, n_samples, targets,
+                         max_windows)
+
+
+def full_eval_rank(ret_result, ret_votes, target):
+    """the reference's rank of one query (audio_sheet_server.py:640-645, sheet_audio_server.py:85-90): position + 1
+    of the target among the returned pieces and its normalised vote, else (number returned, 0.0)"""
+    ret_result = list(ret_result)
+    if target in ret_result:
+        i = ret_result.index(target)
+        return i + 1, float(ret_votes[i])
+    return len(ret_result), 0.0
+
+
+def rank_summary(ranks):
+    """{'<=1', '<=5', '<=10', '>10': (count, fraction)} - what scripts/eval_piece_retrieval.py:66-70 prints per
+    retrieval direction"""
+    ranks = np.sort(np.asarray(ranks))
+    n = len(ranks)
+    out = OrderedDict()
+    for thr in (1, 5, 10):
+        cnt = int(np.sum(ranks <= thr))
+        out["<=%d" % thr] = (cnt, cnt / float(n) if n else 0.0)
+    cnt = int(np.sum(ranks > 10))
+    out[">10"] = (cnt, cnt / float(n) if n else 0.0)
+    return out

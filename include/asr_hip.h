@@ -257,6 +257,28 @@ int asr_slice_windows_dev(asr_ctx *ctx, const float *src_dev, int64_t rows, int6
 int asr_piece_vote_dev(asr_ctx *ctx, const int32_t *idx_dev, int64_t n_idx, const int32_t *ids_dev, int64_t n_db,
                        int32_t n_pieces, int top_k, int32_t *pieces, int32_t *counts, int32_t *n_out);
 
+/* ---- batched piece vote: the full evaluation of audio_sheet_server.py / sheet_audio_server.py --full_eval -----------
+ * asr_piece_vote_dev for n_groups query pieces in one launch, each group's result bit-identical with asr_piece_vote_dev
+ * on that group's slice.  idx_dev: the (n_groups * per_group) int32 indices of one asr_topk_db_dev / asr_topk_dev call,
+ * group g = entries [g * per_group, (g + 1) * per_group) (its n_samples x n_candidates indices); entries -1 or outside
+ * [0, n_db) and piece ids outside [0, n_pieces) are ignored.  Outputs (host):
+ *   pieces / counts (n_groups x top_k): per group the voted pieces by votes descending, equal votes larger piece id
+ *     first; slots past the voted pieces hold piece -1 / count 0.  top_k is not capped (--full_eval: the test pieces);
+ *   n_out[g] = min(top_k, number of voted pieces);
+ *   with targets (n_groups host int32, or NULL): the reference's full-eval rule (:640-645) - target among the n_out[g]
+ *     returned pieces: ranks[g] = position + 1, ratios[g] = its count / sum of the returned counts (float64);
+ *     otherwise ranks[g] = n_out[g] (0 for a group without valid votes) and ratios[g] = 0.0.  ranks / ratios may be
+ *     NULL without targets.
+ * Limits: n_groups, n_db <= 2^31 - 1; 1 <= n_pieces <= 2^30; top_k >= 1.  One workgroup per group; with n_pieces <=
+ * 4096 the counters and the bitonic-sorted (count << 32 | piece) keys stay in LDS (48 KiB, any per_group); above that
+ * they live in a device workspace of n_pieces * 4 + 8 * pow2ceil(min(n_pieces, per_group)) bytes per group (groups in
+ * chunks of ASR_VOTE_BUDGET_MB, default 1024), with the same results.  One launch per chunk, one download; the
+ * workspace stays on the context (freed by asr_destroy).  ASR_VOTE_LDS_PIECES=<n> (debug) sends n_pieces > n to the
+ * workspace path. */
+int asr_piece_vote_batch_dev(asr_ctx *ctx, const int32_t *idx_dev, int64_t n_groups, int64_t per_group,
+                             const int32_t *ids_dev, int64_t n_db, int32_t n_pieces, int top_k, const int32_t *targets,
+                             int32_t *pieces, int32_t *counts, int32_t *n_out, int32_t *ranks, double *ratios);
+
 /* ---- audio front-end -------------------------------------------------
  * The madmom chain the reference feeds its spectrogram tower with (tutorials/Embedding Tutorial.ipynb cell 28,
  * msmd.midi_parser.processor; audio_sheet_server.py:632,678 `processor.process(audio_file).T`):
