@@ -39,6 +39,7 @@ EXPORTS = [
     "asr_comm_unique_id", "asr_comm_init", "asr_comm_init_custom", "asr_comm_destroy", "asr_comm_info", "asr_comm_stats", "asr_comm_timing", "asr_comm_library",
     "asr_comm_allreduce_dev", "asr_comm_allgather_dev",
     "asr_rank_sharded_dev", "asr_slice_windows_dev", "asr_piece_vote_dev", "asr_piece_vote_batch_dev", "asr_gather_windows_dev", "asr_dtw_dev", "asr_dtw_batch_dev", "asr_spectrogram_dev", "asr_debug_tune_report",
+    "asr_seg_create", "asr_seg_set_window", "asr_seg_destroy", "asr_seg_predict_dev",
     "asr_opt_state_size", "asr_get_opt_state", "asr_set_opt_state", "asr_debug_train_tensor", "asr_cca_train_debug",
 ]
 
@@ -182,6 +183,11 @@ def load_library(path=None):
                                           c_void_p]),
         "asr_piece_vote_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int, c_void_p, c_void_p,
                                        POINTER(c_int32)]),
+        "asr_seg_create": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, POINTER(c_void_p)]),
+        "asr_seg_set_window": (c_int, [c_void_p, c_void_p, c_void_p]),
+        "asr_seg_destroy": (c_int, [c_void_p, c_void_p]),
+        "asr_seg_predict_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                        c_double, c_void_p]),
         "asr_piece_vote_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int32, c_int]
                                      + [c_void_p] * 6),
         "asr_gather_windows_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p]),

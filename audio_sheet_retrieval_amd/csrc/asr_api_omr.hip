@@ -1,0 +1,310 @@
+// C-ABI layer of the staff-system detector: asr_seg_create / asr_seg_destroy / asr_seg_predict_dev
+// (sheet_utils/omr.py SegmentationNetwork.load + predict_proba; include/asr_hip.h for the contract).  Kernels:
+// omr_kernels.hip.
+#include "asr_ctx.h"
+#include "omr_kernels.h"
+
+#include <cmath>
+
+namespace {
+
+// the 15 conv blocks of system_detector.build_model() (nf0 = 8), in graph order: input channels, output channels,
+// level (0 = full tile), index of the layer's W in the reference's parameter list
+struct SegConvSpec { int ci, co, level, p; };
+constexpr SegConvSpec SEG_CONV[14] = {
+    {1, 8, 0, 0},   {8, 8, 0, 5},   {8, 16, 1, 10}, {16, 16, 1, 15}, {16, 32, 2, 20}, {32, 32, 2, 25}, {32, 64, 3, 30},
+    {64, 64, 3, 35}, {32, 32, 2, 49}, {32, 32, 2, 54}, {16, 16, 1, 68}, {16, 16, 1, 73}, {8, 8, 0, 87}, {8, 8, 0, 92}};
+// decoder levels: TransposedConv2D W (ci, co, 2, 2) at p, BN at p + 1, BN after the skip add at p + 5
+struct SegUpSpec { int ci, co, p; };
+constexpr SegUpSpec SEG_UP[3] = {{64, 32, 40}, {32, 16, 59}, {16, 8, 78}};
+constexpr int SEG_N_PARAMS = 99, SEG_HEAD_W = 97, SEG_HEAD_B = 98;
+
+size_t seg_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+int64_t seg_env(const char *name, int64_t dflt) {
+    const char *v = getenv(name);
+    return v && *v ? atoll(v) : dflt;
+}
+
+}  // namespace
+
+struct asr_seg {
+    asr_ctx *owner = nullptr;
+    int th = 0, tw = 0;
+    float *w = nullptr;                   // packed device weights (offsets below, in floats)
+    size_t conv_w[14] = {}, conv_bn[14] = {}, up_w[3] = {}, up_bn1[3] = {}, up_bn2[3] = {}, head = 0;
+    double *win = nullptr;                // sqrt(outer(hamming(th), hamming(tw))), computed as numpy does
+    void *ws = nullptr;                   // per call: descriptors, page maxima, tile probabilities, one chunk's activations
+    size_t ws_bytes = 0;
+};
+
+namespace {
+
+// BN of Lasagne's batch_norm(): (x - mean) * (gamma * inv_std) + beta; parameters beta, gamma, mean, inv_std at p
+void seg_pack_bn(std::vector<float> &dst, const float *const *a, int p, int c) {
+    const float *beta = a[p], *gamma = a[p + 1], *mean = a[p + 2], *inv_std = a[p + 3];
+    for (int k = 0; k < c; ++k) dst.push_back(mean[k]);
+    for (int k = 0; k < c; ++k) dst.push_back(gamma[k] * inv_std[k]);
+    for (int k = 0; k < c; ++k) dst.push_back(beta[k]);
+}
+
+// floats of one tile's activation buffers at tile size th x tw (plane = th * tw): A, B (8 planes each), the skips
+// p1 (8), p2 (4), p3 (2)
+int64_t seg_tile_floats(int64_t plane) { return 30 * plane; }
+
+int seg_check(asr_ctx *ctx, const asr_seg *seg, const char *who) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (!seg || seg->owner != ctx) return fail(ctx, ASR_ERR_INVALID, "%s: not a segmentation network of this context", who);
+    return ASR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int asr_seg_create(asr_ctx *ctx, int tile_h, int tile_w, const float *const *arrays, const int64_t *sizes, int n_arrays,
+                   asr_seg **out) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (!out) return fail(ctx, ASR_ERR_INVALID, "seg_create: NULL output");
+    *out = nullptr;
+    if (tile_h < 8 || tile_w < 8 || tile_h % 8 || tile_w % 8 || (int64_t)tile_h * tile_w > (1 << 24))
+        return fail(ctx, ASR_ERR_INVALID, "seg_create: tile %d x %d must be a multiple of 8 on each side (U-Net of "
+                    "three 2x2 pools)", tile_h, tile_w);
+    if (n_arrays != SEG_N_PARAMS || !arrays || !sizes)
+        return fail(ctx, ASR_ERR_INVALID, "seg_create: expected the reference's %d arrays, got %d", SEG_N_PARAMS, n_arrays);
+    // expected sizes, in the reference's order
+    std::vector<int64_t> want(SEG_N_PARAMS, 0);
+    for (const SegConvSpec &c : SEG_CONV) {
+        want[c.p] = (int64_t)c.co * c.ci * 9;
+        for (int k = 1; k <= 4; ++k) want[c.p + k] = c.co;
+    }
+    for (const SegUpSpec &u : SEG_UP) {
+        want[u.p] = (int64_t)u.ci * u.co * 4;
+        for (int k = 1; k <= 8; ++k) want[u.p + k] = u.co;
+    }
+    want[SEG_HEAD_W] = 8;
+    want[SEG_HEAD_B] = 1;
+    for (int i = 0; i < SEG_N_PARAMS; ++i) {
+        if (sizes[i] != want[i])
+            return fail(ctx, ASR_ERR_INVALID, "seg_create: array %d has %lld floats, the U-Net needs %lld", i,
+                        (long long)sizes[i], (long long)want[i]);
+        if (!arrays[i]) return fail(ctx, ASR_ERR_INVALID, "seg_create: array %d is NULL", i);
+    }
+    std::unique_ptr<asr_seg> seg(new asr_seg());
+    seg->owner = ctx; seg->th = tile_h; seg->tw = tile_w;
+
+    std::vector<float> pk;
+    auto pad = [&]() { while (pk.size() % 64) pk.push_back(0.0f); };
+    for (int l = 0; l < 14; ++l) {
+        const SegConvSpec &c = SEG_CONV[l];
+        const float *W = arrays[c.p];                     // (co, ci, 3, 3), flip_filters=True
+        seg->conv_w[l] = pk.size();
+        for (int ci = 0; ci < c.ci; ++ci)
+            for (int dy = 0; dy < 3; ++dy)
+                for (int dx = 0; dx < 3; ++dx)
+                    for (int co = 0; co < c.co; ++co) pk.push_back(W[((co * c.ci + ci) * 3 + (2 - dy)) * 3 + (2 - dx)]);
+        pad();
+        seg->conv_bn[l] = pk.size();
+        seg_pack_bn(pk, arrays, c.p + 1, c.co);
+        pad();
+    }
+    for (int u = 0; u < 3; ++u) {
+        const SegUpSpec &s = SEG_UP[u];
+        const float *W = arrays[s.p];                     // (ci, co, 2, 2); out[2i+a, 2j+b] reads W[ci, co, 1-a, 1-b]
+        seg->up_w[u] = pk.size();
+        for (int ci = 0; ci < s.ci; ++ci)
+            for (int a = 0; a < 2; ++a)
+                for (int b = 0; b < 2; ++b)
+                    for (int co = 0; co < s.co; ++co) pk.push_back(W[((ci * s.co + co) * 2 + (1 - a)) * 2 + (1 - b)]);
+        pad();
+        seg->up_bn1[u] = pk.size();
+        seg_pack_bn(pk, arrays, s.p + 1, s.co);
+        pad();
+        seg->up_bn2[u] = pk.size();
+        seg_pack_bn(pk, arrays, s.p + 5, s.co);
+        pad();
+    }
+    seg->head = pk.size();
+    for (int k = 0; k < 8; ++k) pk.push_back(arrays[SEG_HEAD_W][k]);
+    pk.push_back(arrays[SEG_HEAD_B][0]);
+    pad();
+
+    // np.hamming(M): 0.54 - 0.46 cos(2 pi n / (M - 1)); weight sqrt(outer(h, w))
+    std::vector<double> hh(tile_h), hw(tile_w), win((size_t)tile_h * tile_w);
+    for (int i = 0; i < tile_h; ++i) hh[i] = 0.54 - 0.46 * std::cos(2.0 * M_PI * i / (tile_h - 1));
+    for (int j = 0; j < tile_w; ++j) hw[j] = 0.54 - 0.46 * std::cos(2.0 * M_PI * j / (tile_w - 1));
+    for (int i = 0; i < tile_h; ++i)
+        for (int j = 0; j < tile_w; ++j) win[(size_t)i * tile_w + j] = std::sqrt(hh[i] * hw[j]);
+
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    hipError_t e = hipMalloc((void **)&seg->w, pk.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&seg->win, win.size() * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(seg->w, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(seg->win, win.data(), win.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (seg->w) hipFree(seg->w);
+        if (seg->win) hipFree(seg->win);
+        return fail(ctx, ASR_ERR_HIP, "seg_create: %s", hipGetErrorString(e));
+    }
+    *out = seg.release();
+    return ASR_OK;
+}
+
+int asr_seg_set_window(asr_ctx *ctx, asr_seg *seg, const double *win_host) {
+    int rc = seg_check(ctx, seg, "seg_set_window");
+    if (rc != ASR_OK) return rc;
+    if (!win_host) return fail(ctx, ASR_ERR_INVALID, "seg_set_window: NULL window");
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    rc = sync_all(ctx);
+    if (rc != ASR_OK) return rc;
+    ASR_HIP(ctx, hipMemcpy(seg->win, win_host, (size_t)seg->th * seg->tw * sizeof(double), hipMemcpyHostToDevice));
+    return ASR_OK;
+}
+
+int asr_seg_destroy(asr_ctx *ctx, asr_seg *seg) {
+    if (!seg) return ASR_OK;
+    int rc = seg_check(ctx, seg, "seg_destroy");
+    if (rc != ASR_OK) return rc;
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    rc = sync_all(ctx);
+    if (seg->w) hipFree(seg->w);
+    if (seg->win) hipFree(seg->win);
+    if (seg->ws) hipFree(seg->ws);
+    seg->owner = nullptr;
+    delete seg;
+    return rc;
+}
+
+int asr_seg_predict_dev(asr_ctx *ctx, asr_seg *seg, const void *pages_dev, int in_mode, const int64_t *page_offsets,
+                        const int32_t *heights, const int32_t *widths, int n_pages, double overlap, double *proba_dev) {
+    int rc = seg_check(ctx, seg, "seg_predict");
+    if (rc != ASR_OK) return rc;
+    if (n_pages < 0 || in_mode < 0 || in_mode > 2)
+        return fail(ctx, ASR_ERR_INVALID, "seg_predict: bad n_pages=%d in_mode=%d", n_pages, in_mode);
+    if (n_pages == 0) return ASR_OK;
+    if (!pages_dev || !page_offsets || !heights || !widths || !proba_dev)
+        return fail(ctx, ASR_ERR_INVALID, "seg_predict: NULL argument");
+    const int th = seg->th, tw = seg->tw;
+    // SegmentationNetwork._predict_proba_sliding_window: np.arange(0, Hp - th + 1, int(th * (1 - overlap)))
+    const int step_h = (int)(th * (1.0 - overlap)), step_w = (int)(tw * (1.0 - overlap));
+    if (!(overlap >= 0.0) || step_h < 1 || step_w < 1)
+        return fail(ctx, ASR_ERR_INVALID, "seg_predict: overlap %g leaves no tile step", overlap);
+
+    std::vector<asr::SegPage> pdesc(n_pages);
+    std::vector<asr::SegStitch> sdesc(n_pages);
+    std::vector<asr::SegTile> tiles;
+    int64_t out_off = 0, max_px = 0;
+    for (int p = 0; p < n_pages; ++p) {
+        const int h = heights[p], w = widths[p];
+        if (h < 1 || w < 1 || (int64_t)h * w > (1 << 28) || page_offsets[p] < 0)
+            return fail(ctx, ASR_ERR_INVALID, "seg_predict: page %d has bad geometry %d x %d at %lld", p, h, w,
+                        (long long)page_offsets[p]);
+        pdesc[p] = {page_offsets[p], h, w};
+        asr::SegStitch &S = sdesc[p];
+        S.out_offset = out_off; S.h = h; S.w = w;
+        S.first_tile = (int32_t)tiles.size();
+        S.direct = h == th && w == tw;
+        if (S.direct) {
+            S.n_rows = S.n_cols = 1; S.step_h = step_h; S.step_w = step_w;
+            tiles.push_back({p, 0, 0, 0});
+        } else {
+            const int hp = (int)(th * std::ceil((double)h / th)), wp = (int)(tw * std::ceil((double)w / tw));
+            S.pad_top = (hp - h) / 2; S.pad_left = (wp - w) / 2;
+            S.step_h = step_h; S.step_w = step_w;
+            S.n_rows = (hp - th) / step_h + 1; S.n_cols = (wp - tw) / step_w + 1;
+            for (int r = 0; r < S.n_rows; ++r)
+                for (int c = 0; c < S.n_cols; ++c)
+                    tiles.push_back({p, r * step_h - S.pad_top, c * step_w - S.pad_left, 0});
+        }
+        out_off += (int64_t)h * w;
+        max_px = std::max<int64_t>(max_px, (int64_t)h * w);
+    }
+    const int64_t n_tiles = (int64_t)tiles.size(), plane = (int64_t)th * tw;
+
+    // ASR_OMR_BUDGET_MB: device workspace of one chunk of tiles (activations); whole tiles, at least one per chunk
+    const size_t budget = (size_t)std::max<int64_t>(seg_env("ASR_OMR_BUDGET_MB", 4096), 1) << 20;
+    const size_t per_tile = (size_t)seg_tile_floats(plane) * sizeof(float);
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n_tiles, (int64_t)(budget / per_tile)));
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += seg_align(bytes); return at; };
+    const size_t o_pd = take(pdesc.size() * sizeof(asr::SegPage)), o_sd = take(sdesc.size() * sizeof(asr::SegStitch));
+    const size_t o_td = take(tiles.size() * sizeof(asr::SegTile)), o_mx = take((size_t)n_pages * sizeof(float));
+    const size_t o_tp = take((size_t)n_tiles * plane * sizeof(float)), o_act = take((size_t)chunk * per_tile);
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    if (o > seg->ws_bytes) {
+        rc = sync_all(ctx);
+        if (rc != ASR_OK) return rc;
+        if (seg->ws) ASR_HIP(ctx, hipFree(seg->ws));
+        seg->ws = nullptr; seg->ws_bytes = 0;
+        ASR_HIP(ctx, hipMalloc(&seg->ws, o));
+        seg->ws_bytes = o;
+    }
+    char *ws = (char *)seg->ws;
+    asr::SegPage *d_pd = (asr::SegPage *)(ws + o_pd);
+    asr::SegStitch *d_sd = (asr::SegStitch *)(ws + o_sd);
+    asr::SegTile *d_td = (asr::SegTile *)(ws + o_td);
+    float *d_mx = (float *)(ws + o_mx), *tile_p = (float *)(ws + o_tp), *act = (float *)(ws + o_act);
+    hipStream_t st = ctx->stream;
+    ASR_HIP(ctx, hipMemcpyAsync(d_pd, pdesc.data(), pdesc.size() * sizeof(asr::SegPage), hipMemcpyHostToDevice, st));
+    ASR_HIP(ctx, hipMemcpyAsync(d_sd, sdesc.data(), sdesc.size() * sizeof(asr::SegStitch), hipMemcpyHostToDevice, st));
+    ASR_HIP(ctx, hipMemcpyAsync(d_td, tiles.data(), tiles.size() * sizeof(asr::SegTile), hipMemcpyHostToDevice, st));
+    if (in_mode != 0) ASR_HIP(ctx, asr::launch_seg_page_max(st, pages_dev, in_mode, d_pd, n_pages, d_mx));
+
+    // direct-form FLOP of one tile (3x3 blocks, transposed convs, head) for the profiler
+    double tile_flop = 0.0;
+    for (const SegConvSpec &c : SEG_CONV) tile_flop += 2.0 * 9 * c.ci * c.co * (double)(plane >> (2 * c.level));
+    for (int u = 0; u < 3; ++u) tile_flop += 2.0 * 4 * SEG_UP[u].ci * SEG_UP[u].co * (double)(plane >> (2 * (3 - u)));
+    tile_flop += 2.0 * 8 * (double)plane;
+
+    const float *W = seg->w;
+    for (int64_t t0 = 0; t0 < n_tiles; t0 += chunk) {
+        const int n = (int)std::min<int64_t>(chunk, n_tiles - t0);
+        ProfScope ps(ctx, "seg_unet", 0, tile_flop * n, 4.0 * (double)plane * n * 31);
+        float *A = act, *B = A + (size_t)n * 8 * plane, *P1 = B + (size_t)n * 8 * plane;
+        float *P2 = P1 + (size_t)n * 8 * plane, *P3 = P2 + (size_t)n * 4 * plane;
+        auto conv = [&](int l, const float *in, float *out, float *pooled, bool head, int level) {
+            asr::SegConvArgs a;
+            a.in = in; a.w = W + seg->conv_w[l]; a.bn = W + seg->conv_bn[l];
+            a.head = head ? W + seg->head : nullptr;
+            a.out = out; a.pooled = pooled;
+            a.ci = SEG_CONV[l].ci; a.co = SEG_CONV[l].co; a.H = th >> level; a.W = tw >> level; a.n = n;
+            if (l == 0) {
+                a.pages = pages_dev; a.page_desc = d_pd; a.tiles = d_td + t0; a.page_max = d_mx; a.in_mode = in_mode;
+            }
+            return asr::launch_seg_conv3(st, a);
+        };
+        auto up = [&](int u, const float *in, const float *skip, float *out) {
+            const int lv = 3 - u;                          // level of the input
+            return asr::launch_seg_up(st, in, W + seg->up_w[u], W + seg->up_bn1[u], W + seg->up_bn2[u], skip, out,
+                                      SEG_UP[u].ci, SEG_UP[u].co, th >> lv, tw >> lv, n);
+        };
+        // encoder
+        ASR_HIP(ctx, conv(0, nullptr, A, nullptr, false, 0));
+        ASR_HIP(ctx, conv(1, A, P1, B, false, 0));
+        ASR_HIP(ctx, conv(2, B, A, nullptr, false, 1));
+        ASR_HIP(ctx, conv(3, A, P2, B, false, 1));
+        ASR_HIP(ctx, conv(4, B, A, nullptr, false, 2));
+        ASR_HIP(ctx, conv(5, A, P3, B, false, 2));
+        ASR_HIP(ctx, conv(6, B, A, nullptr, false, 3));
+        ASR_HIP(ctx, conv(7, A, B, nullptr, false, 3));
+        // decoder
+        ASR_HIP(ctx, up(0, B, P3, A));
+        ASR_HIP(ctx, conv(8, A, B, nullptr, false, 2));
+        ASR_HIP(ctx, conv(9, B, A, nullptr, false, 2));
+        ASR_HIP(ctx, up(1, A, P2, B));
+        ASR_HIP(ctx, conv(10, B, A, nullptr, false, 1));
+        ASR_HIP(ctx, conv(11, A, B, nullptr, false, 1));
+        ASR_HIP(ctx, up(2, B, P1, A));
+        ASR_HIP(ctx, conv(12, A, B, nullptr, false, 0));
+        ASR_HIP(ctx, conv(13, B, tile_p + (size_t)t0 * plane, nullptr, true, 0));
+    }
+    {
+        ProfScope ps(ctx, "seg_stitch", 0, 3.0 * (double)out_off, 12.0 * (double)out_off);
+        ASR_HIP(ctx, asr::launch_seg_stitch(st, tile_p, seg->win, th, tw, d_sd, n_pages, (int)max_px, proba_dev));
+    }
+    return mark_main(ctx);
+}
+
+}  // extern "C"

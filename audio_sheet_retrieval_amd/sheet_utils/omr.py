@@ -1,0 +1,441 @@
+"""Staff-system detection on score pages (sheet_utils/omr.py of the reference).
+
+The two U-Nets run on the device (asr_seg_* in include/asr_hip.h, csrc/omr_kernels.hip); what the reference does on the
+host after the probability maps exist - Otsu thresholds, the vertical closing, 8-connected labelling, bounding-box
+shrinking and the snap to the staff-line grid - is restated here in numpy / scipy from the published semantics of the
+libraries the reference ran (scikit-image 0.13.1, OpenCV 3.1), neither of which this package needs.
+"""
+from __future__ import print_function
+
+import ctypes
+import pickle
+from ctypes import byref, c_void_p
+
+import numpy as np
+from scipy import ndimage
+
+SYSTEM_HEIGHT = 160          # utils/data_pools.py: height of an unrolled staff system
+MIN_AREA = 50000             # detect_systems: smallest system blob
+
+IN_F32_PREPARED, IN_F32_RAW, IN_U8_RAW = 0, 1, 2
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# images
+
+def prepare_image(img):
+    """omr.prepare_image: float32, divided by the page maximum unless it is 0."""
+    img = img.astype(np.float32)
+    if img.max() != 0:
+        img /= img.max()
+    return img
+
+
+def imread_gray(path):
+    """cv2.imread(path, 0) for PNG pages, on PIL: alpha dropped, colour converted as libpng's rgb_to_gray with OpenCV's
+    coefficients 0.299 / 0.587 (15-bit fixed point, truncated: 9797, 19234, blue 3737), rounded with +16384 >> 15.
+    16-bit samples keep their high byte."""
+    from PIL import Image
+    im = Image.open(path)
+    if im.mode == "P":
+        im = im.convert("RGBA" if "transparency" in im.info else "RGB")
+    if im.mode in ("I;16", "I;16B", "I"):
+        return (np.asarray(im).astype(np.uint32) >> 8).astype(np.uint8)
+    a = np.asarray(im)
+    if im.mode == "1":
+        return (a.astype(np.uint8) * 255)
+    if im.mode in ("L",):
+        return np.ascontiguousarray(a, dtype=np.uint8)
+    if im.mode == "LA":
+        return np.ascontiguousarray(a[..., 0], dtype=np.uint8)
+    if im.mode not in ("RGB", "RGBA"):
+        a = np.asarray(im.convert("RGB"))
+    rgb = a[..., :3].astype(np.uint32)
+    g = (9797 * rgb[..., 0] + 19234 * rgb[..., 1] + 3737 * rgb[..., 2] + 16384) >> 15
+    return np.ascontiguousarray(g, dtype=np.uint8)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the sliding-window geometry of SegmentationNetwork._predict_proba_sliding_window
+
+def tile_grid(h, w, th, tw, overlap=0.5):
+    """(pad_top, pad_left, row_0, col_0): padding of the page to a multiple of the tile (missing // 2 top / left) and
+    the tile starts in padded coordinates."""
+    missing_h = int(th * np.ceil(float(h) / th) - h)
+    missing_w = int(tw * np.ceil(float(w) / tw) - w)
+    hp, wp = h + missing_h, w + missing_w
+    row_0 = np.arange(0, hp - th + 1, int(th * (1.0 - overlap)))
+    col_0 = np.arange(0, wp - tw + 1, int(tw * (1.0 - overlap)))
+    return missing_h // 2, missing_w // 2, row_0, col_0
+
+
+def tile_window(th, tw):
+    """sqrt(outer(hamming(th), hamming(tw))), float64: the weight of every tile output"""
+    return np.sqrt(np.outer(np.hamming(th), np.hamming(tw)))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# restated library functions
+
+def threshold_otsu(image, nbins=256):
+    """skimage.filters.threshold_otsu (0.13.1) on a float image: np.histogram bins, the bin centre that maximises the
+    between-class variance (first maximum)."""
+    hist, bin_edges = np.histogram(np.asarray(image).ravel(), bins=nbins)
+    bin_centers = (bin_edges[:-1] + bin_edges[1:]) / 2.
+    hist = hist.astype(float)
+    weight1 = np.cumsum(hist)
+    weight2 = np.cumsum(hist[::-1])[::-1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean1 = np.cumsum(hist * bin_centers) / weight1
+        mean2 = (np.cumsum((hist * bin_centers)[::-1]) / weight2[::-1])[::-1]
+        variance12 = weight1[:-1] * weight2[1:] * (mean1[:-1] - mean2[1:]) ** 2
+    idx = np.argmax(variance12)
+    return bin_centers[:-1][idx]
+
+
+def peak_local_max(image, min_distance=1, threshold_abs=None, threshold_rel=None, exclude_border=True):
+    """skimage.feature.peak_local_max (0.13.1), indices=True, no footprint / labels / num_peaks: points equal to the
+    maximum of their (2 min_distance + 1) neighbourhood (zero beyond the border), min_distance points off every border
+    excluded, above max(threshold_abs or image.min(), threshold_rel * image.max()).  A constant image has no peaks.
+    Order: np.nonzero's (row-major), REVERSED ("highest peak first" in that version reverses the index order)."""
+    image = np.asarray(image)
+    if np.all(image == image.flat[0]):
+        return np.empty((0, image.ndim), np.int64)
+    if type(exclude_border) == bool:
+        exclude_border = min_distance if exclude_border else 0
+    image_max = ndimage.maximum_filter(image, size=2 * min_distance + 1, mode="constant")
+    mask = image == image_max
+    if exclude_border:
+        for i in range(mask.ndim):
+            mask = mask.swapaxes(0, i)
+            remove = 2 * exclude_border
+            mask[:remove // 2] = mask[-remove // 2:] = False
+            mask = mask.swapaxes(0, i)
+    thresholds = [image.min() if threshold_abs is None else threshold_abs]
+    if threshold_rel is not None:
+        thresholds.append(threshold_rel * image.max())
+    mask &= image > max(thresholds)
+    coord = np.column_stack(np.nonzero(mask))
+    return coord[::-1]
+
+
+def blur(image, ksize):
+    """cv2.blur(image, ksize=(kw, kh)) on a float32 image: box mean, BORDER_REFLECT_101, sums in float64 (OpenCV's
+    sum type for float input), result float32."""
+    kw, kh = ksize
+    x = np.asarray(image, np.float64)
+    ay, ax = kh // 2, kw // 2
+    xp = np.pad(x, ((ay, kh - 1 - ay), (ax, kw - 1 - ax)), mode="reflect")
+    s = np.zeros_like(x)
+    for dy in range(kh):
+        for dx in range(kw):
+            s += xp[dy:dy + x.shape[0], dx:dx + x.shape[1]]
+    return (s * (1.0 / (kw * kh))).astype(np.float32)
+
+
+def close_vertical(fg, k=15):
+    """cv2.morphologyEx(fg, MORPH_CLOSE, ones((k, 1))) on a 0/1 image: dilation then erosion along columns with the
+    anchor at the centre and OpenCV's default border (neither dilates nor erodes: outside counts as 0 for the dilation
+    and as 1 for the erosion).  uint8 0/1."""
+    st = np.ones((k, 1), bool)
+    d = ndimage.binary_dilation(fg.astype(bool), structure=st, border_value=0)
+    e = ndimage.binary_erosion(d, structure=st, border_value=1)
+    return e.astype(np.uint8)
+
+
+def label8(fg):
+    """skimage.measure.label(fg, neighbors=8): background 0, labels 1.. in raster order of each blob's first pixel."""
+    lab, n = ndimage.label(np.asarray(fg) != 0, structure=np.ones((3, 3), int))
+    return lab, n
+
+
+def regionprops(label_img, n):
+    """area and bbox (min_row, min_col, max_row, max_col; max exclusive) of labels 1..n, in label order"""
+    areas = np.bincount(label_img.ravel(), minlength=n + 1)
+    out = []
+    for i, sl in enumerate(ndimage.find_objects(label_img, max_label=n)):
+        if sl is None:
+            continue
+        out.append((i + 1, int(areas[i + 1]), (sl[0].start, sl[1].start, sl[0].stop, sl[1].stop)))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# detect_systems' host steps (omr.py)
+
+def shrink_bounding_box(fg_img, bbox):
+    """OpticalMusicRecognizer._shrink_bounding_box"""
+    min_row, min_col, max_row, max_col = bbox
+    min_row = max(min_row, 0)
+    min_col = max(min_col, 0)
+    max_row = min(max_row, fg_img.shape[0] - 1)
+    max_col = min(max_col, fg_img.shape[1] - 1)
+    while np.mean(fg_img[min_row, min_col:max_col]) < 0.9:
+        min_row += 1
+    while np.mean(fg_img[max_row, min_col:max_col]) < 0.9:
+        max_row -= 1
+    while np.mean(fg_img[min_row:max_row, min_col]) < 0.9:
+        min_col += 1
+    while np.mean(fg_img[min_row:max_row, max_col]) < 0.9:
+        max_col -= 1
+    return min_row, min_col, max_row, max_col
+
+
+def snap_system_to_grid(image, min_row, max_row, min_col, max_col):
+    """omr.snap_system_to_grid, including its x-direction comparison against max_row (not max_col)."""
+    image = 1.0 - image[0, 0]
+    imagex = blur(image, (1, 3))
+    imagey = blur(image, (3, 1))
+
+    # y-direction
+    edge_signal = imagey.mean(axis=1)
+    edge_candidates = peak_local_max(edge_signal, threshold_rel=0.5)
+    min_dists = np.abs(min_row - edge_candidates)
+    min_idx_min = np.argmin(min_dists)
+    min_dist = min_dists[min_idx_min]
+    max_dists = np.abs(max_row - edge_candidates)
+    min_idx_max = np.argmin(max_dists)
+    max_dist = max_dists[min_idx_max]
+    thresh = 10
+    if min_dist < thresh and max_dist < thresh:
+        min_row = edge_candidates[min_idx_min, 0]
+        max_row = edge_candidates[min_idx_max, 0]
+
+    # x-direction
+    edge_signal = imagex[min_row:max_row, :].mean(axis=0)
+    edge_candidates = peak_local_max(edge_signal, threshold_rel=0.5)
+    min_dists = np.abs(min_col - edge_candidates)
+    min_idx_min = np.argmin(min_dists)
+    min_dist = min_dists[min_idx_min]
+    max_dists = np.abs(max_row - edge_candidates)
+    min_idx_max = np.argmin(max_dists)
+    max_dist = max_dists[min_idx_max]
+    if min_dist < thresh and max_dist < thresh:
+        min_col = edge_candidates[min_idx_min, 0]
+        max_col = edge_candidates[min_idx_max, 0]
+
+    return min_row, max_row, min_col, max_col
+
+
+def systems_from_maps(image, system_probs, bar_probs=None):
+    """detect_systems after the two probability maps exist.  image: the prepared page (h, w); the maps: (h, w).
+    Raises where the reference raises (IndexError when no row of the projection lies below its Otsu threshold,
+    ValueError when the snap finds no edge candidate)."""
+    if image.ndim == 2:
+        image = image[np.newaxis, np.newaxis]
+    system_probs = np.array(system_probs, copy=True)
+    projection = (bar_probs if bar_probs is not None else system_probs).sum(1)
+
+    thresh = threshold_otsu(projection)
+    space_indices = np.nonzero(projection < thresh)[0]
+    start_idx = prev_idx = space_indices[0]
+    for idx in space_indices[1:]:
+        if (idx - prev_idx) == 1:
+            prev_idx = idx
+        else:
+            if prev_idx - start_idx > 15:
+                system_probs[start_idx:prev_idx, :] = 0
+            start_idx = prev_idx = idx
+
+    fg_img = system_probs > threshold_otsu(system_probs)
+    fg_img = close_vertical(fg_img, 15)
+
+    label_img, n = label8(fg_img)
+    detected_systems = np.zeros((0, 4, 2))
+    for lab, area, bbox in regionprops(label_img, n):
+        if area < MIN_AREA:
+            continue
+        min_row, min_col, max_row, max_col = shrink_bounding_box(label_img == lab, bbox)
+        min_row, max_row, min_col, max_col = snap_system_to_grid(image, min_row, max_row, min_col, max_col)
+        system_coords = np.zeros((4, 2))
+        system_coords[0] = np.asarray([min_row, min_col])
+        system_coords[1] = np.asarray([min_row, max_col])
+        system_coords[2] = np.asarray([max_row, max_col])
+        system_coords[3] = np.asarray([max_row, min_col])
+        detected_systems = np.concatenate((detected_systems, system_coords[np.newaxis]))
+    return detected_systems
+
+
+def unwrap_systems(page, systems, system_height=SYSTEM_HEIGHT):
+    """The unrolling loop of the tutorial and load_umc_sheets: rows centred on each system, clamped to the page,
+    columns system[0, 1]:system[1, 1], edge-padded when up to 10 % of the rows are missing, skipped (with the
+    reference's message) when more are; the systems side by side.  uint8 (system_height, total width)."""
+    unwrapped_sheet = np.zeros((system_height, 0), dtype=np.uint8)
+    for system in systems:
+        r0 = int(np.mean([system[0, 0], system[2, 0]])) - system_height // 2
+        r1 = r0 + system_height
+        c0 = int(system[0, 1])
+        c1 = int(system[1, 1])
+        r0 = max(0, r0)
+        r1 = min(r1, page.shape[0])
+        r0 = max(r0, r1 - system_height)
+        staff_img = page[r0:r1, c0:c1].astype(np.uint8)
+        if staff_img.shape[0] < system_height:
+            to_pad = system_height - staff_img.shape[0]
+            if to_pad > (0.1 * system_height):
+                print("Problem in system padding!!!")
+                continue
+            staff_img = np.pad(staff_img, ((0, to_pad), (0, 0)), mode="edge")
+        unwrapped_sheet = np.hstack((unwrapped_sheet, staff_img))
+    return unwrapped_sheet
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# networks
+
+def load_net_params(file_path):
+    """utils/net_utils.load_net_params: the pickled list of parameter arrays (Python-2 pickles read as latin1)."""
+    with open(file_path, "rb") as fp:
+        try:
+            return pickle.load(fp)
+        except UnicodeDecodeError:
+            fp.seek(0)
+            return pickle.load(fp, encoding="latin1")
+
+
+_ENGINES = {}
+
+
+def _engine(device):
+    """one context per device for all segmentation networks of the process"""
+    from audio_sheet_retrieval_amd import _lib
+    eng = _ENGINES.get(device)
+    if eng is None or eng.ctx is None:
+        eng = _ENGINES[device] = _lib.Engine("mutopia_ccal_cont", device=device)
+    return eng
+
+
+class SegmentationNetwork(object):
+    """SegmentationNetwork(net) of the reference on the device.  `net` is a graph of system_detector.build_model() /
+    bar_detector.build_model(); load() takes the reference's pickle (or a list of its 99 arrays)."""
+
+    def __init__(self, net, device=0, print_architecture=False):
+        self.net = net
+        self.input_shape = (None,) + tuple(net.input_shape)
+        self.device = device
+        self.handle = None
+        self.engine = None
+
+    @property
+    def tile_shape(self):
+        return tuple(self.net.input_shape[-2:])
+
+    def load(self, file_path):
+        params = load_net_params(file_path) if isinstance(file_path, str) else list(file_path)
+        self.set_params(params)
+
+    def set_params(self, params):
+        from audio_sheet_retrieval_amd import _lib
+        self.close()
+        arrs = [np.ascontiguousarray(np.asarray(p), dtype=np.float32) for p in params]
+        eng = _engine(self.device)
+        ptrs = (ctypes.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+        sizes = np.asarray([a.size for a in arrs], np.int64)
+        h = c_void_p()
+        th, tw = self.tile_shape
+        eng._check(eng.lib.asr_seg_create(eng.ctx, th, tw, ptrs, sizes.ctypes.data, len(arrs), byref(h)))
+        self.engine, self.handle = eng, h
+        win = np.ascontiguousarray(tile_window(th, tw))
+        eng._check(eng.lib.asr_seg_set_window(eng.ctx, h, win.ctypes.data))
+        self._lib = _lib
+
+    def close(self):
+        if self.handle is not None and self.engine is not None and self.engine.ctx is not None:
+            self.engine.lib.asr_seg_destroy(self.engine.ctx, self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # -- device call ------------------------------------------------------------------------------------------------
+    def predict_pages(self, pages, overlap=0.5, in_mode=IN_F32_PREPARED):
+        """float64 probability maps of a list of 2-D pages in ONE device call (every tile of every page in one forward,
+        chunked under ASR_OMR_BUDGET_MB).  in_mode: IN_F32_PREPARED (float32 pages as prepare_image leaves them),
+        IN_F32_RAW / IN_U8_RAW (prepare_image on the device)."""
+        if self.handle is None:
+            raise RuntimeError("SegmentationNetwork: load() the parameters first")
+        if not pages:
+            return []
+        dt = np.uint8 if in_mode == IN_U8_RAW else np.float32
+        flat = [np.ascontiguousarray(p, dtype=dt) for p in pages]
+        for p in flat:
+            if p.ndim != 2:
+                raise ValueError("pages are 2-D, got shape %s" % (p.shape,))
+        sizes = np.asarray([p.size for p in flat], np.int64)
+        offs = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+        hs = np.asarray([p.shape[0] for p in flat], np.int32)
+        ws = np.asarray([p.shape[1] for p in flat], np.int32)
+        eng = self.engine
+        host = np.concatenate([p.ravel() for p in flat])
+        x = eng.alloc(host.nbytes).upload(host)
+        out = eng.alloc(int(sizes.sum()) * 8)
+        try:
+            eng._check(eng.lib.asr_seg_predict_dev(eng.ctx, self.handle, c_void_p(x.ptr),
+                                                   in_mode, offs.ctypes.data, hs.ctypes.data, ws.ctypes.data, len(flat),
+                                                   float(overlap), c_void_p(out.ptr)))
+            eng.sync()
+            res = out.download((int(sizes.sum()),), np.float64)
+        finally:
+            x.free()
+            out.free()
+        return [res[o:o + s].reshape(h, w) for o, s, h, w in zip(offs, sizes, hs, ws)]
+
+    # -- the reference's interface ----------------------------------------------------------------------------------
+    def predict_proba(self, input, squeeze=True, overlap=0.5):
+        """input: (n, 1, h, w) prepared float32 (or (h, w)).  A tile-sized input goes through the network directly
+        (float32 output, as theano's); any other is stitched from overlapping tiles (float64)."""
+        x = np.asarray(input)
+        if x.ndim == 2:
+            x = x[np.newaxis, np.newaxis]
+        maps = self.predict_pages([img[0] for img in x.astype(np.float32)], overlap=overlap)
+        proba = np.stack(maps)[:, np.newaxis]
+        if x.shape[-2:] == self.tile_shape:
+            proba = proba.astype(np.float32)
+        if squeeze:
+            proba = proba.squeeze()
+        return proba
+
+    def predict(self, input, thresh=0.5):
+        P = self.predict_proba(input, squeeze=False)
+        if P.shape[1] == 1:
+            return (P > thresh).squeeze()
+        return np.argmax(P, axis=1).squeeze()
+
+
+class OpticalMusicRecognizer(object):
+    """Score segmentation networks (omr.OpticalMusicRecognizer): system detection."""
+
+    def __init__(self, note_detector=None, system_detector=None, bar_detector=None):
+        self.note_detector = note_detector
+        self.system_detector = system_detector
+        self.bar_detector = bar_detector
+
+    def detect_systems(self, image, verbose=False):
+        """(n_systems, 4, 2) float64 corners (row, col): top-left, top-right, bottom-right, bottom-left"""
+        img = image[0, 0] if image.ndim == 4 else image
+        system_probs = self.system_detector.predict_proba(img[np.newaxis, np.newaxis])
+        bar_probs = self.bar_detector.predict_proba(img[np.newaxis, np.newaxis]) if self.bar_detector else None
+        return systems_from_maps(img, system_probs, bar_probs)
+
+    def detect_systems_pages(self, pages, in_mode=IN_F32_PREPARED, prepared=None):
+        """detect_systems for many pages: one device call per network.  pages: 2-D arrays (prepared float32, or raw
+        uint8 with in_mode=IN_U8_RAW).  Returns one entry per page: the corner array, or the exception the reference's
+        detect_systems would have raised on that page."""
+        sys_maps = self.system_detector.predict_pages(pages, in_mode=in_mode)
+        bar_maps = self.bar_detector.predict_pages(pages, in_mode=in_mode) if self.bar_detector else [None] * len(pages)
+        out = []
+        for i, page in enumerate(pages):
+            img = prepare_image(page) if in_mode != IN_F32_PREPARED else page
+            sp, bp = sys_maps[i], bar_maps[i]
+            if page.shape == self.system_detector.tile_shape:
+                sp = sp.astype(np.float32)
+            if bp is not None and page.shape == self.bar_detector.tile_shape:
+                bp = bp.astype(np.float32)
+            try:
+                out.append(systems_from_maps(img, sp, bp))
+            except Exception as e:          # the reference's callers catch every exception of detect_systems
+                out.append(e)
+        return out

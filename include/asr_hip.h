@@ -534,6 +534,31 @@ int asr_cca_train_debug(asr_ctx *ctx, const float *H1, const float *H2, int64_t 
                         const float *cca_in, float *cca_out, float *loss_corr,
                         float *lv1, float *lv2, float *dH1, float *dH2);
 
+/* ---- staff-system detection (sheet_utils/omr.py, system_detector.py, bar_detector.py) ----------------
+ * One U-Net of SegmentationNetwork (system_detector.build_model(), bar_detector's graph at its own input size) as a
+ * handle of the context that created it, like asr_db.
+ *   asr_seg_create      = build_model(in_shape=(1, tile_h, tile_w)) + SegmentationNetwork.load(pkl): `arrays` are the
+ *                         reference's 99 parameter arrays in pickle order (float32, C order), sizes[i] their element
+ *                         counts, checked against the graph (nf0 = 8).  tile_h, tile_w: multiples of 8.
+ *   asr_seg_set_window  = the tile weight sqrt(outer(hamming(tile_h), hamming(tile_w))) as float64, tile_h x tile_w
+ *                         (optional: asr_seg_create computes it; a caller that wants numpy's bits passes numpy's)
+ *   asr_seg_predict_dev = predict_proba(page, squeeze=True, overlap) for n_pages pages in one call: page p is
+ *                         heights[p] x widths[p], row-major at element page_offsets[p] of pages_dev; in_mode as
+ *                         asr_embed_view1 (0 prepared float32, 1 raw float32, 2 raw uint8: prepare_image is folded
+ *                         in).  A page of exactly the tile size goes through the network directly; any other is
+ *                         zero-padded to a multiple of the tile and cut into tiles with the reference's steps, and the
+ *                         float64 map R / V is cropped back (NaN where no tile covers a pixel).  proba_dev: float64,
+ *                         the pages' maps back to back.  All tiles of all pages form one forward, in chunks of whole
+ *                         tiles under ASR_OMR_BUDGET_MB of device workspace (default 4096). */
+typedef struct asr_seg asr_seg;
+int asr_seg_create(asr_ctx *ctx, int tile_h, int tile_w, const float *const *arrays, const int64_t *sizes,
+                   int n_arrays, asr_seg **out);
+int asr_seg_set_window(asr_ctx *ctx, asr_seg *seg, const double *win_host);
+int asr_seg_destroy(asr_ctx *ctx, asr_seg *seg);
+int asr_seg_predict_dev(asr_ctx *ctx, asr_seg *seg, const void *pages_dev, int in_mode, const int64_t *page_offsets,
+                        const int32_t *heights, const int32_t *widths, int n_pages, double overlap,
+                        double *proba_dev);
+
 /* ---- device memory (plain pointers; library-owned allocations) ---------- */
 int asr_dev_alloc(asr_ctx *ctx, size_t bytes, void **dptr);
 int asr_dev_free(asr_ctx *ctx, void *dptr);
