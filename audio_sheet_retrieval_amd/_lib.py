@@ -40,6 +40,7 @@ EXPORTS = [
     "asr_comm_allreduce_dev", "asr_comm_allgather_dev",
     "asr_rank_sharded_dev", "asr_slice_windows_dev", "asr_piece_vote_dev", "asr_piece_vote_batch_dev", "asr_gather_windows_dev", "asr_dtw_dev", "asr_dtw_batch_dev", "asr_spectrogram_dev", "asr_debug_tune_report",
     "asr_seg_create", "asr_seg_set_window", "asr_seg_destroy", "asr_seg_predict_dev",
+    "asr_unroll_systems_dev", "asr_spectrogram_batch_dev",
     "asr_opt_state_size", "asr_get_opt_state", "asr_set_opt_state", "asr_debug_train_tensor", "asr_cca_train_debug",
 ]
 
@@ -196,6 +197,11 @@ def load_library(path=None):
         "asr_dtw_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 7),
         "asr_spectrogram_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_int, c_float, c_float, c_int64, c_int, c_void_p]),
+        "asr_unroll_systems_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                           c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64]),
+        "asr_spectrogram_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                              c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
+                                              c_float, c_int, c_void_p, c_int64]),
         "asr_debug_tune_report": (c_int, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_float)]),
         "asr_comm_unique_id": (c_int, [c_void_p]),
         "asr_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),
@@ -523,6 +529,44 @@ class Engine(object):
         self._check(self.lib.asr_spectrogram_dev(self.ctx, samples_ptr, n_samples, frame_size, hop, window.ctypes.data,
                                                  fb_start.ctypes.data, fb_len.ctypes.data, fb_weights.ctypes.data,
                                                  fb_start.size, mul, add, n_frames, 1 if transposed else 0, out_ptr))
+
+    def spectrogram_batch_dev(self, samples_ptr, samples_floats, sample_offsets, sample_counts, n_frames, out_offsets,
+                              frame_size, hop, window, fb_start, fb_len, fb_weights, out_ptr, out_floats, mul=1.0,
+                              add=1.0, transposed=True):
+        """spectrogram_dev for many recordings of one concatenated sample buffer in one launch
+        (asr_spectrogram_batch_dev); per recording bit-identical with spectrogram_dev on it alone"""
+        i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
+        sample_offsets, sample_counts, n_frames, out_offsets = map(i64, (sample_offsets, sample_counts, n_frames,
+                                                                         out_offsets))
+        n = sample_counts.size
+        if not (sample_offsets.size == n_frames.size == out_offsets.size == n):
+            raise ValueError("spectrogram_batch_dev: the per-recording tables differ in length")
+        window = np.ascontiguousarray(window, np.float32)
+        fb_start = np.ascontiguousarray(fb_start, np.int32)
+        fb_len = np.ascontiguousarray(fb_len, np.int32)
+        fb_weights = np.ascontiguousarray(fb_weights, np.float32)
+        self._check(self.lib.asr_spectrogram_batch_dev(
+            self.ctx, samples_ptr, int(samples_floats), sample_offsets.ctypes.data, sample_counts.ctypes.data,
+            n_frames.ctypes.data, out_offsets.ctypes.data, n, frame_size, hop, window.ctypes.data, fb_start.ctypes.data,
+            fb_len.ctypes.data, fb_weights.ctypes.data, fb_start.size, mul, add, 1 if transposed else 0, out_ptr,
+            int(out_floats)))
+
+    def unroll_systems_dev(self, pages_ptr, pages_bytes, page_offsets, heights, widths, systems, system_height,
+                           strip_offsets, strip_widths, strips_ptr, strips_floats):
+        """the systems of `systems` ((n, 8) int32: page, r0, r1, c0, c1, pad, piece, dst_col) copied out of the uint8
+        pages into the pieces' float32 strips in one launch (asr_unroll_systems_dev)"""
+        page_offsets = np.ascontiguousarray(page_offsets, dtype=np.int64)
+        heights = np.ascontiguousarray(heights, dtype=np.int32)
+        widths = np.ascontiguousarray(widths, dtype=np.int32)
+        systems = np.ascontiguousarray(systems, dtype=np.int32).reshape(-1, 8)
+        strip_offsets = np.ascontiguousarray(strip_offsets, dtype=np.int64)
+        strip_widths = np.ascontiguousarray(strip_widths, dtype=np.int32)
+        if not (page_offsets.size == heights.size == widths.size) or strip_offsets.size != strip_widths.size:
+            raise ValueError("unroll_systems_dev: the per-page / per-piece tables differ in length")
+        self._check(self.lib.asr_unroll_systems_dev(
+            self.ctx, pages_ptr, int(pages_bytes), page_offsets.ctypes.data, heights.ctypes.data, widths.ctypes.data,
+            heights.size, systems.ctypes.data, systems.shape[0], int(system_height), strip_offsets.ctypes.data,
+            strip_widths.ctypes.data, strip_widths.size, strips_ptr, int(strips_floats)))
 
     def tune_report(self):
         """(comparisons, mismatches, max deviation) of the autotuner's self-check (ASR_TUNE_VERIFY=1)."""

@@ -35,24 +35,30 @@ DIRECTIONS = {
 }
 
 
+def common_arguments(p, init_flag, db_file, result_name):
+    """the flags the MSMD drivers and the UMC drivers (umc_a2s_server.py) share"""
+    p.add_argument("--model", help="model definition, e.g. models/mutopia_ccal_cont.py",
+                   default="models/mutopia_ccal_cont.py")
+    p.add_argument("--estimate_UV", action="store_true", help="use the parameters written by refine_cca")
+    p.add_argument(init_flag, dest="init_db", action="store_true",
+                   help="build the data base from the test pieces and save it to %s" % db_file)
+    p.add_argument("--full_eval", action="store_true", help="rank every test piece")
+    p.add_argument("--n_candidates", type=int, default=25, help="neighbours retrieved per query window")
+    p.add_argument("--train_split", type=str, default=None)
+    p.add_argument("--config", type=str, default=None)
+    p.add_argument("--dump_results", action="store_true", help="write the ranks to %s" % result_name)
+    return p
+
+
 def _arguments(argv, direction):
     d = DIRECTIONS[direction]
     p = argparse.ArgumentParser(description="Identify every test piece: %s." %
                                 ("audio -> sheet music" if direction == "A2S" else "sheet music -> audio"))
-    p.add_argument("--model", help="model definition, e.g. models/mutopia_ccal_cont.py",
-                   default="models/mutopia_ccal_cont.py")
+    common_arguments(p, d["init_flag"], d["db_file"], "retrieval_<tag>_%s.yaml" % direction)
     p.add_argument("--data", type=str, default="synthetic", help="test pieces ('synthetic[:n_pieces]')")
-    p.add_argument("--estimate_UV", action="store_true", help="use the parameters written by refine_cca")
-    p.add_argument(d["init_flag"], dest="init_db", action="store_true",
-                   help="build the data base from the test pieces and save it to %s" % d["db_file"])
-    p.add_argument("--full_eval", action="store_true", help="rank every test piece")
     if direction == "A2S":
         p.add_argument("--real_audio", action="store_true", help="(audio decoding is not part of this implementation)")
     p.add_argument("--running_frames", type=int, default=100, help="(live server only; accepted)")
-    p.add_argument("--n_candidates", type=int, default=25, help="neighbours retrieved per query window")
-    p.add_argument("--train_split", type=str, default=None)
-    p.add_argument("--config", type=str, default=None)
-    p.add_argument("--dump_results", action="store_true", help="write the ranks to retrieval_<tag>_%s.yaml" % direction)
     p.add_argument("--seed", type=int, default=23)
     return p.parse_args(argv)
 
@@ -98,18 +104,25 @@ def run(argv, direction):
 
     print("\nRunning full evaluation:")
     ranks, ratios, _ = identify(engine, db, direction, pool, data["names"], args.n_candidates)
-    for name, rank, ratio in zip(data["names"], ranks, ratios):
+    return report_ranks(data["names"], ranks, ratios, d["found"],
+                        result_file(param_file, direction) if args.dump_results else None)
+
+
+def report_ranks(names, ranks, ratios, found, res_file=None):
+    """the per-piece rank lines, the "n of m retrieved ... ranked at position r." lines and the summary of a full
+    evaluation; with res_file the ranks are dumped there as yaml (:647-657) -> the ranks as a list of int"""
+    ranks = np.asarray(ranks)
+    for name, rank, ratio in zip(names, ranks, ratios):
         print("rank: %02d (%.2f) %s" % (rank, ratio, name))
     n_queries = len(ranks)
     for r in range(1, n_queries + 1):
         n_correct = int(np.sum(ranks == r))
         if n_correct > 0:
-            print("%d of %d retrieved %s ranked at position %d." % (n_correct, n_queries, d["found"], r))
+            print("%d of %d retrieved %s ranked at position %d." % (n_correct, n_queries, found, r))
     for key, (cnt, frac) in rank_summary(ranks).items():
         print("rank %-4s %d (%.2f)" % (key, cnt, frac))
     results = [int(r) for r in ranks]
-    if args.dump_results:
-        res_file = result_file(param_file, direction)
+    if res_file is not None:
         with open(res_file, "w") as fp:
             yaml.dump(results, fp, default_flow_style=False)
         print("ranks of %d pieces written to %s" % (n_queries, res_file))

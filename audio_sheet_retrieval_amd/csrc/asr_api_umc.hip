@@ -1,0 +1,143 @@
+// C-ABI layer of the UMC drivers' device stages: asr_unroll_systems_dev (page scans -> unrolled strips) and
+// asr_spectrogram_batch_dev (recordings -> spectrograms); include/asr_hip.h for the contract.  Kernels:
+// umc_kernels.hip, piece_vote_kernels.hip (spectrogram_batch_kernel).  Both calls check every offset against the
+// buffer sizes the caller states before anything is launched, and return after the work is done.
+#include "asr_ctx.h"
+
+int asr_unroll_systems_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
+                           const int32_t *heights, const int32_t *widths, int n_pages, const int32_t *systems,
+                           int n_systems, int system_height, const int64_t *strip_offsets, const int32_t *strip_widths,
+                           int n_pieces, float *strips_dev, int64_t strips_floats) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_pages < 0 || n_systems < 0 || n_pieces < 0 || system_height < 1 || pages_bytes < 0 || strips_floats < 0)
+        return fail(ctx, ASR_ERR_INVALID, "unroll_systems: bad sizes");
+    if (n_systems == 0) return ASR_OK;
+    if (!pages_dev || !page_offsets || !heights || !widths || !systems || !strip_offsets || !strip_widths || !strips_dev)
+        return fail(ctx, ASR_ERR_INVALID, "unroll_systems: NULL argument");
+    for (int p = 0; p < n_pages; ++p)
+        if (heights[p] < 0 || widths[p] < 0 || page_offsets[p] < 0 ||
+            page_offsets[p] + (int64_t)heights[p] * widths[p] > pages_bytes)
+            return fail(ctx, ASR_ERR_INVALID, "unroll_systems: page %d (%d x %d at %lld) outside the %lld-byte buffer", p,
+                        heights[p], widths[p], (long long)page_offsets[p], (long long)pages_bytes);
+    for (int q = 0; q < n_pieces; ++q)
+        if (strip_widths[q] < 0 || strip_offsets[q] < 0 ||
+            strip_offsets[q] + (int64_t)system_height * strip_widths[q] > strips_floats)
+            return fail(ctx, ASR_ERR_INVALID, "unroll_systems: strip %d (%d x %d at %lld) outside the %lld-float buffer", q,
+                        system_height, strip_widths[q], (long long)strip_offsets[q], (long long)strips_floats);
+    std::vector<asr::UnrollSystem> table(n_systems);
+    double pixels = 0.0;
+    for (int i = 0; i < n_systems; ++i) {
+        const int32_t *t = systems + (size_t)i * 8;
+        const int32_t page = t[0], r0 = t[1], r1 = t[2], c0 = t[3], c1 = t[4], pad = t[5], piece = t[6], col = t[7];
+        if (page < 0 || page >= n_pages || piece < 0 || piece >= n_pieces)
+            return fail(ctx, ASR_ERR_INVALID, "unroll_systems: system %d names page %d / piece %d", i, page, piece);
+        if (r0 < 0 || r1 <= r0 || r1 > heights[page] || c0 < 0 || c1 <= c0 || c1 > widths[page] || pad < 0 ||
+            (int64_t)r1 - r0 + pad != system_height)
+            return fail(ctx, ASR_ERR_INVALID, "unroll_systems: system %d rows [%d, %d) + %d, columns [%d, %d) do not fit "
+                        "page %d (%d x %d) / height %d", i, r0, r1, pad, c0, c1, page, heights[page], widths[page],
+                        system_height);
+        if (col < 0 || (int64_t)col + (c1 - c0) > strip_widths[piece])
+            return fail(ctx, ASR_ERR_INVALID, "unroll_systems: system %d columns [%d, %d) outside strip %d of width %d", i,
+                        col, col + (c1 - c0), piece, strip_widths[piece]);
+        asr::UnrollSystem &u = table[i];
+        u.src = page_offsets[page] + (int64_t)r0 * widths[page] + c0;
+        u.dst = strip_offsets[piece] + col;
+        u.src_stride = widths[page];
+        u.dst_stride = strip_widths[piece];
+        u.rows = r1 - r0;
+        u.width = c1 - c0;
+        pixels += (double)system_height * (c1 - c0);
+    }
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    int rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    asr::UnrollSystem *d_table = nullptr;
+    const size_t bytes = table.size() * sizeof(asr::UnrollSystem);
+    ASR_HIP(ctx, hipMalloc((void **)&d_table, bytes));
+    hipError_t e = hipMemcpyAsync(d_table, table.data(), bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        ProfScope ps(ctx, "unroll_systems", 0, 0.0, 5.0 * pixels);
+        e = asr::launch_unroll_systems(ctx->stream, (const uint8_t *)pages_dev, d_table, n_systems, system_height, strips_dev);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d_table);
+    if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "unroll_systems: %s", hipGetErrorString(e));
+    return mark_main(ctx);
+}
+
+int asr_spectrogram_batch_dev(asr_ctx *ctx, const float *samples_dev, int64_t samples_floats,
+                              const int64_t *sample_offsets, const int64_t *sample_counts, const int64_t *n_frames,
+                              const int64_t *out_offsets, int n_recordings, int frame_size, double hop,
+                              const float *window, const int32_t *fb_start, const int32_t *fb_len,
+                              const float *fb_weights, int n_filters, float mul, float add, int transposed,
+                              float *out_dev, int64_t out_floats) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_recordings < 0 || samples_floats < 0 || out_floats < 0 || frame_size < 64 || frame_size > 8192 ||
+        (frame_size & (frame_size - 1)) || !(hop > 0.0) || n_filters < 1 || n_filters > 4096)
+        return fail(ctx, ASR_ERR_INVALID, "spectrogram_batch: bad sizes (frame_size must be a power of two in [64, 8192])");
+    if (n_recordings == 0) return ASR_OK;
+    if (!sample_offsets || !sample_counts || !n_frames || !out_offsets)
+        return fail(ctx, ASR_ERR_INVALID, "spectrogram_batch: NULL argument");
+    std::vector<int64_t> tab((size_t)4 * n_recordings + 1);      // frame_first (n + 1) | sample_off | sample_cnt | out_off
+    int64_t *first = tab.data(), *s_off = first + n_recordings + 1, *s_cnt = s_off + n_recordings,
+            *o_off = s_cnt + n_recordings;
+    int64_t total = 0;
+    for (int i = 0; i < n_recordings; ++i) {
+        if (sample_counts[i] < 0 || n_frames[i] < 0 || sample_offsets[i] < 0 || out_offsets[i] < 0 ||
+            sample_offsets[i] + sample_counts[i] > samples_floats ||
+            out_offsets[i] + n_frames[i] * (int64_t)n_filters > out_floats)
+            return fail(ctx, ASR_ERR_INVALID, "spectrogram_batch: recording %d (%lld samples at %lld, %lld frames at %lld) "
+                        "outside its buffers (%lld / %lld floats)", i, (long long)sample_counts[i],
+                        (long long)sample_offsets[i], (long long)n_frames[i], (long long)out_offsets[i],
+                        (long long)samples_floats, (long long)out_floats);
+        first[i] = total;
+        s_off[i] = sample_offsets[i];
+        s_cnt[i] = sample_counts[i];
+        o_off[i] = out_offsets[i];
+        total += n_frames[i];
+    }
+    first[n_recordings] = total;
+    if (total == 0) return ASR_OK;
+    if (!samples_dev || !window || !fb_start || !fb_len || !fb_weights || !out_dev)
+        return fail(ctx, ASR_ERR_INVALID, "spectrogram_batch: NULL argument");
+    std::vector<int32_t> off(n_filters);
+    int64_t total_w = 0;
+    int max_bin = 0;
+    for (int f = 0; f < n_filters; ++f) {
+        if (fb_start[f] < 0 || fb_len[f] < 0 || fb_start[f] + fb_len[f] > frame_size / 2)
+            return fail(ctx, ASR_ERR_INVALID, "spectrogram_batch: filter %d covers bins [%d, %d) outside [0, %d)", f,
+                        fb_start[f], fb_start[f] + fb_len[f], frame_size / 2);
+        off[f] = (int32_t)total_w;
+        total_w += fb_len[f];
+        max_bin = std::max(max_bin, fb_start[f] + fb_len[f]);
+    }
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    int rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    char *buf = nullptr;
+    const size_t b_tab = tab.size() * 8, b_win = (size_t)frame_size * 4, b_i = (size_t)n_filters * 4,
+                 b_w = (size_t)std::max<int64_t>(total_w, 1) * 4;
+    ASR_HIP(ctx, hipMalloc((void **)&buf, b_tab + b_win + 3 * b_i + b_w));
+    int64_t *d_tab = (int64_t *)buf;
+    float *d_win = (float *)(buf + b_tab);
+    int32_t *d_start = (int32_t *)(buf + b_tab + b_win), *d_len = d_start + n_filters, *d_off = d_len + n_filters;
+    float *d_w = (float *)(buf + b_tab + b_win + 3 * b_i);
+    hipError_t e = hipMemcpyAsync(d_tab, tab.data(), b_tab, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_win, window, b_win, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_start, fb_start, b_i, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_len, fb_len, b_i, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_off, off.data(), b_i, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && total_w) e = hipMemcpyAsync(d_w, fb_weights, (size_t)total_w * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        ProfScope ps(ctx, "spectrogram_batch", 0, 4.0 * frame_size * (double)max_bin * (double)total,
+                     4.0 * hop * (double)total);
+        e = asr::launch_spectrogram_batch(ctx->stream, samples_dev, d_tab, d_tab + n_recordings + 1,
+                                          d_tab + 2 * n_recordings + 1, d_tab + 3 * n_recordings + 1, n_recordings, total,
+                                          d_win, frame_size, hop, max_bin, d_start, d_len, d_off, d_w, n_filters, mul, add,
+                                          out_dev, transposed);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(buf);
+    if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "spectrogram_batch: %s", hipGetErrorString(e));
+    return mark_main(ctx);
+}

@@ -247,6 +247,24 @@ hipError_t launch_spectrogram(hipStream_t s, const float *samples, int64_t n_sam
                               double hop, int max_bin, const int32_t *fb_start, const int32_t *fb_len,
                               const int32_t *fb_off, const float *fb_w, int nf, float mul, float add, float *out,
                               int64_t n_frames, int transposed);
+// the same for n_rec recordings in one launch: frame_first (n_rec + 1 running frame counts), sample_off / sample_cnt /
+// out_off (per recording, in floats) on the device; bit-identical per recording with launch_spectrogram
+hipError_t launch_spectrogram_batch(hipStream_t s, const float *samples, const int64_t *frame_first,
+                                    const int64_t *sample_off, const int64_t *sample_cnt, const int64_t *out_off, int n_rec,
+                                    int64_t total_frames, const float *window, int frame_size, double hop, int max_bin,
+                                    const int32_t *fb_start, const int32_t *fb_len, const int32_t *fb_off, const float *fb_w,
+                                    int nf, float mul, float add, float *out, int transposed);
+// unrolled score strips (umc_kernels.hip): one row of the table per staff system, offsets resolved by the host
+struct UnrollSystem {
+    int64_t src;            // byte offset of (r0, c0) in the uint8 page buffer
+    int64_t dst;            // float offset of (0, dst_col) in the strip buffer
+    int32_t src_stride;     // page width
+    int32_t dst_stride;     // strip width
+    int32_t rows;           // r1 - r0: strip rows >= rows repeat source row rows - 1
+    int32_t width;          // c1 - c0
+};
+hipError_t launch_unroll_systems(hipStream_t s, const uint8_t *pages, const UnrollSystem *systems_dev, int n_systems,
+                                 int system_height, float *strips);
 // batch assembly of the training pool: desc_dev holds n x 9 doubles (see piece_vote_kernels.hip)
 hipError_t launch_gather_windows(hipStream_t s, const float *src, const double *desc_dev, int n, int out_h, int out_w,
                                  float *out);

@@ -144,44 +144,84 @@ struct SpecArgs {
     float *out; int64_t n_frames; int transposed;      // out: (n_frames, nf) or (nf, n_frames)
 };
 
-__global__ __launch_bounds__(256) void spectrogram_kernel(SpecArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float sl[];
-    const int F = a.frame_size;
-    float *x = sl, *tc = sl + F, *ts = sl + 2 * F, *mag = sl + 3 * F;
-    const int tid = threadIdx.x;
-    for (int t = tid; t < F; t += 256) {
+// twiddle table of the workgroup: tc[t] = cos(2 pi t / F), ts[t] = sin(2 pi t / F)
+__device__ __forceinline__ void spectrogram_twiddles(int F, float *tc, float *ts) {
+    for (int t = threadIdx.x; t < F; t += 256) {
         double s, c;
         sincospi(2.0 * (double)t / (double)F, &s, &c);
         tc[t] = (float)c; ts[t] = (float)s;
     }
-    for (int64_t frame = blockIdx.x; frame < a.n_frames; frame += gridDim.x) {
-        const int64_t start = (int64_t)((double)frame * a.hop);        // int(index * hop_size), origin 'future'
-        __syncthreads();
-        for (int t = tid; t < F; t += 256) {
-            const int64_t i = start + t;
-            x[t] = (i < a.n_samples ? a.samples[i] : 0.0f) * a.window[t];
+}
+
+// one frame of one recording (samples[0 .. n_samples), output of n_frames frames at out), by the whole workgroup: the
+// only place the arithmetic of a frame is written down - spectrogram_kernel and spectrogram_batch_kernel both call it,
+// which is what makes the batched result bit-identical with the single one
+__device__ __forceinline__ void spectrogram_frame(const SpecArgs &a, const float *__restrict__ samples, int64_t n_samples,
+                                                  int64_t frame, float *__restrict__ out, int64_t n_frames, float *x,
+                                                  const float *tc, const float *ts, float *mag) {
+    const int F = a.frame_size;
+    const int tid = threadIdx.x;
+    const int64_t start = (int64_t)((double)frame * a.hop);        // int(index * hop_size), origin 'future'
+    __syncthreads();
+    for (int t = tid; t < F; t += 256) {
+        const int64_t i = start + t;
+        x[t] = (i < n_samples ? samples[i] : 0.0f) * a.window[t];
+    }
+    __syncthreads();
+    for (int k = tid; k < a.max_bin; k += 256) {
+        float re = 0.0f, im = 0.0f;
+        int idx = 0;
+        for (int n = 0; n < F; ++n) {
+            re = fmaf(x[n], tc[idx], re);
+            im = fmaf(-x[n], ts[idx], im);
+            idx = (idx + k) & (F - 1);                              // (k * n) mod F, F a power of two
         }
-        __syncthreads();
-        for (int k = tid; k < a.max_bin; k += 256) {
-            float re = 0.0f, im = 0.0f;
-            int idx = 0;
-            for (int n = 0; n < F; ++n) {
-                re = fmaf(x[n], tc[idx], re);
-                im = fmaf(-x[n], ts[idx], im);
-                idx = (idx + k) & (F - 1);                              // (k * n) mod F, F a power of two
-            }
-            mag[k] = sqrtf(re * re + im * im);
+        mag[k] = sqrtf(re * re + im * im);
+    }
+    __syncthreads();
+    for (int f = tid; f < a.nf; f += 256) {
+        const float *w = a.fb_w + a.fb_off[f];
+        const int b0 = a.fb_start[f];
+        float s = 0.0f;
+        for (int q = 0; q < a.fb_len[f]; ++q) s = fmaf(mag[b0 + q], w[q], s);
+        const float v = log10f(a.mul * s + a.add);
+        if (a.transposed) out[(int64_t)f * n_frames + frame] = v;
+        else out[frame * a.nf + f] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void spectrogram_kernel(SpecArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float sl[];
+    const int F = a.frame_size;
+    float *x = sl, *tc = sl + F, *ts = sl + 2 * F, *mag = sl + 3 * F;
+    spectrogram_twiddles(F, tc, ts);
+    for (int64_t frame = blockIdx.x; frame < a.n_frames; frame += gridDim.x)
+        spectrogram_frame(a, a.samples, a.n_samples, frame, a.out, a.n_frames, x, tc, ts, mag);
+}
+
+// many recordings in one launch (asr_spectrogram_batch_dev): the frames of all recordings are numbered through,
+// frame_first[r] = number of the first frame of recording r (n_rec + 1 entries, ascending; equal neighbours = a
+// recording without frames).  a.samples / a.out are the bases of the concatenated buffers; a.n_samples / a.n_frames
+// are unused.
+struct SpecBatchArgs {
+    const int64_t *frame_first, *sample_off, *sample_cnt, *out_off;
+    int n_rec; int64_t total_frames;
+};
+
+__global__ __launch_bounds__(256) void spectrogram_batch_kernel(SpecArgs a, SpecBatchArgs b) {
+    extern __shared__ __attribute__((aligned(16))) float sl[];
+    const int F = a.frame_size;
+    float *x = sl, *tc = sl + F, *ts = sl + 2 * F, *mag = sl + 3 * F;
+    spectrogram_twiddles(F, tc, ts);
+    for (int64_t g = blockIdx.x; g < b.total_frames; g += gridDim.x) {
+        int lo = 0, hi = b.n_rec - 1;                               // last r with frame_first[r] <= g
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (b.frame_first[mid] <= g) lo = mid; else hi = mid - 1;
         }
-        __syncthreads();
-        for (int f = tid; f < a.nf; f += 256) {
-            const float *w = a.fb_w + a.fb_off[f];
-            const int b0 = a.fb_start[f];
-            float s = 0.0f;
-            for (int q = 0; q < a.fb_len[f]; ++q) s = fmaf(mag[b0 + q], w[q], s);
-            const float v = log10f(a.mul * s + a.add);
-            if (a.transposed) a.out[(int64_t)f * a.n_frames + frame] = v;
-            else a.out[frame * a.nf + f] = v;
-        }
+        const int64_t n_frames = b.frame_first[lo + 1] - b.frame_first[lo];
+        spectrogram_frame(a, a.samples + b.sample_off[lo], b.sample_cnt[lo], g - b.frame_first[lo], a.out + b.out_off[lo],
+                          n_frames, x, tc, ts, mag);
     }
 }
 
@@ -197,6 +237,22 @@ hipError_t launch_spectrogram(hipStream_t s, const float *samples, int64_t n_sam
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     const int grid = (int)std::min<int64_t>(n_frames, 2048);
     hipLaunchKernelGGL(spectrogram_kernel, dim3(grid), dim3(256), lds, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_spectrogram_batch(hipStream_t s, const float *samples, const int64_t *frame_first,
+                                    const int64_t *sample_off, const int64_t *sample_cnt, const int64_t *out_off, int n_rec,
+                                    int64_t total_frames, const float *window, int frame_size, double hop, int max_bin,
+                                    const int32_t *fb_start, const int32_t *fb_len, const int32_t *fb_off, const float *fb_w,
+                                    int nf, float mul, float add, float *out, int transposed) {
+    if (total_frames == 0 || n_rec == 0) return hipSuccess;
+    SpecArgs a{samples, 0, window, frame_size, hop, max_bin, fb_start, fb_len, fb_off, fb_w, nf, mul, add, out, 0, transposed};
+    SpecBatchArgs b{frame_first, sample_off, sample_cnt, out_off, n_rec, total_frames};
+    const size_t lds = (size_t)(3 * frame_size + max_bin) * sizeof(float);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(spectrogram_batch_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    const int grid = (int)std::min<int64_t>(total_frames, 2048);
+    hipLaunchKernelGGL(spectrogram_batch_kernel, dim3(grid), dim3(256), lds, s, a, b);
     return hipGetLastError();
 }
 

@@ -8,9 +8,103 @@ the resident data base, vote histogram and selection (csrc/piece_vote_kernels.hi
 from __future__ import annotations
 
 import pickle
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
+
+#: 2-d float32 arrays that already lie on the device, back to back in one buffer: `buf` a DeviceBuffer, `offsets[i]`
+#: the first float of array i, `shapes[i]` its (rows, columns).  Engine-side producers: sheet_utils.umc.load_umc_sheets
+#: (return_device=True; unrolled strips) and SpectrogramProcessor.process_many_dev (spectrograms).  Every function
+#: here that takes a list of strips or spectrograms takes one of these instead (a plain 3-tuple works too).
+DeviceArrays = namedtuple("DeviceArrays", ["buf", "offsets", "shapes"])
+
+
+def _is_device(inputs):
+    return isinstance(inputs, tuple) and len(inputs) == 3 and hasattr(inputs[0], "ptr")
+
+
+def _to_device(engine, inputs):
+    """-> (DeviceArrays, owned): host arrays are concatenated as float32 and uploaded once (owned: free the buffer
+    afterwards); a device handle is passed through."""
+    if _is_device(inputs):
+        buf, offsets, shapes = inputs
+        shapes = [tuple(int(v) for v in shp) for shp in shapes]
+        if len(offsets) != len(shapes):
+            raise ValueError("device handle: %d offsets for %d shapes" % (len(offsets), len(shapes)))
+        return DeviceArrays(buf, [int(o) for o in offsets], shapes), False
+    arrs = []
+    for i, x in enumerate(inputs):
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2:
+            raise ValueError("input %d: expected a 2-d array, got shape %r" % (i, x.shape))
+        arrs.append(x)
+    sizes = [a.size for a in arrs]
+    offsets = [int(o) for o in np.concatenate([[0], np.cumsum(sizes)[:-1]])] if arrs else []
+    flat = np.concatenate([a.ravel() for a in arrs]) if arrs else np.zeros(0, np.float32)
+    buf = engine.alloc(max(flat.nbytes, 4)).upload(flat)
+    return DeviceArrays(buf, offsets, [a.shape for a in arrs]), True
+
+
+def _identity_desc(off, rows, T, r0, starts):
+    """identity gather of the windows at columns `starts`: out[y, x] = src[off + (r0 + y) * T + start + x]"""
+    d = np.zeros((len(starts), 9), np.float64)
+    d[:, 0], d[:, 1], d[:, 2], d[:, 3], d[:, 4] = off, T, r0, 1.0, rows - 1
+    d[:, 5], d[:, 6], d[:, 7] = starts, 1.0, T - 1
+    return d
+
+
+def db_window_plan(shapes, offsets, win_shape, centre_rows):
+    """The windows of initialize_sheet_db_from_imges / initialize_audio_db_from_specs (audio_sheet_server.py:403-494)
+    for arrays of `shapes` at float `offsets` of one buffer -> (per array its window columns, gather descriptors
+    (n, 9), ids (n,) int32).  Columns: np.arange(0, W - w, w // 4) - W - w itself is excluded and an array with
+    W <= w has no window; rows: the central win_h of a sheet (centre_rows, :468-469), 0.. of a spectrogram."""
+    win_h, win_w = win_shape
+    indices, desc, ids = [], [], []
+    for i, ((rows, T), off) in enumerate(zip(shapes, offsets)):
+        r0 = rows // 2 - win_h // 2 if centre_rows else 0
+        if r0 < 0 or r0 + win_h > rows:
+            raise ValueError("input %d has %d rows, a window needs %d" % (i, rows, win_h))
+        idx = np.arange(0, T - win_w, win_w // 4)
+        indices.append(idx)
+        desc.append(_identity_desc(off, rows, T, r0, idx))
+        ids.append(np.full(len(idx), i, np.int32))
+    return (indices, np.concatenate(desc) if desc else np.zeros((0, 9), np.float64),
+            np.concatenate(ids) if ids else np.zeros(0, np.int32))
+
+
+def query_window_plan(shapes, offsets, win_shape, n_samples, centre_rows):
+    """window_plan for arrays described by shape and offset only -> (per array its window starts, descriptors)"""
+    win_h, win_w = win_shape
+    starts, desc = [], []
+    for i, ((rows, T), off) in enumerate(zip(shapes, offsets)):
+        r0 = rows // 2 - win_h // 2 if centre_rows else 0
+        if T < win_w:
+            raise ValueError("input %d has %d columns, a window needs %d" % (i, T, win_w))
+        if r0 < 0 or r0 + win_h > rows:
+            raise ValueError("input %d has %d rows, a window needs %d" % (i, rows, win_h))
+        st = np.linspace(start=0, stop=T - win_w, num=n_samples).astype(np.int32)
+        starts.append(st)
+        desc.append(_identity_desc(off, rows, T, r0, st))
+    return starts, (np.concatenate(desc) if desc else np.zeros((0, 9), np.float64))
+
+
+def embed_windows_dev(engine, view, src_ptr, src_floats, desc, win_shape, d_win, d_codes, chunk, after_chunk=None):
+    """cut-and-embed of a window table: per chunk of `chunk` descriptors one gather_windows_dev into d_win and one
+    embed_view{1,2}_dev into rows s.. of d_codes; after_chunk(s, m) runs after each chunk (the query path's top-k)."""
+    from . import _lib
+    win_h, win_w = win_shape
+    if (getattr(engine.cfg, "h%d" % view), getattr(engine.cfg, "w%d" % view)) != (win_h, win_w):
+        engine.set_input_size(view, win_h, win_w)
+    n_win = len(desc)
+    for s in range(0, n_win, chunk):
+        m = min(chunk, n_win - s)
+        engine.gather_windows_dev(src_ptr, src_floats, desc[s:s + m], win_h, win_w, d_win.ptr)
+        if view == 2:
+            engine.embed_view2_dev(d_win.ptr, m, d_codes.offset(s * 32 * 4))
+        else:
+            engine.embed_view1_dev(d_win.ptr, _lib.IN_F32_RAW, m, d_codes.offset(s * 32 * 4))
+        if after_chunk is not None:
+            after_chunk(s, m)
 
 
 class EmbeddingDB(object):
@@ -126,6 +220,51 @@ class EmbeddingDB(object):
         snippets = np.zeros((0, win_h // 2, win_w // 2), dtype=np.uint8)
         return cls(engine, codes, pool.train_entities[:, 0], id_to_name, snippets)
 
+    @classmethod
+    def _from_arrays(cls, engine, names, arrays, view, win_shape, centre_rows, max_windows):
+        names = list(names)
+        dev, owned = _to_device(engine, arrays)
+        try:
+            if len(names) != len(dev.shapes):
+                raise ValueError("%d names for %d pieces" % (len(names), len(dev.shapes)))
+            if max_windows < 1:
+                raise ValueError("max_windows must be >= 1")
+            _, desc, ids = db_window_plan(dev.shapes, dev.offsets, win_shape, centre_rows)
+            n = len(desc)
+            codes = np.zeros((0, 32), np.float32)
+            if n:
+                win_h, win_w = win_shape
+                chunk = min(n, int(max_windows))
+                d_win = engine.alloc(chunk * win_h * win_w * 4)
+                d_codes = engine.alloc(n * 32 * 4)
+                try:
+                    embed_windows_dev(engine, view, dev.buf.ptr, dev.buf.nbytes // 4, desc, win_shape, d_win, d_codes,
+                                      chunk)
+                    codes = d_codes.download((n, 32), np.float32)
+                finally:
+                    d_win.free()
+                    d_codes.free()
+        finally:
+            if owned:
+                dev.buf.free()
+        snippets = np.zeros((0, win_shape[0] // 2, win_shape[1] // 2), dtype=np.uint8)
+        return cls(engine, codes, ids, {i: name for i, name in enumerate(names)}, snippets)
+
+    @classmethod
+    def from_images(cls, engine, names, strips, sheet_shape=(160, 200), max_windows=4096):
+        """initialize_sheet_db_from_imges (:447-494): the data base of unrolled score strips (0..255 values).  Per piece
+        the windows at columns np.arange(0, W - w, w // 4) of the central sheet_shape[0] rows, cut on the device
+        max_windows at a time and embedded with one call per chunk; ids = piece index, id_to_name = {index: name},
+        empty snippets (keep_snippets=False).  A strip with W <= w has no window and no codes.  `strips`: a list of
+        host arrays (uploaded once) or a DeviceArrays handle."""
+        return cls._from_arrays(engine, names, strips, 1, tuple(sheet_shape), True, max_windows)
+
+    @classmethod
+    def from_specs(cls, engine, names, spectrograms, spec_shape=(92, 42), max_windows=4096):
+        """initialize_audio_db_from_specs (:403-445): as from_images for (bins, frames) spectrograms, stride
+        spec_shape[1] // 4, rows from 0."""
+        return cls._from_arrays(engine, names, spectrograms, 2, tuple(spec_shape), False, max_windows)
+
     def save(self, path):
         with open(path, "wb") as fp:
             pickle.dump([self.codes, self.ids.astype(np.int64), self.id_to_name, self.snippets], fp, protocol=2)
@@ -199,13 +338,9 @@ def window_plan(inputs, win_shape, n_samples, centre_rows):
         if r0 < 0 or r0 + win_h > rows:
             raise ValueError("input %d has %d rows, a window needs %d" % (i, rows, win_h))
         st = np.linspace(start=0, stop=T - win_w, num=n_samples).astype(np.int32)
-        # identity gather: out[y, x] = src[off + (r0 + y) * T + start + x]
-        d = np.zeros((len(st), 9), np.float64)
-        d[:, 0], d[:, 1], d[:, 2], d[:, 3], d[:, 4] = off, T, r0, 1.0, rows - 1
-        d[:, 5], d[:, 6], d[:, 7] = st, 1.0, T - 1
         srcs.append(x.ravel())
         starts.append(st)
-        desc.append(d)
+        desc.append(_identity_desc(off, rows, T, r0, st))
         off += x.size
     flat = np.concatenate(srcs) if srcs else np.zeros(0, np.float32)
     return flat, starts, (np.concatenate(desc) if desc else np.zeros((0, 9), np.float64))
@@ -213,14 +348,21 @@ def window_plan(inputs, win_shape, n_samples, centre_rows):
 
 def _detect_batch(engine, db, inputs, view, win_shape, centre_rows, top_k, n_candidates, n_samples, targets,
                   max_windows):
-    from . import _lib
-    inputs = list(inputs)
+    on_device = _is_device(inputs)
+    if not on_device:
+        inputs = list(inputs)
+    n_in = len(inputs[2]) if on_device else len(inputs)
     if n_samples < 1 or n_candidates < 1 or top_k < 1 or max_windows < 1:
         raise ValueError("n_samples, n_candidates, top_k and max_windows must be >= 1")
-    if targets is not None and len(targets) != len(inputs):
-        raise ValueError("%d targets for %d inputs" % (len(targets), len(inputs)))
-    flat, _, desc = window_plan(inputs, win_shape, n_samples, centre_rows)
-    n_in = len(inputs)
+    if targets is not None and len(targets) != n_in:
+        raise ValueError("%d targets for %d inputs" % (len(targets), n_in))
+    if on_device:
+        dev, _ = _to_device(engine, inputs)
+        _, desc = query_window_plan(dev.shapes, dev.offsets, win_shape, n_samples, centre_rows)
+        d_src, src_floats = None, dev.buf.nbytes // 4
+    else:
+        flat, _, desc = window_plan(inputs, win_shape, n_samples, centre_rows)
+        src_floats = flat.size
     if n_in == 0:
         return ([], np.zeros(0, np.int32), np.zeros(0, np.float64)) if targets is not None else []
     win_h, win_w = win_shape
@@ -228,25 +370,24 @@ def _detect_batch(engine, db, inputs, view, win_shape, centre_rows, top_k, n_can
     chunk = min(n_win, int(max_windows))
     if (getattr(engine.cfg, "h%d" % view), getattr(engine.cfg, "w%d" % view)) != (win_h, win_w):
         engine.set_input_size(view, win_h, win_w)
-    d_src = engine.alloc(flat.nbytes).upload(flat)
+    if not on_device:
+        d_src = engine.alloc(flat.nbytes).upload(flat)
     d_win = engine.alloc(chunk * win_h * win_w * 4)
     d_codes = engine.alloc(n_win * 32 * 4)
     d_idx, d_dist = engine.alloc(n_win * n_candidates * 4), engine.alloc(n_win * n_candidates * 8)
+
+    def topk(s, m):
+        db.topk_dev(d_codes.offset(s * 32 * 4), m, n_candidates, d_idx.offset(s * n_candidates * 4),
+                    d_dist.offset(s * n_candidates * 8))
     try:
-        for s in range(0, n_win, chunk):
-            m = min(chunk, n_win - s)
-            engine.gather_windows_dev(d_src.ptr, flat.size, desc[s:s + m], win_h, win_w, d_win.ptr)
-            if view == 2:
-                engine.embed_view2_dev(d_win.ptr, m, d_codes.offset(s * 32 * 4))
-            else:
-                engine.embed_view1_dev(d_win.ptr, _lib.IN_F32_RAW, m, d_codes.offset(s * 32 * 4))
-            db.topk_dev(d_codes.offset(s * 32 * 4), m, n_candidates, d_idx.offset(s * n_candidates * 4),
-                        d_dist.offset(s * n_candidates * 8))
+        embed_windows_dev(engine, view, dev.buf.ptr if on_device else d_src.ptr, src_floats, desc, win_shape, d_win,
+                          d_codes, chunk, after_chunk=topk)
         pieces, counts, n_out, ranks, ratios = engine.piece_vote_batch_dev(
             d_idx.ptr, n_in, n_samples * n_candidates, db._d_ids.ptr, len(db), db.n_pieces, top_k, targets)
     finally:
         for b in (d_src, d_win, d_codes, d_idx, d_dist):
-            b.free()
+            if b is not None:
+                b.free()
     results = []
     for g in range(n_in):
         c = counts[g, :n_out[g]]
@@ -260,7 +401,8 @@ def detect_scores(engine, sheet_db, spectrograms, top_k=1, n_candidates=1, n_sam
     """detect_score for a list of spectrograms of any lengths: all windows cut on the device in one gather per chunk of
     max_windows, one embedding and one top-k call per chunk, one asr_piece_vote_batch_dev call for all inputs.
     -> [(piece names, normalised votes)] per input, each equal to detect_score's; with targets (one piece id per
-    input): (that list, ranks, ratios) of the reference's full-eval rule (see full_eval_rank)."""
+    input): (that list, ranks, ratios) of the reference's full-eval rule (see full_eval_rank).  `spectrograms`: a
+    list of host arrays or a DeviceArrays handle (SpectrogramProcessor.process_many_dev) - no upload then."""
     return _detect_batch(engine, sheet_db, spectrograms, 2, spec_shape, False, top_k, n_candidates, n_samples, targets,
                          max_windows)
 
@@ -268,7 +410,7 @@ def detect_scores(engine, sheet_db, spectrograms, top_k=1, n_candidates=1, n_sam
 def detect_performances(engine, audio_db, sheets, top_k=1, n_candidates=1, n_samples=100, sheet_shape=(160, 200),
                         targets=None, max_windows=4096):
     """detect_performance for a list of unrolled score strips (central sheet_shape[0] rows), batched as
-    detect_scores."""
+    detect_scores.  `sheets`: host arrays or a DeviceArrays handle (load_umc_sheets(..., return_device=True))."""
     return _detect_batch(engine, audio_db, sheets, 1, sheet_shape, True, top_k, n_candidates, n_samples, targets,
                          max_windows)
 

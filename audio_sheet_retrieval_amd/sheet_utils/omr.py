@@ -280,6 +280,90 @@ def unwrap_systems(page, systems, system_height=SYSTEM_HEIGHT):
     return unwrapped_sheet
 
 
+def unroll_rows(page_shape, systems, system_height=SYSTEM_HEIGHT):
+    """The integer rules of unwrap_systems without the copy: one (r0, r1, c0, c1, pad) per kept system - rows
+    r0..r1-1, columns c0..c1-1 of the page, `pad` edge rows below them - in order; skipped systems print the
+    reference's message.  Slices resolve as numpy resolves page[r0:r1, c0:c1] on a page of page_shape."""
+    h, w = page_shape
+    rows = []
+    for system in systems:
+        r0 = int(np.mean([system[0, 0], system[2, 0]])) - system_height // 2
+        r1 = r0 + system_height
+        c0 = int(system[0, 1])
+        c1 = int(system[1, 1])
+        r0 = max(0, r0)
+        r1 = min(r1, h)
+        r0 = max(r0, r1 - system_height)
+        r0, r1, _ = slice(r0, r1).indices(h)
+        c0, c1, _ = slice(c0, c1).indices(w)
+        n_rows, n_cols = max(0, r1 - r0), max(0, c1 - c0)
+        if n_rows > system_height:
+            raise ValueError("system rows %d:%d exceed the system height %d" % (r0, r1, system_height))
+        to_pad = system_height - n_rows
+        if to_pad > (0.1 * system_height):
+            print("Problem in system padding!!!")
+            continue
+        if n_cols == 0:
+            continue                         # an empty slice adds no column
+        rows.append((r0, r1, c0, c1, to_pad))
+    return rows
+
+
+class DevicePages(object):
+    """uint8 pages back to back in one device buffer, as asr_seg_predict_dev (IN_U8_RAW) and asr_unroll_systems_dev
+    read them: uploaded once, used by both networks and by the unroll."""
+
+    def __init__(self, engine, pages):
+        flat = [np.ascontiguousarray(p, dtype=np.uint8) for p in pages]
+        for p in flat:
+            if p.ndim != 2:
+                raise ValueError("pages are 2-D, got shape %s" % (p.shape,))
+        self.engine = engine
+        self.sizes = np.asarray([p.size for p in flat], np.int64)
+        self.offsets = np.concatenate([[0], np.cumsum(self.sizes)[:-1]]).astype(np.int64)
+        self.heights = np.asarray([p.shape[0] for p in flat], np.int32)
+        self.widths = np.asarray([p.shape[1] for p in flat], np.int32)
+        self.nbytes = int(self.sizes.sum())
+        host = np.concatenate([p.ravel() for p in flat]) if flat else np.zeros(0, np.uint8)
+        self.buf = engine.alloc(max(self.nbytes, 4)).upload(host)
+
+    def __len__(self):
+        return len(self.sizes)
+
+    def free(self):
+        self.buf.free()
+
+
+def unroll_systems_dev(dev_pages, page_rows, piece_of_page, n_pieces, system_height=SYSTEM_HEIGHT):
+    """unwrap_systems + hstack for all pages of all pieces in one device call (asr_unroll_systems_dev).
+    page_rows[p]: unroll_rows of page p, or None for a page that is not unrolled; piece_of_page[p]: index of the piece
+    page p belongs to (pages of a piece in order).  -> (DeviceBuffer of the float32 strips, float offsets, shapes
+    [(system_height, W_piece)]): piece_identification.DeviceArrays fields."""
+    table, widths = [], np.zeros(n_pieces, np.int64)
+    for p, rows in enumerate(page_rows):
+        if rows is None:
+            continue
+        q = int(piece_of_page[p])
+        for r0, r1, c0, c1, pad in rows:
+            table.append((p, r0, r1, c0, c1, pad, q, widths[q]))
+            widths[q] += c1 - c0
+    if widths.size and widths.max() > np.iinfo(np.int32).max:
+        raise ValueError("a strip of %d columns is too wide" % widths.max())
+    offsets = np.concatenate([[0], np.cumsum(widths * system_height)[:-1]]).astype(np.int64) if n_pieces else \
+        np.zeros(0, np.int64)
+    total = int(widths.sum()) * system_height
+    eng = dev_pages.engine
+    strips = eng.alloc(max(total * 4, 4))
+    try:
+        eng.unroll_systems_dev(dev_pages.buf.ptr, dev_pages.nbytes, dev_pages.offsets, dev_pages.heights,
+                               dev_pages.widths, np.asarray(table, np.int32).reshape(-1, 8), system_height, offsets,
+                               widths.astype(np.int32), strips.ptr, total)
+    except Exception:
+        strips.free()
+        raise
+    return strips, [int(o) for o in offsets], [(system_height, int(w)) for w in widths]
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # networks
 
@@ -354,32 +438,41 @@ class SegmentationNetwork(object):
     def predict_pages(self, pages, overlap=0.5, in_mode=IN_F32_PREPARED):
         """float64 probability maps of a list of 2-D pages in ONE device call (every tile of every page in one forward,
         chunked under ASR_OMR_BUDGET_MB).  in_mode: IN_F32_PREPARED (float32 pages as prepare_image leaves them),
-        IN_F32_RAW / IN_U8_RAW (prepare_image on the device)."""
+        IN_F32_RAW / IN_U8_RAW (prepare_image on the device).  `pages` may be a DevicePages (raw uint8 pages that are
+        already on the device; in_mode is IN_U8_RAW then)."""
         if self.handle is None:
             raise RuntimeError("SegmentationNetwork: load() the parameters first")
-        if not pages:
+        if len(pages) == 0:
             return []
-        dt = np.uint8 if in_mode == IN_U8_RAW else np.float32
-        flat = [np.ascontiguousarray(p, dtype=dt) for p in pages]
-        for p in flat:
-            if p.ndim != 2:
-                raise ValueError("pages are 2-D, got shape %s" % (p.shape,))
-        sizes = np.asarray([p.size for p in flat], np.int64)
-        offs = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
-        hs = np.asarray([p.shape[0] for p in flat], np.int32)
-        ws = np.asarray([p.shape[1] for p in flat], np.int32)
         eng = self.engine
-        host = np.concatenate([p.ravel() for p in flat])
-        x = eng.alloc(host.nbytes).upload(host)
+        if isinstance(pages, DevicePages):
+            if pages.engine is not eng:
+                raise ValueError("the pages were uploaded through another engine")
+            in_mode, x = IN_U8_RAW, None
+            ptr, sizes, offs, hs, ws = pages.buf.ptr, pages.sizes, pages.offsets, pages.heights, pages.widths
+        else:
+            dt = np.uint8 if in_mode == IN_U8_RAW else np.float32
+            flat = [np.ascontiguousarray(p, dtype=dt) for p in pages]
+            for p in flat:
+                if p.ndim != 2:
+                    raise ValueError("pages are 2-D, got shape %s" % (p.shape,))
+            sizes = np.asarray([p.size for p in flat], np.int64)
+            offs = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+            hs = np.asarray([p.shape[0] for p in flat], np.int32)
+            ws = np.asarray([p.shape[1] for p in flat], np.int32)
+            host = np.concatenate([p.ravel() for p in flat])
+            x = eng.alloc(host.nbytes).upload(host)
+            ptr = x.ptr
         out = eng.alloc(int(sizes.sum()) * 8)
         try:
-            eng._check(eng.lib.asr_seg_predict_dev(eng.ctx, self.handle, c_void_p(x.ptr),
-                                                   in_mode, offs.ctypes.data, hs.ctypes.data, ws.ctypes.data, len(flat),
+            eng._check(eng.lib.asr_seg_predict_dev(eng.ctx, self.handle, c_void_p(ptr),
+                                                   in_mode, offs.ctypes.data, hs.ctypes.data, ws.ctypes.data, len(sizes),
                                                    float(overlap), c_void_p(out.ptr)))
             eng.sync()
             res = out.download((int(sizes.sum()),), np.float64)
         finally:
-            x.free()
+            if x is not None:
+                x.free()
             out.free()
         return [res[o:o + s].reshape(h, w) for o, s, h, w in zip(offs, sizes, hs, ws)]
 
@@ -420,12 +513,16 @@ class OpticalMusicRecognizer(object):
         bar_probs = self.bar_detector.predict_proba(img[np.newaxis, np.newaxis]) if self.bar_detector else None
         return systems_from_maps(img, system_probs, bar_probs)
 
-    def detect_systems_pages(self, pages, in_mode=IN_F32_PREPARED, prepared=None):
+    def detect_systems_pages(self, pages, in_mode=IN_F32_PREPARED, prepared=None, dev_pages=None):
         """detect_systems for many pages: one device call per network.  pages: 2-D arrays (prepared float32, or raw
         uint8 with in_mode=IN_U8_RAW).  Returns one entry per page: the corner array, or the exception the reference's
-        detect_systems would have raised on that page."""
-        sys_maps = self.system_detector.predict_pages(pages, in_mode=in_mode)
-        bar_maps = self.bar_detector.predict_pages(pages, in_mode=in_mode) if self.bar_detector else [None] * len(pages)
+        detect_systems would have raised on that page.  dev_pages: the same raw uint8 pages as a DevicePages - the
+        networks read them there instead of uploading `pages` once each."""
+        if dev_pages is not None and (in_mode != IN_U8_RAW or len(dev_pages) != len(pages)):
+            raise ValueError("dev_pages goes with the same number of raw uint8 pages (in_mode=IN_U8_RAW)")
+        src = pages if dev_pages is None else dev_pages
+        sys_maps = self.system_detector.predict_pages(src, in_mode=in_mode)
+        bar_maps = self.bar_detector.predict_pages(src, in_mode=in_mode) if self.bar_detector else [None] * len(pages)
         out = []
         for i, page in enumerate(pages):
             img = prepare_image(page) if in_mode != IN_F32_PREPARED else page

@@ -1,5 +1,7 @@
 """load_umc_sheets of umc_a2s_server.py / umc_s2a_server.py: unrolled sheets of every piece under a data directory
-(<piece>/sheet/*.png), with the systems of all pages detected in one device call per network."""
+(<piece>/sheet/*.png), with the systems of all pages detected in one device call per network - and, with
+return_device, unrolled in one more (the strips stay on the device for the data base and the queries).  load_specs /
+get_performance_audio_path: the recordings of the pieces (umc_a2s_server.py:28-45)."""
 from __future__ import print_function
 
 import glob
@@ -8,8 +10,9 @@ import os
 import numpy as np
 
 from audio_sheet_retrieval_amd.sheet_utils import bar_detector, system_detector
-from audio_sheet_retrieval_amd.sheet_utils.omr import (IN_U8_RAW, SYSTEM_HEIGHT, OpticalMusicRecognizer,
-                                                       SegmentationNetwork, imread_gray, unwrap_systems)
+from audio_sheet_retrieval_amd.sheet_utils.omr import (IN_U8_RAW, SYSTEM_HEIGHT, DevicePages, OpticalMusicRecognizer,
+                                                       SegmentationNetwork, imread_gray, unroll_rows,
+                                                       unroll_systems_dev, unwrap_systems)
 
 OKBLUE, ENDC = "\033[94m", "\033[0m"       # utils/plotting.BColors
 
@@ -23,12 +26,50 @@ def build_recognizer(system_params, bar_params, device=0):
     return OpticalMusicRecognizer(note_detector=None, system_detector=system_net, bar_detector=bar_net)
 
 
-def load_umc_sheets(data_dir, require_performance=False, omr=None, system_params=None, bar_params=None, device=0):
+def get_performance_audio_path(piece_path, file_pattern):
+    """the recording of a piece: the reference takes glob(piece_path/file_pattern*)[0]; here the sorted matches are
+    tried in order and the first with a loadable extension wins (score_ppq.wav next to score_ppq.flac).  Without a
+    loadable match the first match is returned (loading it names the format); IndexError without any match, as
+    the reference."""
+    from audio_sheet_retrieval_amd.audio_frontend import LOADABLE
+    matches = sorted(glob.glob(os.path.join(piece_path, file_pattern + "*")))
+    for path in matches:
+        if os.path.splitext(path)[1].lower() in LOADABLE:
+            return path
+    return matches[0]
+
+
+def load_specs(piece_paths, audio_file, processor, return_device=False):
+    """ Compute spectrograms given piece paths
+
+    The recordings <piece_path>/<audio_file>* of all pieces, read with audio_frontend.load_audio and turned into
+    (92, frames) spectrograms in one device call.  -> list of arrays; with return_device the
+    piece_identification.DeviceArrays handle instead (the spectrograms stay on the device)."""
+    from audio_sheet_retrieval_amd.audio_frontend import load_audio
+    recordings, scales = [], []
+    for piece_path in piece_paths:
+        try:
+            audio_path = get_performance_audio_path(piece_path, audio_file)
+        except IndexError:
+            raise IOError("piece %s: no recording %s* in %s" % (os.path.basename(piece_path), audio_file, piece_path))
+        samples, scale = load_audio(audio_path)
+        recordings.append(samples)
+        scales.append(scale)
+    if return_device:
+        return processor.process_many_dev(recordings, scales)
+    return processor.process_many(recordings, scales)
+
+
+def load_umc_sheets(data_dir, require_performance=False, omr=None, system_params=None, bar_params=None, device=0,
+                    return_device=False):
     """ load unwarpped sheets
 
     Returns (piece_names, piece_paths, unwrapped_sheets) as the reference: pieces without a sheet directory (or,
     with require_performance, without a performance) are skipped, and so is every piece with a page on which system
-    detection failed.  `omr`: an OpticalMusicRecognizer; otherwise one is built from system_params / bar_params."""
+    detection failed.  `omr`: an OpticalMusicRecognizer; otherwise one is built from system_params / bar_params.
+    return_device=True: the pages are uploaded once, both networks and the unrolling read them on the device, and a
+    fourth value is returned - the strips as a piece_identification.DeviceArrays (float32, 0..255; free its .buf when
+    done).  The host strips are then the downloaded device strips; they equal the host unrolling bit for bit."""
     if omr is None:
         omr = build_recognizer(system_params, bar_params, device=device)
 
@@ -55,6 +96,8 @@ def load_umc_sheets(data_dir, require_performance=False, omr=None, system_params
 
     # every page of every piece: one call per network (prepare_image on the device)
     all_pages = [I for _, _, pages in jobs for I in pages]
+    if return_device:
+        return _unroll_on_device(omr, jobs, all_pages)
     results = omr.detect_systems_pages(all_pages, in_mode=IN_U8_RAW) if all_pages else []
 
     kept_pages = 0
@@ -78,3 +121,42 @@ def load_umc_sheets(data_dir, require_performance=False, omr=None, system_params
 
     print("%d pieces covering %d pages of sheet music." % (len(piece_names), kept_pages))
     return piece_names, piece_paths, unwrapped_sheets
+
+
+def _unroll_on_device(omr, jobs, all_pages):
+    """the second half of load_umc_sheets with the pages resident on the device"""
+    from audio_sheet_retrieval_amd.piece_identification import DeviceArrays
+    from audio_sheet_retrieval_amd.sheet_utils.omr import _engine
+    engine = omr.system_detector.engine or _engine(omr.system_detector.device)
+    dev_pages = DevicePages(engine, all_pages)
+    try:
+        results = omr.detect_systems_pages(all_pages, in_mode=IN_U8_RAW, dev_pages=dev_pages) if all_pages else []
+        piece_names, piece_paths = [], []
+        kept_pages = 0
+        k = 0
+        page_rows, piece_of_page = [None] * len(all_pages), np.zeros(len(all_pages), np.int64)
+        for piece_name, piece_dir, pages in jobs:
+            first = k
+            system_problem = False
+            for I in pages:
+                kept_pages += 1
+                if isinstance(results[k], Exception):
+                    print("Problem in system detection!!!")
+                    system_problem = True
+                else:                       # the reference unrolls the good pages of a piece it drops, too: messages
+                    page_rows[k] = unroll_rows(I.shape, results[k], SYSTEM_HEIGHT)
+                k += 1
+            if system_problem:
+                page_rows[first:k] = [None] * (k - first)
+            else:
+                piece_of_page[first:k] = len(piece_names)
+                piece_names.append(piece_name)
+                piece_paths.append(piece_dir)
+        buf, offsets, shapes = unroll_systems_dev(dev_pages, page_rows, piece_of_page, len(piece_names), SYSTEM_HEIGHT)
+    finally:
+        dev_pages.free()
+    total = sum(r * c for r, c in shapes)
+    flat = buf.download((total,), np.float32) if total else np.zeros(0, np.float32)
+    unwrapped_sheets = [flat[o:o + r * c].reshape(r, c).astype(np.uint8) for o, (r, c) in zip(offsets, shapes)]
+    print("%d pieces covering %d pages of sheet music." % (len(piece_names), kept_pages))
+    return piece_names, piece_paths, unwrapped_sheets, DeviceArrays(buf, offsets, shapes)

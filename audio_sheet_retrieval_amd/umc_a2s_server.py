@@ -1,0 +1,128 @@
+#!/usr/bin/env python
+"""Piece identification on scanned commercial scores ("UMC"), audio -> sheet ("A2S").  Command line of the reference's
+umc_a2s_server.py (:178-189):
+
+    python -m audio_sheet_retrieval_amd.umc_a2s_server --model models/mutopia_ccal_cont.py --data_dir <dir> \
+        --train_split splits/all_split.yaml --config exp_configs/mutopia_full_aug.yaml \
+        --init_sheet_db --full_eval --dump_results [--real_perf] [--n_candidates 25] [--estimate_UV] \
+        --system_params system_params.pkl --bar_params bar_params.pkl
+
+<dir> holds one folder per piece: sheet/*.png (the page scans), score_ppq.* (the synthesised recording) and, for
+--real_perf, 01_performance*.  The pages go through the two segmentation networks (their parameter pickles:
+--system_params / --bar_params; the reference hard-codes sheet_utils/omr_models/), the detected staff systems are
+unrolled into one strip per piece (sheet_utils/umc.load_umc_sheets, require_performance=True).  --init_sheet_db embeds
+the strip windows (EmbeddingDB.from_images: initialize_sheet_db_from_imges) into umc_sheet_db_file.pkl in the working
+directory; without it that file is loaded.  --full_eval queries the data base with every piece's recording: 100
+windows per piece, n_candidates neighbours per window, top_k = number of pieces, the reference's rank rule; a piece
+whose recording is missing is left out of the ranks (:234-235).  --dump_results writes
+umc_retrieval_<tag>_<dset>_A2S[_real].yaml next to the parameters.
+
+All pages go through each network in one call, all systems are unrolled in one call, all recordings become
+spectrograms in one call, and strips and spectrograms stay on the device for the data base and the queries
+(piece_identification.detect_scores / detect_performances).  umc_s2a_server.py is the S2A direction of this driver.
+Recordings are read by audio_frontend.load_audio: .wav or .npy at 22050 Hz.
+"""
+import argparse
+import os
+
+import numpy as np
+
+from . import audio2sheet_align
+from .audio_frontend import SpectrogramProcessor
+from .audio_sheet_server import common_arguments, report_ranks
+from .piece_identification import EmbeddingDB, detect_performances, detect_scores
+from .sheet_utils import umc
+
+# per direction: data-base flag, data-base file, data-base view
+DIRECTIONS = {
+    "A2S": dict(init_flag="--init_sheet_db", db_file="umc_sheet_db_file.pkl", db_view=1),
+    "S2A": dict(init_flag="--init_audio_db", db_file="umc_audio_db_file.pkl", db_view=2),
+}
+
+
+def _arguments(argv, direction):
+    d = DIRECTIONS[direction]
+    p = argparse.ArgumentParser(description="Identify every piece of a directory of scanned scores: %s." %
+                                ("audio -> sheet music" if direction == "A2S" else "sheet music -> audio"))
+    common_arguments(p, d["init_flag"], d["db_file"], "umc_retrieval_<tag>_<dset>_%s[_real].yaml" % direction)
+    p.add_argument("--real_perf", action="store_true", help="use the real recordings (01_performance*)")
+    p.add_argument("--data_dir", type=str, default=None, help="one folder per piece: sheet/*.png and the recordings")
+    p.add_argument("--system_params", type=str, default="sheet_utils/omr_models/system_params.pkl",
+                   help="parameters of the system detector")
+    p.add_argument("--bar_params", type=str, default="sheet_utils/omr_models/bar_params.pkl",
+                   help="parameters of the bar detector")
+    return p.parse_args(argv)
+
+
+def result_file(param_file, dset, direction, real_perf=False):
+    """the reference's dump name (:270-274): a tag-less params.pkl gives params_<dset>_<direction>.yaml"""
+    ret_dir = direction + ("_real" if real_perf else "")
+    return param_file.replace("params_", "umc_retrieval_").replace(".pkl", "_%s_%s.yaml") % (dset, ret_dir)
+
+
+def run(argv, direction):
+    d = DIRECTIONS[direction]
+    args = _arguments(argv, direction)
+    if args.data_dir is None:
+        raise SystemExit("--data_dir: the directory of pieces is required")
+    omr = umc.build_recognizer(args.system_params, args.bar_params)
+    te_pieces, piece_paths, _, strips = umc.load_umc_sheets(args.data_dir, require_performance=True, omr=omr,
+                                                           return_device=True)
+    try:
+        dset = os.path.basename(args.data_dir)
+        audio_file = "01_performance" if args.real_perf else "score_ppq"
+        engine, param_file = audio2sheet_align.load_network(args.model, args.estimate_UV, args.train_split, args.config)
+        processor = SpectrogramProcessor(engine)
+        if direction == "A2S":
+            # a piece without the recording is left out of the ranks
+            queried = []
+            for i, piece_path in enumerate(piece_paths):
+                try:
+                    umc.get_performance_audio_path(piece_path, audio_file)
+                    queried.append(i)
+                except IndexError:
+                    pass
+        else:
+            print("Loading spectrograms ...")
+            queried = list(range(len(te_pieces)))
+        specs = umc.load_specs([piece_paths[i] for i in queried], audio_file, processor, return_device=True)
+        try:
+            if args.init_db:
+                print("Initializing %s db ..." % ("sheet music" if direction == "A2S" else "audio"))
+                if direction == "A2S":
+                    db = EmbeddingDB.from_images(engine, te_pieces, strips)
+                else:
+                    db = EmbeddingDB.from_specs(engine, te_pieces, specs)
+                print("%d %s of %d pieces collected" % (len(db), "sheet snippet codes" if direction == "A2S" else
+                                                        "audio excerpts", len(te_pieces)))
+                db.save(d["db_file"])
+            else:
+                db = EmbeddingDB.load(engine, d["db_file"])
+            if not args.full_eval:
+                return []
+            print("\nRunning full evaluation:")
+            ids = {name: i for i, name in db.id_to_name.items()}
+            names = [te_pieces[i] for i in queried]
+            targets = np.array([ids.get(n, -1) for n in names], np.int32)
+            if not names:
+                ranks, ratios = np.zeros(0, np.int32), np.zeros(0, np.float64)
+            elif direction == "A2S":
+                _, ranks, ratios = detect_scores(engine, db, specs, top_k=len(te_pieces), n_candidates=args.n_candidates,
+                                                 targets=targets)
+            else:
+                _, ranks, ratios = detect_performances(engine, db, strips, top_k=len(te_pieces),
+                                                       n_candidates=args.n_candidates, targets=targets)
+        finally:
+            specs.buf.free()
+    finally:
+        strips.buf.free()
+    return report_ranks(names, ranks, ratios, "scores",
+                        result_file(param_file, dset, direction, args.real_perf) if args.dump_results else None)
+
+
+def main(argv=None):
+    return run(argv, "A2S")
+
+
+if __name__ == "__main__":
+    main()

@@ -559,6 +559,37 @@ int asr_seg_predict_dev(asr_ctx *ctx, asr_seg *seg, const void *pages_dev, int i
                         const int32_t *heights, const int32_t *widths, int n_pages, double overlap,
                         double *proba_dev);
 
+/* ---- scanned scores and recordings to strips and spectrograms (umc_a2s_server.py / umc_s2a_server.py) ----------
+ * asr_unroll_systems_dev = the unrolling loop of load_umc_sheets (umc_a2s_server.py:136-158) for all systems of all
+ *   pages of all pieces in one launch.  pages_dev: the uint8 pages exactly as asr_seg_predict_dev (in_mode 2) reads
+ *   them (page p is heights[p] x widths[p], row-major at byte page_offsets[p]; pages_bytes = size of the buffer).
+ *   systems: n_systems rows of 8 int32 that the host computes with the reference's integer rules (:139-147):
+ *       page, r0, r1, c0, c1, pad, piece, dst_col
+ *   rows r0..r1-1 and columns c0..c1-1 of the page go to columns dst_col.. of the piece's strip; the last `pad` rows of
+ *   the strip repeat row r1-1 (np.pad mode="edge", :156); r1 - r0 + pad == system_height.  Systems the reference skips
+ *   (:153-155) are simply not in the table.  Strip of piece q: (system_height, strip_widths[q]) float32 holding the
+ *   0..255 values, row-major at float strip_offsets[q] of strips_dev (strips_floats = size of that buffer in floats) -
+ *   the layout asr_gather_windows_dev and asr_slice_windows_dev read.  Every row is checked against the page, the
+ *   strip and both buffer sizes before anything is launched; columns of a strip that no system covers are left as
+ *   they are.
+ * asr_spectrogram_batch_dev = asr_spectrogram_dev (processor.process(audio_path), umc_a2s_server.py:35-45, :238) for
+ *   n_recordings recordings of different lengths in one launch.  Recording i: sample_counts[i] samples at float
+ *   sample_offsets[i] of samples_dev (samples_floats = size of that buffer), n_frames[i] frames, written at float
+ *   out_offsets[i] of out_dev (out_floats = its size) as (n_filters, n_frames[i]) if transposed else
+ *   (n_frames[i], n_filters).  Every recording's output is bit-identical with asr_spectrogram_dev on it alone: a frame
+ *   is computed by the same device code, only the frame-to-recording lookup is added.  Recordings of zero samples /
+ *   zero frames and n_recordings == 0 are valid and write nothing. */
+int asr_unroll_systems_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
+                           const int32_t *heights, const int32_t *widths, int n_pages, const int32_t *systems,
+                           int n_systems, int system_height, const int64_t *strip_offsets, const int32_t *strip_widths,
+                           int n_pieces, float *strips_dev, int64_t strips_floats);
+int asr_spectrogram_batch_dev(asr_ctx *ctx, const float *samples_dev, int64_t samples_floats,
+                              const int64_t *sample_offsets, const int64_t *sample_counts, const int64_t *n_frames,
+                              const int64_t *out_offsets, int n_recordings, int frame_size, double hop,
+                              const float *window, const int32_t *fb_start, const int32_t *fb_len,
+                              const float *fb_weights, int n_filters, float mul, float add, int transposed,
+                              float *out_dev, int64_t out_floats);
+
 /* ---- device memory (plain pointers; library-owned allocations) ---------- */
 int asr_dev_alloc(asr_ctx *ctx, size_t bytes, void **dptr);
 int asr_dev_free(asr_ctx *ctx, void *dptr);
