@@ -20,6 +20,7 @@ ASR_OK = 0
 ASR_ERR_INVALID, ASR_ERR_HIP, ASR_ERR_STATE, ASR_ERR_COMM, ASR_ERR_NOMEM = 1, 2, 3, 4, 5      # include/asr_hip.h
 IN_F32_PREPARED, IN_F32_RAW, IN_U8_RAW = 0, 1, 2
 OUT_LATENT, OUT_FEATURES = 0, 1
+SYSTEM_MIN_AREA = 50000            # detect_systems: smallest system blob (asr_systems_from_maps_dev's capacity rule)
 
 #: every symbol include/asr_hip.h declares (tests check the .so exports them all)
 EXPORTS = [
@@ -39,7 +40,7 @@ EXPORTS = [
     "asr_comm_unique_id", "asr_comm_init", "asr_comm_init_custom", "asr_comm_destroy", "asr_comm_info", "asr_comm_stats", "asr_comm_timing", "asr_comm_library",
     "asr_comm_allreduce_dev", "asr_comm_allgather_dev",
     "asr_rank_sharded_dev", "asr_slice_windows_dev", "asr_piece_vote_dev", "asr_piece_vote_batch_dev", "asr_gather_windows_dev", "asr_dtw_dev", "asr_dtw_batch_dev", "asr_spectrogram_dev", "asr_debug_tune_report",
-    "asr_seg_create", "asr_seg_set_window", "asr_seg_destroy", "asr_seg_predict_dev",
+    "asr_seg_create", "asr_seg_set_window", "asr_seg_destroy", "asr_seg_predict_dev", "asr_systems_from_maps_dev",
     "asr_unroll_systems_dev", "asr_spectrogram_batch_dev",
     "asr_opt_state_size", "asr_get_opt_state", "asr_set_opt_state", "asr_debug_train_tensor", "asr_cca_train_debug",
 ]
@@ -189,6 +190,9 @@ def load_library(path=None):
         "asr_seg_destroy": (c_int, [c_void_p, c_void_p]),
         "asr_seg_predict_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                         c_double, c_void_p]),
+        "asr_systems_from_maps_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                              c_void_p]),
         "asr_piece_vote_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int32, c_int]
                                      + [c_void_p] * 6),
         "asr_gather_windows_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p]),
@@ -567,6 +571,36 @@ class Engine(object):
             self.ctx, pages_ptr, int(pages_bytes), page_offsets.ctypes.data, heights.ctypes.data, widths.ctypes.data,
             heights.size, systems.ctypes.data, systems.shape[0], int(system_height), strip_offsets.ctypes.data,
             strip_widths.ctypes.data, strip_widths.size, strips_ptr, int(strips_floats)))
+
+    def systems_from_maps_dev(self, pages_ptr, in_mode, page_offsets, heights, widths, system_maps_ptr,
+                              bar_maps_ptr=None, max_systems=None, system_seg=None, bar_seg=None):
+        """systems_from_maps of sheet_utils/omr.py for all pages in one call, on maps that are on the device
+        (asr_systems_from_maps_dev).  Pages as seg_predict reads them; the float64 maps back to back.  ->
+        (status (n,), counts (n,), systems (n, max_systems, 4) int32 rows of min_row, max_row, min_col, max_col,
+        labelling passes).  status 0 ok, 1 the host's IndexError, 2 its ValueError, 3 not decided on the device."""
+        page_offsets = np.ascontiguousarray(page_offsets, dtype=np.int64)
+        heights = np.ascontiguousarray(heights, dtype=np.int32)
+        widths = np.ascontiguousarray(widths, dtype=np.int32)
+        if not (page_offsets.ndim == heights.ndim == widths.ndim == 1) or \
+                not (page_offsets.size == heights.size == widths.size):
+            raise ValueError("systems_from_maps_dev: the per-page tables differ in length")
+        n = int(heights.size)
+        need = int((heights.astype(np.int64) * widths // SYSTEM_MIN_AREA).max()) if n else 0
+        if max_systems is None:
+            max_systems = max(need, 1)
+        max_systems = int(max_systems)
+        if max_systems < need:
+            raise ValueError("systems_from_maps_dev: a page can hold %d systems of %d pixels, max_systems is %d"
+                             % (need, SYSTEM_MIN_AREA, max_systems))
+        status = np.full(n, 3, np.int32)
+        counts = np.zeros(n, np.int32)
+        systems = np.zeros((n, max_systems, 4), np.int32)
+        passes = c_int32(0)
+        self._check(self.lib.asr_systems_from_maps_dev(
+            self.ctx, pages_ptr, int(in_mode), page_offsets.ctypes.data, heights.ctypes.data, widths.ctypes.data, n,
+            system_maps_ptr, bar_maps_ptr, system_seg, bar_seg, max_systems, status.ctypes.data, counts.ctypes.data,
+            systems.ctypes.data, byref(passes)))
+        return status, counts, systems, int(passes.value)
 
     def tune_report(self):
         """(comparisons, mismatches, max deviation) of the autotuner's self-check (ASR_TUNE_VERIFY=1)."""

@@ -22,6 +22,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 BASE_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wno-comment", "-Wno-unused-result", "-Wno-unused-value"]
 EXTRA_FLAGS = os.environ.get("ASR_EXTRA_HIPCC_FLAGS", "").split()      # timing experiments (tools/ablate_*.sh): -DASR_WINOG_ABL=...
 FLAGS = BASE_FLAGS + ["-I", INCLUDE] + EXTRA_FLAGS
+# per-source flags: the restated numpy arithmetic of systems_from_maps compares bits, so no fused multiply-adds there
+FILE_FLAGS = {"omr_post_kernels.hip": ["-ffp-contract=off"]}
 
 
 def sources():
@@ -49,6 +51,7 @@ def source_hash():
     # design) left behind by an interrupted tools/ablate_*.sh must not pass for the default build.  (The include path
     # is machine dependent and not hashed.)
     h.update(("\0flags\0" + " ".join(BASE_FLAGS + EXTRA_FLAGS)).encode())
+    h.update(("\0file flags\0" + repr(sorted(FILE_FLAGS.items()))).encode())
     return h.hexdigest()[:12]
 
 
@@ -80,7 +83,7 @@ def build(force=False, verbose=True):
     dep_t = max(os.path.getmtime(p) for p in _deps() + [os.path.abspath(__file__)])
     shash = source_hash()
     flags_stamp = os.path.join(OBJ_DIR, "flags.txt")
-    flags_now = " ".join(BASE_FLAGS + EXTRA_FLAGS)
+    flags_now = " ".join(BASE_FLAGS + EXTRA_FLAGS) + " " + repr(sorted(FILE_FLAGS.items()))
     try:
         with open(flags_stamp) as fp:
             force = force or fp.read().strip() != flags_now        # objects built with other flags are not reusable
@@ -93,7 +96,8 @@ def build(force=False, verbose=True):
         if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(src), dep_t) and \
                 not (is_version and _built_hash() != shash):
             return obj
-        cmd = [HIPCC] + FLAGS + (['-DASR_SOURCE_HASH="%s"' % shash] if is_version else []) + ["-c", src, "-o", obj]
+        cmd = [HIPCC] + FLAGS + FILE_FLAGS.get(os.path.basename(src), []) + \
+            (['-DASR_SOURCE_HASH="%s"' % shash] if is_version else []) + ["-c", src, "-o", obj]
         if verbose:
             print("[build]", " ".join(cmd), flush=True)
         subprocess.check_call(cmd)

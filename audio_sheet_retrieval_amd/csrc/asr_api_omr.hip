@@ -1,6 +1,7 @@
 // C-ABI layer of the staff-system detector: asr_seg_create / asr_seg_destroy / asr_seg_predict_dev
-// (sheet_utils/omr.py SegmentationNetwork.load + predict_proba; include/asr_hip.h for the contract).  Kernels:
-// omr_kernels.hip.
+// (sheet_utils/omr.py SegmentationNetwork.load + predict_proba; include/asr_hip.h for the contract) and
+// asr_systems_from_maps_dev (systems_from_maps: the maps to system corners).  Kernels: omr_kernels.hip,
+// omr_post_kernels.hip.
 #include "asr_ctx.h"
 #include "omr_kernels.h"
 
@@ -304,6 +305,244 @@ int asr_seg_predict_dev(asr_ctx *ctx, asr_seg *seg, const void *pages_dev, int i
         ProfScope ps(ctx, "seg_stitch", 0, 3.0 * (double)out_off, 12.0 * (double)out_off);
         ASR_HIP(ctx, asr::launch_seg_stitch(st, tile_p, seg->win, th, tw, d_sd, n_pages, (int)max_px, proba_dev));
     }
+    return mark_main(ctx);
+}
+
+namespace {
+
+// the leaves of numpy's pairwise sum over n >= 8 contiguous elements and the postfix program that adds them up in the
+// order of the recursion (0: push the next leaf, 1: add the two topmost values)
+void post_leaves(int off, int n, std::vector<asr::PostLeaf> &leaves, std::vector<uint8_t> &prog) {
+    if (n <= 128) {
+        leaves.push_back({off, n});
+        prog.push_back(0);
+        return;
+    }
+    int n2 = n / 2;
+    n2 -= n2 % 8;
+    post_leaves(off, n2, leaves, prog);
+    post_leaves(off + n2, n - n2, leaves, prog);
+    prog.push_back(1);
+}
+
+}  // namespace
+
+int asr_systems_from_maps_dev(asr_ctx *ctx, const void *pages_dev, int in_mode, const int64_t *page_offsets,
+                              const int32_t *heights, const int32_t *widths, int n_pages, const double *system_maps_dev,
+                              const double *bar_maps_dev, const asr_seg *system_seg, const asr_seg *bar_seg,
+                              int max_systems, int32_t *status, int32_t *counts, int32_t *systems,
+                              int32_t *label_passes) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_pages < 0 || in_mode < 0 || in_mode > 2 || max_systems < 0)
+        return fail(ctx, ASR_ERR_INVALID, "systems_from_maps: bad n_pages=%d in_mode=%d max_systems=%d", n_pages, in_mode,
+                    max_systems);
+    if (label_passes) *label_passes = 0;
+    if (n_pages == 0) return ASR_OK;
+    if (!pages_dev || !page_offsets || !heights || !widths || !system_maps_dev || !status || !counts ||
+        (max_systems && !systems))
+        return fail(ctx, ASR_ERR_INVALID, "systems_from_maps: NULL argument");
+    for (const asr_seg *g : {system_seg, bar_seg})
+        if (g && g->owner != ctx)
+            return fail(ctx, ASR_ERR_INVALID, "systems_from_maps: not a segmentation network of this context");
+    for (int p = 0; p < n_pages; ++p) {
+        const int h = heights[p], w = widths[p];
+        if (h < 1 || w < 1 || (int64_t)h * w > (1 << 28) || page_offsets[p] < 0)
+            return fail(ctx, ASR_ERR_INVALID, "systems_from_maps: page %d has bad geometry %d x %d at %lld", p, h, w,
+                        (long long)page_offsets[p]);
+        if ((int64_t)h * w / asr::POST_MIN_AREA > max_systems)
+            return fail(ctx, ASR_ERR_INVALID, "systems_from_maps: page %d (%d x %d) can hold %lld systems, max_systems "
+                        "is %d", p, h, w, (long long)((int64_t)h * w / asr::POST_MIN_AREA), max_systems);
+    }
+    const int cap = std::max(max_systems, 1);
+
+    // pages that are decided here, their geometry tables; every other page is status 3 from the start
+    std::vector<asr::SegPage> sdesc(n_pages);
+    std::vector<asr::PostPage> all;
+    std::vector<asr::PostLeaf> leaves;
+    std::vector<uint8_t> prog;
+    int64_t map_off = 0;
+    for (int p = 0; p < n_pages; ++p) {
+        const int h = heights[p], w = widths[p];
+        sdesc[p] = {page_offsets[p], h, w};
+        status[p] = 3;
+        counts[p] = 0;
+        const bool tile = (system_seg && h == system_seg->th && w == system_seg->tw) ||
+                          (bar_seg && h == bar_seg->th && w == bar_seg->tw);      // the host works on float32 maps there
+        if (!tile && h >= 3 && w >= 8) {
+            asr::PostPage P{};
+            P.page_off = page_offsets[p]; P.map_off = map_off; P.h = h; P.w = w; P.page = p;
+            // one table per distinct width; a width of more leaves than a wave holds gets none and stays status 3
+            bool found = false;
+            for (const asr::PostPage &Q : all)
+                if (Q.w == w) { P.leaf_off = Q.leaf_off; P.n_leaves = Q.n_leaves; P.prog_off = Q.prog_off; P.n_prog = Q.n_prog; found = true; break; }
+            if (!found) {
+                std::vector<asr::PostLeaf> lv;
+                std::vector<uint8_t> pg;
+                post_leaves(0, w, lv, pg);
+                P.leaf_off = (int32_t)leaves.size(); P.prog_off = (int32_t)prog.size();
+                P.n_leaves = (int32_t)lv.size(); P.n_prog = (int32_t)pg.size();
+                if (P.n_leaves <= asr::POST_MAX_LEAVES) {
+                    leaves.insert(leaves.end(), lv.begin(), lv.end());
+                    prog.insert(prog.end(), pg.begin(), pg.end());
+                }
+            }
+            if (P.n_leaves <= asr::POST_MAX_LEAVES) all.push_back(P);
+        }
+        map_off += (int64_t)h * w;
+    }
+    if (max_systems) memset(systems, 0, (size_t)n_pages * max_systems * 4 * sizeof(int32_t));
+    if (all.empty()) return ASR_OK;
+
+    // chunks of whole pages under ASR_OMR_BUDGET_MB (at least one page each) and the workspace of the largest
+    const size_t budget = (size_t)std::max<int64_t>(seg_env("ASR_OMR_BUDGET_MB", 4096), 1) << 20;
+    struct Lay { size_t pd, st, bl, e2, h2, proj, rmin, rmax, ys, rz, fg, tmp, lab, area, xs, chg, end; };
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += seg_align(bytes); return at; };
+    const size_t o_sd = take(sdesc.size() * sizeof(asr::SegPage)), o_mx = take((size_t)n_pages * sizeof(float));
+    const size_t o_lv = take(leaves.size() * sizeof(asr::PostLeaf)), o_pg = take(prog.size());
+    const size_t fixed = o;
+    auto layout = [&](int n, int64_t px, int64_t rows, int max_w) {
+        Lay L;
+        o = fixed;
+        L.pd = take((size_t)n * sizeof(asr::PostPage));
+        // cleared before every chunk: state .. changed flag (contiguous)
+        L.st = take((size_t)n * sizeof(asr::PostState));
+        L.bl = take((size_t)n * cap * sizeof(asr::PostBlob));
+        L.h2 = take((size_t)n * 256 * sizeof(uint32_t));
+        L.chg = take(sizeof(int32_t));
+        L.area = take((size_t)px * sizeof(int32_t));
+        L.e2 = take((size_t)n * 257 * sizeof(double));
+        L.proj = take((size_t)rows * sizeof(double)); L.rmin = take((size_t)rows * sizeof(double));
+        L.rmax = take((size_t)rows * sizeof(double)); L.ys = take((size_t)rows * sizeof(float));
+        L.rz = take((size_t)rows);
+        L.fg = take((size_t)px); L.tmp = take((size_t)px);
+        L.lab = take((size_t)px * sizeof(int32_t));
+        L.xs = take((size_t)n * cap * max_w * sizeof(float));
+        L.end = o;
+        return L;
+    };
+    struct Chunk { int first, n, max_h, max_w; int64_t px, rows, max_px; };
+    std::vector<Chunk> chunks;
+    size_t need = 0;
+    for (int i = 0; i < (int)all.size();) {
+        Chunk c{i, 0, 0, 0, 0, 0, 0};
+        while (i < (int)all.size()) {
+            const asr::PostPage &P = all[i];
+            const int64_t px = c.px + (int64_t)P.h * P.w, rows = c.rows + P.h;
+            const int mw = std::max(c.max_w, P.w);
+            // (the pages of a chunk are the y dimension of every launch grid)
+            if (c.n && (c.n >= asr::POST_MAX_CHUNK_PAGES || layout(c.n + 1, px, rows, mw).end > budget ||
+                        px > (1ll << 30))) break;
+            c.n += 1; c.px = px; c.rows = rows; c.max_w = mw; c.max_h = std::max(c.max_h, P.h);
+            c.max_px = std::max<int64_t>(c.max_px, (int64_t)P.h * P.w);
+            ++i;
+        }
+        need = std::max(need, layout(c.n, c.px, c.rows, c.max_w).end);
+        chunks.push_back(c);
+    }
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    int rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    if (need > ctx->post_ws_bytes) {
+        rc = sync_all(ctx);
+        if (rc != ASR_OK) return rc;
+        if (ctx->post_ws) ASR_HIP(ctx, hipFree(ctx->post_ws));
+        ctx->post_ws = nullptr; ctx->post_ws_bytes = 0;
+        ASR_HIP(ctx, hipMalloc(&ctx->post_ws, need));
+        ctx->post_ws_bytes = need;
+    }
+    char *ws = (char *)ctx->post_ws;
+    hipStream_t st = ctx->stream;
+    asr::SegPage *d_sd = (asr::SegPage *)(ws + o_sd);
+    float *d_mx = (float *)(ws + o_mx);
+    ASR_HIP(ctx, hipMemcpyAsync(d_sd, sdesc.data(), sdesc.size() * sizeof(asr::SegPage), hipMemcpyHostToDevice, st));
+    ASR_HIP(ctx, hipMemcpyAsync(ws + o_lv, leaves.data(), leaves.size() * sizeof(asr::PostLeaf), hipMemcpyHostToDevice, st));
+    ASR_HIP(ctx, hipMemcpyAsync(ws + o_pg, prog.data(), prog.size(), hipMemcpyHostToDevice, st));
+    if (in_mode != 0) ASR_HIP(ctx, asr::launch_seg_page_max(st, pages_dev, in_mode, d_sd, n_pages, d_mx));
+
+    std::vector<asr::PostState> h_state;
+    std::vector<asr::PostBlob> h_blobs;
+    int passes = 0;
+    for (const Chunk &c : chunks) {
+        const Lay L = layout(c.n, c.px, c.rows, c.max_w);
+        std::vector<asr::PostPage> pd(all.begin() + c.first, all.begin() + c.first + c.n);
+        int64_t px = 0;
+        int32_t rows = 0;
+        for (asr::PostPage &P : pd) {
+            P.px_off = px; P.row_off = rows;
+            px += (int64_t)P.h * P.w; rows += P.h;
+        }
+        asr::PostArgs a;
+        a.pages = (const asr::PostPage *)(ws + L.pd);
+        a.n_pages = c.n; a.max_h = c.max_h; a.max_w = c.max_w; a.cap = cap; a.max_px = c.max_px;
+        a.page_buf = pages_dev; a.in_mode = in_mode; a.page_max = d_mx;
+        a.sys_maps = system_maps_dev; a.bar_maps = bar_maps_dev;
+        a.leaves = (const asr::PostLeaf *)(ws + o_lv); a.prog = (const uint8_t *)(ws + o_pg);
+        a.state = (asr::PostState *)(ws + L.st); a.blobs = (asr::PostBlob *)(ws + L.bl);
+        a.proj = (double *)(ws + L.proj); a.rmin = (double *)(ws + L.rmin); a.rmax = (double *)(ws + L.rmax);
+        a.ysig = (float *)(ws + L.ys); a.rowzero = (uint8_t *)(ws + L.rz);
+        a.edges2 = (double *)(ws + L.e2); a.hist2 = (uint32_t *)(ws + L.h2);
+        a.fg = (uint8_t *)(ws + L.fg); a.tmp = (uint8_t *)(ws + L.tmp);
+        a.label = (int32_t *)(ws + L.lab); a.area = (int32_t *)(ws + L.area);
+        a.xsig = (float *)(ws + L.xs); a.changed = (int32_t *)(ws + L.chg);
+        ASR_HIP(ctx, hipMemcpyAsync(ws + L.pd, pd.data(), pd.size() * sizeof(asr::PostPage), hipMemcpyHostToDevice, st));
+        ASR_HIP(ctx, hipMemsetAsync(ws + L.st, 0, L.e2 - L.st, st));
+        const double dpx = (double)c.px;
+        {
+            ProfScope ps(ctx, "post_rows", 0, 4.0 * dpx, 17.0 * dpx);
+            ASR_HIP(ctx, asr::launch_post_rows(st, a));
+        }
+        {
+            ProfScope ps(ctx, "post_threshold", 0, 6.0 * dpx, 8.0 * dpx);
+            ASR_HIP(ctx, asr::launch_post_threshold(st, a));
+        }
+        {
+            ProfScope ps(ctx, "post_close", 0, 0.0, 8.0 * dpx + 15.0 * 2 * dpx + 6.0 * dpx);
+            ASR_HIP(ctx, asr::launch_post_close(st, a));
+        }
+        // label equivalence: until a scan changes nothing (every changing pass lowers a label, so this ends)
+        for (;;) {
+            int32_t changed = 0;
+            ASR_HIP(ctx, hipMemsetAsync(a.changed, 0, sizeof(int32_t), st));
+            {
+                ProfScope ps(ctx, "post_label_pass", 0, 0.0, 48.0 * dpx);
+                ASR_HIP(ctx, asr::launch_post_label_pass(st, a));
+            }
+            ASR_HIP(ctx, hipMemcpyAsync(&changed, a.changed, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            ASR_HIP(ctx, hipStreamSynchronize(st));
+            ++passes;
+            if (!changed) break;
+        }
+        {
+            ProfScope ps(ctx, "post_blobs", 0, 0.0, 24.0 * dpx);
+            ASR_HIP(ctx, asr::launch_post_blobs(st, a));
+        }
+        h_state.resize(c.n);
+        h_blobs.resize((size_t)c.n * cap);
+        ASR_HIP(ctx, hipMemcpyAsync(h_state.data(), a.state, h_state.size() * sizeof(asr::PostState), hipMemcpyDeviceToHost, st));
+        ASR_HIP(ctx, hipMemcpyAsync(h_blobs.data(), a.blobs, h_blobs.size() * sizeof(asr::PostBlob), hipMemcpyDeviceToHost, st));
+        ASR_HIP(ctx, hipStreamSynchronize(st));
+        for (int j = 0; j < c.n; ++j) {
+            const int p = pd[j].page;
+            const asr::PostState &S = h_state[j];
+            if (S.status != 0) {
+                status[p] = S.status == 1 ? 1 : 3;
+                continue;
+            }
+            if (S.n_kept > (uint32_t)max_systems) continue;          // (cannot happen: the capacity was checked)
+            int worst = 0;
+            for (uint32_t k = 0; k < S.n_kept; ++k) {
+                const int bs = h_blobs[(size_t)j * cap + k].status;
+                worst = bs == 3 || worst == 3 ? 3 : std::max(worst, bs);
+            }
+            status[p] = worst;
+            if (worst) continue;
+            counts[p] = (int32_t)S.n_kept;
+            for (uint32_t k = 0; k < S.n_kept; ++k)
+                memcpy(systems + ((size_t)p * max_systems + k) * 4, h_blobs[(size_t)j * cap + k].out, 4 * sizeof(int32_t));
+        }
+    }
+    if (label_passes) *label_passes = passes;
     return mark_main(ctx);
 }
 

@@ -261,6 +261,8 @@ struct asr_ctx {
     size_t dtw_ws_bytes = 0;
     void *vote_ws = nullptr;                  // asr_piece_vote_batch_dev: results, targets, global-path counters + keys
     size_t vote_ws_bytes = 0;
+    void *post_ws = nullptr;                  // asr_systems_from_maps_dev: one chunk of pages' tables, masks and labels
+    size_t post_ws_bytes = 0;
     unsigned *topk_tickets = nullptr;         // 1024 last-arriver counters of the top-k call (zero between calls)
     float *unit_ws = nullptr;                 // asr_topk_dev on a large pool: unit-length copy + reciprocal norms of the
     size_t unit_ws_floats = 0;                // pool, rebuilt per call (what an asr_db keeps)

@@ -33,6 +33,19 @@ struct SegStitch {
 hipError_t launch_seg_page_max(hipStream_t s, const void *pages, int in_mode, const SegPage *desc, int n_pages,
                                float *page_max);
 
+#ifdef __HIPCC__
+// one prepared pixel (prepare_image folded in: an IEEE divide by the page maximum unless that is 0)
+__device__ __forceinline__ float seg_load_page(const void *pages, int in_mode, int64_t off, float mx) {
+    if (in_mode == 2) {
+        const float v = (float)((const uint8_t *)pages)[off];
+        return mx != 0.0f ? __fdiv_rn(v, mx) : v;
+    }
+    const float v = ((const float *)pages)[off];
+    if (in_mode == 1 && mx != 0.0f) return __fdiv_rn(v, mx);
+    return v;
+}
+#endif
+
 // 3x3 'same' conv (flip_filters=True) + BN + ELU over n tiles of H x W.
 //   w: [ci][3][3][co] of the flipped kernel; bn: mean[co] scale[co] beta[co] (scale = gamma * inv_std)
 //   pooled != nullptr: the 2x2/2 max-pool of the output as well; head != nullptr (ci = co = 8): the 1x1 conv + sigmoid
@@ -59,5 +72,76 @@ hipError_t launch_seg_up(hipStream_t s, const float *in, const float *w, const f
 // gather stitch: out[p] = sum_t P_t * win / sum_t win over the tiles covering p, float64, in the reference's tile order
 hipError_t launch_seg_stitch(hipStream_t s, const float *tile_p, const double *win, int th, int tw,
                              const SegStitch *desc, int n_pages, int max_pixels, double *out);
+
+// ---- systems_from_maps on the device (omr_post_kernels.hip; host side: asr_systems_from_maps_dev) -------------------
+constexpr int POST_MIN_AREA = 50000;       // detect_systems: smallest system blob
+constexpr int POST_MAX_LEAVES = 1024;      // leaves of numpy's pairwise row sum that one row may have (width <= 65536)
+constexpr int POST_MAX_CHUNK_PAGES = 65535; // pages of one chunk: the y dimension of the launch grids
+
+// one leaf (8 <= len <= 128 elements at `off`) of numpy's pairwise sum over a row
+struct PostLeaf {
+    int32_t off, len;
+};
+
+// one page of a chunk: where its pixels, maps and workspace sections start
+struct PostPage {
+    int64_t page_off;               // first pixel in the page buffer (elements)
+    int64_t map_off;                // first pixel in the probability maps
+    int64_t px_off;                 // first pixel in the per-pixel workspace arrays
+    int32_t h, w;
+    int32_t row_off;                // first row in the per-row workspace arrays
+    int32_t leaf_off, n_leaves;     // the row-sum leaves of width w, and the postfix program that combines them
+    int32_t prog_off, n_prog;       // (0: push the next leaf sum, 1: add the two topmost values)
+    int32_t page;                   // index of the page in the call (page maxima)
+};
+
+// per page, written by the kernels and read back by the host
+struct PostState {
+    double thr2;                    // Otsu threshold of the cleaned system map
+    double edges2_first, edges2_last;
+    int32_t status;                 // 0 ok, 1 no row below the projection threshold, 3 not decided here
+    int32_t nonfinite;              // a NaN / infinity in a map or in the page signal
+    uint32_t n_kept;                // blobs of at least POST_MIN_AREA pixels (may exceed the capacity)
+    int32_t pad_;
+};
+
+// per kept blob: bounding box (inclusive) from the labelling, then the result of shrink + snap
+struct PostBlob {
+    int32_t root;                   // smallest linear pixel index of the blob
+    int32_t min_r, min_c, max_r, max_c;
+    int32_t status;                 // 0 ok, 2 no edge candidate, 3 not decided here
+    int32_t out[4];                 // min_row, max_row, min_col, max_col
+    int32_t pad_[2];
+};
+
+struct PostArgs {
+    const PostPage *pages = nullptr;
+    int n_pages = 0, max_h = 0, max_w = 0, cap = 0;
+    int64_t max_px = 0;
+    const void *page_buf = nullptr;
+    int in_mode = 0;
+    const float *page_max = nullptr;
+    const double *sys_maps = nullptr, *bar_maps = nullptr;     // bar_maps may be NULL
+    const PostLeaf *leaves = nullptr;
+    const uint8_t *prog = nullptr;
+    PostState *state = nullptr;
+    PostBlob *blobs = nullptr;      // n_pages x cap
+    double *proj = nullptr, *rmin = nullptr, *rmax = nullptr;  // per row
+    float *ysig = nullptr;          // per row: snap_system_to_grid's y edge signal
+    uint8_t *rowzero = nullptr;     // per row: zeroed by the gap clean-up
+    double *edges2 = nullptr;       // n_pages x 257
+    uint32_t *hist2 = nullptr;      // n_pages x 256
+    uint8_t *fg = nullptr, *tmp = nullptr;                     // per pixel
+    int32_t *label = nullptr, *area = nullptr;                 // per pixel
+    float *xsig = nullptr;          // n_pages x cap x max_w
+    int32_t *changed = nullptr;     // one flag of the labelling passes
+};
+
+// the stages in call order; launch_post_label_pass is repeated until *changed stays 0
+hipError_t launch_post_rows(hipStream_t s, const PostArgs &a);       // row sums, row extrema, y edge signal
+hipError_t launch_post_threshold(hipStream_t s, const PostArgs &a);  // Otsu 1, gap clean-up, histogram + Otsu 2
+hipError_t launch_post_close(hipStream_t s, const PostArgs &a);      // threshold, 15x1 closing, run labels
+hipError_t launch_post_label_pass(hipStream_t s, const PostArgs &a);
+hipError_t launch_post_blobs(hipStream_t s, const PostArgs &a);      // areas, kept blobs, boxes, shrink + snap
 
 }  // namespace asr

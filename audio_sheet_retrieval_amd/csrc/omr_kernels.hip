@@ -25,16 +25,6 @@ namespace {
 
 constexpr int SEG_THREADS = 256;
 
-__device__ __forceinline__ float seg_load_page(const void *pages, int in_mode, int64_t off, float mx) {
-    if (in_mode == 2) {
-        const float v = (float)((const uint8_t *)pages)[off];
-        return mx != 0.0f ? __fdiv_rn(v, mx) : v;
-    }
-    const float v = ((const float *)pages)[off];
-    if (in_mode == 1 && mx != 0.0f) return __fdiv_rn(v, mx);
-    return v;
-}
-
 __global__ __launch_bounds__(SEG_THREADS) void seg_page_max_kernel(const void *__restrict__ pages, int in_mode,
                                                                    const SegPage *__restrict__ desc,
                                                                    float *__restrict__ page_max) {

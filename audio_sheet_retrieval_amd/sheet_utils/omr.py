@@ -364,6 +364,70 @@ def unroll_systems_dev(dev_pages, page_rows, piece_of_page, n_pieces, system_hei
     return strips, [int(o) for o in offsets], [(system_height, int(w)) for w in widths]
 
 
+def pairwise_sum(a):
+    """np.add.reduce over a contiguous 1-D float array, restated: the order asr_systems_from_maps_dev's row sums keep
+    (csrc/omr_post_kernels.hip, wave_pairwise_sum).  Below 8 elements sequential; up to 128 eight interleaved
+    accumulators combined ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the remainder sequentially; above, split at
+    n2 = n / 2 rounded down to a multiple of 8 and recurse.  Bit-equal with a.sum() for float32 and float64."""
+    n, t = a.shape[0], a.dtype.type
+    if n < 8:
+        res = t(0)
+        for v in a:
+            res = t(res + v)
+        return res
+    if n <= 128:
+        r = [a[j] for j in range(8)]
+        m = n - n % 8
+        for i in range(8, m, 8):
+            for j in range(8):
+                r[j] = t(r[j] + a[i + j])
+        res = t(t(t(r[0] + r[1]) + t(r[2] + r[3])) + t(t(r[4] + r[5]) + t(r[6] + r[7])))
+        for i in range(m, n):
+            res = t(res + a[i])
+        return res
+    n2 = n // 2
+    n2 -= n2 % 8
+    return t(pairwise_sum(a[:n2]) + pairwise_sum(a[n2:]))
+
+
+def row_sums(x):
+    """x.sum(1) of a C-contiguous 2-D float array in the restated order (projection = maps.sum(1); with float32 and a
+    division by float32(width), imagey.mean(axis=1) of the snap)"""
+    return np.array([pairwise_sum(r) for r in x], dtype=x.dtype)
+
+
+def column_sums(x):
+    """x.sum(0) of a C-contiguous 2-D float array, restated: row after row into one accumulator per column
+    (imagex[r0:r1].mean(axis=0) of the snap is this in float32, divided by float32(r1 - r0))"""
+    acc = np.zeros(x.shape[1], x.dtype)
+    for r in x:
+        acc = acc + r
+    return acc
+
+
+def systems_from_maps_dev(engine, pages_ptr, in_mode, page_offsets, heights, widths, system_maps_ptr,
+                          bar_maps_ptr=None, max_systems=None, system_seg=None, bar_seg=None):
+    """systems_from_maps for all pages in one device call (asr_systems_from_maps_dev).  -> per page (status, corners):
+    status 0 with the (n, 4, 2) float64 corner array systems_from_maps returns, or 1 / 2 / 3 with None (the host's
+    IndexError / its ValueError / not decided on the device); and the number of labelling passes."""
+    status, counts, systems, passes = engine.systems_from_maps_dev(
+        pages_ptr, in_mode, page_offsets, heights, widths, system_maps_ptr, bar_maps_ptr, max_systems,
+        system_seg, bar_seg)
+    out = []
+    for st, n, rows in zip(status, counts, systems):
+        if st != 0:
+            out.append((int(st), None))
+            continue
+        r = rows[:n].astype(np.float64)
+        corners = np.zeros((int(n), 4, 2))
+        corners[:, 0, 0] = corners[:, 1, 0] = r[:, 0]
+        corners[:, 2, 0] = corners[:, 3, 0] = r[:, 1]
+        corners[:, 0, 1] = corners[:, 3, 1] = r[:, 2]
+        corners[:, 1, 1] = corners[:, 2, 1] = r[:, 3]
+        out.append((0, corners))
+    return out, passes
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # networks
 
@@ -435,15 +499,12 @@ class SegmentationNetwork(object):
             pass
 
     # -- device call ------------------------------------------------------------------------------------------------
-    def predict_pages(self, pages, overlap=0.5, in_mode=IN_F32_PREPARED):
-        """float64 probability maps of a list of 2-D pages in ONE device call (every tile of every page in one forward,
-        chunked under ASR_OMR_BUDGET_MB).  in_mode: IN_F32_PREPARED (float32 pages as prepare_image leaves them),
-        IN_F32_RAW / IN_U8_RAW (prepare_image on the device).  `pages` may be a DevicePages (raw uint8 pages that are
-        already on the device; in_mode is IN_U8_RAW then)."""
+    def predict_pages_dev(self, pages, overlap=0.5, in_mode=IN_F32_PREPARED):
+        """predict_pages with the maps left on the device.  -> (out, x, (ptr, in_mode, sizes, offs, hs, ws)): `out` the
+        DeviceBuffer of the float64 maps back to back, `x` the DeviceBuffer this call uploaded the pages to (None for
+        a DevicePages), and the page table asr_seg_predict_dev read.  The caller frees out and x."""
         if self.handle is None:
             raise RuntimeError("SegmentationNetwork: load() the parameters first")
-        if len(pages) == 0:
-            return []
         eng = self.engine
         if isinstance(pages, DevicePages):
             if pages.engine is not eng:
@@ -463,12 +524,32 @@ class SegmentationNetwork(object):
             host = np.concatenate([p.ravel() for p in flat])
             x = eng.alloc(host.nbytes).upload(host)
             ptr = x.ptr
-        out = eng.alloc(int(sizes.sum()) * 8)
+        out = None
         try:
+            out = eng.alloc(int(sizes.sum()) * 8)
             eng._check(eng.lib.asr_seg_predict_dev(eng.ctx, self.handle, c_void_p(ptr),
                                                    in_mode, offs.ctypes.data, hs.ctypes.data, ws.ctypes.data, len(sizes),
                                                    float(overlap), c_void_p(out.ptr)))
-            eng.sync()
+        except Exception:
+            if x is not None:
+                x.free()
+            if out is not None:
+                out.free()
+            raise
+        return out, x, (ptr, in_mode, sizes, offs, hs, ws)
+
+    def predict_pages(self, pages, overlap=0.5, in_mode=IN_F32_PREPARED):
+        """float64 probability maps of a list of 2-D pages in ONE device call (every tile of every page in one forward,
+        chunked under ASR_OMR_BUDGET_MB).  in_mode: IN_F32_PREPARED (float32 pages as prepare_image leaves them),
+        IN_F32_RAW / IN_U8_RAW (prepare_image on the device).  `pages` may be a DevicePages (raw uint8 pages that are
+        already on the device; in_mode is IN_U8_RAW then)."""
+        if self.handle is None:
+            raise RuntimeError("SegmentationNetwork: load() the parameters first")
+        if len(pages) == 0:
+            return []
+        out, x, (_, _, sizes, offs, hs, ws) = self.predict_pages_dev(pages, overlap=overlap, in_mode=in_mode)
+        try:
+            self.engine.sync()
             res = out.download((int(sizes.sum()),), np.float64)
         finally:
             if x is not None:
@@ -536,3 +617,75 @@ class OpticalMusicRecognizer(object):
             except Exception as e:          # the reference's callers catch every exception of detect_systems
                 out.append(e)
         return out
+
+    def detect_systems_pages_dev(self, pages, in_mode=IN_U8_RAW, dev_pages=None):
+        """detect_systems_pages with the post-processing on the device as well (asr_systems_from_maps_dev): both
+        networks write their maps into device buffers, one more call turns them into system corners, and one small
+        download brings those back.  Returns exactly what detect_systems_pages returns - per page the (n, 4, 2)
+        float64 corner array, or an IndexError / ValueError instance.  Pages the device does not decide (status 3: a
+        page of a network's tile size, a NaN in a map, a shrink loop that leaves its blob, ...) go through
+        systems_from_maps on the host, their maps alone downloaded; self.last_fallback_pages lists their indices.
+        The device restates np.histogram's bin rule as numpy >= 2 computes it (checked with 2.2.6); under numpy 1.x
+        the equality with detect_systems_pages is not established."""
+        if dev_pages is not None and (in_mode != IN_U8_RAW or len(dev_pages) != len(pages)):
+            raise ValueError("dev_pages goes with the same number of raw uint8 pages (in_mode=IN_U8_RAW)")
+        self.last_fallback_pages = []
+        self.last_label_passes = 0
+        if len(pages) == 0:
+            return []
+        sysd, bard = self.system_detector, self.bar_detector
+        eng = sysd.engine
+        if bard is not None and bard.engine is not eng:
+            raise ValueError("both networks must live on one engine")
+        own = None
+        if dev_pages is None:
+            if in_mode == IN_U8_RAW:                 # upload once for both networks and the post-processing
+                own = dev_pages = DevicePages(eng, pages)
+        src = pages if dev_pages is None else dev_pages
+        sys_out = bar_out = x_sys = x_bar = None
+        try:
+            sys_out, x_sys, (ptr, mode, sizes, offs, hs, ws) = sysd.predict_pages_dev(src, in_mode=in_mode)
+            if bard is not None:
+                bar_out, x_bar, _ = bard.predict_pages_dev(src, in_mode=in_mode)
+            decided, self.last_label_passes = systems_from_maps_dev(
+                eng, c_void_p(ptr), mode, offs, hs, ws, c_void_p(sys_out.ptr),
+                c_void_p(bar_out.ptr) if bar_out is not None else None, None, sysd.handle,
+                bard.handle if bard is not None else None)
+            out = []
+            for i, (st, corners) in enumerate(decided):
+                if st == 0:
+                    out.append(corners)
+                elif st == 1:
+                    out.append(IndexError("index 0 is out of bounds for axis 0 with size 0"))
+                elif st == 2:
+                    out.append(ValueError("attempt to get argmin of an empty sequence"))
+                else:
+                    self.last_fallback_pages.append(i)
+                    page = pages[i]
+                    n, o = int(sizes[i]), int(offs[i]) * 8
+                    shape = (int(hs[i]), int(ws[i]))
+                    sp = _download_at(eng, sys_out, o, n).reshape(shape)
+                    bp = _download_at(eng, bar_out, o, n).reshape(shape) if bar_out is not None else None
+                    img = prepare_image(page) if in_mode != IN_F32_PREPARED else page
+                    if shape == sysd.tile_shape:
+                        sp = sp.astype(np.float32)
+                    if bp is not None and shape == bard.tile_shape:
+                        bp = bp.astype(np.float32)
+                    try:
+                        out.append(systems_from_maps(img, sp, bp))
+                    except Exception as e:
+                        out.append(e)
+            return out
+        finally:
+            for b in (sys_out, bar_out, x_sys, x_bar):
+                if b is not None:
+                    b.free()
+            if own is not None:
+                own.free()
+
+
+def _download_at(engine, buf, byte_offset, n_doubles):
+    """n_doubles float64 values at byte_offset of a DeviceBuffer"""
+    out = np.empty(n_doubles, np.float64)
+    engine._check(engine.lib.asr_dev_download(engine.ctx, out.ctypes.data, c_void_p(buf.ptr + byte_offset), out.nbytes))
+    return out

@@ -61,7 +61,7 @@ def load_specs(piece_paths, audio_file, processor, return_device=False):
 
 
 def load_umc_sheets(data_dir, require_performance=False, omr=None, system_params=None, bar_params=None, device=0,
-                    return_device=False):
+                    return_device=False, device_post=False):
     """ load unwarpped sheets
 
     Returns (piece_names, piece_paths, unwrapped_sheets) as the reference: pieces without a sheet directory (or,
@@ -69,7 +69,9 @@ def load_umc_sheets(data_dir, require_performance=False, omr=None, system_params
     detection failed.  `omr`: an OpticalMusicRecognizer; otherwise one is built from system_params / bar_params.
     return_device=True: the pages are uploaded once, both networks and the unrolling read them on the device, and a
     fourth value is returned - the strips as a piece_identification.DeviceArrays (float32, 0..255; free its .buf when
-    done).  The host strips are then the downloaded device strips; they equal the host unrolling bit for bit."""
+    done).  The host strips are then the downloaded device strips; they equal the host unrolling bit for bit.
+    device_post=True: the steps of detect_systems after the networks run on the device too
+    (detect_systems_pages_dev); the systems are the same integers."""
     if omr is None:
         omr = build_recognizer(system_params, bar_params, device=device)
 
@@ -97,8 +99,9 @@ def load_umc_sheets(data_dir, require_performance=False, omr=None, system_params
     # every page of every piece: one call per network (prepare_image on the device)
     all_pages = [I for _, _, pages in jobs for I in pages]
     if return_device:
-        return _unroll_on_device(omr, jobs, all_pages)
-    results = omr.detect_systems_pages(all_pages, in_mode=IN_U8_RAW) if all_pages else []
+        return _unroll_on_device(omr, jobs, all_pages, device_post=device_post)
+    detect = omr.detect_systems_pages_dev if device_post else omr.detect_systems_pages
+    results = detect(all_pages, in_mode=IN_U8_RAW) if all_pages else []
 
     kept_pages = 0
     k = 0
@@ -123,14 +126,15 @@ def load_umc_sheets(data_dir, require_performance=False, omr=None, system_params
     return piece_names, piece_paths, unwrapped_sheets
 
 
-def _unroll_on_device(omr, jobs, all_pages):
+def _unroll_on_device(omr, jobs, all_pages, device_post=False):
     """the second half of load_umc_sheets with the pages resident on the device"""
     from audio_sheet_retrieval_amd.piece_identification import DeviceArrays
     from audio_sheet_retrieval_amd.sheet_utils.omr import _engine
     engine = omr.system_detector.engine or _engine(omr.system_detector.device)
     dev_pages = DevicePages(engine, all_pages)
     try:
-        results = omr.detect_systems_pages(all_pages, in_mode=IN_U8_RAW, dev_pages=dev_pages) if all_pages else []
+        detect = omr.detect_systems_pages_dev if device_post else omr.detect_systems_pages
+        results = detect(all_pages, in_mode=IN_U8_RAW, dev_pages=dev_pages) if all_pages else []
         piece_names, piece_paths = [], []
         kept_pages = 0
         k = 0

@@ -5,12 +5,14 @@ umc_a2s_server.py (:178-189):
     python -m audio_sheet_retrieval_amd.umc_a2s_server --model models/mutopia_ccal_cont.py --data_dir <dir> \
         --train_split splits/all_split.yaml --config exp_configs/mutopia_full_aug.yaml \
         --init_sheet_db --full_eval --dump_results [--real_perf] [--n_candidates 25] [--estimate_UV] \
-        --system_params system_params.pkl --bar_params bar_params.pkl
+        --system_params system_params.pkl --bar_params bar_params.pkl [--device_post]
 
 <dir> holds one folder per piece: sheet/*.png (the page scans), score_ppq.* (the synthesised recording) and, for
 --real_perf, 01_performance*.  The pages go through the two segmentation networks (their parameter pickles:
 --system_params / --bar_params; the reference hard-codes sheet_utils/omr_models/), the detected staff systems are
-unrolled into one strip per piece (sheet_utils/umc.load_umc_sheets, require_performance=True).  --init_sheet_db embeds
+unrolled into one strip per piece (sheet_utils/umc.load_umc_sheets, require_performance=True).  --device_post (off by
+default) also finds the systems from the two maps on the device (asr_systems_from_maps_dev: the maps are not
+downloaded; a page the device does not decide goes through the host path, the result is the same).  --init_sheet_db embeds
 the strip windows (EmbeddingDB.from_images: initialize_sheet_db_from_imges) into umc_sheet_db_file.pkl in the working
 directory; without it that file is loaded.  --full_eval queries the data base with every piece's recording: 100
 windows per piece, n_candidates neighbours per window, top_k = number of pieces, the reference's rank rule; a piece
@@ -51,6 +53,8 @@ def _arguments(argv, direction):
                    help="parameters of the system detector")
     p.add_argument("--bar_params", type=str, default="sheet_utils/omr_models/bar_params.pkl",
                    help="parameters of the bar detector")
+    p.add_argument("--device_post", action="store_true",
+                   help="find the systems from the U-Net maps on the device too (asr_systems_from_maps_dev)")
     return p.parse_args(argv)
 
 
@@ -67,7 +71,7 @@ def run(argv, direction):
         raise SystemExit("--data_dir: the directory of pieces is required")
     omr = umc.build_recognizer(args.system_params, args.bar_params)
     te_pieces, piece_paths, _, strips = umc.load_umc_sheets(args.data_dir, require_performance=True, omr=omr,
-                                                           return_device=True)
+                                                           return_device=True, device_post=args.device_post)
     try:
         dset = os.path.basename(args.data_dir)
         audio_file = "01_performance" if args.real_perf else "score_ppq"

@@ -559,6 +559,40 @@ int asr_seg_predict_dev(asr_ctx *ctx, asr_seg *seg, const void *pages_dev, int i
                         const int32_t *heights, const int32_t *widths, int n_pages, double overlap,
                         double *proba_dev);
 
+/* asr_systems_from_maps_dev = detect_systems after the two probability maps exist (sheet_utils/omr.py
+ *   systems_from_maps: Otsu of the row projection, gap clean-up, Otsu of the system map, the 15x1 closing, 8-connected
+ *   labelling, bounding-box shrink and the snap to the staff-line grid) for n_pages pages in one call, the maps never
+ *   leaving the device.  pages_dev / in_mode / page_offsets / heights / widths: the pages exactly as
+ *   asr_seg_predict_dev reads them (prepare_image folded in for raw pages).  system_maps_dev: the float64 system maps
+ *   back to back as asr_seg_predict_dev writes them; bar_maps_dev: the bar maps in the same layout, or NULL (the
+ *   projection is then taken from the system map, as in the reference).  system_seg / bar_seg: the networks the maps
+ *   came from, or NULL; they only tell which page shapes equal a tile (below).
+ *   Host outputs, per page p: status[p], counts[p] and, for status 0, counts[p] rows of int32
+ *   (min_row, max_row, min_col, max_col) at systems + (p * max_systems + k) * 4, in the order the host returns them.
+ *   A page cannot hold more than heights[p] * widths[p] / 50000 blobs of MIN_AREA; a smaller max_systems is rejected
+ *   before anything is launched.
+ *       status 0  ok
+ *              1  no row of the projection lies below its Otsu threshold (the host raises IndexError)
+ *              2  the snap found no edge candidate (the host raises ValueError)
+ *              3  not decided on the device: the caller runs the host path for this page
+ *   The integers are those of the host path: every comparison that decides a pixel, a row or a peak is made on the
+ *   bits numpy would see (row sums in numpy's pairwise order, np.histogram's bin rule, no contraction).  Status 3,
+ *   never a guess, is returned for what is not restated exactly: a page of a network's tile size (the host casts
+ *   those maps to float32), a NaN or an infinity in a map or in the page, histogram edges numpy would reject, a
+ *   shrink loop that leaves the blob's bounding box, an empty row slice in the snap, pages narrower than 8 columns,
+ *   lower than 3 rows or wider than 65536 columns.
+ *   np.histogram's uniform-bin index is computed as numpy 2.x computes it, ((x - first) / (last - first)) * bins,
+ *   followed by its two corrections against the edges; numpy 1.x multiplies by bins / (last - first) instead.  The
+ *   device path is specified and tested against numpy >= 2 (2.2.6) only: under numpy 1.x the equality tests against the
+ *   host path are the judge, not this restatement.
+ *   Workspace belongs to the context; pages are processed in chunks of whole pages under ASR_OMR_BUDGET_MB (at least
+ *   one page per chunk).  label_passes (may be NULL): the number of labelling passes of the call, over all chunks. */
+int asr_systems_from_maps_dev(asr_ctx *ctx, const void *pages_dev, int in_mode, const int64_t *page_offsets,
+                              const int32_t *heights, const int32_t *widths, int n_pages,
+                              const double *system_maps_dev, const double *bar_maps_dev, const asr_seg *system_seg,
+                              const asr_seg *bar_seg, int max_systems, int32_t *status, int32_t *counts,
+                              int32_t *systems, int32_t *label_passes);
+
 /* ---- scanned scores and recordings to strips and spectrograms (umc_a2s_server.py / umc_s2a_server.py) ----------
  * asr_unroll_systems_dev = the unrolling loop of load_umc_sheets (umc_a2s_server.py:136-158) for all systems of all
  *   pages of all pieces in one launch.  pages_dev: the uint8 pages exactly as asr_seg_predict_dev (in_mode 2) reads

@@ -2,6 +2,7 @@
 """Stage timing of the UMC piece-identification path (umc_a2s_server / umc_s2a_server), batched against per-item:
 
     python tools/bench_umc.py [--pieces 8] [--pages 2] [--seconds 20] [--reps 5] [--out profiles/r12_umc_8x2.json]
+                              [--device_post]
 
 A synthetic UMC directory is written to a temporary folder: --pieces pieces of --pages pages each (PNG; the tutorial
 page of tests/golden and its left-right mirror in turn - the seeded pages of tools/bench_omr.py time the networks
@@ -15,6 +16,9 @@ return after the device is done (every library call here synchronises before it 
     png_read       imread_gray of every page                         the same
     networks       pages uploaded once, both U-Nets read them        predict_pages per network, each uploading the pages
     host_post      systems_from_maps per page                        the same
+    device_post    (--device_post, a third path "batched_device_post": the batched path with the maps left on the
+                   device - the networks stage ends without their download - and asr_systems_from_maps_dev in place of
+                   host_post; pages it does not decide go through systems_from_maps inside this stage)
     unroll         unroll_rows + asr_unroll_systems_dev, one launch  unwrap_systems per page + hstack per piece
     audio_read     load_audio of every recording                     the same
     spectrograms   process_many_dev: one launch                      process() per recording
@@ -40,6 +44,7 @@ sys.path.insert(0, ROOT)
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 HBM_PEAK_GBS = 8000.0              # MI355X HBM3E
 STAGES = ["png_read", "networks", "host_post", "unroll", "audio_read", "spectrograms", "data_base", "queries"]
+STAGES_DEVICE_POST = [s if s != "host_post" else "device_post" for s in STAGES]     # the third path's rows
 N_CANDIDATES = 25
 
 
@@ -61,8 +66,8 @@ def write_directory(root, n_pieces, n_pages, seconds):
 
 
 class Clock(object):
-    def __init__(self):
-        self.t = OrderedDict((s, 0.0) for s in STAGES)
+    def __init__(self, stages):
+        self.t = OrderedDict((s, 0.0) for s in stages)
 
     def stage(self, name):
         clock = self
@@ -91,13 +96,33 @@ def rank_all(results, names):
     return [full_eval_rank(res, votes, name)[0] for (res, votes), name in zip(results, names)]
 
 
-def run_pass(batched, data_dir, rec, engine, proc_of):
+def device_post(O, rec, pages, sys_out, bar_out, table):
+    """asr_systems_from_maps_dev on the maps where the networks left them; undecided pages through the host path"""
+    eng = rec.system_detector.engine
+    ptr, mode, sizes, offs, hs, ws = table
+    decided, _ = O.systems_from_maps_dev(eng, ptr, mode, offs, hs, ws, sys_out.ptr, bar_out.ptr, None,
+                                         rec.system_detector.handle, rec.bar_detector.handle)
+    out, fallbacks = [], 0
+    for i, (st, corners) in enumerate(decided):
+        if st == 3:
+            fallbacks += 1
+            shape = (int(hs[i]), int(ws[i]))
+            sp = O._download_at(eng, sys_out, int(offs[i]) * 8, int(sizes[i])).reshape(shape)
+            bp = O._download_at(eng, bar_out, int(offs[i]) * 8, int(sizes[i])).reshape(shape)
+            out += host_post(O, rec, [pages[i]], [sp], [bp])
+        else:
+            out.append(corners if st == 0 else np.zeros((0, 4, 2)))
+    return out, fallbacks
+
+
+def run_pass(batched, data_dir, rec, engine, proc_of, dev_post=False):
     import glob
     from audio_sheet_retrieval_amd.audio_frontend import load_audio
     from audio_sheet_retrieval_amd.piece_identification import (DeviceArrays, EmbeddingDB, detect_performance,
                                                                 detect_performances, detect_score, detect_scores)
     from audio_sheet_retrieval_amd.sheet_utils import omr as O
-    c = Clock()
+    c = Clock(STAGES_DEVICE_POST if dev_post else STAGES)
+    fallbacks = 0
     piece_dirs = sorted(glob.glob(os.path.join(data_dir, "*")))
     names = [os.path.basename(d) for d in piece_dirs]
     n = len(names)
@@ -112,10 +137,21 @@ def run_pass(batched, data_dir, rec, engine, proc_of):
     if batched:
         with c.stage("networks"):
             dev_pages = O.DevicePages(rec.system_detector.engine, pages)
-            sys_maps = rec.system_detector.predict_pages(dev_pages)
-            bar_maps = rec.bar_detector.predict_pages(dev_pages)
-        with c.stage("host_post"):
-            systems = host_post(O, rec, pages, sys_maps, bar_maps)
+            if dev_post:
+                sys_out, _, table = rec.system_detector.predict_pages_dev(dev_pages)
+                bar_out, _, _ = rec.bar_detector.predict_pages_dev(dev_pages)
+                rec.system_detector.engine.sync()
+            else:
+                sys_maps = rec.system_detector.predict_pages(dev_pages)
+                bar_maps = rec.bar_detector.predict_pages(dev_pages)
+        if dev_post:
+            with c.stage("device_post"):
+                systems, fallbacks = device_post(O, rec, pages, sys_out, bar_out, table)
+            sys_out.free()
+            bar_out.free()
+        else:
+            with c.stage("host_post"):
+                systems = host_post(O, rec, pages, sys_maps, bar_maps)
         with c.stage("unroll"):
             rows = [O.unroll_rows(p.shape, s) for p, s in zip(pages, systems)]
             strips = DeviceArrays(*O.unroll_systems_dev(dev_pages, rows, piece_of_page, n))
@@ -169,7 +205,7 @@ def run_pass(batched, data_dir, rec, engine, proc_of):
     n_windows = (len(sheet_db), len(audio_db))
     sheet_db.close()
     audio_db.close()
-    return c.t, ranks, n_windows, sum(len(s) for s in systems)
+    return c.t, ranks, n_windows, sum(len(s) for s in systems), fallbacks
 
 
 def main():
@@ -179,6 +215,8 @@ def main():
     p.add_argument("--seconds", type=float, default=20.0)
     p.add_argument("--reps", type=int, default=5)
     p.add_argument("--out", default=None)
+    p.add_argument("--device_post", action="store_true",
+                   help="also time the batched path with asr_systems_from_maps_dev in place of host_post")
     a = p.parse_args()
 
     from audio_sheet_retrieval_amd import _lib
@@ -206,14 +244,15 @@ def main():
     with tempfile.TemporaryDirectory() as tmp:
         write_directory(tmp, a.pieces, a.pages, a.seconds)
         ranks = {}
-        for path in ("batched", "per_item"):
-            run_pass(path == "batched", tmp, rec, engine, proc_of)                 # warm-up
+        for path in ("batched", "per_item") + (("batched_device_post",) if a.device_post else ()):
+            args = (path != "per_item", tmp, rec, engine, proc_of, path == "batched_device_post")
+            run_pass(*args)                                                        # warm-up
             passes = []
             for _ in range(a.reps):
-                t, ranks[path], n_windows, n_systems = run_pass(path == "batched", tmp, rec, engine, proc_of)
+                t, ranks[path], n_windows, n_systems, fallbacks = run_pass(*args)
                 passes.append(t)
             table = OrderedDict()
-            for s in STAGES:
+            for s in passes[0]:
                 v = [ps[s] * 1e3 for ps in passes]
                 table[s] = OrderedDict(median_ms=round(float(np.median(v)), 3), min_ms=round(min(v), 3),
                                        max_ms=round(max(v), 3))
@@ -223,21 +262,26 @@ def main():
             out[path] = table
         out["db_windows_sheet_audio"] = list(n_windows)
         out["systems"] = n_systems
-        out["ranks_equal"] = ranks["batched"] == ranks["per_item"]
+        out["ranks_equal"] = all(r == ranks["batched"] for r in ranks.values())
+        if a.device_post:
+            out["device_post_fallback_pages"] = fallbacks
 
         # device time of the two new kernels: one more batched pass under the event profiler
         oe = rec.system_detector.engine
         for e in (oe, engine):
             e.profile_enable(True)
             e.profile_reset()
-        run_pass(True, tmp, rec, engine, proc_of)
+        run_pass(True, tmp, rec, engine, proc_of, a.device_post)
         prof = {r["name"]: r for e in (oe, engine) for r in e.profile()}
         for e in (oe, engine):
             e.profile_enable(False)
-    for label in ("unroll_systems", "spectrogram_batch"):
+    post = ("post_rows", "post_threshold", "post_close", "post_label_pass", "post_blobs") if a.device_post else ()
+    for label in ("unroll_systems", "spectrogram_batch") + post:
         r = prof.get(label)
         if r:
             out[label] = OrderedDict(device_ms=round(r["total_ms"], 4), bytes=r.get("bytes"), flops=r.get("flops"))
+            if label in post:
+                out[label]["launches"] = r.get("launches")
     r = prof.get("unroll_systems")
     if r and r["total_ms"] > 0:
         gbs = r["bytes"] / (r["total_ms"] * 1e-3) / 1e9
