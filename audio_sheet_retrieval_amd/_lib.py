@@ -39,7 +39,7 @@ EXPORTS = [
     "asr_valid_loss_in", "asr_valid_output_in", "asr_valid_output_in_dev",
     "asr_comm_unique_id", "asr_comm_init", "asr_comm_init_custom", "asr_comm_destroy", "asr_comm_info", "asr_comm_stats", "asr_comm_timing", "asr_comm_library",
     "asr_comm_allreduce_dev", "asr_comm_allgather_dev",
-    "asr_rank_sharded_dev", "asr_slice_windows_dev", "asr_piece_vote_dev", "asr_piece_vote_batch_dev", "asr_gather_windows_dev", "asr_dtw_dev", "asr_dtw_batch_dev", "asr_spectrogram_dev", "asr_debug_tune_report",
+    "asr_rank_sharded_dev", "asr_slice_windows_dev", "asr_piece_vote_dev", "asr_piece_vote_batch_dev", "asr_track_gate_dev", "asr_track_vote_batch_dev", "asr_gather_windows_dev", "asr_dtw_dev", "asr_dtw_batch_dev", "asr_spectrogram_dev", "asr_debug_tune_report",
     "asr_seg_create", "asr_seg_set_window", "asr_seg_destroy", "asr_seg_predict_dev", "asr_systems_from_maps_dev",
     "asr_unroll_systems_dev", "asr_spectrogram_batch_dev",
     "asr_opt_state_size", "asr_get_opt_state", "asr_set_opt_state", "asr_debug_train_tensor", "asr_cca_train_debug",
@@ -195,6 +195,9 @@ def load_library(path=None):
                                               c_void_p]),
         "asr_piece_vote_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int32, c_int]
                                      + [c_void_p] * 6),
+        "asr_track_gate_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int] + [c_void_p] * 5 + [c_int] + [c_void_p] * 3),
+        "asr_track_vote_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                             c_void_p, c_int64, c_int32, c_int, c_void_p, c_void_p, c_void_p]),
         "asr_gather_windows_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p]),
         "asr_dtw_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                 POINTER(c_int32), POINTER(c_double)]),
@@ -449,6 +452,52 @@ class Engine(object):
                                                       top_k, ptr(t), ptr(pieces), ptr(counts), ptr(n_out), ptr(ranks),
                                                       ptr(ratios)))
         return pieces, counts, n_out, ranks, ratios
+
+    def track_gate_dev(self, src_ptr, src_floats, offsets, shapes, width, norm=None, frame0=None):
+        """the music gate of the reference's live loop (asr_track_gate_dev) for recordings of `shapes` (bins, frames) at
+        float `offsets` of the device buffer -> (m_prob float32, voiced bool, level float32 per recording); the per-frame
+        arrays hold the recordings one after the other.  norm: per recording a level that replaces its column-sum
+        maximum (NaN: keep the maximum); frame0: per recording the stream position of its column 0."""
+        n = len(shapes)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        bins = np.ascontiguousarray([s[0] for s in shapes], dtype=np.int32)
+        frames = np.ascontiguousarray([s[1] for s in shapes], dtype=np.int32)
+        if off.shape != (n,):
+            raise ValueError("track_gate_dev: %d offsets for %d recordings" % (off.size, n))
+        nrm = None if norm is None else np.ascontiguousarray(norm, dtype=np.float32)
+        f0 = None if frame0 is None else np.ascontiguousarray(frame0, dtype=np.int64)
+        for name, x in (("norm", nrm), ("frame0", f0)):
+            if x is not None and x.shape != (n,):
+                raise ValueError("track_gate_dev: %d %s values for %d recordings" % (x.size, name, n))
+        total = int(np.maximum(frames, 0).sum())
+        m_prob, voiced, level = np.empty(total, np.float32), np.empty(total, np.uint8), np.empty(n, np.float32)
+        ptr = lambda x: None if x is None else x.ctypes.data
+        self._check(self.lib.asr_track_gate_dev(self.ctx, src_ptr, src_floats, n, ptr(off), ptr(bins), ptr(frames), ptr(f0),
+                                                ptr(nrm), width, ptr(m_prob), ptr(voiced), ptr(level)))
+        return m_prob, voiced.astype(bool), level
+
+    def track_vote_batch_dev(self, idx_ptr, n_rows, row_first, row_count, n_candidates, running_frames, ids_ptr, n_db,
+                             n_pieces, top_k, emit_from=None):
+        """the sliding vote over the (n_rows, n_candidates) top-k table of all voiced frames (asr_track_vote_batch_dev):
+        recording r owns rows row_first[r] .. + row_count[r]; per frame from emit_from[r] on (default 0) the vote over
+        its last running_frames frames -> (pieces (E, top_k) int32, counts (E, top_k) int32, n_out (E,) int32), E = the
+        emitted frames of all recordings one after the other; piece -1 / count 0 past n_out."""
+        first = np.ascontiguousarray(row_first, dtype=np.int64)
+        count = np.ascontiguousarray(row_count, dtype=np.int64)
+        n = first.size
+        if first.ndim != 1 or count.shape != (n,):
+            raise ValueError("track_vote_batch_dev: %d row ranges, %d row counts" % (n, count.size))
+        emit = None if emit_from is None else np.ascontiguousarray(emit_from, dtype=np.int64)
+        if emit is not None and emit.shape != (n,):
+            raise ValueError("track_vote_batch_dev: %d emit_from values for %d recordings" % (emit.size, n))
+        e = int(np.maximum(count - (0 if emit is None else emit), 0).sum())
+        k = max(int(top_k), 0)
+        pieces, counts, n_out = np.empty((e, k), np.int32), np.empty((e, k), np.int32), np.empty(e, np.int32)
+        ptr = lambda x: None if x is None else x.ctypes.data
+        self._check(self.lib.asr_track_vote_batch_dev(self.ctx, idx_ptr, n_rows, n, ptr(first), ptr(count), ptr(emit),
+                                                      n_candidates, running_frames, ids_ptr, n_db, n_pieces, top_k,
+                                                      ptr(pieces), ptr(counts), ptr(n_out)))
+        return pieces, counts, n_out
 
     def dtw(self, a, b, want_dists=True):
         """cosine distance matrix + DTW of two code sequences, rows = a (utils/dtw_by_dist.py:5-34 on

@@ -14,9 +14,16 @@ rule (:640-645).  --dump_results writes the ranks to retrieval_<tag>_A2S.yaml ne
 scripts/eval_piece_retrieval.py reads.
 
 Here the windows of all pieces are cut on the device, embedded in one call per tower, and all pieces are voted on in one
-asr_piece_vote_batch_dev call (piece_identification.detect_scores).  The live server loop (microphone, GUI), audio
-decoding (--real_audio) and MSMD loading are not part of this implementation.  sheet_audio_server.py is the S2A
-direction (sheet -> audio) of the same driver.
+asr_piece_vote_batch_dev call (piece_identification.detect_scores).
+
+--track (A2S only) runs the reference's default mode, the running vote of AudioSheetServer.run (:83-211), over every
+test piece's spectrogram instead of its microphone: every frame with music is embedded and looked up, and the vote over
+the last --running_frames such frames ranks the pieces (piece_identification.track_scores, top_k = 7).  Per piece it
+prints the first frame at which the target leads and the share of voiced frames at which it leads; --dump_results
+writes the two lists to tracking_<tag>_A2S.yaml.
+
+The microphone and the GUI of the live server, audio decoding (--real_audio) and MSMD loading are not part of this
+implementation.  sheet_audio_server.py is the S2A direction (sheet -> audio) of the same driver.
 """
 import argparse
 import os
@@ -25,7 +32,7 @@ import numpy as np
 import yaml
 
 from . import audio2sheet_align
-from .piece_identification import EmbeddingDB, detect_performances, detect_scores, rank_summary
+from .piece_identification import EmbeddingDB, detect_performances, detect_scores, rank_summary, track_scores
 from .utils.data_pools import NO_AUGMENT, AudioScoreRetrievalPool
 
 # per direction: data-base flag, data-base file, data-base view, what a query finds (the reference's summary line)
@@ -58,7 +65,11 @@ def _arguments(argv, direction):
     p.add_argument("--data", type=str, default="synthetic", help="test pieces ('synthetic[:n_pieces]')")
     if direction == "A2S":
         p.add_argument("--real_audio", action="store_true", help="(audio decoding is not part of this implementation)")
-    p.add_argument("--running_frames", type=int, default=100, help="(live server only; accepted)")
+    p.add_argument("--running_frames", type=int, default=100,
+                   help="voiced frames in the history of the running vote (--track)")
+    if direction == "A2S":
+        p.add_argument("--track", action="store_true",
+                       help="run the live server's running vote over every test piece's spectrogram")
     p.add_argument("--seed", type=int, default=23)
     return p.parse_args(argv)
 
@@ -83,6 +94,40 @@ def identify(engine, db, direction, pool, names, n_candidates):
     return ranks, ratios, res
 
 
+TRACK_TOP_K = 7
+
+
+def tracking_file(param_file, direction):
+    """result_file's name with tracking_ in place of retrieval_"""
+    return param_file.replace("params_", "tracking_").replace(".pkl", "_%s.yaml") % direction
+
+
+def track(engine, db, pool, names, n_candidates, running_frames):
+    """the running vote over every piece's spectrogram -> (names, per piece the first frame at which its own piece
+    leads the ranking (-1: never), per piece the share of its voiced frames at which it leads (0.0 without voiced
+    frames))"""
+    ids = {name: i for i, name in db.id_to_name.items()}
+    results = track_scores(engine, db, [spec[0] for spec in pool.specs], top_k=TRACK_TOP_K, n_candidates=n_candidates,
+                           running_frames=running_frames, spec_shape=tuple(pool.spec_dim))
+    first_lead, lead_share = [], []
+    for name, res in zip(names, results):
+        leads = (res.n_out > 0) & (res.pieces[:, 0] == ids.get(name, -2)) if len(res.frames) else np.zeros(0, bool)
+        first_lead.append(int(res.frames[np.argmax(leads)]) if leads.any() else -1)
+        lead_share.append(float(leads.mean()) if leads.size else 0.0)
+    return names, first_lead, lead_share
+
+
+def report_tracking(names, first_lead, lead_share, res_file=None):
+    for name, first, share in zip(names, first_lead, lead_share):
+        print("leads from frame %5d, at %.2f of the voiced frames  %s" % (first, share, name))
+    results = {"first_lead": [int(f) for f in first_lead], "lead_share": [float(v) for v in lead_share]}
+    if res_file is not None:
+        with open(res_file, "w") as fp:
+            yaml.dump(results, fp, default_flow_style=False)
+        print("tracking of %d pieces written to %s" % (len(names), res_file))
+    return results
+
+
 def run(argv, direction):
     d = DIRECTIONS[direction]
     args = _arguments(argv, direction)
@@ -99,6 +144,10 @@ def run(argv, direction):
         db.save(d["db_file"])
     else:
         db = EmbeddingDB.load(engine, d["db_file"])
+    if getattr(args, "track", False):
+        print("\nTracking every test piece:")
+        return report_tracking(*track(engine, db, pool, data["names"], args.n_candidates, args.running_frames),
+                               res_file=tracking_file(param_file, direction) if args.dump_results else None)
     if not args.full_eval:
         raise SystemExit("the live server loop (microphone, GUI) is not part of this implementation; use --full_eval")
 

@@ -22,8 +22,9 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 BASE_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wno-comment", "-Wno-unused-result", "-Wno-unused-value"]
 EXTRA_FLAGS = os.environ.get("ASR_EXTRA_HIPCC_FLAGS", "").split()      # timing experiments (tools/ablate_*.sh): -DASR_WINOG_ABL=...
 FLAGS = BASE_FLAGS + ["-I", INCLUDE] + EXTRA_FLAGS
-# per-source flags: the restated numpy arithmetic of systems_from_maps compares bits, so no fused multiply-adds there
-FILE_FLAGS = {"omr_post_kernels.hip": ["-ffp-contract=off"]}
+# per-source flags: the restated numpy arithmetic of systems_from_maps and of the tracking loop's music gate compares
+# bits, so no fused multiply-adds there
+FILE_FLAGS = {"omr_post_kernels.hip": ["-ffp-contract=off"], "track_kernels.hip": ["-ffp-contract=off"]}
 
 
 def sources():

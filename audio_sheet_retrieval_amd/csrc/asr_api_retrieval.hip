@@ -842,6 +842,147 @@ int asr_piece_vote_batch_dev(asr_ctx *ctx, const int32_t *idx_dev, int64_t n_gro
     return mark_main(ctx);
 }
 
+// ---- running piece vote (track_kernels.hip) ---------------------------------------------------------------------------
+// both calls keep their tables and results in the vote workspace of the context
+static int track_ws(asr_ctx *ctx, size_t need) {
+    if (need <= ctx->vote_ws_bytes) return ASR_OK;
+    int rc = sync_all(ctx);
+    if (rc != ASR_OK) return rc;
+    if (ctx->vote_ws) ASR_HIP(ctx, hipFree(ctx->vote_ws));
+    ctx->vote_ws = nullptr; ctx->vote_ws_bytes = 0;
+    ASR_HIP(ctx, hipMalloc(&ctx->vote_ws, need));
+    ctx->vote_ws_bytes = need;
+    return ASR_OK;
+}
+
+int asr_track_gate_dev(asr_ctx *ctx, const float *src_dev, int64_t src_floats, int n_rec, const int64_t *offsets,
+                       const int32_t *bins, const int32_t *frames, const int64_t *frame0, const float *norm, int width,
+                       float *m_prob, uint8_t *voiced, float *level) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_rec < 0 || src_floats < 0 || width < 8 || width > 128)
+        return fail(ctx, ASR_ERR_INVALID, "track_gate: bad sizes n_rec=%d width=%d (8..128)", n_rec, width);
+    if (n_rec == 0) return ASR_OK;
+    if (!src_dev || !offsets || !bins || !frames || !m_prob || !voiced)
+        return fail(ctx, ASR_ERR_INVALID, "track_gate: NULL argument");
+    std::vector<asr::TrackRec> recs(n_rec);
+    int64_t total = 0;
+    for (int r = 0; r < n_rec; ++r) {
+        if (bins[r] < 1 || frames[r] < 1 || offsets[r] < 0 || offsets[r] > src_floats ||
+            (int64_t)bins[r] * frames[r] > src_floats - offsets[r])
+            return fail(ctx, ASR_ERR_INVALID, "track_gate: recording %d (%d x %d at %lld) lies outside the %lld-float buffer",
+                        r, bins[r], frames[r], (long long)offsets[r], (long long)src_floats);
+        asr::TrackRec &R = recs[r];
+        R.off = offsets[r]; R.first = total; R.frame0 = frame0 ? frame0[r] : 0;
+        R.bins = bins[r]; R.frames = frames[r];
+        R.has_norm = norm && norm[r] == norm[r];
+        R.norm = R.has_norm ? norm[r] : 0.0f;
+        total += frames[r];
+        if (total > INT32_MAX) return fail(ctx, ASR_ERR_INVALID, "track_gate: more than 2^31 - 1 frames");
+    }
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    int rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    // results (one download): m_prob | level | voiced; then the recording table and the column sums
+    const size_t T = (size_t)total, o_level = T * 4, o_voiced = o_level + (size_t)n_rec * 4, res_bytes = o_voiced + T;
+    const size_t o_recs = dtw_align(res_bytes), o_colsum = dtw_align(o_recs + recs.size() * sizeof(asr::TrackRec));
+    rc = track_ws(ctx, o_colsum + T * 4);
+    if (rc != ASR_OK) return rc;
+    char *ws = (char *)ctx->vote_ws;
+    ASR_HIP(ctx, hipMemcpyAsync(ws + o_recs, recs.data(), recs.size() * sizeof(asr::TrackRec), hipMemcpyHostToDevice,
+                                ctx->stream));
+    {
+        ProfScope ps(ctx, "track_gate", 0, 0.0, 4.0 * (double)src_floats);
+        asr::TrackGateArgs a;
+        a.src = src_dev; a.recs = (const asr::TrackRec *)(ws + o_recs); a.n_rec = n_rec; a.total_frames = total;
+        a.width = width;
+        a.colsum = (float *)(ws + o_colsum); a.level = (float *)(ws + o_level);
+        a.m_prob = (float *)ws; a.voiced = (uint8_t *)(ws + o_voiced);
+        ASR_HIP(ctx, asr::launch_track_gate(ctx->stream, a));
+    }
+    std::vector<char> host(res_bytes);
+    ASR_HIP(ctx, hipMemcpyAsync(host.data(), ws, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    ASR_HIP(ctx, hipStreamSynchronize(ctx->stream));    // (also: `recs` was read by the upload)
+    memcpy(m_prob, host.data(), T * 4);
+    if (level) memcpy(level, host.data() + o_level, (size_t)n_rec * 4);
+    memcpy(voiced, host.data() + o_voiced, T);
+    return mark_main(ctx);
+}
+
+int asr_track_vote_batch_dev(asr_ctx *ctx, const int32_t *idx_dev, int64_t n_rows, int n_rec, const int64_t *row_first,
+                             const int64_t *row_count, const int64_t *emit_from, int n_candidates, int running_frames,
+                             const int32_t *ids_dev, int64_t n_db, int32_t n_pieces, int top_k, int32_t *pieces,
+                             int32_t *counts, int32_t *n_out) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_rec < 0 || n_rows < 0 || top_k < 1 || top_k > 64 || n_candidates < 1 || running_frames < 1 ||
+        n_db < n_candidates || n_db > INT32_MAX || n_pieces < 1 || n_pieces > (1 << 30) ||
+        n_rows > (INT64_MAX / 4) / n_candidates)
+        return fail(ctx, ASR_ERR_INVALID,
+                    "track_vote_batch: bad sizes n_rows=%lld n_rec=%d n_candidates=%d running_frames=%d n_db=%lld "
+                    "n_pieces=%d top_k=%d (1..64)", (long long)n_rows, n_rec, n_candidates, running_frames,
+                    (long long)n_db, n_pieces, top_k);
+    if (n_rec == 0) return ASR_OK;
+    if (!row_first || !row_count) return fail(ctx, ASR_ERR_INVALID, "track_vote_batch: NULL argument");
+    const int64_t seg_frames = std::max<int64_t>(1, dtw_env("ASR_TRACK_SEG_FRAMES", 64));
+    std::vector<asr::TrackSeg> segs;
+    int64_t n_emit = 0;
+    for (int r = 0; r < n_rec; ++r) {
+        const int64_t from = emit_from ? emit_from[r] : 0;
+        if (row_first[r] < 0 || row_count[r] < 0 || row_first[r] > n_rows || row_count[r] > n_rows - row_first[r] ||
+            from < 0 || from > row_count[r])
+            return fail(ctx, ASR_ERR_INVALID, "track_vote_batch: recording %d: rows [%lld, +%lld) emit_from %lld of %lld rows",
+                        r, (long long)row_first[r], (long long)row_count[r], (long long)from, (long long)n_rows);
+        for (int64_t f = from; f < row_count[r]; f += seg_frames) {
+            asr::TrackSeg S;
+            S.row0 = row_first[r]; S.f0 = f; S.out0 = n_emit + (f - from);
+            S.n = (int32_t)std::min<int64_t>(seg_frames, row_count[r] - f); S.pad = 0;
+            segs.push_back(S);
+        }
+        n_emit += row_count[r] - from;
+    }
+    if (n_emit == 0) return ASR_OK;
+    if (n_emit > INT32_MAX) return fail(ctx, ASR_ERR_INVALID, "track_vote_batch: more than 2^31 - 1 frames");
+    if (!idx_dev || !ids_dev || !pieces || !counts || !n_out)
+        return fail(ctx, ASR_ERR_INVALID, "track_vote_batch: NULL argument");
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    int rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+
+    // ASR_TRACK_SEG_FRAMES=<n> (debug): frames per segment (default 64); ASR_TRACK_LDS_PIECES=<n> (debug): n_pieces above
+    // it take the global-workspace path; ASR_VOTE_BUDGET_MB bounds that workspace (fewer workgroups, more segments each)
+    const int64_t lds_pieces = std::min<int64_t>(asr::TRACK_LDS_PIECES, dtw_env("ASR_TRACK_LDS_PIECES", 1 << 30));
+    const bool global_path = n_pieces > lds_pieces;
+    const size_t budget = (size_t)std::max<int64_t>(dtw_env("ASR_VOTE_BUDGET_MB", 1024), 1) << 20;
+    int64_t grid = std::min<int64_t>((int64_t)segs.size(), 65536);
+    if (global_path) grid = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(grid, 4096), budget / ((size_t)n_pieces * 4)));
+
+    // results block (one download): pieces | counts (n_emit x top_k) | n_out; then the segment table and the counters
+    const size_t E = (size_t)n_emit, EK = E * (size_t)top_k;
+    const size_t o_counts = EK * 4, o_nout = 2 * EK * 4, res_bytes = o_nout + E * 4;
+    const size_t o_segs = dtw_align(res_bytes), o_hist = dtw_align(o_segs + segs.size() * sizeof(asr::TrackSeg));
+    rc = track_ws(ctx, o_hist + (global_path ? (size_t)grid * n_pieces * 4 : 0));
+    if (rc != ASR_OK) return rc;
+    char *ws = (char *)ctx->vote_ws;
+    ASR_HIP(ctx, hipMemcpyAsync(ws + o_segs, segs.data(), segs.size() * sizeof(asr::TrackSeg), hipMemcpyHostToDevice,
+                                ctx->stream));
+    {
+        ProfScope ps(ctx, "track_vote_batch", 0, 0.0, 4.0 * (double)n_rows * n_candidates + 8.0 * (double)EK);
+        asr::TrackVoteArgs a;
+        a.idx = idx_dev; a.segs = (const asr::TrackSeg *)(ws + o_segs); a.n_segs = (int64_t)segs.size();
+        a.n_candidates = n_candidates; a.running_frames = running_frames;
+        a.ids = ids_dev; a.n_db = n_db; a.n_pieces = n_pieces; a.top_k = top_k;
+        a.pieces = (int32_t *)ws; a.counts = (int32_t *)(ws + o_counts); a.n_out = (int32_t *)(ws + o_nout);
+        a.hist_ws = (int32_t *)(ws + o_hist);
+        ASR_HIP(ctx, asr::launch_track_vote(ctx->stream, a, (int)grid, global_path));
+    }
+    std::vector<char> host(res_bytes);
+    ASR_HIP(ctx, hipMemcpyAsync(host.data(), ws, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    ASR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(pieces, host.data(), EK * 4);
+    memcpy(counts, host.data() + o_counts, EK * 4);
+    memcpy(n_out, host.data() + o_nout, E * 4);
+    return mark_main(ctx);
+}
+
 int asr_topk(asr_ctx *ctx, const float *db, int64_t n_db, int64_t ld_db, const float *q, int64_t n_q, int64_t ld_q,
              int dim, int k, int64_t idx_offset, int32_t *idx, double *dist) {
     if (!ctx) return ASR_ERR_INVALID;

@@ -239,6 +239,35 @@ struct VoteBatchArgs {
 };
 hipError_t launch_piece_vote_batch(hipStream_t s, const VoteBatchArgs &a, bool global_path);
 
+// ---- running piece vote (track_kernels.hip): AudioSheetServer.run (audio_sheet_server.py:83-211) over recordings ----
+// music gate: recordings (bins, frames) float32 row-major at float offset `off` of src; `first` = the recording's first
+// entry in the concatenated per-frame arrays (ascending); frame0 = the stream position of its column 0 (0 offline);
+// has_norm: norm replaces spec.sum(axis=0).max().  All pointers on the device.
+struct TrackRec {
+    int64_t off, first, frame0;
+    int32_t bins, frames;
+    float norm; int32_t has_norm;
+};
+struct TrackGateArgs {
+    const float *src; const TrackRec *recs; int n_rec; int64_t total_frames; int width;
+    float *colsum, *level;              // workspace: total_frames / n_rec floats
+    float *m_prob; uint8_t *voiced;     // total_frames each
+};
+hipError_t launch_track_gate(hipStream_t s, const TrackGateArgs &a);
+// sliding vote: one wave per segment = frames f0 .. f0 + n - 1 of a recording whose frame f is row row0 + f of the
+// (rows x n_candidates) top-k index table; frame f0 + i writes output row out0 + i.  n_pieces <= TRACK_LDS_PIECES keeps
+// the counters in LDS (16 KiB), larger ones use hist_ws (grid * n_pieces int32, zeroed by the launcher).
+constexpr int TRACK_LDS_PIECES = 4096;
+struct TrackSeg { int64_t row0, f0, out0; int32_t n, pad; };
+struct TrackVoteArgs {
+    const int32_t *idx; const TrackSeg *segs; int64_t n_segs;
+    int n_candidates, running_frames;
+    const int32_t *ids; int64_t n_db; int32_t n_pieces; int top_k;
+    int32_t *pieces, *counts, *n_out;
+    int32_t *hist_ws;
+};
+hipError_t launch_track_vote(hipStream_t s, const TrackVoteArgs &a, int grid, bool global_path);
+
 // autotuner self-check (ASR_TUNE_VERIFY=1): deterministic input pattern, max |a - b| as float bits
 hipError_t launch_fill_pattern(hipStream_t s, float *p, int64_t n);
 hipError_t launch_max_abs_diff(hipStream_t s, const float *a, const float *b, int64_t n, uint32_t *out_bits);

@@ -4,6 +4,10 @@ embedding data base (:496-522 load/save_*_db_file: pickle of [codes, ids, id_to_
 
 Everything between the long input and the vote result stays on the GPU: window slicing, tower forward, top-k against
 the resident data base, vote histogram and selection (csrc/piece_vote_kernels.hip).  SURVEY.md 8f row 1.
+
+The server's default mode, the running vote of AudioSheetServer.run (:83-211), is track_scores / track_score (whole
+recordings, batched) and PieceTracker (blocks of new frames): music gate and sliding vote in csrc/track_kernels.hip,
+track_score_host the numpy restatement they are tested against.
 """
 from __future__ import annotations
 
@@ -437,3 +441,263 @@ def rank_summary(ranks):
     cnt = int(np.sum(ranks > 10))
     out[">10"] = (cnt, cnt / float(n) if n else 0.0)
     return out
+
+
+# ---- the running vote of the live server (audio_sheet_server.py:83-211 AudioSheetServer.run) ------------------------
+M_THRESH = 0.5              # :116
+
+
+class TrackResult(object):
+    """The loop's state after every frame of one recording (or of one block of a stream).
+    m_prob (T,) float32 and voiced (T,) bool per frame; frames: the indices of the voiced frames; per voiced frame
+    pieces / counts (n_voiced, top_k) int32 (piece -1 / count 0 past n_out), n_out (n_voiced,) int32 and history
+    (n_voiced,) = len(all_piece_ids) at that frame; idx: the (n_voiced, n_candidates) data-base indices, on request."""
+
+    def __init__(self, m_prob, voiced, frames, pieces, counts, n_out, history, id_to_name, idx=None):
+        self.m_prob, self.voiced, self.frames = m_prob, voiced, frames
+        self.pieces, self.counts, self.n_out, self.history = pieces, counts, n_out, history
+        self.id_to_name, self.idx = id_to_name, idx
+
+    def ranking(self, i):
+        """what the server shows at frame i (:167-170): (piece names, float64 probabilities = counts / len(history)) of
+        the last voiced frame <= i - an unvoiced frame changes nothing - or None before the first one"""
+        k = int(np.searchsorted(self.frames, i, side="right")) - 1
+        if k < 0:
+            return None
+        n = int(self.n_out[k])
+        names = [self.id_to_name[int(p)] for p in self.pieces[k, :n]]
+        return names, self.counts[k, :n].astype(np.float64) / float(self.history[k])
+
+
+def _track_check(top_k, n_candidates, running_frames, max_windows=1):
+    if running_frames is None or int(running_frames) != running_frames or running_frames < 1:
+        raise ValueError("running_frames must be an int >= 1, got %r (the reference raises on None)" % (running_frames,))
+    if top_k < 1 or n_candidates < 1 or max_windows < 1:
+        raise ValueError("top_k, n_candidates and max_windows must be >= 1")
+
+
+def _history_lengths(n_before, n_new, n_candidates, running_frames):
+    """len(all_piece_ids) (:126-129) at each of n_new voiced frames that follow n_before earlier ones"""
+    return np.minimum(n_before + 1 + np.arange(n_new, dtype=np.int64), running_frames) * n_candidates
+
+
+def track_gate_host(spectrogram, width, level=None):
+    """the loop's gate, line by line (:92, :110-117, _detect_music :524-528) -> (m_prob (T,) float32, voiced (T,) bool).
+    level: stands in for spec.sum(axis=0).max() (a stream does not know it)."""
+    spec = np.ascontiguousarray(spectrogram, dtype=np.float32)
+    T = spec.shape[1]
+    m_probs, voiced = np.zeros(T, np.float32), np.zeros(T, bool)
+    running_spec = np.zeros((spec.shape[0], width), dtype=np.float32)
+    norm = spec.sum(axis=0).max() if level is None else np.float32(level)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for i_frame in range(T):
+            running_spec = np.hstack((running_spec[:, 1::], spec[:, i_frame:i_frame + 1]))
+            music_prob = running_spec.sum(axis=0).mean()
+            music_prob /= (norm * 0.15)
+            m_prob = np.clip(music_prob, 0.0, 1.0)
+            m_probs[i_frame] = m_prob
+            voiced[i_frame] = m_prob > M_THRESH and i_frame >= running_spec.shape[1]
+    return m_probs, voiced
+
+
+def track_vote_host(piece_id_rows, top_k, running_frames):
+    """the loop's history and vote (:126-138) over the piece ids of the voiced frames, one row of n_candidates ids per
+    frame -> (pieces, counts (n, top_k) int32, n_out (n,) int32, history (n,) int64).  np.argsort(counts)[::-1] leaves
+    the order of equal counts open; here the larger piece id comes first (asr_piece_vote_dev's rule)."""
+    rows = np.asarray(piece_id_rows, dtype=np.int64)
+    n, n_candidates = rows.shape
+    pieces, counts = np.full((n, top_k), -1, np.int32), np.zeros((n, top_k), np.int32)
+    n_out, history = np.zeros(n, np.int32), np.zeros(n, np.int64)
+    all_piece_ids = np.zeros(0, dtype=np.int64)
+    for k in range(n):
+        all_piece_ids = np.concatenate((all_piece_ids, rows[k]))
+        first_idx = running_frames * n_candidates
+        if all_piece_ids.shape[0] > first_idx:
+            all_piece_ids = all_piece_ids[-first_idx:]
+        unique, cnt = np.unique(all_piece_ids, return_counts=True)
+        order = np.lexsort((unique, cnt))[::-1][:top_k]
+        m = len(order)
+        pieces[k, :m], counts[k, :m], n_out[k], history[k] = unique[order], cnt[order], m, all_piece_ids.shape[0]
+    return pieces, counts, n_out, history
+
+
+def track_score_host(engine, sheet_db, spectrogram, top_k=5, n_candidates=5, running_frames=100, spec_shape=(92, 42),
+                     level=None):
+    """AudioSheetServer.run (:83-211) on one spectrogram, restated in numpy - the yardstick of track_scores and
+    PieceTracker.  Gate and vote are track_gate_host / track_vote_host; the window of every voiced frame is embedded
+    (compute_view_2, :120) and looked up (:123) on its own with the single-query functions.  -> TrackResult with idx."""
+    _track_check(top_k, n_candidates, running_frames)
+    spec = np.ascontiguousarray(spectrogram, dtype=np.float32)
+    win_h, win_w = spec_shape
+    if spec.ndim != 2 or spec.shape[0] != win_h:
+        raise ValueError("expected a (%d, frames) spectrogram, got shape %r" % (win_h, spec.shape))
+    m_prob, voiced = track_gate_host(spec, win_w, level)
+    frames = np.flatnonzero(voiced)
+    if (engine.cfg.h2, engine.cfg.w2) != (win_h, win_w):
+        engine.set_input_size(2, win_h, win_w)
+    idx = np.zeros((len(frames), n_candidates), np.int32)
+    for k, i in enumerate(frames):
+        running_spec = np.ascontiguousarray(spec[:, i - win_w + 1:i + 1])
+        spec_code = engine.embed_view2(running_spec[np.newaxis, np.newaxis, :, :])
+        idx[k] = sheet_db.retrieve(spec_code, n_candidates)[0][0]
+    pieces, counts, n_out, history = track_vote_host(sheet_db.ids[idx].reshape(len(frames), n_candidates), top_k,
+                                                     running_frames)
+    return TrackResult(m_prob, voiced, frames, pieces, counts, n_out, history, sheet_db.id_to_name, idx)
+
+
+def _track_lookup(engine, db, src_ptr, src_floats, desc, win_shape, n_candidates, d_win, d_codes, d_idx, d_dist, chunk,
+                  row0=0, stages=None):
+    """gather, tower 2 and top-k of the windows `desc`, `chunk` at a time; the index rows go to rows row0.. of d_idx"""
+    import time
+    win_h, win_w = win_shape
+    if (engine.cfg.h2, engine.cfg.w2) != (win_h, win_w):
+        engine.set_input_size(2, win_h, win_w)
+
+    def timed(name, fn, *args):
+        if stages is None:
+            return fn(*args)
+        t0 = time.perf_counter()
+        fn(*args)
+        engine.sync()
+        stages[name] = stages.get(name, 0.0) + time.perf_counter() - t0
+    n_win = len(desc)
+    for s in range(0, n_win, chunk):
+        m = min(chunk, n_win - s)
+        timed("gather", engine.gather_windows_dev, src_ptr, src_floats, desc[s:s + m], win_h, win_w, d_win.ptr)
+        timed("embed", engine.embed_view2_dev, d_win.ptr, m, d_codes.ptr)
+        timed("topk", db.topk_dev, d_codes.ptr, m, n_candidates, d_idx.offset((row0 + s) * n_candidates * 4), d_dist.ptr)
+
+
+def track_scores(engine, sheet_db, spectrograms, top_k=5, n_candidates=5, running_frames=100, spec_shape=(92, 42),
+                 max_windows=4096, return_idx=False, stages=None):
+    """The running vote of the reference's live server (AudioSheetServer.run, :83-211) over every frame of a list of
+    recordings, in one pass: one asr_track_gate_dev call for all frames; the windows of the voiced frames only are cut,
+    embedded and looked up max_windows at a time; one asr_track_vote_batch_dev call slides the vote over the last
+    running_frames voiced frames of every recording.  -> one TrackResult per recording, equal to track_score_host's.
+    `spectrograms`: (spec_shape[0], frames) host arrays or a DeviceArrays handle.  return_idx: keep the top-k index
+    table.  stages: a dict that receives the seconds per stage (gate / gather / embed / topk / vote; synchronises
+    after every stage)."""
+    import time
+    _track_check(top_k, n_candidates, running_frames, max_windows)
+    if n_candidates > len(sheet_db):
+        raise ValueError("n_candidates=%d for a data base of %d codes" % (n_candidates, len(sheet_db)))
+    win_h, win_w = spec_shape
+    if not _is_device(spectrograms):
+        spectrograms = [np.ascontiguousarray(x, dtype=np.float32) for x in spectrograms]
+        for i, x in enumerate(spectrograms):
+            if x.ndim != 2 or x.shape[0] != win_h or x.shape[1] < 1:
+                raise ValueError("input %d: expected a (%d, frames >= 1) array, got shape %r" % (i, win_h, x.shape))
+    dev, owned = _to_device(engine, spectrograms)
+    bufs = []
+    try:
+        for i, (rows, T) in enumerate(dev.shapes):
+            if rows != win_h or T < 1:
+                raise ValueError("input %d: expected a (%d, frames >= 1) array, got shape %r" % (i, win_h, (rows, T)))
+        if not dev.shapes:
+            return []
+        src_floats = dev.buf.nbytes // 4
+        t0 = time.perf_counter()
+        m_prob, voiced, _ = engine.track_gate_dev(dev.buf.ptr, src_floats, dev.offsets, dev.shapes, win_w)
+        if stages is not None:
+            stages["gate"] = stages.get("gate", 0.0) + time.perf_counter() - t0
+        first = np.concatenate([[0], np.cumsum([T for _, T in dev.shapes])])
+        frames = [np.flatnonzero(voiced[first[r]:first[r + 1]]) for r in range(len(dev.shapes))]
+        desc = np.concatenate([_identity_desc(off, rows, T, 0, f - (win_w - 1))
+                               for (rows, T), off, f in zip(dev.shapes, dev.offsets, frames)])
+        n_win = len(desc)
+        count = np.array([len(f) for f in frames], np.int64)
+        row_first = np.concatenate([[0], np.cumsum(count)[:-1]]).astype(np.int64)
+        idx = np.zeros((0, n_candidates), np.int32)
+        if n_win:
+            chunk = min(n_win, int(max_windows))
+            d_win, d_codes = engine.alloc(chunk * win_h * win_w * 4), engine.alloc(chunk * 32 * 4)
+            d_idx, d_dist = engine.alloc(n_win * n_candidates * 4), engine.alloc(chunk * n_candidates * 8)
+            bufs += [d_win, d_codes, d_idx, d_dist]
+            _track_lookup(engine, sheet_db, dev.buf.ptr, src_floats, desc, spec_shape, n_candidates, d_win, d_codes,
+                          d_idx, d_dist, chunk, stages=stages)
+            t0 = time.perf_counter()
+            pieces, counts, n_out = engine.track_vote_batch_dev(d_idx.ptr, n_win, row_first, count, n_candidates,
+                                                                running_frames, sheet_db._d_ids.ptr, len(sheet_db),
+                                                                sheet_db.n_pieces, top_k)
+            if stages is not None:
+                stages["vote"] = stages.get("vote", 0.0) + time.perf_counter() - t0
+            if return_idx:
+                idx = d_idx.download((n_win, n_candidates), np.int32)
+        else:
+            pieces = counts = np.zeros((0, top_k), np.int32)
+            n_out = np.zeros(0, np.int32)
+    finally:
+        for b in bufs:
+            b.free()
+        if owned:
+            dev.buf.free()
+    results = []
+    for r in range(len(dev.shapes)):
+        a, b = int(row_first[r]), int(row_first[r] + count[r])
+        results.append(TrackResult(m_prob[first[r]:first[r + 1]], voiced[first[r]:first[r + 1]], frames[r], pieces[a:b],
+                                   counts[a:b], n_out[a:b], _history_lengths(0, b - a, n_candidates, running_frames),
+                                   sheet_db.id_to_name, idx[a:b] if return_idx else None))
+    return results
+
+
+def track_score(engine, sheet_db, spectrogram, top_k=5, n_candidates=5, running_frames=100, spec_shape=(92, 42),
+                max_windows=4096, return_idx=False):
+    """track_scores for one recording -> its TrackResult"""
+    return track_scores(engine, sheet_db, [spectrogram], top_k, n_candidates, running_frames, spec_shape, max_windows,
+                        return_idx)[0]
+
+
+class PieceTracker(object):
+    """The running vote as a streaming session: push(columns) takes a (bins, n >= 1) block of new spectrogram columns
+    and returns the TrackResult of these n frames (frames: indices within the block; idx included), equal to the
+    matching slice of track_score on the whole recording when `level` is its spec.sum(axis=0).max() - the normaliser of
+    _detect_music (:527), which a stream cannot know.  The session carries the last w - 1 columns and the top-k rows of
+    its last running_frames - 1 voiced frames from block to block; every block is one gate call, one gather / tower /
+    top-k call over its voiced frames and one vote call in which the carried rows only feed the history."""
+
+    def __init__(self, engine, sheet_db, level, top_k=5, n_candidates=5, running_frames=100, spec_shape=(92, 42)):
+        _track_check(top_k, n_candidates, running_frames)
+        if n_candidates > len(sheet_db):
+            raise ValueError("n_candidates=%d for a data base of %d codes" % (n_candidates, len(sheet_db)))
+        self.engine, self.db, self.level = engine, sheet_db, np.float32(level)
+        self.top_k, self.n_candidates, self.running_frames = int(top_k), int(n_candidates), int(running_frames)
+        self.spec_shape = tuple(spec_shape)
+        self.n_frames = 0                                   # frames pushed so far
+        self.n_voiced = 0                                   # voiced frames so far
+        self._tail = np.zeros((spec_shape[0], spec_shape[1] - 1), np.float32)          # running_spec[:, 1:] (:92)
+        self._rows = np.zeros((0, self.n_candidates), np.int32)
+
+    def push(self, columns):
+        cols = np.ascontiguousarray(columns, dtype=np.float32)
+        win_h, win_w = self.spec_shape
+        if cols.ndim != 2 or cols.shape[0] != win_h or cols.shape[1] < 1:
+            raise ValueError("expected a (%d, n >= 1) block of columns, got shape %r" % (win_h, cols.shape))
+        n, C = cols.shape[1], self.n_candidates
+        block = np.ascontiguousarray(np.hstack((self._tail, cols)))
+        eng, db = self.engine, self.db
+        d_src = db.scratch("track_src", block.nbytes).upload(block)
+        m_prob, voiced, _ = eng.track_gate_dev(d_src.ptr, block.size, [0], [block.shape], win_w, norm=[self.level],
+                                               frame0=[self.n_frames - (win_w - 1)])
+        m_prob, voiced = m_prob[win_w - 1:], voiced[win_w - 1:]
+        frames = np.flatnonzero(voiced)                     # window of block frame j: block columns j .. j + w - 1
+        h, m = len(self._rows), len(frames)
+        pieces = counts = np.zeros((0, self.top_k), np.int32)
+        n_out, new_rows = np.zeros(0, np.int32), np.zeros((0, C), np.int32)
+        if m:
+            d_win, d_codes = db.scratch("track_win", m * win_h * win_w * 4), db.scratch("track_codes", m * 32 * 4)
+            d_idx, d_dist = db.scratch("track_idx", (h + m) * C * 4), db.scratch("track_dist", m * C * 8)
+            if h:
+                d_idx.upload(self._rows)
+            _track_lookup(eng, db, d_src.ptr, block.size, _identity_desc(0, win_h, block.shape[1], 0, frames),
+                          self.spec_shape, C, d_win, d_codes, d_idx, d_dist, m, row0=h)
+            pieces, counts, n_out = eng.track_vote_batch_dev(d_idx.ptr, h + m, [0], [h + m], C, self.running_frames,
+                                                             db._d_ids.ptr, len(db), db.n_pieces, self.top_k,
+                                                             emit_from=[h])
+            new_rows = d_idx.download((h + m, C), np.int32)[h:]
+            keep = self.running_frames - 1
+            self._rows = np.concatenate((self._rows, new_rows))[max(0, h + m - keep):] if keep else new_rows[:0]
+        history = _history_lengths(self.n_voiced, m, C, self.running_frames)
+        self._tail = np.ascontiguousarray(block[:, block.shape[1] - (win_w - 1):])
+        self.n_frames += n
+        self.n_voiced += m
+        return TrackResult(m_prob, voiced, frames, pieces, counts, n_out, history, db.id_to_name, new_rows)

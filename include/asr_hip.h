@@ -279,6 +279,49 @@ int asr_piece_vote_batch_dev(asr_ctx *ctx, const int32_t *idx_dev, int64_t n_gro
                              const int32_t *ids_dev, int64_t n_db, int32_t n_pieces, int top_k, const int32_t *targets,
                              int32_t *pieces, int32_t *counts, int32_t *n_out, int32_t *ranks, double *ratios);
 
+/* ---- running piece vote: the live loop of audio_sheet_server.py (AudioSheetServer.run, :83-211) over recordings ------
+ * The reference slides a (bins, w) window over the spectrogram frame by frame (:110), gates every frame by its music
+ * probability (_detect_music, :524-528; :117), embeds the window of a frame with music, retrieves its n_candidates
+ * nearest data-base entries (:120-123), keeps the piece ids of the last running_frames such frames (:126-129) and ranks
+ * the pieces by their votes over that history (:132-138).  Window cutting, tower and top-k are the existing calls
+ * (asr_gather_windows_dev, asr_embed_view2_dev, asr_topk_db_dev); these two are the gate and the sliding vote.
+ *
+ * asr_track_gate_dev: n_rec recordings (bins[r], frames[r]) float32 row-major at float offsets[r] of src_dev (src_floats
+ *   floats; every recording is checked against it).  Per frame i of recording r, concatenated in recording order:
+ *     m_prob = clip(mean(colsum[i-w+1 .. i]) / (level * 0.15), 0, 1), colsum[t] = the float32 sum of column t over the
+ *       bins, added row after row (zero before the recording's start), the mean as numpy >= 2 computes the float32
+ *       .mean() of w values (pairwise sum: eight accumulators over the full blocks of eight, combined ((r0+r1)+(r2+r3))+
+ *       ((r4+r5)+(r6+r7)), the remainder added in order; divided by float32(w)), the divisor float32(level *
+ *       float32(0.15)); level = max_t colsum[t] (:527), or norm[r] where norm is given and norm[r] is not NaN - what a
+ *       stream, which cannot know its maximum, passes.  A silent recording gives 0 / 0 = NaN;
+ *     voiced = m_prob > 0.5 and frame0[r] + i >= w (:117; frame0: the stream position of column 0, NULL: 0).
+ *   Outputs (host): m_prob (float32) and voiced (bytes), sum(frames) each; level (n_rec, may be NULL): the divisor's
+ *   level per recording.  8 <= width <= 128 (numpy sums other lengths in another order), bins, frames >= 1; anything else
+ *   returns ASR_ERR_INVALID.  Compiled without contraction: bit-equal with numpy on finite inputs.
+ *
+ * asr_track_vote_batch_dev: idx_dev = (n_rows x n_candidates) int32 data-base indices, one row per voiced frame (what
+ *   asr_topk_db_dev wrote for the voiced frames of all recordings); recording r owns rows row_first[r] .. row_first[r] +
+ *   row_count[r] - 1 in frame order; ids_dev[j] = piece id of data-base entry j.  For frame f >= emit_from[r] (NULL: 0)
+ *   of recording r the votes of frames max(0, f - running_frames + 1) .. f are counted per piece and the first top_k
+ *   pieces with votes returned: votes descending, equal votes the larger piece id first (asr_piece_vote_dev's rule).
+ *   Frames before emit_from[r] only feed the history (a stream passes the rows of its last running_frames - 1 voiced
+ *   frames in front of the new ones).  Outputs (host), one row per emitted frame in recording order: pieces / counts
+ *   (x top_k; piece -1 / count 0 past the voted pieces), n_out = pieces returned.  Indices outside [0, n_db) and piece
+ *   ids outside [0, n_pieces) are ignored.  ASR_ERR_INVALID before anything is launched: top_k outside 1..64,
+ *   n_candidates < 1, running_frames < 1, n_db < n_candidates, n_pieces < 1 (or > 2^30), a row range outside the table,
+ *   emit_from outside [0, row_count].  One wave per segment of 64 frames rebuilds the histogram of the history before
+ *   its first frame, then adds the entering and removes the leaving frame's ids per frame; the counters live in LDS up
+ *   to n_pieces = 4096 and in a per-workgroup device workspace above (bounded by ASR_VOTE_BUDGET_MB).  Results do not
+ *   depend on either; ASR_TRACK_SEG_FRAMES=<n> / ASR_TRACK_LDS_PIECES=<n> (debug) set the segment length and send
+ *   n_pieces > n to the workspace path. */
+int asr_track_gate_dev(asr_ctx *ctx, const float *src_dev, int64_t src_floats, int n_rec, const int64_t *offsets,
+                       const int32_t *bins, const int32_t *frames, const int64_t *frame0, const float *norm, int width,
+                       float *m_prob, uint8_t *voiced, float *level);
+int asr_track_vote_batch_dev(asr_ctx *ctx, const int32_t *idx_dev, int64_t n_rows, int n_rec, const int64_t *row_first,
+                             const int64_t *row_count, const int64_t *emit_from, int n_candidates, int running_frames,
+                             const int32_t *ids_dev, int64_t n_db, int32_t n_pieces, int top_k, int32_t *pieces,
+                             int32_t *counts, int32_t *n_out);
+
 /* ---- audio front-end -------------------------------------------------
  * The madmom chain the reference feeds its spectrogram tower with (tutorials/Embedding Tutorial.ipynb cell 28,
  * msmd.midi_parser.processor; audio_sheet_server.py:632,678 `processor.process(audio_file).T`):
