@@ -41,6 +41,7 @@ EXPORTS = [
     "asr_comm_allreduce_dev", "asr_comm_allgather_dev",
     "asr_rank_sharded_dev", "asr_slice_windows_dev", "asr_piece_vote_dev", "asr_piece_vote_batch_dev", "asr_track_gate_dev", "asr_track_vote_batch_dev", "asr_gather_windows_dev", "asr_dtw_dev", "asr_dtw_batch_dev", "asr_spectrogram_dev", "asr_debug_tune_report",
     "asr_seg_create", "asr_seg_set_window", "asr_seg_destroy", "asr_seg_predict_dev", "asr_systems_from_maps_dev",
+    "asr_notes_from_map_dev", "asr_bars_from_map_dev",
     "asr_unroll_systems_dev", "asr_spectrogram_batch_dev",
     "asr_opt_state_size", "asr_get_opt_state", "asr_set_opt_state", "asr_debug_train_tensor", "asr_cca_train_debug",
 ]
@@ -193,6 +194,10 @@ def load_library(path=None):
         "asr_systems_from_maps_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                               c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                               c_void_p]),
+        "asr_notes_from_map_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_double, c_double,
+                                           c_int, c_int, c_void_p, c_void_p, c_void_p]),
+        "asr_bars_from_map_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                          c_void_p, c_void_p, c_void_p]),
         "asr_piece_vote_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int32, c_int]
                                      + [c_void_p] * 6),
         "asr_track_gate_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int] + [c_void_p] * 5 + [c_int] + [c_void_p] * 3),
@@ -650,6 +655,47 @@ class Engine(object):
             system_maps_ptr, bar_maps_ptr, system_seg, bar_seg, max_systems, status.ctypes.data, counts.ctypes.data,
             systems.ctypes.data, byref(passes)))
         return status, counts, systems, int(passes.value)
+
+    @staticmethod
+    def _map_tables(who, heights, widths):
+        heights = np.ascontiguousarray(heights, dtype=np.int32)
+        widths = np.ascontiguousarray(widths, dtype=np.int32)
+        if not (heights.ndim == widths.ndim == 1) or heights.size != widths.size:
+            raise ValueError("%s: the per-page tables differ in length" % who)
+        return heights, widths
+
+    def notes_from_map_dev(self, maps_ptr, heights, widths, threshold_abs=0.5, threshold_rel=None, min_distance=3,
+                           max_peaks=4096, seg=None):
+        """notes_from_map of sheet_utils/omr.py (peak_local_max in two dimensions) for all pages in one call, on
+        float64 maps that lie back to back on the device (asr_notes_from_map_dev).  None for a threshold: not given.
+        -> (status (n,), counts (n,), coords (n, max_peaks, 2) int32 (row, col) in the host's order).  status 0
+        decided, 3 not decided on the device, 4 more than max_peaks peaks (counts holds the true number)."""
+        heights, widths = self._map_tables("notes_from_map_dev", heights, widths)
+        n, max_peaks = int(heights.size), int(max_peaks)
+        status = np.full(n, 3, np.int32)
+        counts = np.zeros(n, np.int32)
+        coords = np.zeros((n, max(max_peaks, 0), 2), np.int32)
+        nan = float("nan")
+        self._check(self.lib.asr_notes_from_map_dev(
+            self.ctx, maps_ptr, heights.ctypes.data, widths.ctypes.data, n, seg,
+            nan if threshold_abs is None else float(threshold_abs), nan if threshold_rel is None else float(threshold_rel),
+            int(min_distance), max_peaks, status.ctypes.data, counts.ctypes.data, coords.ctypes.data))
+        return status, counts, coords
+
+    def bars_from_map_dev(self, maps_ptr, heights, widths, max_blobs=16384, seg=None):
+        """bar_blobs_from_map of sheet_utils/omr.py (Otsu, 8-connected labels, blob_stats) for all pages in one call
+        (asr_bars_from_map_dev).  -> (status (n,), counts (n,), blobs (n, max_blobs, 10) int64 in label order,
+        labelling passes).  status 0 decided, 3 not decided on the device, 4 more than max_blobs blobs."""
+        heights, widths = self._map_tables("bars_from_map_dev", heights, widths)
+        n, max_blobs = int(heights.size), int(max_blobs)
+        status = np.full(n, 3, np.int32)
+        counts = np.zeros(n, np.int32)
+        blobs = np.zeros((n, max(max_blobs, 0), 10), np.int64)
+        passes = c_int32(0)
+        self._check(self.lib.asr_bars_from_map_dev(
+            self.ctx, maps_ptr, heights.ctypes.data, widths.ctypes.data, n, seg, max_blobs, status.ctypes.data,
+            counts.ctypes.data, blobs.ctypes.data, byref(passes)))
+        return status, counts, blobs, int(passes.value)
 
     def tune_report(self):
         """(comparisons, mismatches, max deviation) of the autotuner's self-check (ASR_TUNE_VERIFY=1)."""

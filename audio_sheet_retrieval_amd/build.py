@@ -22,9 +22,10 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 BASE_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wno-comment", "-Wno-unused-result", "-Wno-unused-value"]
 EXTRA_FLAGS = os.environ.get("ASR_EXTRA_HIPCC_FLAGS", "").split()      # timing experiments (tools/ablate_*.sh): -DASR_WINOG_ABL=...
 FLAGS = BASE_FLAGS + ["-I", INCLUDE] + EXTRA_FLAGS
-# per-source flags: the restated numpy arithmetic of systems_from_maps and of the tracking loop's music gate compares
-# bits, so no fused multiply-adds there
-FILE_FLAGS = {"omr_post_kernels.hip": ["-ffp-contract=off"], "track_kernels.hip": ["-ffp-contract=off"]}
+# per-source flags: the restated numpy arithmetic of systems_from_maps, of the bar / note-head detection and of the
+# tracking loop's music gate compares bits, so no fused multiply-adds there
+FILE_FLAGS = {"omr_post_kernels.hip": ["-ffp-contract=off"], "omr_detect_kernels.hip": ["-ffp-contract=off"],
+              "track_kernels.hip": ["-ffp-contract=off"]}
 
 
 def sources():

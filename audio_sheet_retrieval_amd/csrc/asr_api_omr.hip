@@ -1,7 +1,8 @@
 // C-ABI layer of the staff-system detector: asr_seg_create / asr_seg_destroy / asr_seg_predict_dev
 // (sheet_utils/omr.py SegmentationNetwork.load + predict_proba; include/asr_hip.h for the contract) and
-// asr_systems_from_maps_dev (systems_from_maps: the maps to system corners).  Kernels: omr_kernels.hip,
-// omr_post_kernels.hip.
+// asr_systems_from_maps_dev (systems_from_maps: the maps to system corners), asr_notes_from_map_dev and
+// asr_bars_from_map_dev (notes_from_map, bar_blobs_from_map).  Kernels: omr_kernels.hip, omr_post_kernels.hip,
+// omr_detect_kernels.hip.
 #include "asr_ctx.h"
 #include "omr_kernels.h"
 
@@ -541,6 +542,296 @@ int asr_systems_from_maps_dev(asr_ctx *ctx, const void *pages_dev, int in_mode, 
             for (uint32_t k = 0; k < S.n_kept; ++k)
                 memcpy(systems + ((size_t)p * max_systems + k) * 4, h_blobs[(size_t)j * cap + k].out, 4 * sizeof(int32_t));
         }
+    }
+    if (label_passes) *label_passes = passes;
+    return mark_main(ctx);
+}
+
+}  // extern "C"
+
+namespace {
+
+// asr_notes_from_map_dev / asr_bars_from_map_dev: the pages the device decides, cut into chunks of whole pages whose
+// workspace fits ASR_OMR_BUDGET_MB (at least one page each).  bytes(n, px, rows): the workspace of such a chunk.
+struct DetChunk { int first, n, max_h, max_w; int64_t px, rows, max_px; };
+
+template <typename Bytes>
+std::vector<DetChunk> det_chunks(const std::vector<asr::PostPage> &all, Bytes bytes, size_t *need) {
+    const size_t budget = (size_t)std::max<int64_t>(seg_env("ASR_OMR_BUDGET_MB", 4096), 1) << 20;
+    std::vector<DetChunk> chunks;
+    *need = 0;
+    for (int i = 0; i < (int)all.size();) {
+        DetChunk c{i, 0, 0, 0, 0, 0, 0};
+        while (i < (int)all.size()) {
+            const asr::PostPage &P = all[i];
+            const int64_t px = c.px + (int64_t)P.h * P.w, rows = c.rows + P.h;
+            if (c.n && (c.n >= asr::POST_MAX_CHUNK_PAGES || bytes(c.n + 1, px, rows) > budget || px > (1ll << 30) ||
+                        rows > INT32_MAX))
+                break;
+            c.n += 1; c.px = px; c.rows = rows;
+            c.max_w = std::max(c.max_w, P.w); c.max_h = std::max(c.max_h, P.h);
+            c.max_px = std::max<int64_t>(c.max_px, (int64_t)P.h * P.w);
+            ++i;
+        }
+        *need = std::max(*need, bytes(c.n, c.px, c.rows));
+        chunks.push_back(c);
+    }
+    return chunks;
+}
+
+// the context's post-processing workspace, at least `need` bytes
+int det_workspace(asr_ctx *ctx, size_t need) {
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    int rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    if (need > ctx->post_ws_bytes) {
+        rc = sync_all(ctx);
+        if (rc != ASR_OK) return rc;
+        if (ctx->post_ws) ASR_HIP(ctx, hipFree(ctx->post_ws));
+        ctx->post_ws = nullptr; ctx->post_ws_bytes = 0;
+        ASR_HIP(ctx, hipMalloc(&ctx->post_ws, need));
+        ctx->post_ws_bytes = need;
+    }
+    return ASR_OK;
+}
+
+// argument checks and the page table both calls share; pages of the tile size (the host works on float32 maps
+// there) and pages `skip` rejects stay status 3
+template <typename Skip>
+int det_pages(asr_ctx *ctx, const char *who, const int32_t *heights, const int32_t *widths, int n_pages,
+              const asr_seg *seg, int32_t *status, int32_t *counts, Skip skip, std::vector<asr::PostPage> &all) {
+    if (seg && seg->owner != ctx) return fail(ctx, ASR_ERR_INVALID, "%s: not a segmentation network of this context", who);
+    for (int p = 0; p < n_pages; ++p)
+        if (heights[p] < 1 || widths[p] < 1 || (int64_t)heights[p] * widths[p] > (1 << 28))
+            return fail(ctx, ASR_ERR_INVALID, "%s: page %d has bad geometry %d x %d", who, p, heights[p], widths[p]);
+    int64_t map_off = 0;
+    for (int p = 0; p < n_pages; ++p) {
+        const int h = heights[p], w = widths[p];
+        status[p] = 3;
+        counts[p] = 0;
+        if (!(seg && h == seg->th && w == seg->tw) && !skip(h, w)) {
+            asr::PostPage P{};
+            P.map_off = map_off; P.h = h; P.w = w; P.page = p;
+            all.push_back(P);
+        }
+        map_off += (int64_t)h * w;
+    }
+    return ASR_OK;
+}
+
+// the chunk's page table with its workspace offsets
+std::vector<asr::PostPage> det_chunk_pages(const std::vector<asr::PostPage> &all, const DetChunk &c) {
+    std::vector<asr::PostPage> pd(all.begin() + c.first, all.begin() + c.first + c.n);
+    int64_t px = 0;
+    int32_t rows = 0;
+    for (asr::PostPage &P : pd) {
+        P.px_off = px; P.row_off = rows;
+        px += (int64_t)P.h * P.w; rows += P.h;
+    }
+    return pd;
+}
+
+}  // namespace
+
+extern "C" {
+
+int asr_notes_from_map_dev(asr_ctx *ctx, const double *maps_dev, const int32_t *heights, const int32_t *widths,
+                           int n_pages, const asr_seg *seg, double threshold_abs, double threshold_rel,
+                           int min_distance, int max_peaks, int32_t *status, int32_t *counts, int32_t *coords) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_pages < 0 || max_peaks < 0 || min_distance < 1 || min_distance > asr::DET_MAX_DISTANCE)
+        return fail(ctx, ASR_ERR_INVALID, "notes_from_map: bad n_pages=%d max_peaks=%d min_distance=%d (1..%d)", n_pages,
+                    max_peaks, min_distance, asr::DET_MAX_DISTANCE);
+    if (std::isinf(threshold_abs) || std::isinf(threshold_rel))
+        return fail(ctx, ASR_ERR_INVALID, "notes_from_map: an infinite threshold");
+    if (n_pages == 0) return ASR_OK;
+    if (!maps_dev || !heights || !widths || !status || !counts || (max_peaks && !coords))
+        return fail(ctx, ASR_ERR_INVALID, "notes_from_map: NULL argument");
+    std::vector<asr::PostPage> all;
+    int rc = det_pages(ctx, "notes_from_map", heights, widths, n_pages, seg, status, counts,
+                       [](int, int) { return false; }, all);
+    if (rc != ASR_OK) return rc;
+    if (all.empty()) return ASR_OK;
+    const int cap = std::max(max_peaks, 1);
+
+    struct Lay { size_t pd, st, mm, rc, mask, co, end; };
+    auto layout = [&](int n, int64_t px, int64_t rows) {
+        Lay L;
+        size_t o = 0;
+        auto take = [&](size_t bytes) { const size_t at = o; o += seg_align(bytes); return at; };
+        L.pd = take((size_t)n * sizeof(asr::PostPage));
+        L.st = take((size_t)n * sizeof(asr::PostState));      // cleared before every chunk: state, extrema
+        L.mm = take((size_t)n * 2 * sizeof(uint64_t));
+        L.rc = take((size_t)rows * sizeof(int32_t));
+        L.mask = take((size_t)px);
+        L.co = take((size_t)n * cap * 2 * sizeof(int32_t));
+        L.end = o;
+        return L;
+    };
+    size_t need = 0;
+    const std::vector<DetChunk> chunks =
+        det_chunks(all, [&](int n, int64_t px, int64_t rows) { return layout(n, px, rows).end; }, &need);
+    rc = det_workspace(ctx, need);
+    if (rc != ASR_OK) return rc;
+    char *ws = (char *)ctx->post_ws;
+    hipStream_t st = ctx->stream;
+
+    std::vector<asr::PostState> h_state;
+    std::vector<int32_t> h_coords;
+    for (const DetChunk &c : chunks) {
+        const Lay L = layout(c.n, c.px, c.rows);
+        const std::vector<asr::PostPage> pd = det_chunk_pages(all, c);
+        asr::DetArgs a;
+        a.pages = (const asr::PostPage *)(ws + L.pd);
+        a.n_pages = c.n; a.max_h = c.max_h; a.max_w = c.max_w; a.cap = cap; a.max_px = c.max_px;
+        a.maps = maps_dev;
+        a.state = (asr::PostState *)(ws + L.st); a.minmax = (unsigned long long *)(ws + L.mm);
+        a.threshold_abs = threshold_abs; a.threshold_rel = threshold_rel; a.distance = min_distance;
+        a.rowcnt = (int32_t *)(ws + L.rc); a.mask = (uint8_t *)(ws + L.mask); a.coords = (int32_t *)(ws + L.co);
+        ASR_HIP(ctx, hipMemcpyAsync(ws + L.pd, pd.data(), pd.size() * sizeof(asr::PostPage), hipMemcpyHostToDevice, st));
+        ASR_HIP(ctx, hipMemsetAsync(ws + L.st, 0, L.rc - L.st, st));
+        const double dpx = (double)c.px;
+        {
+            ProfScope ps(ctx, "det_minmax", 0, 2.0 * dpx, 8.0 * dpx);
+            ASR_HIP(ctx, asr::launch_det_minmax(st, a));
+        }
+        {
+            ProfScope ps(ctx, "det_peaks", 0, 4.0 * min_distance * dpx, 12.0 * dpx);
+            ASR_HIP(ctx, asr::launch_det_peaks(st, a));
+        }
+        h_state.resize(c.n);
+        h_coords.resize((size_t)c.n * cap * 2);
+        ASR_HIP(ctx, hipMemcpyAsync(h_state.data(), a.state, h_state.size() * sizeof(asr::PostState), hipMemcpyDeviceToHost, st));
+        ASR_HIP(ctx, hipMemcpyAsync(h_coords.data(), a.coords, h_coords.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        ASR_HIP(ctx, hipStreamSynchronize(st));
+        for (int j = 0; j < c.n; ++j) {
+            const int p = pd[j].page;
+            const asr::PostState &S = h_state[j];
+            if (S.status != 0) continue;                         // (stays 3)
+            counts[p] = (int32_t)S.n_kept;
+            if (S.n_kept > (uint32_t)max_peaks) {
+                status[p] = 4;
+                continue;
+            }
+            status[p] = 0;
+            if (S.n_kept)
+                memcpy(coords + (size_t)p * max_peaks * 2, h_coords.data() + (size_t)j * cap * 2,
+                       (size_t)S.n_kept * 2 * sizeof(int32_t));
+        }
+    }
+    return mark_main(ctx);
+}
+
+int asr_bars_from_map_dev(asr_ctx *ctx, const double *maps_dev, const int32_t *heights, const int32_t *widths,
+                          int n_pages, const asr_seg *seg, int max_blobs, int32_t *status, int32_t *counts,
+                          int64_t *blobs, int32_t *label_passes) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_pages < 0 || max_blobs < 0)
+        return fail(ctx, ASR_ERR_INVALID, "bars_from_map: bad n_pages=%d max_blobs=%d", n_pages, max_blobs);
+    if (label_passes) *label_passes = 0;
+    if (n_pages == 0) return ASR_OK;
+    if (!maps_dev || !heights || !widths || !status || !counts || (max_blobs && !blobs))
+        return fail(ctx, ASR_ERR_INVALID, "bars_from_map: NULL argument");
+    std::vector<asr::PostPage> all;
+    // the largest raw sum of a blob is below h * w * max(h, w)^2: it has to fit a signed 64-bit integer
+    auto too_large = [](int h, int w) {
+        const long double m = (long double)std::max(h, w);
+        return (long double)h * (long double)w * m * m >= 9223372036854775807.0L;
+    };
+    int rc = det_pages(ctx, "bars_from_map", heights, widths, n_pages, seg, status, counts, too_large, all);
+    if (rc != ASR_OK) return rc;
+    if (all.empty()) return ASR_OK;
+    const int cap = std::max(max_blobs, 1);
+
+    struct Lay { size_t pd, st, mm, hist, chg, ed, rc, lab, slot, bl, end; };
+    auto layout = [&](int n, int64_t px, int64_t rows) {
+        Lay L;
+        size_t o = 0;
+        auto take = [&](size_t bytes) { const size_t at = o; o += seg_align(bytes); return at; };
+        L.pd = take((size_t)n * sizeof(asr::PostPage));
+        L.st = take((size_t)n * sizeof(asr::PostState));      // cleared before every chunk: state .. changed flag
+        L.mm = take((size_t)n * 2 * sizeof(uint64_t));
+        L.hist = take((size_t)n * 256 * sizeof(uint32_t));
+        L.chg = take(sizeof(int32_t));
+        L.ed = take((size_t)n * 257 * sizeof(double));
+        L.rc = take((size_t)rows * sizeof(int32_t));
+        L.lab = take((size_t)px * sizeof(int32_t));
+        L.slot = take((size_t)px * sizeof(int32_t));
+        L.bl = take((size_t)n * cap * asr::DET_BLOB_FIELDS * sizeof(int64_t));
+        L.end = o;
+        return L;
+    };
+    size_t need = 0;
+    const std::vector<DetChunk> chunks =
+        det_chunks(all, [&](int n, int64_t px, int64_t rows) { return layout(n, px, rows).end; }, &need);
+    rc = det_workspace(ctx, need);
+    if (rc != ASR_OK) return rc;
+    char *ws = (char *)ctx->post_ws;
+    hipStream_t st = ctx->stream;
+
+    std::vector<asr::PostState> h_state;
+    int passes = 0;
+    for (const DetChunk &c : chunks) {
+        const Lay L = layout(c.n, c.px, c.rows);
+        const std::vector<asr::PostPage> pd = det_chunk_pages(all, c);
+        asr::DetArgs a;
+        a.pages = (const asr::PostPage *)(ws + L.pd);
+        a.n_pages = c.n; a.max_h = c.max_h; a.max_w = c.max_w; a.cap = cap; a.max_px = c.max_px;
+        a.maps = maps_dev;
+        a.state = (asr::PostState *)(ws + L.st); a.minmax = (unsigned long long *)(ws + L.mm);
+        a.rowcnt = (int32_t *)(ws + L.rc);
+        a.edges = (double *)(ws + L.ed); a.hist = (uint32_t *)(ws + L.hist);
+        a.label = (int32_t *)(ws + L.lab); a.slot = (int32_t *)(ws + L.slot); a.blobs = (long long *)(ws + L.bl);
+        asr::PostArgs la;                                        // the labelling passes of systems_from_maps
+        la.pages = a.pages; la.n_pages = c.n; la.max_px = c.max_px; la.state = a.state; la.label = a.label;
+        la.changed = (int32_t *)(ws + L.chg);
+        ASR_HIP(ctx, hipMemcpyAsync(ws + L.pd, pd.data(), pd.size() * sizeof(asr::PostPage), hipMemcpyHostToDevice, st));
+        ASR_HIP(ctx, hipMemsetAsync(ws + L.st, 0, L.ed - L.st, st));
+        const double dpx = (double)c.px;
+        {
+            ProfScope ps(ctx, "det_minmax", 0, 2.0 * dpx, 8.0 * dpx);
+            ASR_HIP(ctx, asr::launch_det_minmax(st, a));
+        }
+        {
+            ProfScope ps(ctx, "det_bar_threshold", 0, 6.0 * dpx, 20.0 * dpx);
+            ASR_HIP(ctx, asr::launch_det_bar_threshold(st, a));
+        }
+        for (;;) {                                               // until a scan changes nothing
+            int32_t changed = 0;
+            ASR_HIP(ctx, hipMemsetAsync(la.changed, 0, sizeof(int32_t), st));
+            {
+                ProfScope ps(ctx, "post_label_pass", 0, 0.0, 48.0 * dpx);
+                ASR_HIP(ctx, asr::launch_post_label_pass(st, la));
+            }
+            ASR_HIP(ctx, hipMemcpyAsync(&changed, la.changed, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            ASR_HIP(ctx, hipStreamSynchronize(st));
+            ++passes;
+            if (!changed) break;
+        }
+        {
+            ProfScope ps(ctx, "det_bar_blobs", 0, 0.0, 20.0 * dpx);
+            ASR_HIP(ctx, asr::launch_det_bar_blobs(st, a));
+        }
+        h_state.resize(c.n);
+        ASR_HIP(ctx, hipMemcpyAsync(h_state.data(), a.state, h_state.size() * sizeof(asr::PostState), hipMemcpyDeviceToHost, st));
+        ASR_HIP(ctx, hipStreamSynchronize(st));
+        for (int j = 0; j < c.n; ++j) {
+            const int p = pd[j].page;
+            const asr::PostState &S = h_state[j];
+            if (S.status != 0) continue;                         // (stays 3)
+            counts[p] = (int32_t)S.n_kept;
+            if (S.n_kept > (uint32_t)max_blobs) {
+                status[p] = 4;
+                continue;
+            }
+            status[p] = 0;
+            if (S.n_kept)
+                ASR_HIP(ctx, hipMemcpyAsync(blobs + (size_t)p * max_blobs * asr::DET_BLOB_FIELDS,
+                                            a.blobs + (size_t)j * cap * asr::DET_BLOB_FIELDS,
+                                            (size_t)S.n_kept * asr::DET_BLOB_FIELDS * sizeof(int64_t),
+                                            hipMemcpyDeviceToHost, st));
+        }
+        ASR_HIP(ctx, hipStreamSynchronize(st));
     }
     if (label_passes) *label_passes = passes;
     return mark_main(ctx);

@@ -144,4 +144,35 @@ hipError_t launch_post_close(hipStream_t s, const PostArgs &a);      // threshol
 hipError_t launch_post_label_pass(hipStream_t s, const PostArgs &a);
 hipError_t launch_post_blobs(hipStream_t s, const PostArgs &a);      // areas, kept blobs, boxes, shrink + snap
 
+// ---- bars and note heads from the maps (omr_detect_kernels.hip; host side: asr_notes_from_map_dev,
+// asr_bars_from_map_dev).  Pages are PostPage (map_off, px_off, row_off, h, w), the per-page state is PostState
+// (status, nonfinite, thr2 = the Otsu threshold, n_kept = peaks / blobs found), so that the labelling passes of
+// omr_post_kernels.hip run on the same tables.
+constexpr int DET_MAX_DISTANCE = 8;        // largest min_distance of the peak search: the halo of its LDS tile
+constexpr int DET_TILE_H = 32, DET_TILE_W = 64;   // page pixels one workgroup of the peak search decides
+constexpr int DET_BLOB_FIELDS = 10;        // area, min_row, min_col, max_row, max_col, sum r, c, r*r, c*c, r*c
+
+struct DetArgs {
+    const PostPage *pages = nullptr;
+    int n_pages = 0, max_h = 0, max_w = 0, cap = 0;            // cap: peaks / blobs per page the outputs hold
+    int64_t max_px = 0;
+    const double *maps = nullptr;
+    PostState *state = nullptr;
+    unsigned long long *minmax = nullptr;   // per page: ~key(min), key(max) of the order-preserving integer key
+    double threshold_abs = 0.0, threshold_rel = 0.0;           // NaN: not given
+    int distance = 0;
+    int32_t *rowcnt = nullptr;              // per row: flagged pixels, then their exclusive prefix sum over the page
+    uint8_t *mask = nullptr;                // notes, per pixel: is a peak
+    int32_t *coords = nullptr;              // notes: n_pages x cap x (row, col)
+    double *edges = nullptr;                // bars: n_pages x 257
+    uint32_t *hist = nullptr;               // bars: n_pages x 256
+    int32_t *label = nullptr, *slot = nullptr;                 // bars, per pixel: root; at a root: its blob index
+    long long *blobs = nullptr;             // bars: n_pages x cap x DET_BLOB_FIELDS
+};
+
+hipError_t launch_det_minmax(hipStream_t s, const DetArgs &a);        // page extrema, non-finite flag, status
+hipError_t launch_det_peaks(hipStream_t s, const DetArgs &a);         // peak mask, row counts, scan, ordered write
+hipError_t launch_det_bar_threshold(hipStream_t s, const DetArgs &a); // np.histogram + Otsu, map > t, run labels
+hipError_t launch_det_bar_blobs(hipStream_t s, const DetArgs &a);     // roots in raster order, the ten integers each
+
 }  // namespace asr

@@ -429,6 +429,173 @@ def systems_from_maps_dev(engine, pages_ptr, in_mode, page_offsets, heights, wid
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# detect_notes' and detect_bars' host steps (omr.py)
+
+BAR_MIN_LENGTH = 80          # detect_bars: shortest major axis of a bar blob
+BAR_ANGLE_TOL = 5            # ... degrees off the vertical
+BAR_MIN_ECC = 0.95           # ... smallest eccentricity
+BAR_MISSING_TOL = 10         # ... a system whose outermost bar is further than this from its edge gets one added
+
+ST_OK, ST_UNDECIDED, ST_OVERFLOW = 0, 3, 4      # asr_notes_from_map_dev / asr_bars_from_map_dev per page
+
+
+def notes_from_map(note_probs, threshold_abs=0.5, min_distance=3):
+    """detect_notes after the probability map exists: peak_local_max in two dimensions.  (n, 2) int64 (row, col) in
+    reversed raster order."""
+    return peak_local_max(note_probs, min_distance=min_distance, threshold_abs=threshold_abs).astype(np.int64)
+
+
+def blob_stats(label_img, n):
+    """(n, 10) int64, one row per label 1..n in label order: area, the bounding box min_row, min_col, max_row,
+    max_col (max exclusive), and the raw sums sum(r), sum(c), sum(r*r), sum(c*c), sum(r*c) over the blob's pixels in
+    page coordinates.  Every label 1..n must occur."""
+    out = np.zeros((n, 10), np.int64)
+    if n == 0:
+        return out
+    rr, cc = np.nonzero(label_img)
+    lab = label_img[rr, cc]
+    order = np.argsort(lab, kind="stable")
+    rr, cc, lab = rr[order].astype(np.int64), cc[order].astype(np.int64), lab[order]
+    first = np.searchsorted(lab, np.arange(1, n + 1))
+    if lab.size == 0 or np.any(lab[first.clip(max=lab.size - 1)] != np.arange(1, n + 1)):
+        raise ValueError("blob_stats: a label of 1..%d does not occur" % n)
+    out[:, 0] = np.diff(np.append(first, lab.size))
+    out[:, 1] = np.minimum.reduceat(rr, first)
+    out[:, 2] = np.minimum.reduceat(cc, first)
+    out[:, 3] = np.maximum.reduceat(rr, first) + 1
+    out[:, 4] = np.maximum.reduceat(cc, first) + 1
+    for k, v in enumerate((rr, cc, rr * rr, cc * cc, rr * cc)):
+        out[:, 5 + k] = np.add.reduceat(v, first)
+    return out
+
+
+def bar_blob_props(stats_row):
+    """(major_axis_length, orientation, eccentricity) of one blob_stats row, by the formulas of scikit-image 0.13.1's
+    regionprops (inertia_tensor, inertia_tensor_eigvals, major_axis_length, orientation, eccentricity), restated from
+    its published source because the package cannot be installed here (as threshold_otsu above).  With x = column and
+    y = row: a = mu20 / mu00, b = -mu11 / mu00, c = mu02 / mu00.  The central second moments are formed exactly from
+    the integer sums (n * sum(c*c) - sum(c)**2 and the other two in Python integers); only the division by n * n and
+    what follows is float64.  This differs from scikit-image in rounding only: it subtracts a float centroid from
+    every pixel first."""
+    n, _, _, _, _, sr, sc, srr, scc, src = [int(v) for v in stats_row]
+    nn = n * n
+    a = (n * scc - sc * sc) / nn
+    b = -((n * src - sr * sc) / nn)
+    c = (n * srr - sr * sr) / nn
+    root = np.sqrt(4 * b ** 2 + (a - c) ** 2)
+    l1 = (a + c) / 2 + root / 2
+    l2 = (a + c) / 2 - root / 2
+    major = 4 * np.sqrt(l1)
+    ecc = 0.0 if l1 == 0 else float(np.sqrt(1 - l2 / l1))
+    b = -b
+    if a - c == 0:
+        orientation = -np.pi / 4. if b > 0 else np.pi / 4.
+    else:
+        orientation = -0.5 * np.arctan2(2 * b, (a - c))
+    return float(major), float(orientation), ecc
+
+
+def bars_from_stats(stats):
+    """detect_bars' filters on blob_stats rows: (n, 2, 2) float64 [[min_row, col], [max_row, col]] of the blobs whose
+    major axis is at least BAR_MIN_LENGTH, whose orientation is within BAR_ANGLE_TOL degrees of the vertical and
+    whose eccentricity is at least BAR_MIN_ECC; col = mean of the box's min_col and max_col."""
+    detected_bars = np.zeros((0, 2, 2))
+    for row in np.asarray(stats).reshape(-1, 10):
+        major, orientation, ecc = bar_blob_props(row)
+        if major < BAR_MIN_LENGTH:
+            continue
+        if np.abs(90 - np.abs(np.degrees(orientation))) > BAR_ANGLE_TOL:
+            continue
+        if ecc < BAR_MIN_ECC:
+            continue
+        min_row, min_col, max_row, max_col = [int(v) for v in row[1:5]]
+        col = np.mean([min_col, max_col])
+        bar_coords = np.asarray([[min_row, col], [max_row, col]], np.float64)
+        detected_bars = np.concatenate((detected_bars, bar_coords[np.newaxis]))
+    return detected_bars
+
+
+def bar_blobs_from_map(bar_probs):
+    """detect_bars up to the region properties: Otsu of the whole map, map > t, 8-connected labels, blob_stats"""
+    fg_img = bar_probs > threshold_otsu(bar_probs)
+    label_img, n = label8(fg_img)
+    return blob_stats(label_img, n)
+
+
+def bars_from_map(bar_probs):
+    """detect_bars after the probability map exists and before the alignment with the systems"""
+    return bars_from_stats(bar_blobs_from_map(bar_probs))
+
+
+def bars_by_systems(bars, systems):
+    """OpticalMusicRecognizer._bars_by_systems: every bar goes to the system whose vertical centre is nearest to its
+    own (abs of the centre difference - sklearn's Euclidean distance in one dimension without its rounding; argmin
+    takes the first minimum), the bars of a system sorted by column (stable).  Raises ValueError when there is no bar
+    at all while systems are given (sklearn rejects an array of 0 samples)."""
+    bars, systems = np.asarray(bars, np.float64), np.asarray(systems, np.float64)
+    if bars.shape[0] == 0 and systems.shape[0] > 0:
+        raise ValueError("Found array with 0 sample(s) (shape=(0, 1)) while a minimum of 1 is required.")
+    system_centers = systems.mean(1)[:, 0]
+    bar_centers = bars.mean(1)[:, 0]
+    by_system = [np.zeros((0, 2, 2))] * systems.shape[0]
+    for i in range(bars.shape[0]):
+        min_idx = int(np.argmin(np.abs(bar_centers[i] - system_centers)))
+        by_system[min_idx] = np.vstack((by_system[min_idx], bars[i][np.newaxis]))
+    for i in range(systems.shape[0]):
+        by_system[i] = by_system[i][np.argsort(by_system[i][:, 0, 1], kind="stable")]
+    return by_system
+
+
+def align_bars_with_systems(bars, systems):
+    """detect_bars' "align bars with system" block, as the reference has it: a system whose first bar is not at its
+    left edge gets one there, a system whose last bar is more than BAR_MISSING_TOL off its right edge gets one there
+    (stacked in FRONT of the system's bars, and both inserted bars take their second corner from the column entries
+    systems[i, 3, 1] / systems[i, 2, 1] - the reference's indices), and every bar takes its system's rows.  (n, 2, 2)
+    float64.  Raises IndexError for a system that receives no bar and ValueError when there are no bars at all."""
+    systems = np.asarray(systems, np.float64)
+    detected_bars = np.zeros((0, 2, 2))
+    for i_sys, bars_i in enumerate(bars_by_systems(bars, systems)):
+        s = systems[i_sys]
+        if bars_i[0, 0, 1] != s[0, 1]:
+            bars_i = np.vstack((np.asarray([[[s[0, 0], s[0, 1]], [s[3, 1], s[3, 1]]]]), bars_i))
+        if np.abs(bars_i[0, 0, 1] - s[0, 1]) > BAR_MISSING_TOL:
+            bars_i = np.vstack((np.asarray([[[s[0, 0], s[0, 1]], [s[3, 1], s[3, 1]]]]), bars_i))
+        if np.abs(bars_i[-1, 0, 1] - s[1, 1]) > BAR_MISSING_TOL:
+            bars_i = np.vstack((np.asarray([[[s[1, 0], s[1, 1]], [s[2, 1], s[2, 1]]]]), bars_i))
+        for bar in bars_i:
+            bar[0, 0] = s[0, 0]
+            bar[1, 0] = s[3, 0]
+            detected_bars = np.concatenate((detected_bars, bar[np.newaxis]))
+    return detected_bars
+
+
+def _map_table(heights, widths):
+    heights = np.ascontiguousarray(heights, np.int32)
+    widths = np.ascontiguousarray(widths, np.int32)
+    sizes = heights.astype(np.int64) * widths
+    return heights, widths, sizes, np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+
+
+def notes_from_map_dev(engine, maps_ptr, heights, widths, threshold_abs=0.5, threshold_rel=None, min_distance=3,
+                       max_peaks=4096, seg=None):
+    """notes_from_map for all pages in one device call (asr_notes_from_map_dev) on float64 maps that lie back to back
+    on the device.  -> per page (status, coords): ST_OK with the (n, 2) int64 array of the host, ST_UNDECIDED or
+    ST_OVERFLOW (more than max_peaks peaks) with None."""
+    status, counts, coords = engine.notes_from_map_dev(maps_ptr, heights, widths, threshold_abs, threshold_rel,
+                                                       min_distance, max_peaks, seg)
+    return [(int(st), coords[p, :n].astype(np.int64) if st == 0 else None)
+            for p, (st, n) in enumerate(zip(status, counts))]
+
+
+def bar_blobs_from_map_dev(engine, maps_ptr, heights, widths, max_blobs=16384, seg=None):
+    """bar_blobs_from_map for all pages in one device call (asr_bars_from_map_dev).  -> (per page (status, stats):
+    ST_OK with the (n, 10) int64 rows of blob_stats, else None; labelling passes)."""
+    status, counts, blobs, passes = engine.bars_from_map_dev(maps_ptr, heights, widths, max_blobs, seg)
+    return [(int(st), blobs[p, :n].copy() if st == 0 else None)
+            for p, (st, n) in enumerate(zip(status, counts))], passes
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # networks
 
 def load_net_params(file_path):
@@ -580,7 +747,7 @@ class SegmentationNetwork(object):
 
 
 class OpticalMusicRecognizer(object):
-    """Score segmentation networks (omr.OpticalMusicRecognizer): system detection."""
+    """Score segmentation networks (omr.OpticalMusicRecognizer): system, bar and note-head detection."""
 
     def __init__(self, note_detector=None, system_detector=None, bar_detector=None):
         self.note_detector = note_detector
@@ -682,6 +849,124 @@ class OpticalMusicRecognizer(object):
                     b.free()
             if own is not None:
                 own.free()
+
+    # -- bars and note heads ----------------------------------------------------------------------------------------
+    def detect_notes(self, image, threshold_abs=0.5, min_distance=3):
+        """(n, 2) int64 (row, col) of the note heads: the local maxima of the note network's map"""
+        img = image[0, 0] if image.ndim == 4 else image
+        note_probs = self.note_detector.predict_proba(img[np.newaxis, np.newaxis])
+        return notes_from_map(note_probs, threshold_abs=threshold_abs, min_distance=min_distance)
+
+    def detect_bars(self, image, systems=None):
+        """(n, 2, 2) float64 [[min_row, col], [max_row, col]] of the bar lines; with `systems` (detect_systems'
+        corners) aligned to them as align_bars_with_systems does."""
+        img = image[0, 0] if image.ndim == 4 else image
+        bars = bars_from_map(self.bar_detector.predict_proba(img[np.newaxis, np.newaxis]))
+        return bars if systems is None else align_bars_with_systems(bars, systems)
+
+    def _maps_pages(self, net, pages, in_mode, dev_pages):
+        if dev_pages is not None and (in_mode != IN_U8_RAW or len(dev_pages) != len(pages)):
+            raise ValueError("dev_pages goes with the same number of raw uint8 pages (in_mode=IN_U8_RAW)")
+        maps = net.predict_pages(pages if dev_pages is None else dev_pages, in_mode=in_mode)
+        return [m.astype(np.float32) if m.shape == net.tile_shape else m for m in maps]
+
+    def detect_notes_pages(self, pages, in_mode=IN_F32_PREPARED, dev_pages=None, threshold_abs=0.5, min_distance=3):
+        """detect_notes for many pages: one device call for the network, notes_from_map per page.  One entry per
+        page: the coordinate array, or the exception the host steps raised on it."""
+        out = []
+        for m in self._maps_pages(self.note_detector, pages, in_mode, dev_pages):
+            try:
+                out.append(notes_from_map(m, threshold_abs=threshold_abs, min_distance=min_distance))
+            except Exception as e:
+                out.append(e)
+        return out
+
+    def detect_bars_pages(self, pages, systems=None, in_mode=IN_F32_PREPARED, dev_pages=None):
+        """detect_bars for many pages: one device call for the network, bars_from_map (and, with systems[i] given for
+        page i, align_bars_with_systems) per page.  One entry per page: the bar array, or the exception instance."""
+        out = []
+        for i, m in enumerate(self._maps_pages(self.bar_detector, pages, in_mode, dev_pages)):
+            try:
+                bars = bars_from_map(m)
+                if systems is not None and systems[i] is not None:
+                    bars = align_bars_with_systems(bars, systems[i])
+                out.append(bars)
+            except Exception as e:
+                out.append(e)
+        return out
+
+    def _maps_dev(self, net, pages, in_mode, dev_pages, post):
+        """the network's maps left on the device, post(engine, out, heights, widths) -> per page (status, result or
+        None), and the host path - post given one downloaded map - for the pages the device did not decide"""
+        if dev_pages is not None and (in_mode != IN_U8_RAW or len(dev_pages) != len(pages)):
+            raise ValueError("dev_pages goes with the same number of raw uint8 pages (in_mode=IN_U8_RAW)")
+        self.last_fallback_pages = []
+        if len(pages) == 0:
+            return []
+        out = x = None
+        try:
+            out, x, (_, _, sizes, _, hs, ws) = net.predict_pages_dev(pages if dev_pages is None else dev_pages,
+                                                                     in_mode=in_mode)
+            eng = net.engine
+            _, _, _, map_offs = _map_table(hs, ws)
+            res = []
+            for i, (st, val) in enumerate(post(eng, out, hs, ws)):
+                if st != 0:
+                    self.last_fallback_pages.append(i)
+                    m = _download_at(eng, out, int(map_offs[i]) * 8, int(sizes[i])).reshape(int(hs[i]), int(ws[i]))
+                    if m.shape == net.tile_shape:
+                        m = m.astype(np.float32)
+                    val = m
+                res.append((st, val))
+            return res
+        finally:
+            for b in (out, x):
+                if b is not None:
+                    b.free()
+
+    def detect_notes_pages_dev(self, pages, in_mode=IN_U8_RAW, dev_pages=None, threshold_abs=0.5, min_distance=3,
+                               max_peaks=4096):
+        """detect_notes_pages with the peak search on the device as well (asr_notes_from_map_dev): the map stays
+        there and one small download brings the coordinates back.  Returns exactly what detect_notes_pages returns.
+        Pages the device does not decide (a page of the tile size, a NaN in the map, more than max_peaks peaks) go
+        through notes_from_map on the host, their map alone downloaded; self.last_fallback_pages lists them."""
+        net = self.note_detector
+
+        def post(eng, out, hs, ws):
+            return notes_from_map_dev(eng, c_void_p(out.ptr), hs, ws, threshold_abs, None, min_distance, max_peaks,
+                                      net.handle)
+        res = []
+        for st, val in self._maps_dev(net, pages, in_mode, dev_pages, post):
+            try:
+                res.append(val if st == 0 else notes_from_map(val, threshold_abs=threshold_abs,
+                                                              min_distance=min_distance))
+            except Exception as e:
+                res.append(e)
+        return res
+
+    def detect_bars_pages_dev(self, pages, systems=None, in_mode=IN_U8_RAW, dev_pages=None, max_blobs=16384):
+        """detect_bars_pages with threshold, labelling and the blob statistics on the device (asr_bars_from_map_dev);
+        the filters and the alignment are the host path's own functions, bars_from_stats and align_bars_with_systems,
+        on the downloaded integers.  Returns exactly what detect_bars_pages returns; undecided pages go through the
+        host path (self.last_fallback_pages).  The bar network runs here again even when detect_systems_pages_dev
+        ran it just before: that call frees its maps."""
+        net = self.bar_detector
+        self.last_label_passes = 0
+
+        def post(eng, out, hs, ws):
+            decided, self.last_label_passes = bar_blobs_from_map_dev(eng, c_void_p(out.ptr), hs, ws, max_blobs,
+                                                                     net.handle)
+            return decided
+        res = []
+        for i, (st, val) in enumerate(self._maps_dev(net, pages, in_mode, dev_pages, post)):
+            try:
+                bars = bars_from_stats(val) if st == 0 else bars_from_map(val)
+                if systems is not None and systems[i] is not None:
+                    bars = align_bars_with_systems(bars, systems[i])
+                res.append(bars)
+            except Exception as e:
+                res.append(e)
+        return res
 
 
 def _download_at(engine, buf, byte_offset, n_doubles):

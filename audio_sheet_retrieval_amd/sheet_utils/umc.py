@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-from audio_sheet_retrieval_amd.sheet_utils import bar_detector, system_detector
+from audio_sheet_retrieval_amd.sheet_utils import bar_detector, note_detector, system_detector
 from audio_sheet_retrieval_amd.sheet_utils.omr import (IN_U8_RAW, SYSTEM_HEIGHT, DevicePages, OpticalMusicRecognizer,
                                                        SegmentationNetwork, imread_gray, unroll_rows,
                                                        unroll_systems_dev, unwrap_systems)
@@ -17,13 +17,18 @@ from audio_sheet_retrieval_amd.sheet_utils.omr import (IN_U8_RAW, SYSTEM_HEIGHT,
 OKBLUE, ENDC = "\033[94m", "\033[0m"       # utils/plotting.BColors
 
 
-def build_recognizer(system_params, bar_params, device=0):
-    """the two networks with their parameters: pickle paths or lists of the 99 arrays"""
+def build_recognizer(system_params, bar_params, device=0, note_params=None):
+    """the system and bar networks - and, with note_params, the note-head network - with their parameters: pickle
+    paths or lists of the 99 arrays"""
     system_net = SegmentationNetwork(system_detector.build_model(), device=device)
     system_net.load(system_params)
     bar_net = SegmentationNetwork(bar_detector.build_model(), device=device)
     bar_net.load(bar_params)
-    return OpticalMusicRecognizer(note_detector=None, system_detector=system_net, bar_detector=bar_net)
+    note_net = None
+    if note_params is not None:
+        note_net = SegmentationNetwork(note_detector.build_model(), device=device)
+        note_net.load(note_params)
+    return OpticalMusicRecognizer(note_detector=note_net, system_detector=system_net, bar_detector=bar_net)
 
 
 def get_performance_audio_path(piece_path, file_pattern):

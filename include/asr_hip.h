@@ -636,6 +636,37 @@ int asr_systems_from_maps_dev(asr_ctx *ctx, const void *pages_dev, int in_mode, 
                               const asr_seg *bar_seg, int max_systems, int32_t *status, int32_t *counts,
                               int32_t *systems, int32_t *label_passes);
 
+/* asr_notes_from_map_dev = detect_notes after the note map exists (sheet_utils/omr.py notes_from_map: peak_local_max
+ *   in two dimensions) and asr_bars_from_map_dev = detect_bars after the bar map exists, up to and including the
+ *   region properties (bar_blobs_from_map: threshold_otsu of the whole map, map > t, 8-connected labels, blob_stats),
+ *   for n_pages pages in one call each.  maps_dev: the float64 maps back to back exactly as asr_seg_predict_dev
+ *   writes them - page p is heights[p] x widths[p] at element sum of heights[q] * widths[q] over q < p; the page
+ *   pixels themselves are not read, so the table has no page_offsets.  seg: the network the maps came from, or NULL;
+ *   it only tells which page shape equals the tile.  Outputs are host arrays.
+ *   notes: a pixel is a peak if it equals the maximum of its (2 min_distance + 1)^2 neighbourhood (zero beyond the
+ *   page), lies at least min_distance pixels off every border and is strictly above max(threshold_abs,
+ *   threshold_rel * page maximum).  A NaN threshold argument means "not given"; without threshold_abs the page
+ *   minimum takes its place.  min_distance: 1..8.  A constant page has no peaks.  coords: counts[p] int32 (row, col)
+ *   pairs at coords + p * max_peaks * 2, in the host's order (raster order reversed).
+ *   bars: blobs holds counts[p] rows of 10 int64 at blobs + p * max_blobs * 10 in label order (raster order of each
+ *   blob's first pixel): area, min_row, min_col, max_row, max_col (max exclusive), and the sums of r, c, r*r, c*c,
+ *   r*c over the blob's pixels in page coordinates.  Rows beyond counts[p] are not written.  The filters of
+ *   detect_bars (bars_from_stats) and the alignment with the systems run on the host, on these integers.
+ *       status 0  decided
+ *              3  not decided on the device: the caller runs the host path for this page.  A page of the tile size
+ *                 (the host works on a float32 map there), a NaN or an infinity in the map; for bars also histogram
+ *                 edges numpy would reject and a page with h * w * max(h, w)^2 >= 2^63.
+ *              4  more than max_peaks / max_blobs results: counts[p] holds the true number, nothing is written
+ *   The np.histogram restatement is that of asr_systems_from_maps_dev (numpy >= 2).  Workspace belongs to the
+ *   context; pages are processed in chunks of whole pages under ASR_OMR_BUDGET_MB (at least one page per chunk).
+ *   label_passes (may be NULL): the number of labelling passes of the call, over all chunks. */
+int asr_notes_from_map_dev(asr_ctx *ctx, const double *maps_dev, const int32_t *heights, const int32_t *widths,
+                           int n_pages, const asr_seg *seg, double threshold_abs, double threshold_rel,
+                           int min_distance, int max_peaks, int32_t *status, int32_t *counts, int32_t *coords);
+int asr_bars_from_map_dev(asr_ctx *ctx, const double *maps_dev, const int32_t *heights, const int32_t *widths,
+                          int n_pages, const asr_seg *seg, int max_blobs, int32_t *status, int32_t *counts,
+                          int64_t *blobs, int32_t *label_passes);
+
 /* ---- scanned scores and recordings to strips and spectrograms (umc_a2s_server.py / umc_s2a_server.py) ----------
  * asr_unroll_systems_dev = the unrolling loop of load_umc_sheets (umc_a2s_server.py:136-158) for all systems of all
  *   pages of all pieces in one launch.  pages_dev: the uint8 pages exactly as asr_seg_predict_dev (in_mode 2) reads

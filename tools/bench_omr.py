@@ -15,6 +15,12 @@ median of --reps.  Device time per label comes from the library's event profiler
 and the stitch.  FLOP per page: direct-form 3x3 / transposed / 1x1 convolutions over every tile.  --cpu-baseline: one
 page through the float32 CPU port of the same graph (tests/omr_ref.py: torch's CPU correlation for the 3x3 convs,
 numpy for the rest) on 16 threads.  Prints one JSON line (also written to --out).
+
+    python tools/bench_omr.py --pages tutorial --notes --bars
+    python tools/bench_omr.py --pages 32 --notes --bars
+
+--notes / --bars time the stage after the note / bar network's map exists instead (detect_stage below): one JSON line
+per mode.  Without them the output is what it always was.
 """
 import argparse
 import json
@@ -54,12 +60,75 @@ def unet_flop(th, tw):
     return f + 2.0 * 8 * plane
 
 
+def detect_stage(a, pages, which):
+    """--notes / --bars: the stage after the network's map exists, on the device (asr_notes_from_map_dev /
+    asr_bars_from_map_dev + bars_from_stats, the maps where the network left them) and on the host (notes_from_map /
+    bars_from_map on the same maps, downloaded once outside the timing) in the same process: median, minimum and
+    maximum of --reps each after one warm-up, and that the two agree.  The host stage is the baseline."""
+    from ctypes import c_void_p
+
+    from audio_sheet_retrieval_amd.sheet_utils import omr as O
+    from audio_sheet_retrieval_amd.sheet_utils.umc import build_recognizer
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import omr_ref
+    params = {k: omr_ref.params_from_npz(os.path.join(GOLDEN, "omr_%s_params.npz" % k)) for k in ("system", "bar", "note")}
+    rec = build_recognizer(params["system"], params["bar"], note_params=params["note"])
+    net = rec.note_detector if which == "notes" else rec.bar_detector
+    eng = net.engine
+    out, x, (_, _, sizes, _, hs, ws) = net.predict_pages_dev(pages, in_mode=O.IN_U8_RAW)
+    eng.sync()
+    flat = out.download((int(sizes.sum()),), np.float64)
+    offs = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    maps = [flat[o:o + n].reshape(h, w) for o, n, h, w in zip(offs, sizes, hs, ws)]
+
+    def device():
+        if which == "notes":
+            return [c for _, c in O.notes_from_map_dev(eng, c_void_p(out.ptr), hs, ws, seg=net.handle)]
+        res, _ = O.bar_blobs_from_map_dev(eng, c_void_p(out.ptr), hs, ws, seg=net.handle)
+        return [None if st is None else O.bars_from_stats(st) for _, st in res]
+
+    def host():
+        return [O.notes_from_map(m) if which == "notes" else O.bars_from_map(m) for m in maps]
+
+    def timed(f):
+        res = f()
+        ts = []
+        for _ in range(a.reps):
+            t = time.perf_counter()
+            res = f()
+            ts.append((time.perf_counter() - t) * 1e3)
+        return res, {"median": float(np.median(ts)), "min": float(min(ts)), "max": float(max(ts))}
+
+    try:
+        dev_res, dev_ms = timed(device)
+        host_res, host_ms = timed(host)
+    finally:
+        out.free()
+        if x is not None:
+            x.free()
+    h, w = pages[0].shape
+    return {
+        "what": "%s after the network's map exists, %s pages of %dx%d: device stage against the host stage on the same "
+                "maps, same process" % (which, a.pages, h, w),
+        "pages": len(pages),
+        "device_stage_ms": dev_ms,
+        "host_stage_ms": host_ms,
+        "host_over_device": host_ms["median"] / dev_ms["median"],
+        "undecided_on_device": int(sum(r is None for r in dev_res)),
+        "equal": bool(all(d is not None and np.array_equal(d, hh) for d, hh in zip(dev_res, host_res))),
+        "found": [int(len(r)) for r in host_res][:8],
+        "reps": a.reps,
+    }
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--pages", default="tutorial", help="'tutorial' or a number of synthetic pages")
     p.add_argument("--reps", type=int, default=5)
     p.add_argument("--cpu-baseline", action="store_true")
     p.add_argument("--out", default=None)
+    p.add_argument("--notes", action="store_true", help="time note-head detection after the map: device and host stage")
+    p.add_argument("--bars", action="store_true", help="time bar detection after the map: device and host stage")
     a = p.parse_args()
 
     from audio_sheet_retrieval_amd.sheet_utils import omr as O
@@ -74,6 +143,13 @@ def main():
     else:
         pages = [synth_page(1000 + i) for i in range(int(a.pages))]
     n = len(pages)
+    if a.notes or a.bars:
+        lines = [json.dumps(detect_stage(a, pages, which)) for which, on in (("notes", a.notes), ("bars", a.bars)) if on]
+        print("\n".join(lines))
+        if a.out:
+            with open(a.out, "w") as fp:
+                fp.write("\n".join(lines) + "\n")
+        return
     rec = build_recognizer(ps, pb)
     eng = rec.system_detector.engine
 
