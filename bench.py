@@ -14,13 +14,18 @@ consecutive repeats (fewer when K is smaller), each timed on its own, and the ME
 steps instead of K: on the MI355X, K = 20 split 5 ways and timed as one window gave the same ms_per_step within
 run-to-run noise.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 
-Run length beyond the K timed steps and the W warm-up steps: N > 1 runs K more steps with the exchange timed (comm_ms);
-N = 1 runs the untimed-for-the-headline side legs - the host-buffer leg (--repeats windows of K batches each: its
-double-buffered copies are timed over whole K-batch windows, so the pipeline's fill is not counted once per few steps),
-the trained-weights recall leg (K + 1 steps), and the fixed-size secondary and reference-API legs.  The CPU baseline
-leg depends on --cpu-pairs only.
+A plain run does what the headline figure needs and nothing else: set-up, the W warm-up steps (whose last ones are
+the surveyed ones), the K timed steps, --dump-outputs, the line.  Its "roofline" and "kernels" blocks come from those
+same steps and from committed files; every leg that takes steps of its own is None / absent in its line.
 
-    python bench.py --gpus N --steps K --warmup W
+--full adds the side legs, all after the timed steps and the dump, none of them part of the headline: N > 1 runs K more
+steps with the exchange timed (comm_ms); N = 1 runs the host-buffer leg (--repeats windows of K batches each: its
+double-buffered copies are timed over whole K-batch windows, so the pipeline's fill is not counted once per few steps),
+the trained-weights recall leg (K + 1 steps), the CPU baseline leg (--cpu-pairs), and the fixed-size secondary and
+reference-API legs.  --no-host-leg / --no-cpu-baseline / --no-secondary / --no-dropin / --no-isolated take single legs
+out of a --full run.  The pool2m and train workloads are single measurements of their own and do not change with --full.
+
+    python bench.py --gpus N --steps K --warmup W [--full]
         N > 1: this process (which never touches a GPU) starts one child per GPU
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -30,10 +35,11 @@ Control plane (communicator id, barriers, max-over-ranks): distributed.HubComm, 
 Data plane: asr_comm_init (RCCL inside libasr_hip.so) + asr_rank_sharded_dev, enqueued on the library's stream; no
 host synchronisation inside a step.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including
+Prints ONE JSON line on rank 0 including "full" (whether --full was given) and
   "roofline":     dominant kernel, algorithmic FLOP / measured HIP-event time vs the dense fp32-MFMA peak
                   (157.3 TFLOP/s, MI355X_MICROARCH.md); HBM traffic and MFMA-pipe utilisation of that kernel from the
                   committed rocprofv3 PMC runs of this same command (profiles/, `traffic_source` names the file)
+with --full only:
   "cpu_baseline": the CPU oracle (oracle/, a NumPy/C port of the reference path - NOT Theano, which cannot run here)
                   timed on a bounded sample on this host's cores (N=1 only)
   "value_host_buffers": the same step fed from page-locked HOST memory (H2D of the inputs and D2H of the ranks inside
@@ -78,9 +84,13 @@ def parse_args(argv=None):
     ap.add_argument("--batches", type=int, default=8, help="distinct resident input batches the steps rotate through")
     ap.add_argument("--pairs", type=int, default=PAIRS_PER_GPU, help="pairs per GPU per step")
     ap.add_argument("--chunk", type=int, default=0, help="samples per internal launch (0 = library default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-leg", action="store_true", help="skip the host-buffer (PCIe-inclusive) measurement")
-    ap.add_argument("--no-isolated", action="store_true", help="skip the informational single-stream pass")
+    ap.add_argument("--full", action="store_true",
+                    help="pairs workload: after the timed steps also run the side legs - exchange timing (N > 1), "
+                         "host-buffer leg, trained-weights recall, CPU baseline, secondary configs, reference-API legs. "
+                         "Off by default: a plain run times the headline and prints its line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-host-leg", action="store_true", help="--full: skip the host-buffer (PCIe-inclusive) measurement")
+    ap.add_argument("--no-isolated", action="store_true", help="--full: skip the informational single-stream pass")
     ap.add_argument("--profile-all", action="store_true",
                     help="bracket EVERY kernel with events inside the timed region too (tools/profile_round.sh: the "
                          "launch log then covers all timed launches)")
@@ -101,8 +111,8 @@ def parse_args(argv=None):
                          "all-gathered and merged, the rank counters all-reduced. pool: the pool's embeddings are "
                          "all-gathered (256 MB) and every GPU searches all of it for its own queries")
     ap.add_argument("--queries", type=int, default=4096, help="pool2m: queries in the whole job")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the configs[2]/[3]/[4] measurements")
-    ap.add_argument("--no-dropin", action="store_true", help="skip the reference-API legs (RetrievalWrapper, refine_cca)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the configs[2]/[3]/[4] measurements")
+    ap.add_argument("--no-dropin", action="store_true", help="--full: skip the reference-API legs (RetrievalWrapper, refine_cca)")
     ap.add_argument("--refine-pairs", type=int, default=25000, help="host pairs of the refine_cca leg")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="pairs workload: write what the last timed step computed (embeddings of both views, ranks, d*, "
@@ -799,7 +809,7 @@ def run_rank(args):
             ranks=d_ranks.download((n,), np.int32), dstar=d_dstar.download((n,), np.float64),
             ties=d_ties.download((n,), np.int32)), rank, world)
     comm_ms = comm_calls = None
-    if use_dist:                                   # the all-gather of the candidate embeddings, per step (asr_comm_timing)
+    if use_dist and args.full:                     # the all-gather of the candidate embeddings, per step (asr_comm_timing)
         eng.comm_timing(True)
         fence()
         for _ in range(args.steps):
@@ -816,9 +826,9 @@ def run_rank(args):
         hits = eng.allreduce_host(hits)          # over the communicator (RCCL / host callbacks)
     prof = eng.profile()
 
-    # ---- host-buffer leg (N=1): the same step fed from page-locked host memory, copies inside the timed region
+    # ---- host-buffer leg (--full, N=1): the same step fed from page-locked host memory, copies inside the timed region
     host_leg = None
-    if world == 1 and not use_dist and not args.no_host_leg:
+    if args.full and world == 1 and not use_dist and not args.no_host_leg:
         pin = []
         for s, z in host:
             ps, pz = eng.host_array(s.shape, s.dtype), eng.host_array(z.shape, z.dtype)
@@ -849,10 +859,11 @@ def run_rank(args):
                         note="asr_eval_batches: pinned host inputs, H2D of batch k+1 and D2H of batch k-1 on copy "
                              "streams while batch k computes")
 
-    # ---- only with ASR_TWO_STREAMS=1 (towers overlapping on two streams, which stretches every kernel's own duration):
+    # ---- only with --full and ASR_TWO_STREAMS=1 (towers overlapping on two streams, which stretches every kernel's own duration):
     # the same kernels WITHOUT the other tower sharing the GPU, a few untimed steps, reported next to the timed figures.
     iso = None
-    if rank == 0 and world == 1 and not use_dist and not args.no_isolated and os.environ.get("ASR_TWO_STREAMS") == "1":
+    if args.full and rank == 0 and world == 1 and not use_dist and not args.no_isolated and \
+            os.environ.get("ASR_TWO_STREAMS") == "1":
         os.environ["ASR_TWO_STREAMS"] = "0"
         eng2 = _lib.Engine(MODEL, device=local_rank, max_chunk=args.chunk)
         os.environ["ASR_TWO_STREAMS"] = "1"
@@ -957,6 +968,7 @@ def run_rank(args):
         out = {
             "metric": "snippet-pairs/sec embedded+ranked (32-d CCA)",
             "value": value, "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": warmup_ran,
+            "full": bool(args.full),              # False: the legs below that take steps of their own did not run
             "warmup_requested": args.warmup,
             "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -999,13 +1011,13 @@ def run_rank(args):
             "dumped_outputs": None if dumped is None else {"dir": args.dump_outputs, "arrays": dumped,
                                                            "step": it_last_timed},
         }
-        # ---- Recall@k that means something: the timed region runs random-init weights (the contract's workload:
+        # ---- --full: Recall@k that means something: the timed region runs random-init weights (the contract's workload:
         # chance-level recall by construction); the same batch 0 - pairs the model never saw - embedded and ranked once
         # more, untimed, with the committed weights of a 600-update training run on the synthetic pool
         # (tests/golden/trained_cont_params.npz, written by tools/train_demo.py: batch 100, Adam, lr 0.002, then
         # refine_cca on 5000 pairs)
         trained = os.path.join(ROOT, "tests", "golden", "trained_cont_params.npz")
-        if world == 1 and not use_dist and MODEL == "mutopia_ccal_cont" and os.path.exists(trained) and \
+        if args.full and world == 1 and not use_dist and MODEL == "mutopia_ccal_cont" and os.path.exists(trained) and \
                 not os.environ.get("ASR_BENCH_PARAMS"):
             try:
                 with np.load(trained) as z:
@@ -1042,12 +1054,12 @@ def run_rank(args):
                 eng.set_params(weights)
             except Exception as e:
                 out["recall_trained_weights"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_pairs, seed=23)
         else:
             out["cpu_baseline"] = None
-        # ---- N = 1: the other BASELINE configs and the reference's own API, after the timed region
-        if (world == 1 and not use_dist) or os.environ.get("ASR_BENCH_SECONDARY") == "1":
+        # ---- --full, N = 1: the other BASELINE configs and the reference's own API, after the timed region
+        if args.full and ((world == 1 and not use_dist) or os.environ.get("ASR_BENCH_SECONDARY") == "1"):
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import bench_secondary as BS
 

@@ -21,6 +21,15 @@ def test_dump_option_is_for_the_pairs_workload_only(tmp_path):
         bench.parse_args(["--workload", "train", "--dump-outputs", str(tmp_path)])
 
 
+def test_side_legs_are_behind_full():
+    """a plain command line asks for the headline alone; --full is what turns the side legs on, the --no-* switches then
+    take single ones out"""
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert plain.full is False and (plain.steps, plain.warmup, plain.gpus) == (20, 5, 1)
+    full = bench.parse_args(["--full", "--no-cpu-baseline"])
+    assert full.full is True and full.no_cpu_baseline is True and full.no_host_leg is False
+
+
 def test_dump_writes_float32_and_float64_arrays(tmp_path):
     rng = np.random.default_rng(0)
     lv = rng.standard_normal((10, 32)).astype(np.float32)

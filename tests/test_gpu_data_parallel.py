@@ -282,9 +282,32 @@ def test_bench_rccl_hand_off_on_one_rank():
     assert rec["value"] > 0 and rec["roofline"]["frac"] > 0
 
 
+def test_bench_plain_line_is_the_headline_alone(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the contract fields of the headline, the roofline and
+    per-kernel blocks that its own warm-up and timed steps give, the dump of the last timed step - and no side leg: the
+    legs that take steps or processes of their own are None or absent, and the line says `full: false`."""
+    import numpy as np
+    rec, _ = _run_bench(dict(ASR_AUTOTUNE="0"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--batches", "2",
+                        "--pairs", "250", "--dump-outputs", str(tmp_path))
+    assert rec["full"] is False and rec["n_gpus"] == 1 and rec["steps"] == 3 and rec["warmup"] == 2
+    assert rec["metric"] == "snippet-pairs/sec embedded+ranked (32-d CCA)" and rec["unit"] == "pairs/s"
+    assert rec["higher_is_better"] is True and rec["dtype"] == "f32" and rec["repeats"]["n"] == 3
+    assert rec["ms_per_step"] > 0 and abs(rec["value"] - 250 / (rec["ms_per_step"] * 1e-3)) <= 1e-6 * rec["value"]
+    r = rec["roofline"]
+    assert r["bound"] == "mfma" and r["frac"] > 0 and len(r["largest_two_symbols"]) == 2 and rec["kernels"]
+    for key in ("cpu_baseline", "value_host_buffers", "host_buffers", "roofline_isolated", "comm_ms", "comm"):
+        assert key in rec and rec[key] is None, key
+    for key in ("secondary", "dropin_api", "value_dropin_api", "refine_cca", "refine_cca_s", "recall_trained_weights"):
+        assert key not in rec, key
+    assert rec["dumped_outputs"]["arrays"] == ["dstar", "lv1", "lv2", "ranks", "ties"] and rec["dumped_outputs"]["step"] == 4
+    lv1, ranks = np.load(tmp_path / "lv1.npy"), np.load(tmp_path / "ranks.npy")
+    assert lv1.shape == (250, 32) and lv1.dtype == np.float32 and ranks.shape == (250,) and ranks.min() >= 1
+
+
 def test_bench_default_line_carries_the_contract_fields():
-    rec, _ = _run_bench(dict(ASR_AUTOTUNE="0"), "--steps", "3", "--warmup", "1", "--repeats", "3", "--batches", "3",
-                        "--cpu-pairs", "100", "--refine-pairs", "3000")
+    rec, _ = _run_bench(dict(ASR_AUTOTUNE="0"), "--full", "--steps", "3", "--warmup", "1", "--repeats", "3", "--batches",
+                        "3", "--cpu-pairs", "100", "--refine-pairs", "3000")
+    assert rec["full"] is True
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "value_host_buffers",
                 "secondary", "value_dropin_api", "dropin_api", "refine_cca_s"):

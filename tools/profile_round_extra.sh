@@ -60,6 +60,6 @@ PY
 bash tools/train_kernel_table.sh > $P/${TAG}_train_kernel_table.txt 2>&1
 bash tools/train_timeline.sh > $P/${TAG}_train_timeline.txt 2>&1
 python3 tools/train_batch_sizes.py 64 100 512 > $P/${TAG}_train_batch_sizes.txt 2>&1
-ASR_BENCH_MODEL=mutopia_ccal_cont_rsz python3 bench.py --no-cpu-baseline --no-secondary --no-dropin 2> /dev/null | grep '^{' | tail -1 > $P/${TAG}_rsz_bench_line.json
+ASR_BENCH_MODEL=mutopia_ccal_cont_rsz python3 bench.py --full --no-cpu-baseline --no-secondary --no-dropin 2> /dev/null | grep '^{' | tail -1 > $P/${TAG}_rsz_bench_line.json
 bash tools/pmc_train.sh wgrad > $P/${TAG}_train_wgrad_pmc.txt 2>&1
 ls -la $P | tail -12

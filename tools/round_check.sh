@@ -1,11 +1,12 @@
 # Run ON THE GPU BOX: the whole GPU suite, then the default bench line with a short digest (tools/round_check.sh)
 cd $GRAFT_REPO_ROOT
 python -m pytest tests -q -m gpu -x 2>&1 | tail -8
-python bench.py --steps 20 --warmup 5 > gpurun_out/r04_bench_mid.json 2> gpurun_out/r04_bench_mid.err
-tail -c 600 gpurun_out/r04_bench_mid.err
-python - <<'PY'
-import json
-r = json.loads(open("gpurun_out/r04_bench_mid.json").read().strip().splitlines()[-1])
+OUT=$(mktemp -d)
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench_line.err
+tail -c 600 $OUT/bench_line.err
+python - $OUT/bench_line.json <<'PY'
+import json, sys
+r = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print({k: r[k] for k in ("value", "warmup", "ms_per_step", "value_host_buffers", "value_dropin_api", "refine_cca_s")})
 print(r["roofline"]["kernel"][:60], r["roofline"]["frac"],
       [(t["kernel"][:40], round(t["frac"], 3)) for t in r["roofline"]["largest_two_symbols"]])
