@@ -42,7 +42,7 @@ EXPORTS = [
     "asr_rank_sharded_dev", "asr_slice_windows_dev", "asr_piece_vote_dev", "asr_piece_vote_batch_dev", "asr_track_gate_dev", "asr_track_vote_batch_dev", "asr_gather_windows_dev", "asr_dtw_dev", "asr_dtw_batch_dev", "asr_spectrogram_dev", "asr_debug_tune_report",
     "asr_seg_create", "asr_seg_set_window", "asr_seg_destroy", "asr_seg_predict_dev", "asr_systems_from_maps_dev",
     "asr_notes_from_map_dev", "asr_bars_from_map_dev",
-    "asr_unroll_systems_dev", "asr_spectrogram_batch_dev",
+    "asr_unroll_systems_dev", "asr_spectrogram_batch_dev", "asr_resample_batch_dev",
     "asr_opt_state_size", "asr_get_opt_state", "asr_set_opt_state", "asr_debug_train_tensor", "asr_cca_train_debug",
 ]
 
@@ -214,6 +214,8 @@ def load_library(path=None):
         "asr_spectrogram_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                               c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
                                               c_float, c_int, c_void_p, c_int64]),
+        "asr_resample_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                           c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int64]),
         "asr_debug_tune_report": (c_int, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_float)]),
         "asr_comm_unique_id": (c_int, [c_void_p]),
         "asr_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),
@@ -608,6 +610,25 @@ class Engine(object):
             n_frames.ctypes.data, out_offsets.ctypes.data, n, frame_size, hop, window.ctypes.data, fb_start.ctypes.data,
             fb_len.ctypes.data, fb_weights.ctypes.data, fb_start.size, mul, add, 1 if transposed else 0, out_ptr,
             int(out_floats)))
+
+    def resample_batch_dev(self, in_ptr, in_floats, in_offsets, in_counts, out_offsets, out_counts, up, down,
+                           taps_phase_major, half, round_int16, out_ptr, out_floats):
+        """recordings of one input rate resampled by up / down in one launch (asr_resample_batch_dev): recording i is
+        in_counts[i] floats at in_offsets[i] of the buffer at in_ptr, its out_counts[i] outputs go to out_offsets[i]
+        of the buffer at out_ptr.  taps_phase_major: float64 (up, taps per phase), audio_frontend.resample_plan's.
+        Bit-identical per recording with audio_frontend.resample_host"""
+        i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
+        in_offsets, in_counts, out_offsets, out_counts = map(i64, (in_offsets, in_counts, out_offsets, out_counts))
+        n = in_counts.size
+        if not (in_offsets.size == out_offsets.size == out_counts.size == n):
+            raise ValueError("resample_batch_dev: the per-recording tables differ in length")
+        taps = np.ascontiguousarray(taps_phase_major, dtype=np.float64)
+        if taps.ndim != 2 or taps.shape[0] < up:
+            raise ValueError("resample_batch_dev: taps of shape %r for %d phases" % (taps.shape, up))
+        self._check(self.lib.asr_resample_batch_dev(
+            self.ctx, in_ptr, int(in_floats), in_offsets.ctypes.data, in_counts.ctypes.data, out_offsets.ctypes.data,
+            out_counts.ctypes.data, n, int(up), int(down), taps.ctypes.data, taps.shape[1], int(half),
+            1 if round_int16 else 0, out_ptr, int(out_floats)))
 
     def unroll_systems_dev(self, pages_ptr, pages_bytes, page_offsets, heights, widths, systems, system_height,
                            strip_offsets, strip_widths, strips_ptr, strips_floats):

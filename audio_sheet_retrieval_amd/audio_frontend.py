@@ -7,7 +7,11 @@ spectrogram tower takes, i.e. the madmom processor chain of the reference (tutor
     -> LogarithmicSpectrogramProcessor()
 
 `process(samples)` takes mono samples at SAMPLE_RATE; `load_audio(path)` reads them from a .wav or .npy file.  Decoding
-compressed formats and resampling (ffmpeg inside madmom) stay with the caller.  The filterbank is built on the host with madmom's published construction (third-party
+compressed formats stays with the caller.  Recordings at another rate: `read_audio(path)` reads them at their own rate
+and `process*(..., sample_rate(s)=...)` resamples them on the device between the upload and the spectrogram
+(asr_resample_batch_dev, csrc/resample_kernels.hip).  madmom resamples through ffmpeg, whose filter cannot be restated;
+the resampler here is a definition of its own (include/asr_hip.h; `resample_plan`, `resample_host`).  Without a sample
+rate everything behaves as before: a foreign rate is an error.  The filterbank is built on the host with madmom's published construction (third-party
 semantic, unverified offline; it reproduces the reference's 92 bands); framing, windowed DFT magnitudes,
 filterbank and logarithm run in one kernel per call (csrc/piece_vote_kernels.hip: spectrogram_kernel).
 """
@@ -61,25 +65,21 @@ def logarithmic_filterbank(sample_rate=SAMPLE_RATE, frame_size=FRAME_SIZE, num_b
 LOADABLE = (".wav", ".npy")
 
 
-def load_audio(path, sample_rate=SAMPLE_RATE):
-    """-> (mono float32 samples, window_scale) of a .wav (PCM 16-bit or float32) or .npy (mono float samples) file -
-    what madmom's SignalProcessor(num_channels=1, sample_rate=22050) hands on.  Channels are averaged.  16-bit PCM
-    keeps its integer values and comes with window_scale = 1 / 32767 (madmom scales the STFT window by the integer
-    range instead of the samples); float input has window_scale 1.  A file at another rate is an error: resampling is
-    the caller's."""
+def _read(path, sample_rate, any_rate):
+    """load_audio / read_audio -> (samples, window_scale, rate, integer)"""
     ext = os.path.splitext(path)[1].lower()
     if ext == ".npy":
         samples = np.load(path)
         if samples.ndim != 1 or samples.dtype.kind != "f":
             raise ValueError("%s: expected mono float samples (1-d), got %s %r" % (path, samples.dtype, samples.shape))
-        return np.ascontiguousarray(samples, dtype=np.float32), 1.0
+        return np.ascontiguousarray(samples, dtype=np.float32), 1.0, sample_rate, False
     if ext != ".wav":
         raise ValueError("%s: no decoder for '%s' files is part of this implementation; convert the recording to "
                          "a %d Hz .wav (PCM 16-bit or float32) or .npy (mono float samples) file" %
                          (path, ext or "extension-less", sample_rate))
     from scipy.io import wavfile
     rate, data = wavfile.read(path)
-    if rate != sample_rate:
+    if rate != sample_rate and not any_rate:
         raise ValueError("%s: sample rate %d Hz, expected %d Hz (resample the file first)" % (path, rate, sample_rate))
     if data.dtype == np.int16:
         scale = 1.0 / 32767
@@ -90,7 +90,87 @@ def load_audio(path, sample_rate=SAMPLE_RATE):
     if data.ndim == 2:
         # madmom's remix: the channel mean, in the sample type (integers truncate as astype does)
         data = np.mean(data, axis=-1).astype(data.dtype)
-    return np.ascontiguousarray(data, dtype=np.float32), scale
+    return np.ascontiguousarray(data, dtype=np.float32), scale, int(rate), bool(data.dtype == np.int16)
+
+
+def load_audio(path, sample_rate=SAMPLE_RATE):
+    """-> (mono float32 samples, window_scale) of a .wav (PCM 16-bit or float32) or .npy (mono float samples) file -
+    what madmom's SignalProcessor(num_channels=1, sample_rate=22050) hands on.  Channels are averaged.  16-bit PCM
+    keeps its integer values and comes with window_scale = 1 / 32767 (madmom scales the STFT window by the integer
+    range instead of the samples); float input has window_scale 1.  A file at another rate is an error: read_audio
+    reads it, and the processor resamples it when it is told the rate."""
+    return _read(path, sample_rate, False)[:2]
+
+
+def read_audio(path):
+    """load_audio for a file of any sample rate -> (mono float32 samples, window_scale, rate, integer).  integer: the
+    samples are 16-bit PCM values, and resampling them yields 16-bit values again (rounded and clipped), as a decoder
+    hands them to madmom.  A .npy file carries no rate: its samples are taken to be at SAMPLE_RATE."""
+    return _read(path, SAMPLE_RATE, True)
+
+
+RESAMPLE_TILE = 1024          # outputs per workgroup of resample_batch_kernel (csrc/asr_kernels.h)
+RESAMPLE_RATES = (4000, 192000)
+_plans = {}
+
+
+def resample_plan(rate_in, rate_out=SAMPLE_RATE):
+    """-> (up, down, half, taps_phase_major float64 (up, T)): the resampler rate_in -> rate_out as include/asr_hip.h
+    defines it (asr_resample_batch_dev).  up / down = rate_out / rate_in in lowest terms; the filter is a windowed sinc
+    of 2 * half + 1 taps, half = 16 * max(up, down), Kaiser window with beta 8.6, cut-off at the lower of the two
+    Nyquist frequencies, gain up; row p of the table holds taps p, p + up, p + 2 up, ... (zeros past the end).  Rates
+    are integers from 4000 to 192000 Hz."""
+    for r in (rate_in, rate_out):
+        if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not RESAMPLE_RATES[0] <= r <= RESAMPLE_RATES[1]:
+            raise ValueError("sample rate %r: integer rates from %d to %d Hz are resampled" % ((r,) + RESAMPLE_RATES))
+    key = (int(rate_in), int(rate_out))
+    if key not in _plans:
+        import math
+        g = math.gcd(*key)
+        up, down = key[1] // g, key[0] // g
+        q = max(up, down)
+        half = 16 * q
+        n_taps = 2 * half + 1
+        h = np.sinc((np.arange(n_taps) - half) / float(q)) * np.kaiser(n_taps, 8.6)
+        h *= up / h.sum()
+        T = -(-n_taps // up)
+        table = np.zeros(T * up, np.float64)
+        table[:n_taps] = h
+        table = np.ascontiguousarray(table.reshape(T, up).T)
+        table.setflags(write=False)
+        if len(_plans) >= 8:                  # a table is up to 49 MB
+            _plans.clear()
+        _plans[key] = (up, down, half, table)
+    return _plans[key]
+
+
+def resample_host(samples, rate_in, integer=False, rate_out=SAMPLE_RATE):
+    """the numpy restatement of asr_resample_batch_dev (include/asr_hip.h): mono samples at rate_in -> float32 samples
+    at rate_out; integer=True rounds to even and clips to the 16-bit range.  The sum of an output runs over the taps in
+    ascending order, float64 product then float64 sum, as on the device (bit-identical for finite samples)."""
+    up, down, half, hp = resample_plan(rate_in, rate_out)
+    T = hp.shape[1]
+    x = np.ascontiguousarray(samples, dtype=np.float32).ravel().astype(np.float64)
+    n = x.size
+    n_out = -(-n * up // down)
+    y = np.zeros(n_out, np.float64)
+    block = 1 << 18
+    for m0 in range(0, n_out, block):
+        m = np.arange(m0, min(m0 + block, n_out), dtype=np.int64)
+        c = m * down + half
+        p, j0 = c % up, c // up
+        acc = y[m0:m0 + m.size]
+        if j0[0] - (T - 1) >= 0 and j0[-1] < n:       # every tap of every output of the block meets a sample
+            for t in range(T):
+                acc += (hp[0, t] if up == 1 else hp[p, t]) * x[j0 - t]
+        else:
+            for t in range(T):
+                j = j0 - t
+                ok = (j >= 0) & (j < n)
+                acc[ok] = acc[ok] + hp[p[ok], t] * x[j[ok]]
+    if integer:
+        y = np.clip(np.rint(y), -32768, 32767)
+    return y.astype(np.float32)
 
 
 class SpectrogramProcessor(object):
@@ -112,8 +192,13 @@ class SpectrogramProcessor(object):
     def num_frames(self, n_samples):
         return int(np.ceil(n_samples / float(self.hop)))
 
-    def process_dev(self, samples):
-        """-> (DeviceBuffer holding the (num_bins, n_frames) float32 spectrogram, n_frames)"""
+    def process_dev(self, samples, sample_rate=None, integer=False):
+        """-> (DeviceBuffer holding the (num_bins, n_frames) float32 spectrogram, n_frames).  sample_rate: the rate of
+        `samples` where it is not the processor's - they are resampled on the device first (integer: 16-bit PCM
+        values, see read_audio)"""
+        if sample_rate is not None and sample_rate != self.sample_rate:
+            dev = self.process_many_dev([samples], None, [sample_rate], [integer])
+            return dev.buf, dev.shapes[0][1]
         samples = np.ascontiguousarray(samples, dtype=np.float32)
         n = self.num_frames(samples.size)
         eng = self.engine
@@ -126,23 +211,32 @@ class SpectrogramProcessor(object):
             d_in.free()
         return d_out, n
 
-    def process(self, samples):
+    def process(self, samples, sample_rate=None, integer=False):
         """the reference's `processor.process(audio).T`: (num_bins, n_frames) float32"""
-        d_out, n = self.process_dev(samples)
+        d_out, n = self.process_dev(samples, sample_rate, integer)
         out = d_out.download((self.num_bins, n), np.float32)
         d_out.free()
         return out
 
-    def process_many_dev(self, recordings, window_scales=None):
+    def process_many_dev(self, recordings, window_scales=None, sample_rates=None, integer=None):
         """process_dev for a list of recordings of any lengths (an empty one gives no frames) in one launch
         (asr_spectrogram_batch_dev) -> piece_identification.DeviceArrays: the (num_bins, n_frames_i) spectrograms back
         to back in one device buffer, each bit-identical with process()'s.  window_scales: one per recording (what
-        load_audio returned; default: the processor's) - recordings of equal scale share a launch."""
+        load_audio returned; default: the processor's) - recordings of equal scale share a launch.
+        sample_rates: one per recording (what read_audio returned).  Recordings at the processor's rate are uploaded
+        to their place in the buffer the spectrogram launch reads; the others are uploaded at their own rate and
+        resampled into place on the device, one asr_resample_batch_dev call per (rate, integer) group - each result
+        bit-identical with process() on resample_host()'s.  integer: one flag per recording (read_audio's; default
+        False)."""
         from .piece_identification import DeviceArrays
         recs = [np.ascontiguousarray(r, dtype=np.float32).ravel() for r in recordings]
         scales = [self.window_scale] * len(recs) if window_scales is None else [float(w) for w in window_scales]
         if len(scales) != len(recs):
             raise ValueError("%d window scales for %d recordings" % (len(scales), len(recs)))
+        if sample_rates is not None:
+            return self._process_many_rates_dev(recs, scales, sample_rates, integer)
+        if integer is not None:
+            raise ValueError("integer flags without sample rates")
         counts = np.asarray([r.size for r in recs], np.int64)
         frames = np.asarray([self.num_frames(r.size) for r in recs], np.int64)
         s_off = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64) if recs else np.zeros(0, np.int64)
@@ -167,9 +261,68 @@ class SpectrogramProcessor(object):
             d_in.free()
         return DeviceArrays(d_out, [int(o) for o in o_off], [(self.num_bins, int(n)) for n in frames])
 
-    def process_many(self, recordings, window_scales=None):
+    def _process_many_rates_dev(self, recs, scales, sample_rates, integer):
+        """process_many_dev with sample rates: upload, resample into place, one spectrogram launch per window scale"""
+        from .piece_identification import DeviceArrays
+        rates = list(sample_rates)
+        flags = [False] * len(recs) if integer is None else [bool(f) for f in integer]
+        if len(rates) != len(recs) or len(flags) != len(recs):
+            raise ValueError("%d sample rates and %d integer flags for %d recordings" % (len(rates), len(flags), len(recs)))
+        foreign = [i for i, r in enumerate(rates) if r != self.sample_rate]
+        plans = {r: resample_plan(r, self.sample_rate) for r in set(rates[i] for i in foreign)}
+        counts = np.asarray([r.size for r in recs], np.int64)          # at the processor's rate
+        for i in foreign:
+            up, down = plans[rates[i]][:2]
+            counts[i] = -(-recs[i].size * up // down)
+        frames = np.asarray([self.num_frames(int(c)) for c in counts], np.int64)
+        zero = np.zeros(0, np.int64)
+        s_off = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64) if recs else zero
+        o_off = np.concatenate([[0], np.cumsum(frames * self.num_bins)[:-1]]).astype(np.int64) if recs else zero
+        n_off = np.zeros(len(recs), np.int64)                          # of the foreign ones in the native-rate buffer
+        native_floats = 0
+        for i in foreign:
+            n_off[i] = native_floats
+            native_floats += recs[i].size
+        eng = self.engine
+        in_floats = int(counts.sum())
+        out_floats = int(frames.sum()) * self.num_bins
+        d_in = eng.alloc(max(4, in_floats * 4))
+        d_native = eng.alloc(max(4, native_floats * 4)) if foreign else None
+        d_out = eng.alloc(max(4, out_floats * 4))
+        try:
+            own = [i for i in range(len(recs)) if rates[i] == self.sample_rate and recs[i].size]
+            k = 0
+            while k < len(own):                                       # neighbours in the buffer travel together
+                e = k + 1
+                while e < len(own) and own[e] == own[e - 1] + 1:
+                    e += 1
+                eng.raw_upload(d_in.offset(4 * int(s_off[own[k]])), np.concatenate([recs[i] for i in own[k:e]]))
+                k = e
+            if native_floats:
+                d_native.upload(np.concatenate([recs[i] for i in foreign]))
+            for rate, flag in sorted(set((rates[i], flags[i]) for i in foreign)):
+                sel = np.asarray([i for i in foreign if rates[i] == rate and flags[i] == flag], np.int64)
+                up, down, half, taps = plans[rate]
+                eng.resample_batch_dev(d_native.ptr, native_floats, n_off[sel], [recs[i].size for i in sel], s_off[sel],
+                                       counts[sel], up, down, taps, half, flag, d_in.ptr, in_floats)
+            for scale in sorted(set(scales)):
+                sel = np.asarray([i for i, w in enumerate(scales) if w == scale], np.int64)
+                window = self.window if scale == self.window_scale else self._window(scale)
+                eng.spectrogram_batch_dev(d_in.ptr, in_floats, s_off[sel], counts[sel], frames[sel], o_off[sel],
+                                          self.frame_size, self.hop, window, self.fb_start, self.fb_len, self.fb_w,
+                                          d_out.ptr, out_floats, transposed=True)
+        except Exception:
+            d_out.free()
+            raise
+        finally:
+            d_in.free()
+            if d_native is not None:
+                d_native.free()
+        return DeviceArrays(d_out, [int(o) for o in o_off], [(self.num_bins, int(n)) for n in frames])
+
+    def process_many(self, recordings, window_scales=None, sample_rates=None, integer=None):
         """process() for a list of recordings in one launch -> list of (num_bins, n_frames_i) float32 arrays"""
-        dev = self.process_many_dev(recordings, window_scales)
+        dev = self.process_many_dev(recordings, window_scales, sample_rates, integer)
         try:
             total = sum(r * c for r, c in dev.shapes)
             flat = dev.buf.download((total,), np.float32) if total else np.zeros(0, np.float32)

@@ -23,9 +23,10 @@ BASE_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wno-comm
 EXTRA_FLAGS = os.environ.get("ASR_EXTRA_HIPCC_FLAGS", "").split()      # timing experiments (tools/ablate_*.sh): -DASR_WINOG_ABL=...
 FLAGS = BASE_FLAGS + ["-I", INCLUDE] + EXTRA_FLAGS
 # per-source flags: the restated numpy arithmetic of systems_from_maps, of the bar / note-head detection and of the
-# tracking loop's music gate compares bits, so no fused multiply-adds there
+# tracking loop's music gate compares bits, and so does the resampler's float64 polyphase sum, so no fused
+# multiply-adds there
 FILE_FLAGS = {"omr_post_kernels.hip": ["-ffp-contract=off"], "omr_detect_kernels.hip": ["-ffp-contract=off"],
-              "track_kernels.hip": ["-ffp-contract=off"]}
+              "track_kernels.hip": ["-ffp-contract=off"], "resample_kernels.hip": ["-ffp-contract=off"]}
 
 
 def sources():

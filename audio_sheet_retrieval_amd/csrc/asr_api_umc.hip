@@ -1,7 +1,8 @@
-// C-ABI layer of the UMC drivers' device stages: asr_unroll_systems_dev (page scans -> unrolled strips) and
-// asr_spectrogram_batch_dev (recordings -> spectrograms); include/asr_hip.h for the contract.  Kernels:
-// umc_kernels.hip, piece_vote_kernels.hip (spectrogram_batch_kernel).  Both calls check every offset against the
-// buffer sizes the caller states before anything is launched, and return after the work is done.
+// C-ABI layer of the UMC drivers' device stages: asr_unroll_systems_dev (page scans -> unrolled strips),
+// asr_resample_batch_dev (recordings at any rate -> recordings at the front-end's rate) and asr_spectrogram_batch_dev
+// (recordings -> spectrograms); include/asr_hip.h for the contract.  Kernels: umc_kernels.hip, resample_kernels.hip,
+// piece_vote_kernels.hip (spectrogram_batch_kernel).  Every call checks every offset against the buffer sizes the
+// caller states before anything is launched, and returns after the work is done.
 #include "asr_ctx.h"
 
 int asr_unroll_systems_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
@@ -139,5 +140,85 @@ int asr_spectrogram_batch_dev(asr_ctx *ctx, const float *samples_dev, int64_t sa
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     (void)hipFree(buf);
     if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "spectrogram_batch: %s", hipGetErrorString(e));
+    return mark_main(ctx);
+}
+
+int asr_resample_batch_dev(asr_ctx *ctx, const float *in_dev, int64_t in_floats, const int64_t *in_offsets,
+                           const int64_t *in_counts, const int64_t *out_offsets, const int64_t *out_counts,
+                           int n_recordings, int up, int down, const double *taps_phase_major, int taps_per_phase,
+                           int half, int round_int16, float *out_dev, int64_t out_floats) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_recordings < 0 || in_floats < 0 || out_floats < 0)
+        return fail(ctx, ASR_ERR_INVALID, "resample_batch: bad sizes");
+    if (up < 1 || down < 1)
+        return fail(ctx, ASR_ERR_INVALID, "resample_batch: ratio %d / %d (up and down must be at least 1)", up, down);
+    if (half < 0 || taps_per_phase < 1 || (int64_t)taps_per_phase * up < 2 * (int64_t)half + 1)
+        return fail(ctx, ASR_ERR_INVALID, "resample_batch: %d taps per phase x %d phases do not hold the %lld taps of "
+                    "half = %d", taps_per_phase, up, 2 * (long long)half + 1, half);
+    if (((int64_t)asr::RESAMPLE_TILE * down + up - 1) / up + taps_per_phase + 1 > (int64_t)(asr::RESAMPLE_MAX_LDS / 4))
+        return fail(ctx, ASR_ERR_INVALID, "resample_batch: ratio %d / %d with %d taps per phase: the input span of a tile "
+                    "does not fit %zu bytes of LDS", up, down, taps_per_phase, asr::RESAMPLE_MAX_LDS);
+    if (n_recordings == 0) return ASR_OK;
+    if (!in_offsets || !in_counts || !out_offsets || !out_counts)
+        return fail(ctx, ASR_ERR_INVALID, "resample_batch: NULL argument");
+    std::vector<int64_t> tab((size_t)5 * n_recordings + 1);      // tile_first (n + 1) | in_off | in_cnt | out_off | out_cnt
+    int64_t *first = tab.data(), *i_off = first + n_recordings + 1, *i_cnt = i_off + n_recordings,
+            *o_off = i_cnt + n_recordings, *o_cnt = o_off + n_recordings;
+    // every index the kernel forms stays below in_counts * up + half + down: keep that inside int64
+    const int64_t max_count = (INT64_MAX - half - down) / up - 1;
+    int64_t tiles = 0, total_out = 0;
+    for (int i = 0; i < n_recordings; ++i) {
+        if (in_counts[i] < 0 || out_counts[i] < 0 || in_offsets[i] < 0 || out_offsets[i] < 0 ||
+            in_counts[i] > in_floats || in_offsets[i] > in_floats - in_counts[i] ||
+            out_counts[i] > out_floats || out_offsets[i] > out_floats - out_counts[i])
+            return fail(ctx, ASR_ERR_INVALID, "resample_batch: recording %d (%lld samples at %lld, %lld outputs at %lld) "
+                        "outside its buffers (%lld / %lld floats)", i, (long long)in_counts[i], (long long)in_offsets[i],
+                        (long long)out_counts[i], (long long)out_offsets[i], (long long)in_floats, (long long)out_floats);
+        if (in_counts[i] > max_count)
+            return fail(ctx, ASR_ERR_INVALID, "resample_batch: recording %d: %lld samples x %d overflow", i,
+                        (long long)in_counts[i], up);
+        const int64_t want = (in_counts[i] * up + down - 1) / down;
+        if (out_counts[i] != want)
+            return fail(ctx, ASR_ERR_INVALID, "resample_batch: recording %d: %lld outputs stated, %lld samples x %d / %d "
+                        "give %lld", i, (long long)out_counts[i], (long long)in_counts[i], up, down, (long long)want);
+        first[i] = tiles;
+        i_off[i] = in_offsets[i];
+        i_cnt[i] = in_counts[i];
+        o_off[i] = out_offsets[i];
+        o_cnt[i] = out_counts[i];
+        tiles += (out_counts[i] + asr::RESAMPLE_TILE - 1) / asr::RESAMPLE_TILE;
+        total_out += out_counts[i];
+    }
+    first[n_recordings] = tiles;
+    if (tiles == 0) return ASR_OK;
+    if (tiles > 0x7fffffffLL)
+        return fail(ctx, ASR_ERR_INVALID, "resample_batch: %lld tiles in one call", (long long)tiles);
+    if (!in_dev || !out_dev || !taps_phase_major) return fail(ctx, ASR_ERR_INVALID, "resample_batch: NULL argument");
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    int rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    const size_t b_tab = tab.size() * 8, b_taps = (size_t)up * taps_per_phase * 8, need = b_tab + b_taps;
+    if (need > ctx->resample_ws_bytes) {
+        ASR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->resample_ws) ASR_HIP(ctx, hipFree(ctx->resample_ws));
+        ctx->resample_ws = nullptr; ctx->resample_ws_bytes = 0;
+        ASR_HIP(ctx, hipMalloc(&ctx->resample_ws, need));
+        ctx->resample_ws_bytes = need;
+    }
+    int64_t *d_tab = (int64_t *)ctx->resample_ws;
+    double *d_taps = (double *)((char *)ctx->resample_ws + b_tab);
+    hipError_t e = hipMemcpyAsync(d_tab, tab.data(), b_tab, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_taps, taps_phase_major, b_taps, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        const double n_in_total = (double)total_out * down / up;
+        ProfScope ps(ctx, "resample_batch", 0, 2.0 * taps_per_phase * (double)total_out,
+                     4.0 * (n_in_total + (double)total_out));
+        const int n = n_recordings;
+        e = asr::launch_resample_batch(ctx->stream, in_dev, out_dev, d_tab, d_tab + n + 1, d_tab + 2 * n + 1,
+                                       d_tab + 3 * n + 1, d_tab + 4 * n + 1, n, tiles, up, down, half, taps_per_phase,
+                                       d_taps, round_int16 ? 1 : 0);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "resample_batch: %s", hipGetErrorString(e));
     return mark_main(ctx);
 }

@@ -294,6 +294,17 @@ struct UnrollSystem {
 };
 hipError_t launch_unroll_systems(hipStream_t s, const uint8_t *pages, const UnrollSystem *systems_dev, int n_systems,
                                  int system_height, float *strips);
+// recordings at another sample rate (resample_kernels.hip): rational polyphase resampling, one workgroup per tile of
+// RESAMPLE_TILE consecutive outputs of one recording.  tile_first (n_rec + 1 running tile counts), in_off / in_cnt /
+// out_off / out_cnt (per recording, in floats) and the phase-major float64 taps (up x taps_per_phase) on the device.
+// A tile stages resample_span() input samples in LDS, which has to fit RESAMPLE_MAX_LDS bytes.
+constexpr int RESAMPLE_TILE = 1024;
+constexpr size_t RESAMPLE_MAX_LDS = 64 * 1024;
+int resample_span(int up, int down, int taps_per_phase);
+hipError_t launch_resample_batch(hipStream_t s, const float *in, float *out, const int64_t *tile_first,
+                                 const int64_t *in_off, const int64_t *in_cnt, const int64_t *out_off,
+                                 const int64_t *out_cnt, int n_rec, int64_t total_tiles, int up, int down, int half,
+                                 int taps_per_phase, const double *taps, int round_int16);
 // batch assembly of the training pool: desc_dev holds n x 9 doubles (see piece_vote_kernels.hip)
 hipError_t launch_gather_windows(hipStream_t s, const float *src, const double *desc_dev, int n, int out_h, int out_w,
                                  float *out);

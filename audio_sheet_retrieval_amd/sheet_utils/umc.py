@@ -44,25 +44,32 @@ def get_performance_audio_path(piece_path, file_pattern):
     return matches[0]
 
 
-def load_specs(piece_paths, audio_file, processor, return_device=False):
+def load_specs(piece_paths, audio_file, processor, return_device=False, resample=False):
     """ Compute spectrograms given piece paths
 
     The recordings <piece_path>/<audio_file>* of all pieces, read with audio_frontend.load_audio and turned into
     (92, frames) spectrograms in one device call.  -> list of arrays; with return_device the
-    piece_identification.DeviceArrays handle instead (the spectrograms stay on the device)."""
-    from audio_sheet_retrieval_amd.audio_frontend import load_audio
-    recordings, scales = [], []
+    piece_identification.DeviceArrays handle instead (the spectrograms stay on the device).  resample=True: the
+    recordings may be at any sample rate (audio_frontend.read_audio) and are resampled on the device on the way."""
+    from audio_sheet_retrieval_amd.audio_frontend import load_audio, read_audio
+    recordings, scales, rates, integer = [], [], [], []
     for piece_path in piece_paths:
         try:
             audio_path = get_performance_audio_path(piece_path, audio_file)
         except IndexError:
             raise IOError("piece %s: no recording %s* in %s" % (os.path.basename(piece_path), audio_file, piece_path))
-        samples, scale = load_audio(audio_path)
+        if resample:
+            samples, scale, rate, is_int = read_audio(audio_path)
+            rates.append(rate)
+            integer.append(is_int)
+        else:
+            samples, scale = load_audio(audio_path)
         recordings.append(samples)
         scales.append(scale)
-    if return_device:
-        return processor.process_many_dev(recordings, scales)
-    return processor.process_many(recordings, scales)
+    process = processor.process_many_dev if return_device else processor.process_many
+    if resample:
+        return process(recordings, scales, rates, integer)
+    return process(recordings, scales)
 
 
 def load_umc_sheets(data_dir, require_performance=False, omr=None, system_params=None, bar_params=None, device=0,

@@ -5,7 +5,7 @@ umc_a2s_server.py (:178-189):
     python -m audio_sheet_retrieval_amd.umc_a2s_server --model models/mutopia_ccal_cont.py --data_dir <dir> \
         --train_split splits/all_split.yaml --config exp_configs/mutopia_full_aug.yaml \
         --init_sheet_db --full_eval --dump_results [--real_perf] [--n_candidates 25] [--estimate_UV] \
-        --system_params system_params.pkl --bar_params bar_params.pkl [--device_post]
+        --system_params system_params.pkl --bar_params bar_params.pkl [--device_post] [--resample]
 
 <dir> holds one folder per piece: sheet/*.png (the page scans), score_ppq.* (the synthesised recording) and, for
 --real_perf, 01_performance*.  The pages go through the two segmentation networks (their parameter pickles:
@@ -22,7 +22,9 @@ umc_retrieval_<tag>_<dset>_A2S[_real].yaml next to the parameters.
 All pages go through each network in one call, all systems are unrolled in one call, all recordings become
 spectrograms in one call, and strips and spectrograms stay on the device for the data base and the queries
 (piece_identification.detect_scores / detect_performances).  umc_s2a_server.py is the S2A direction of this driver.
-Recordings are read by audio_frontend.load_audio: .wav or .npy at 22050 Hz.
+Recordings are read by audio_frontend.load_audio: .wav or .npy at 22050 Hz.  --resample (off by default) reads .wav
+files of any sample rate (audio_frontend.read_audio) and resamples them to 22050 Hz on the device, between the upload
+and the spectrogram launch (asr_resample_batch_dev).
 """
 import argparse
 import os
@@ -55,6 +57,8 @@ def _arguments(argv, direction):
                    help="parameters of the bar detector")
     p.add_argument("--device_post", action="store_true",
                    help="find the systems from the U-Net maps on the device too (asr_systems_from_maps_dev)")
+    p.add_argument("--resample", action="store_true",
+                   help="accept recordings at any sample rate and resample them on the device (asr_resample_batch_dev)")
     return p.parse_args(argv)
 
 
@@ -89,7 +93,8 @@ def run(argv, direction):
         else:
             print("Loading spectrograms ...")
             queried = list(range(len(te_pieces)))
-        specs = umc.load_specs([piece_paths[i] for i in queried], audio_file, processor, return_device=True)
+        specs = umc.load_specs([piece_paths[i] for i in queried], audio_file, processor, return_device=True,
+                               resample=args.resample)
         try:
             if args.init_db:
                 print("Initializing %s db ..." % ("sheet music" if direction == "A2S" else "audio"))

@@ -686,7 +686,31 @@ int asr_bars_from_map_dev(asr_ctx *ctx, const double *maps_dev, const int32_t *h
  *   out_offsets[i] of out_dev (out_floats = its size) as (n_filters, n_frames[i]) if transposed else
  *   (n_frames[i], n_filters).  Every recording's output is bit-identical with asr_spectrogram_dev on it alone: a frame
  *   is computed by the same device code, only the frame-to-recording lookup is added.  Recordings of zero samples /
- *   zero frames and n_recordings == 0 are valid and write nothing. */
+ *   zero frames and n_recordings == 0 are valid and write nothing.
+ * asr_resample_batch_dev = what madmom's SignalProcessor(sample_rate=22050) has its decoder do to a recording at
+ *   another rate, for n_recordings recordings of one input rate in one launch, between the upload and
+ *   asr_spectrogram_batch_dev.  The reference's resampler (ffmpeg's) is not restated; the yardstick is this definition,
+ *   which audio_frontend.resample_host restates in numpy and the device reproduces bit for bit (finite samples):
+ *     ratio   g = gcd(rate_in, rate_out), up = rate_out / g, down = rate_in / g (both >= 1)
+ *     taps    q = max(up, down), half = 16 * q; float64, i = 0 .. 2 * half:
+ *             h[i] = sinc((i - half) / q) * kaiser(2 * half + 1, beta 8.6)[i], scaled so that sum(h) == up
+ *             (up to rounding scipy.signal.firwin(2 * half + 1, 1 / q, window=("kaiser", 8.6)) * up)
+ *     table   taps_phase_major[p * taps_per_phase + t] = h[p + t * up], 0 past the end of h; p = 0 .. up-1,
+ *             taps_per_phase = ceil((2 * half + 1) / up)     (65 at 44.1 kHz, 70 at 48 kHz, 33 when upsampling)
+ *     output  n_out = ceil(n_in * up / down); for output m, in int64: c = m * down + half, p = c % up, j0 = c / up,
+ *             y[m] = sum over t = 0 .. taps_per_phase-1 with 0 <= j0 - t < n_in of
+ *                    taps_phase_major[p][t] * (double)x[j0 - t]
+ *             starting from 0.0, in ascending t, one rounding per product and one per sum (no fused multiply-add)
+ *             = scipy.signal.resample_poly(x, up, down, window=h / up)
+ *     result  round_int16 == 0: (float)y[m];  != 0 (integer PCM): (float)clip(rint(y[m]), -32768, 32767), rint to even
+ *   Recording i: in_counts[i] floats at float in_offsets[i] of in_dev (in_floats = size of that buffer); its
+ *   out_counts[i] outputs go to float out_offsets[i] of out_dev (out_floats = its size); floats of out_dev that belong
+ *   to no recording are left as they are.  taps_phase_major is a host array of up * taps_per_phase doubles; the copy on
+ *   the device and the per-recording tables are workspace of the context.  Before anything is launched every row is
+ *   checked against both buffer sizes and out_counts[i] against ceil(in_counts[i] * up / down), and up, down >= 1,
+ *   taps_per_phase * up >= 2 * half + 1 and the size of a tile's input span (ratios down / up up to 13 fit) are
+ *   checked: a violation returns ASR_ERR_INVALID with a message.  Recordings of zero samples and n_recordings == 0 are
+ *   valid and write nothing. */
 int asr_unroll_systems_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
                            const int32_t *heights, const int32_t *widths, int n_pages, const int32_t *systems,
                            int n_systems, int system_height, const int64_t *strip_offsets, const int32_t *strip_widths,
@@ -697,6 +721,10 @@ int asr_spectrogram_batch_dev(asr_ctx *ctx, const float *samples_dev, int64_t sa
                               const float *window, const int32_t *fb_start, const int32_t *fb_len,
                               const float *fb_weights, int n_filters, float mul, float add, int transposed,
                               float *out_dev, int64_t out_floats);
+int asr_resample_batch_dev(asr_ctx *ctx, const float *in_dev, int64_t in_floats, const int64_t *in_offsets,
+                           const int64_t *in_counts, const int64_t *out_offsets, const int64_t *out_counts,
+                           int n_recordings, int up, int down, const double *taps_phase_major, int taps_per_phase,
+                           int half, int round_int16, float *out_dev, int64_t out_floats);
 
 /* ---- device memory (plain pointers; library-owned allocations) ---------- */
 int asr_dev_alloc(asr_ctx *ctx, size_t bytes, void **dptr);
