@@ -732,7 +732,9 @@ void conv_candidates_wino4(int cin, int cout, int pool, int H, int W, std::vecto
         bp.cin = cin; bp.cout = cout; bp.pool = pool;
         bp.H = H; bp.W = W; bp.OH = pool ? H / 2 : H; bp.OW = pool ? W / 2 : W;
         bp.TH = 4; bp.TW = 64; bp.NI = 16;
-        bp.tiles_y = (H + 3) / 4; bp.tiles_x = (W + 3) / 4;
+        // pooled: only the tiles that feed a kept output (floor pooling keeps 2 OH x 2 OW of the map; the kernels clamp
+        // and mask against the real H, W as before)
+        bp.tiles_y = ((pool ? 2 * bp.OH : H) + 3) / 4; bp.tiles_x = ((pool ? 2 * bp.OW : W) + 3) / 4;
         bp.threads = 64 * v.waves;
         bp.lds_bytes = lds;
         bp.blocks_per_cu = v.spec ? 1 : std::min(nb, 4);     // specialised: one wave per SIMD (its registers need it)

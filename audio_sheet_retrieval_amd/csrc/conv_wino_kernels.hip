@@ -36,6 +36,7 @@
 #include <vector>
 #include "asr_kernels.h"
 #include "repack_elems.inl"
+#include "wino_tile_order.h"
 
 #ifndef ASR_WINOG_ABL
 #define ASR_WINOG_ABL 0      // timing experiments only (wrong results).  LDS form: 1 = no patch DMA after the first region,
@@ -668,12 +669,10 @@ struct WinoGArgs {
     const float *in, *wpk, *bnp;
     float *out;
     int N, H, W, OH, OW;
-    int ty_img, tx_img;    // winograd tiles per image (rows, columns)
     int coutp;
-    int tiles;             // winograd tiles in the launch = N * ty_img * tx_img
+    int tiles;             // winograd tiles in the launch = N * tiles per image
     int total;             // M-tiles in the launch = ceil(tiles / 16)
-    int strips;            // tile list order: strips of this many tile rows (1, 2, 4 or 8), column-major inside
-    int strip_shift;       // log2(strips)
+    WinoTileOrder ord;     // tile list order: strips of 1, 2, 4 or 8 tile rows, column-major inside (wino_tile_order.h)
     double *stats;         // RAW only, may be null: per-wave [sum | sum of squares] of the outputs, [row][2][C_out]
     BnBwdFuse bf;          // RAW + stats, bf.z != null: the sums are those of a BatchNorm backward instead (asr_kernels.h)
 };
@@ -689,6 +688,10 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void conv3x3_winog(WinoGArgs a) {
     // by one M-tile): needs ~50 more live registers - the one-wave-per-SIMD builds have them, the two-wave builds
     // (256 registers) would spill and rely on the second wave to cover memory latency instead
     constexpr bool PIPE = (MINW == 1);
+    // the two-wave builds take the first half of that pipeline: the next M-tile's addressing and first loads go out in
+    // this one's last channel block (the registers of the block prefetch are free there) and land under the epilogue;
+    // the stores stay where they are.  (Not with the remainder k-step of C_in = 12, which still needs this tile's loads.)
+    constexpr bool EARLY = !PIPE && !REM;
     static_assert(CIN % 4 == 0, "k-steps of 4 channels");
     extern __shared__ __align__(16) float w_lds[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -728,7 +731,6 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void conv3x3_winog(WinoGArgs a) {
             bscale[nt] = a.bf.cst[2 * COUT + ch]; bbeta[nt] = a.bf.cst[3 * COUT + ch];
         }
     }
-    const int per_img = a.ty_img * a.tx_img;
 
     // Which M-tiles this wave owns.  Blocks b and b + 8 share an XCD (observed placement; correctness does not depend
     // on it): every XCD walks ONE contiguous eighth of the tile list, consecutive M-tiles going to the waves of one
@@ -766,66 +768,68 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void conv3x3_winog(WinoGArgs a) {
 
     // per-tile addressing of an M-tile: the lane's 4x4 patch as clamped element offsets (always loadable), which of
     // its pixels lie inside the image, and where the tile's output goes
-    int off[4][4];
+    // (the patch as 32-bit BYTE offsets from a wave-uniform base, the image of the M-tile's first tile: every load is
+    // "scalar base + lane offset", no 64-bit vector address arithmetic per load; the launcher checks that the images an
+    // M-tile can touch fit 4 GiB)
+    unsigned off[4][4];
     unsigned okm, my_off;
     int my_flags;
-    const float *ibase;
+    const char *ibase;
     auto setup = [&](int mtile) {
         // this lane's tile: number 16*mtile + m of the batch's tile list (lanes past the end compute on clamped
         // addresses and store nothing)
-        const int tnum = mtile * 16 + m;
-        const bool tvalid = tnum < a.tiles;
-        const int tcl = min(tnum, a.tiles - 1);
-        const int img = tcl / per_img;
-        const int trest = tcl - img * per_img;
-        // a.strips = S: tiles are listed strip by strip (S tile rows), column-major inside a strip, so 16 consecutive
-        // tiles form a (16/S) x S block: S = 2 shares 6 x 18 patch pixels, S = 1 (plain row-major) 4 x 34 - and a strip
-        // re-reads only 2 of its 2S + 2 input rows from the strip above (S = 1: two of four, from another CU when a
-        // tile row is longer than a workgroup's M-tiles; conv4: 1.37 GB read per 1000 sheets at S = 1, 1.01 GB at
-        // S = 2).  A last strip with fewer rows is listed the same way with its own height.  Which S is fastest
-        // depends on the layer and the build (measured +-4 %): the tuner times S = 1 and 2 (4 and 8 never won).
+        // The list goes strip by strip (S tile rows), column-major inside a strip, so 16 consecutive tiles form a
+        // (16/S) x S block: S = 2 shares 6 x 18 patch pixels, S = 1 (plain row-major) 4 x 34 - and a strip re-reads only
+        // 2 of its 2S + 2 input rows from the strip above (S = 1: two of four, from another CU when a tile row is longer
+        // than a workgroup's M-tiles; conv4: 1.37 GB read per 1000 sheets at S = 1, 1.01 GB at S = 2).  A last strip
+        // with fewer rows is listed the same way with its own height.  Which S is fastest depends on the layer and the
+        // build (measured +-4 %): the tuner times S = 1 and 2 (4 and 8 never won).
+        // The divisions that place the M-tile's FIRST tile are wave-uniform (scalar unit); the lane walks its m tiles
+        // on from there with compares (wino_tile_order.h) - no per-lane division, no quarter-rate multiply.
+        const int tnum0 = mtile * 16;
+        const int dmax = a.tiles - 1 - tnum0;                    // >= 0: the M-tile exists
+        const bool tvalid = m <= dmax;
+        int img0, sidx0, q0;
+        wino_tile_base(a.ord, tnum0, img0, sidx0, q0);
+        unsigned ioff = 0;                                       // bytes past image img0, where this lane's tile lies
+        unsigned ooff = (unsigned)img0 * a.ord.out_img;          // (unsigned 32-bit element offsets: output buffers of up to 16 GiB)
         int tty, ttx;
-        {
-            const int S = a.strips, strip_tiles = S * a.tx_img;
-            const int sidx = trest / strip_tiles, q = trest - sidx * strip_tiles;
-            const int rows_here = min(S, a.ty_img - sidx * S);            // height of this (possibly last) strip
-            if (rows_here == S) {
-                // (q mod S without the mask S - 1: held in a VGPR across the M-tile loop the mask was spilled to scratch
-                // and reloaded - with a vmcnt(0) wait - once per M-tile; the shift count sits in an SGPR)
-                ttx = q >> a.strip_shift;
-                tty = sidx * S + (q - (ttx << a.strip_shift));
-            } else {
-                ttx = q / rows_here;
-                tty = sidx * S + (q - ttx * rows_here);
-            }
-        }
+        wino_tile_lane(a.ord, sidx0, q0 + min(m, dmax), ioff, ooff, tty, ttx);
         const int py = 2 * tty, px = 2 * ttx;                          // top-left output pixel of the tile
-        ibase = a.in + (int64_t)img * a.H * a.W * CIN;           // (+ 2g: in the element offsets below)
-        int yo[4], xo[4];
-        unsigned oy_m = 0, ox_m = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int y = py - 1 + i, x = px - 1 + i;
-            oy_m |= (unsigned)(y >= 0 && y < a.H) << i;
-            ox_m |= (unsigned)(x >= 0 && x < a.W) << i;
-            yo[i] = min(max(y, 0), a.H - 1) * a.W;
-            xo[i] = min(max(x, 0), a.W - 1);
-        }
+        ibase = reinterpret_cast<const char *>(a.in + (int64_t)img0 * a.ord.in_img);      // wave-uniform
+        // patch rows py - 1 .. py + 2 and columns px - 1 .. px + 2, clamped into the image (0 <= py < H, 0 <= px < W for
+        // every listed tile): one multiply each for row py and column px, the neighbours by adding the pitch
+        const unsigned rs = (unsigned)(a.W * CIN) * 4u;
+        const bool yt = py > 0, yb = py + 1 < a.H, yc = py + 2 < a.H;
+        const bool xl = px > 0, xr = px + 1 < a.W, xc = px + 2 < a.W;
+        unsigned yo[4], xo[4];
+        yo[1] = ioff + (unsigned)py * rs;
+        yo[0] = yt ? yo[1] - rs : yo[1];
+        yo[2] = yb ? yo[1] + rs : yo[1];
+        yo[3] = yc ? yo[1] + 2 * rs : yo[2];
+        xo[1] = (unsigned)(px * CIN + 2 * g) * 4u;               // (+ 2g: the lane group's channel pair)
+        xo[0] = xl ? xo[1] - 4u * CIN : xo[1];
+        xo[2] = xr ? xo[1] + 4u * CIN : xo[1];
+        xo[3] = xc ? xo[1] + 8u * CIN : xo[2];
+        const unsigned oy_m = (unsigned)yt | 2u | ((unsigned)yb << 2) | ((unsigned)yc << 3);
+        const unsigned ox_m = (unsigned)xl | 2u | ((unsigned)xr << 2) | ((unsigned)xc << 3);
         okm = 0;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                off[i][j] = (yo[i] + xo[j]) * CIN + 2 * g;
+                off[i][j] = yo[i] + xo[j];
                 okm |= (((oy_m >> i) & (ox_m >> j)) & 1u) << (i * 4 + j);
             }
         if (!tvalid) okm = 0;
-        // (unsigned 32-bit element offsets: output buffers of up to 16 GiB)
+        // (opaque from here on: seen through, the compiler carries the eight row / column tests across the M-tile
+        // instead of this one packed word, and the two-wave 12 -> 24 build spills 33 registers)
+        asm volatile("" : "+v"(okm));
         if (POOL) {
-            my_off = (((unsigned)img * a.OH + tty) * a.OW + ttx) * COUT;
+            my_off = ooff + (unsigned)tty * (unsigned)(a.OW * COUT) + (unsigned)ttx * COUT;
             my_flags = (tvalid && tty < a.OH && ttx < a.OW) ? 1 : 0;
         } else {
-            my_off = (((unsigned)img * a.H + py) * a.W + px) * COUT;
+            my_off = ooff + (unsigned)py * (unsigned)(a.W * COUT) + (unsigned)px * COUT;
             my_flags = tvalid ? (1 | ((px + 1 < a.W) ? 2 : 0) | ((py + 1 < a.H) ? 4 : 0)) : 0;
         }
     };
@@ -843,7 +847,8 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void conv3x3_winog(WinoGArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) drem[i][j] = ibase[off[i][j] + 8 * NB - g];       // off carries + 2g
+            for (int j = 0; j < 4; ++j)                                               // off carries + 2g
+                drem[i][j] = *reinterpret_cast<const float *>(ibase + 32 * NB + (off[i][j] - 4u * g));
     };
     setup(mt);
     load_first();
@@ -895,7 +900,7 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void conv3x3_winog(WinoGArgs a) {
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) { gst1[nt] = 0.0; gst2[nt] = 0.0; }
     for (; mt < mt_end; mt += mt_stride) {
-        const bool more = PIPE && mt + mt_stride < mt_end;             // wave-uniform
+        const bool more = (PIPE || EARLY) && mt + mt_stride < mt_end;  // wave-uniform
         const unsigned okm_cur = okm, off_cur = my_off;
         const int flags_cur = my_flags;
         // every patch of the M-tile inside its image: no border selects (wave-uniform)
@@ -929,11 +934,11 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void conv3x3_winog(WinoGArgs a) {
             }
             if (t + 1 < NB) {
                 if (!(ASR_WINOG_ABL & (2 | 256))) {
+                    const char *cb = ibase + 32 * (t + 1);             // uniform
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
 #pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            nxt[i][j] = *reinterpret_cast<const float2w *>(ibase + off[i][j] + 8 * (t + 1));
+                        for (int j = 0; j < 4; ++j) nxt[i][j] = *reinterpret_cast<const float2w *>(cb + off[i][j]);
                 }
             } else if (more && !REM) {
                 setup(mt + mt_stride);
@@ -1078,7 +1083,7 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void conv3x3_winog(WinoGArgs a) {
             have_pend = true;
         } else {
             flush();
-            if (mt + mt_stride < mt_end) {
+            if (!EARLY && mt + mt_stride < mt_end) {
                 setup(mt + mt_stride);
                 load_first();
                 if (REM) load_rem();
@@ -1329,7 +1334,9 @@ static void candidates_winog(int cin, int cout, int pool, int H, int W, std::vec
         bp.H = H; bp.W = W; bp.OH = pool ? H / 2 : H; bp.OW = pool ? W / 2 : W;
         bp.TH = 2; bp.TW = 32; bp.NI = 16;           // an M-tile: 16 consecutive tiles of the batch's tile list,
                                                      // listed in strips of TH tile rows (1 = row-major)
-        bp.tiles_y = (H + 1) / 2; bp.tiles_x = (W + 1) / 2;
+        // tiles that feed a kept output: the floor pooling drops the last row / column of an odd map, and with it the
+        // tiles that would only compute those (the kernel clamps and masks against the real H, W as before)
+        bp.tiles_y = pool ? bp.OH : (H + 1) / 2; bp.tiles_x = pool ? bp.OW : (W + 1) / 2;
         bp.threads = 64 * v.waves;
         bp.lds_bytes = lds;
         bp.blocks_per_cu = std::min(nb, 4);
@@ -1468,13 +1475,15 @@ hipError_t launch_conv_wino(hipStream_t s, const ConvPlan &p, const float *in, c
         WinoGArgs a;
         a.in = in; a.wpk = wpk; a.bnp = bnp; a.out = out;
         a.N = N; a.H = p.H; a.W = p.W; a.OH = p.OH; a.OW = p.OW;
-        a.ty_img = p.tiles_y; a.tx_img = p.tiles_x;
         a.coutp = (p.cout + 15) / 16 * 16;
-        a.tiles = N * a.ty_img * a.tx_img;
+        a.tiles = N * p.tiles_y * p.tiles_x;
         a.total = (a.tiles + 15) / 16;
-        a.strips = (p.TH == 1 || p.TH == 4 || p.TH == 8) ? p.TH : 2;
-        a.strip_shift = a.strips == 8 ? 3 : a.strips == 4 ? 2 : a.strips == 2 ? 1 : 0;
         if (a.total == 0) return hipSuccess;
+        // strips of p.TH tile rows; the reciprocals of the kernel's tile decode depend on the plan's geometry alone
+        const int strips = (p.TH == 1 || p.TH == 4 || p.TH == 8) ? p.TH : 2;
+        if (!wino_tile_order_make(&a.ord, p.tiles_y, p.tiles_x, strips, (int64_t)p.H * p.W * p.cin,
+                                  (unsigned)p.OH * (unsigned)p.OW * (unsigned)p.cout))
+            return hipErrorInvalidValue;
         const int waves = p.threads / 64;
         const int ngroups = (a.coutp / 16 + v.nt - 1) / v.nt;
         const int slots = std::max(1, num_cus * std::max(1, p.blocks_per_cu) / ngroups);
