@@ -68,6 +68,7 @@ struct ConvPlan {           // chosen on the host per layer geometry
     int variant;            // index into the instantiation table
     const char *symbol;     // kernel symbol as rocprofv3 prints it
     int c4p, rp;            // Winograd schedule: LDS patch layout (chunks per pixel / per row)
+    int epi;                // conv3x3_wino4s: rows-full M-tiles take the branch-free epilogue (ASR_WINO4_EPI)
 };
 // Returns false when no instantiation exists for (cin, cout, pool).
 // raw = 1: plain convolution output (no BN/ELU/pool) - train-mode forward and data gradients

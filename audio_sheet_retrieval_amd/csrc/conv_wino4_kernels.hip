@@ -27,6 +27,7 @@
 #include <vector>
 #include "asr_kernels.h"
 #include "repack_elems.inl"
+#include "wino4_epilogue.h"
 
 #ifndef ASR_WINO4_ABL
 #define ASR_WINO4_ABL 0      // timing experiments only (wrong results): 2 = no input loads after the first block;
@@ -49,9 +50,26 @@ struct Wino4Args {
     int total;             // M-tiles in the launch = ceil(tiles / 16)
     double *stats;         // RAW builds of conv3x3_wino4s, may be null: per-workgroup [sum | sum of squares] of the outputs
     BnBwdFuse bf;          // RAW + stats, bf.z != null: the sums are those of a BatchNorm backward instead (asr_kernels.h)
+    int epi;               // conv3x3_wino4s, non-RAW: 1 = rows-full M-tiles take the branch-free epilogue (ASR_WINO4_EPI;
+                           // last, so that the other builds read their arguments where they did)
 };
 
 __device__ __forceinline__ float elu_fastq(float y) { return y > 0.0f ? y : __expf(y) - 1.0f; }
+
+// BN + ELU of a lane's four tiles at once: the scalar expression of the guarded epilogue per component (a subtract and
+// one fma once contracted), so both epilogues give the same bits
+__device__ __forceinline__ floatx4q bn_elu4q(floatx4q x, float mean, float scale, float beta) {
+    const floatx4q y = (x - floatx4q{mean, mean, mean, mean}) * floatx4q{scale, scale, scale, scale} +
+                       floatx4q{beta, beta, beta, beta};
+    return floatx4q{elu_fastq(y[0]), elu_fastq(y[1]), elu_fastq(y[2]), elu_fastq(y[3])};
+}
+typedef int int4q __attribute__((ext_vector_type(4)));
+// one dword through a raw buffer descriptor: address = base + soff (scalar) + voff (lane); the range check compares voff
+// alone with num_records and drops the store when it is not below.  Inline assembly for the reason given at
+// conv3x3_wino's LDS-DMA: with the buffer builtins inside a function template the host pass emits no kernel stub.
+__device__ __forceinline__ void buffer_store_q(float v, unsigned voff, int4q rsrc, unsigned soff) {
+    asm volatile("buffer_store_dword %0, %1, %2, %3 offen" ::"v"(v), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
+}
 
 template <typename T> __device__ __forceinline__ T splatq(float c);
 template <> __device__ __forceinline__ float2q splatq<float2q>(float c) { return float2q{c, c}; }
@@ -452,6 +470,16 @@ __global__ __launch_bounds__(64 * (PW + (SLICE + 15) / 16), 1) void conv3x3_wino
         bscale = a.bf.cst[2 * COUT + chn]; bbeta = a.bf.cst[3 * COUT + chn];
     }
     double st1 = 0.0, st2 = 0.0;                              // RAW + a.stats: sums of this lane's channel
+    // the output tensor as a raw buffer (stride 0) for the branch-free epilogue; the launcher sets a.epi only when
+    // num_records is below the sentinel offset
+    int4q orsrc;
+    {
+        const uint64_t obase = reinterpret_cast<uint64_t>(a.out);
+        orsrc.x = (int)(uint32_t)obase;
+        orsrc.y = (int)(uint32_t)(obase >> 32);
+        orsrc.z = (int)((unsigned)a.N * a.OH * a.OW * COUT * 4u);         // (unsigned: launches that are not admitted wrap, and do not use it)
+        orsrc.w = 0x00020000;
+    }
     // B operands of a channel block: 18 float4 per lane (row = k-step parity * 36 + position, four rows per float4; see
     // wino4_pack_kernel), at [block][row / 4][g][coutp][4] - a uniform block pointer (scalar arithmetic) + this lane's
     // 32-bit byte offset + a compile-time row-group offset
@@ -477,15 +505,17 @@ __global__ __launch_bounds__(64 * (PW + (SLICE + 15) / 16), 1) void conv3x3_wino
             int img, tty, ttx;
             bool tvalid;
             tile_of(mt, img, tty, ttx, tvalid);
-            if (POOL) {
-                my_off = (((unsigned)img * a.OH + 2 * tty) * a.OW + 2 * ttx) * COUT;
-                const int nr = min(2, a.OH - 2 * tty), nc = min(2, a.OW - 2 * ttx);
-                my_ext = (tvalid && nr > 0 && nc > 0) ? (nr | (nc << 8)) : 0;
-            } else {
-                my_off = (((unsigned)img * a.H + 4 * tty) * a.W + 4 * ttx) * COUT;
-                const int nr = min(4, a.H - 4 * tty), nc = min(4, a.W - 4 * ttx);
-                my_ext = tvalid ? (nr | (nc << 8)) : 0;
-            }
+            if (POOL) my_off = (((unsigned)img * a.OH + 2 * tty) * a.OW + 2 * ttx) * COUT;
+            else my_off = (((unsigned)img * a.H + 4 * tty) * a.W + 4 * ttx) * COUT;
+            my_ext = wino4_extent(POOL, POOL ? a.OH : a.H, POOL ? a.OW : a.W, tty, ttx, tvalid);
+        }
+        // which epilogue (wino4_epilogue.h; wave-uniform): 1 = rows-full M-tile - every tile has all its output rows or
+        // nothing to store; 2 = any other M-tile of an un-pooled build - branch-free as well, one select per store;
+        // 0 = the guarded one
+        int epi_mode = 0;
+        if constexpr (!RAW) {
+            if (a.epi)
+                epi_mode = __builtin_amdgcn_ballot_w64(!wino4_rows_full(my_ext, POOL)) == 0 ? 1 : (wino4_general_form(POOL) ? 2 : 0);
         }
         // byte offsets of this lane in row groups 0, 2, 4 ... 16 of a channel block (the odd ones are an immediate
         // offset away); opaque, so that the weight loads - which do not depend on the M-tile - are neither hoisted out
@@ -589,6 +619,54 @@ __global__ __launch_bounds__(64 * (PW + (SLICE + 15) / 16), 1) void conv3x3_wino
         for (int nu = 0; nu < 6; ++nu)
             out6(acc[nu], acc[6 + nu], acc[12 + nu], acc[18 + nu], acc[24 + nu], acc[30 + nu], tc[0][nu], tc[1][nu], tc[2][nu],
                  tc[3][nu]);
+        // branch-free: the columns a tile lacks carry the sentinel offset and the buffer's range check drops them; the
+        // row is a scalar offset.  ROWS: the tile's row count is folded in as well, by a select between the offset
+        // and the sentinel.  Same values in the same order as the guarded code below.
+        auto fast_epilogue = [&](auto rows_c) {
+            constexpr bool ROWS = decltype(rows_c)::value;
+            constexpr int SP = POOL ? 2 : 4;
+            unsigned vo[4][SP];
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int c = 0; c < SP; ++c) vo[r][c] = wino4_store_offset(eo[r], ee[r], chn, c, COUT);
+#pragma unroll
+            for (int i = 0; i < SP; ++i) {
+                const unsigned soff = wino4_row_bytes(i, a.OW, COUT);
+                floatx4q res[SP];
+                if constexpr (POOL) {
+                    floatx4q ya[4], yb[4];
+                    out6(tc[2 * i][0], tc[2 * i][1], tc[2 * i][2], tc[2 * i][3], tc[2 * i][4], tc[2 * i][5], ya[0], ya[1], ya[2],
+                         ya[3]);
+                    out6(tc[2 * i + 1][0], tc[2 * i + 1][1], tc[2 * i + 1][2], tc[2 * i + 1][3], tc[2 * i + 1][4],
+                         tc[2 * i + 1][5], yb[0], yb[1], yb[2], yb[3]);
+#pragma unroll
+                    for (int pc = 0; pc < 2; ++pc) {
+                        const floatx4q hi = __builtin_elementwise_max(__builtin_elementwise_max(ya[2 * pc], ya[2 * pc + 1]),
+                                                                      __builtin_elementwise_max(yb[2 * pc], yb[2 * pc + 1]));
+                        const floatx4q lo = __builtin_elementwise_min(__builtin_elementwise_min(ya[2 * pc], ya[2 * pc + 1]),
+                                                                      __builtin_elementwise_min(yb[2 * pc], yb[2 * pc + 1]));
+                        res[pc] = bn_elu4q(bscale >= 0.0f ? hi : lo, bmean, bscale, bbeta);
+                    }
+                } else {
+                    floatx4q y[4];
+                    out6(tc[i][0], tc[i][1], tc[i][2], tc[i][3], tc[i][4], tc[i][5], y[0], y[1], y[2], y[3]);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) res[j] = bn_elu4q(y[j], bmean, bscale, bbeta);
+                }
+#pragma unroll
+                for (int j = 0; j < SP; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        if (ASR_WINO4_ABL & 32) asm volatile("" ::"v"(res[j][r]));
+                        else buffer_store_q(res[j][r], ROWS ? wino4_store_offset_row(vo[r][j], ee[r], i) : vo[r][j], orsrc, soff);
+                    }
+            }
+        };
+        if (epi_mode == 1) { fast_epilogue(std::false_type{}); continue; }
+        if constexpr (!RAW && wino4_general_form(POOL)) {
+            if (epi_mode == 2) { fast_epilogue(std::true_type{}); continue; }
+        }
         if (POOL) {
 #pragma unroll
             for (int pr = 0; pr < 2; ++pr) {                 // pooled row: output rows 2pr, 2pr+1 of the tile
@@ -715,6 +793,9 @@ void conv_candidates_wino4(int cin, int cout, int pool, int H, int W, std::vecto
     // with ASR_CONV_WINO4=1; ASR_CONV_WINO4=0 removes both
     static const int use = getenv("ASR_CONV_WINO4") ? atoi(getenv("ASR_CONV_WINO4")) : -1;
     if (use == 0) return;
+    // ASR_WINO4_EPI=0: the guarded epilogue on every M-tile (A/B, tests).  Read whenever an engine lists its candidates,
+    // not once per process: tests/test_gpu_wino4_epilogue.py sets two engines of one process side by side.
+    const int epi = getenv("ASR_WINO4_EPI") ? (atoi(getenv("ASR_WINO4_EPI")) != 0) : 1;
     for (int vi = 0; vi < g_num_wino4; ++vi) {
         const Wino4Variant &v = g_wino4[vi];
         if (v.cin != cin || v.cout != cout || v.pool != pool || v.raw) continue;
@@ -742,6 +823,7 @@ void conv_candidates_wino4(int cin, int cout, int pool, int H, int W, std::vecto
                   (v.spec ? 0.4 : 1.0);
         bp.variant = 4000 + vi;
         bp.symbol = v.symbol;
+        bp.epi = v.spec ? epi : 0;
         out->push_back(bp);
     }
 }
@@ -789,6 +871,8 @@ hipError_t launch_conv_wino4(hipStream_t s, const ConvPlan &p, const float *in, 
                              const BnBwdFuse *bf) {
     const Wino4Variant &v = g_wino4[p.variant - 4000];
     Wino4Args a;
+    // the branch-free epilogue needs every byte offset of the output below its sentinel (p.epi: ASR_WINO4_EPI)
+    a.epi = (p.epi && v.spec && !v.raw && wino4_fast_epilogue_admitted(N, p.OH, p.OW, p.cout)) ? 1 : 0;
     a.stats = nullptr;
     a.bf = BnBwdFuse{nullptr, nullptr, nullptr};
     a.in = in; a.wpk = wpk; a.bnp = bnp; a.out = out;
