@@ -33,10 +33,19 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 #include "asr_kernels.h"
 #include "repack_elems.inl"
 #include "wino_tile_order.h"
+#include "wino_weight_layout.h"
+
+// conv3x3_winog, per-item A/B switches of round 19 (results are the same bits either way; ASR_WINOG_DENSEW, the dense
+// weight layout of the NT = 2 builds, lives in wino_weight_layout.h)
+#ifndef ASR_WINOG_NOCOPY
+#define ASR_WINOG_NOCOPY 1   // 1: the column pass of the input transform reads the loaded patch where it landed and the
+                             // next loads go out behind it; 0: copy the patch first, loads before the transform
+#endif
 
 #ifndef ASR_WINOG_ABL
 #define ASR_WINOG_ABL 0      // timing experiments only (wrong results).  LDS form: 1 = no patch DMA after the first region,
@@ -680,7 +689,11 @@ struct WinoGArgs {
 template <int CIN, int COUT, bool POOL, int NT, int WAVES, int MINW, bool RAW>
 __global__ __launch_bounds__(64 * WAVES, MINW) void conv3x3_winog(WinoGArgs a) {
     constexpr int KS = CIN / 4, NB = CIN / 8, WROW = NT * 16, T = 64 * WAVES;
-    constexpr int WS = NT == 2 ? 48 : WROW;      // LDS row stride: 32 would put lane groups g and g+1 on the same banks
+    // weights in LDS (wino_weight_layout.h): NT = 2 with C_in % 8 == 0 dense, [k-step][position][g][n][nt] - one 64-bit
+    // read per lane and (k-step, position), every operand of a channel block within the read's 16-bit offset of one
+    // base register; the others row-major
+    constexpr bool DENSE = wino_w_dense(CIN, NT);
+    constexpr int KF = wino_w_kstep_floats(CIN, NT);      // floats per k-step
     constexpr int WD = 4 * NT;                   // B operands in flight ahead of the MFMA that uses them (4 positions)
     constexpr int WQ = 32 * NT;                  // B operands per channel block (2 k-steps x 16 positions x NT)
     constexpr bool REM = (CIN % 8) != 0;         // one more k-step on the last 4 channels (C_in = 12)
@@ -698,19 +711,48 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void conv3x3_winog(WinoGArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // NT n-tiles of this workgroup's group (blockIdx.y; one group unless the weights of all n-tiles exceed the LDS)
     const int ng = blockIdx.y;
-    for (int i = tid; i < 16 * CIN * WROW / 4; i += T) {
-        const int row = i / (WROW / 4), q = i - row * (WROW / 4);
-        const int col = ng * WROW + q * 4;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (col < a.coutp) v = *reinterpret_cast<const float4 *>(a.wpk + (size_t)row * a.coutp + col);
-        reinterpret_cast<float4 *>(w_lds + row * WS)[q] = v;
+    if constexpr (DENSE) {
+#pragma unroll 1
+        for (int i = tid; i < 16 * CIN * 4; i += T) {      // four columns n of a row, in each of the NT n-tiles
+            const int row = i >> 2, n4 = (i & 3) * 4;
+            float v[NT][4];
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                const int col = ng * WROW + nt * 16 + n4;
+                float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (col < a.coutp) x = *reinterpret_cast<const float4 *>(a.wpk + (size_t)row * a.coutp + col);
+                v[nt][0] = x.x; v[nt][1] = x.y; v[nt][2] = x.z; v[nt][3] = x.w;
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e)                    // NT contiguous floats per column: 4 NT in all
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) w_lds[wino_w_stage_off(CIN, NT, row, nt * 16 + n4 + e)] = v[nt][e];
+        }
+    } else {
+        for (int i = tid; i < 16 * CIN * WROW / 4; i += T) {
+            const int row = i / (WROW / 4), q = i - row * (WROW / 4);
+            const int col = ng * WROW + q * 4;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (col < a.coutp) v = *reinterpret_cast<const float4 *>(a.wpk + (size_t)row * a.coutp + col);
+            *reinterpret_cast<float4 *>(w_lds + wino_w_stage_off(CIN, NT, row, q * 4)) = v;
+        }
     }
     __syncthreads();
 
     const int m = lane & 15, g = lane >> 4, n = lane & 15;
-    const float *w_lane = w_lds + g * WS + n;
+    const float *w_lane = w_lds + wino_w_lane_off(CIN, NT, g, n);
     // B operand q of a channel block: k-step q / (16 NT), position (q / NT) % 16, n-tile q % NT
-    auto wq_off = [](int q) { return ((q / (16 * NT)) * 16 + (q / NT) % 16) * 4 * WS + (q % NT) * 16; };
+    auto wq_off = [](int q) { return wino_w_q_off(CIN, NT, q); };
+    // the NT operands of one (k-step, position), q a multiple of NT
+    auto wread = [&](float *dst, const float *base, int q) {
+        if constexpr (DENSE) {
+            const float2w v = *reinterpret_cast<const float2w *>(base + wq_off(q));
+            dst[0] = v[0]; dst[1] = v[1];
+        } else {
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) dst[nt] = base[wq_off(q + nt)];
+        }
+    };
     float bmean[NT], bscale[NT], bbeta[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
@@ -857,7 +899,7 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void conv3x3_winog(WinoGArgs a) {
     // the 4-bit lgkmcnt cannot express "the older half of 96 reads")
     float wpre[WD];
 #pragma unroll
-    for (int q = 0; q < WD; ++q) wpre[q] = w_lane[wq_off(q)];
+    for (int q = 0; q < WD; q += NT) wread(wpre + q, w_lane, q);
 
     // Stores are DEFERRED by one M-tile.  vmcnt counts loads and stores together, in issue order, and the number of
     // store instructions an epilogue issues is not static (edge tiles), so the compiler can only wait for "everything"
@@ -911,9 +953,56 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void conv3x3_winog(WinoGArgs a) {
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) acc[p][nt] = floatx4w{0.f, 0.f, 0.f, 0.f};
 
-#pragma unroll 1
-        for (int t = 0; t < NB; ++t) {
+        // one channel block (8 channels = two k-steps)
+        auto block = [&](const int t) {
             float2w dp[4][4];
+            // the next block's patch - or, in the last block, the next M-tile's addressing and first loads
+            auto load_next = [&]() {
+                if (t + 1 < NB) {
+                    if (!(ASR_WINOG_ABL & (2 | 256))) {
+                        const char *cb = ibase + 32 * (t + 1);             // uniform
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) nxt[i][j] = *reinterpret_cast<const float2w *>(cb + off[i][j]);
+                    }
+                } else if (more && !REM) {
+                    setup(mt + mt_stride);
+                    load_first();
+                }
+            };
+#if ASR_WINOG_NOCOPY
+            // The column pass reads the patch where the loads put it (border M-tiles: the selected values) and the
+            // next loads into the same registers go out behind it, 16 packed adds later than they could: copying
+            // the patch aside first, only to free `nxt` that much earlier, was 16 v_mov_b64 per block.
+            auto columns = [&](auto sel) {                 // B^T d
+                // (a real branch on the wave-uniform `interior`: merged into one body, every block of every M-tile
+                // pays the 32 selects of the border form)
+                asm volatile("");
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float2w d[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        d[i] = (!decltype(sel)::value || ((okm_cur >> (i * 4 + j)) & 1u)) ? nxt[i][j] : float2w{0.f, 0.f};
+                    if (ASR_WINOG_ABL & 8) {
+                        dp[0][j] = d[0]; dp[1][j] = d[1]; dp[2][j] = d[2]; dp[3][j] = d[3];
+                    } else {
+                        dp[0][j] = psub(d[0], d[2]); dp[1][j] = padd(d[1], d[2]);
+                        dp[2][j] = psub(d[2], d[1]); dp[3][j] = psub(d[1], d[3]);
+                    }
+                }
+            };
+            if (interior) columns(std::false_type{});
+            else columns(std::true_type{});
+            if (t == 0 && have_pend) {
+                // block 0's loads have landed, nothing else is outstanding - the previous M-tile's stores go out now
+                // and retire under this block's MFMAs
+                asm volatile("" ::"v"(dp[3][3]));
+                flush();
+            }
+            load_next();
+#else
             if (interior) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
@@ -932,33 +1021,25 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void conv3x3_winog(WinoGArgs a) {
                 asm volatile("" ::"v"(dp[3][3]));
                 flush();
             }
-            if (t + 1 < NB) {
-                if (!(ASR_WINOG_ABL & (2 | 256))) {
-                    const char *cb = ibase + 32 * (t + 1);             // uniform
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) nxt[i][j] = *reinterpret_cast<const float2w *>(cb + off[i][j]);
-                }
-            } else if (more && !REM) {
-                setup(mt + mt_stride);
-                load_first();
-            }
+            load_next();
             if (!(ASR_WINOG_ABL & 8)) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {              // columns: B^T d
                 const float2w d0 = dp[0][j], d1 = dp[1][j], d2 = dp[2][j], d3 = dp[3][j];
                 dp[0][j] = psub(d0, d2); dp[1][j] = padd(d1, d2); dp[2][j] = psub(d2, d1); dp[3][j] = psub(d1, d3);
             }
+            }
+#endif
+            if (!(ASR_WINOG_ABL & 8)) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {              // rows: (B^T d) B
                 const float2w t0 = dp[i][0], t1 = dp[i][1], t2 = dp[i][2], t3 = dp[i][3];
                 dp[i][0] = psub(t0, t2); dp[i][1] = padd(t1, t2); dp[i][2] = psub(t2, t1); dp[i][3] = psub(t1, t3);
             }
             }
-            const float *wk = w_lane + (2 * t) * (16 * 4 * WS);
+            const float *wk = w_lane + (2 * t) * KF;
             // next block; after the last one the remainder k-step's rows (or any valid rows)
-            const float *wn = (t + 1 < NB || REM) ? wk + 2 * 16 * 4 * WS : w_lane;
+            const float *wn = (t + 1 < NB || REM) ? wk + 2 * KF : w_lane;
             float wv[WQ + WD];
 #pragma unroll
             for (int q = 0; q < WD; ++q) wv[q] = wpre[q];
@@ -966,9 +1047,15 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void conv3x3_winog(WinoGArgs a) {
             for (int q0 = 0; q0 < WQ; q0 += NT) {
                 // the operands WD steps ahead - inside this block, or the first ones of the next block - are issued
                 // before this position's MFMAs; the scheduling barriers keep the compiler from sinking them again
+                // (and from pairing the dense form's 64-bit reads into ds_read2_b64, whose offsets are short again)
+                if (ASR_WINOG_ABL & 4) {
 #pragma unroll
-                for (int q = q0; q < q0 + NT; ++q)
-                    wv[q + WD] = (ASR_WINOG_ABL & 4) ? wv[q] : (q + WD < WQ) ? wk[wq_off(q + WD)] : wn[wq_off(q + WD - WQ)];
+                    for (int q = q0; q < q0 + NT; ++q) wv[q + WD] = wv[q];
+                } else if (q0 + WD < WQ) {
+                    wread(wv + q0 + WD, wk, q0 + WD);
+                } else {
+                    wread(wv + q0 + WD, wn, q0 + WD - WQ);
+                }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int q = q0; q < q0 + NT; ++q) {
@@ -979,7 +1066,9 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void conv3x3_winog(WinoGArgs a) {
             }
 #pragma unroll
             for (int q = 0; q < WD; ++q) wpre[q] = wv[WQ + q];
-        }
+        };
+#pragma unroll 1
+        for (int t = 0; t < NB; ++t) block(t);
         if (REM) {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
@@ -1006,15 +1095,15 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void conv3x3_winog(WinoGArgs a) {
                 load_first();
                 load_rem();
             }
-            const float *wk = w_lane + (2 * NB) * (16 * 4 * WS);
+            const float *wk = w_lane + (2 * NB) * KF;
             constexpr int WQR = 16 * NT;
             float wv[WQR + WD];
 #pragma unroll
             for (int q = 0; q < WD; ++q) wv[q] = wpre[q];
 #pragma unroll
             for (int q0 = 0; q0 < WQR; q0 += NT) {
-#pragma unroll
-                for (int q = q0; q < q0 + NT; ++q) wv[q + WD] = (q + WD < WQR) ? wk[wq_off(q + WD)] : w_lane[wq_off(q + WD - WQR)];
+                if (q0 + WD < WQR) wread(wv + q0 + WD, wk, q0 + WD);
+                else wread(wv + q0 + WD, w_lane, q0 + WD - WQR);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int q = q0; q < q0 + NT; ++q) {
@@ -1319,7 +1408,7 @@ static void candidates_winog(int cin, int cout, int pool, int H, int W, std::vec
     for (int vi = 0; vi < g_num_winog; ++vi) {
         const WinoGVariant &v = g_winog[vi];
         if (v.cin != cin || v.cout != cout || v.pool != pool || v.raw != raw) continue;
-        const int lds = 16 * cin * (v.nt == 2 ? 48 : v.nt * 16) * 4;
+        const int lds = wino_w_lds_floats(cin, v.nt) * 4;
         if (lds > 160 * 1024) continue;
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(v.kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   160 * 1024);
