@@ -42,7 +42,7 @@ EXPORTS = [
     "asr_rank_sharded_dev", "asr_slice_windows_dev", "asr_piece_vote_dev", "asr_piece_vote_batch_dev", "asr_track_gate_dev", "asr_track_vote_batch_dev", "asr_gather_windows_dev", "asr_dtw_dev", "asr_dtw_batch_dev", "asr_spectrogram_dev", "asr_debug_tune_report",
     "asr_seg_create", "asr_seg_set_window", "asr_seg_destroy", "asr_seg_predict_dev", "asr_systems_from_maps_dev",
     "asr_notes_from_map_dev", "asr_bars_from_map_dev",
-    "asr_unroll_systems_dev", "asr_spectrogram_batch_dev", "asr_resample_batch_dev",
+    "asr_unroll_systems_dev", "asr_spectrogram_batch_dev", "asr_resample_batch_dev", "asr_resize_pages_dev",
     "asr_opt_state_size", "asr_get_opt_state", "asr_set_opt_state", "asr_debug_train_tensor", "asr_cca_train_debug",
 ]
 
@@ -216,6 +216,8 @@ def load_library(path=None):
                                               c_float, c_int, c_void_p, c_int64]),
         "asr_resample_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                            c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int64]),
+        "asr_resize_pages_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_int64]),
         "asr_debug_tune_report": (c_int, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_float)]),
         "asr_comm_unique_id": (c_int, [c_void_p]),
         "asr_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),
@@ -629,6 +631,23 @@ class Engine(object):
             self.ctx, in_ptr, int(in_floats), in_offsets.ctypes.data, in_counts.ctypes.data, out_offsets.ctypes.data,
             out_counts.ctypes.data, n, int(up), int(down), taps.ctypes.data, taps.shape[1], int(half),
             1 if round_int16 else 0, out_ptr, int(out_floats)))
+
+    def resize_pages_dev(self, pages_ptr, pages_bytes, page_offsets, heights, widths, out_offsets, out_heights,
+                         out_widths, out_ptr, out_bytes):
+        """uint8 pages of any sizes resampled to out_heights x out_widths in one launch (asr_resize_pages_dev): page i is
+        heights[i] x widths[i] bytes at byte page_offsets[i] of the buffer at pages_ptr, its result goes to byte
+        out_offsets[i] of the buffer at out_ptr in the same layout.  Exact integer area resampling: byte for byte
+        sheet_utils.omr.resize_page_host per page"""
+        i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        page_offsets, out_offsets = i64(page_offsets), i64(out_offsets)
+        heights, widths, out_heights, out_widths = map(i32, (heights, widths, out_heights, out_widths))
+        n = heights.size
+        if not (page_offsets.size == widths.size == out_offsets.size == out_heights.size == out_widths.size == n):
+            raise ValueError("resize_pages_dev: the per-page tables differ in length")
+        self._check(self.lib.asr_resize_pages_dev(
+            self.ctx, pages_ptr, int(pages_bytes), page_offsets.ctypes.data, heights.ctypes.data, widths.ctypes.data, n,
+            out_offsets.ctypes.data, out_heights.ctypes.data, out_widths.ctypes.data, out_ptr, int(out_bytes)))
 
     def unroll_systems_dev(self, pages_ptr, pages_bytes, page_offsets, heights, widths, systems, system_height,
                            strip_offsets, strip_widths, strips_ptr, strips_floats):

@@ -1,6 +1,7 @@
-// C-ABI layer of the UMC drivers' device stages: asr_unroll_systems_dev (page scans -> unrolled strips),
-// asr_resample_batch_dev (recordings at any rate -> recordings at the front-end's rate) and asr_spectrogram_batch_dev
-// (recordings -> spectrograms); include/asr_hip.h for the contract.  Kernels: umc_kernels.hip, resample_kernels.hip,
+// C-ABI layer of the UMC drivers' device stages: asr_resize_pages_dev (page scans of any resolution -> pages of the
+// networks' width), asr_unroll_systems_dev (page scans -> unrolled strips), asr_resample_batch_dev (recordings at any
+// rate -> recordings at the front-end's rate) and asr_spectrogram_batch_dev (recordings -> spectrograms);
+// include/asr_hip.h for the contract.  Kernels: page_resize_kernels.hip, umc_kernels.hip, resample_kernels.hip,
 // piece_vote_kernels.hip (spectrogram_batch_kernel).  Every call checks every offset against the buffer sizes the
 // caller states before anything is launched, and returns after the work is done.
 #include "asr_ctx.h"
@@ -220,5 +221,75 @@ int asr_resample_batch_dev(asr_ctx *ctx, const float *in_dev, int64_t in_floats,
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "resample_batch: %s", hipGetErrorString(e));
+    return mark_main(ctx);
+}
+
+int asr_resize_pages_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
+                         const int32_t *heights, const int32_t *widths, int n_pages, const int64_t *out_offsets,
+                         const int32_t *out_heights, const int32_t *out_widths, void *out_dev, int64_t out_bytes) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_pages < 0 || pages_bytes < 0 || out_bytes < 0) return fail(ctx, ASR_ERR_INVALID, "resize_pages: bad sizes");
+    if (n_pages == 0) return ASR_OK;
+    if (!page_offsets || !heights || !widths || !out_offsets || !out_heights || !out_widths)
+        return fail(ctx, ASR_ERR_INVALID, "resize_pages: NULL argument");
+    const size_t b_first = ((size_t)n_pages + 1) * sizeof(int64_t);
+    std::vector<char> tab(b_first + (size_t)n_pages * sizeof(asr::ResizePage));   // tile_first (n + 1) | page table
+    int64_t *first = (int64_t *)tab.data();
+    asr::ResizePage *table = (asr::ResizePage *)(tab.data() + b_first);
+    int64_t tiles = 0;
+    double bytes = 0.0;
+    for (int p = 0; p < n_pages; ++p) {
+        const int64_t h = heights[p], w = widths[p], ho = out_heights[p], wo = out_widths[p];
+        if (h < 1 || w < 1 || ho < 1 || wo < 1)
+            return fail(ctx, ASR_ERR_INVALID, "resize_pages: page %d: %lld x %lld -> %lld x %lld (every dimension must be at "
+                        "least 1)", p, (long long)h, (long long)w, (long long)ho, (long long)wo);
+        if (h > asr::RESIZE_MAX_DIM || w > asr::RESIZE_MAX_DIM || ho > asr::RESIZE_MAX_DIM || wo > asr::RESIZE_MAX_DIM ||
+            h * w > 0x7fffffffLL)
+            return fail(ctx, ASR_ERR_INVALID, "resize_pages: page %d: %lld x %lld -> %lld x %lld (a dimension above %d, or "
+                        "2^31 source pixels and more)", p, (long long)h, (long long)w, (long long)ho, (long long)wo,
+                        asr::RESIZE_MAX_DIM);
+        if (h > asr::RESIZE_MAX_DOWN * ho || w > asr::RESIZE_MAX_DOWN * wo || ho > asr::RESIZE_MAX_UP * h ||
+            wo > asr::RESIZE_MAX_UP * w)
+            return fail(ctx, ASR_ERR_INVALID, "resize_pages: page %d: %lld x %lld -> %lld x %lld: the ratio in / out per axis "
+                        "must lie in [1/%d, %d]", p, (long long)h, (long long)w, (long long)ho, (long long)wo,
+                        asr::RESIZE_MAX_UP, asr::RESIZE_MAX_DOWN);
+        if (page_offsets[p] < 0 || h * w > pages_bytes || page_offsets[p] > pages_bytes - h * w)
+            return fail(ctx, ASR_ERR_INVALID, "resize_pages: page %d (%lld x %lld at %lld) outside the %lld-byte buffer", p,
+                        (long long)h, (long long)w, (long long)page_offsets[p], (long long)pages_bytes);
+        if (out_offsets[p] < 0 || ho * wo > out_bytes || out_offsets[p] > out_bytes - ho * wo)
+            return fail(ctx, ASR_ERR_INVALID, "resize_pages: output %d (%lld x %lld at %lld) outside the %lld-byte buffer", p,
+                        (long long)ho, (long long)wo, (long long)out_offsets[p], (long long)out_bytes);
+        asr::ResizePage &r = table[p];
+        r.src = page_offsets[p];
+        r.dst = out_offsets[p];
+        r.h_in = (int32_t)h; r.w_in = (int32_t)w; r.h_out = (int32_t)ho; r.w_out = (int32_t)wo;
+        r.tiles_x = (int32_t)((wo + asr::RESIZE_TILE_W - 1) / asr::RESIZE_TILE_W);
+        r.pad = 0;
+        first[p] = tiles;
+        tiles += (int64_t)r.tiles_x * ((ho + asr::RESIZE_TILE_H - 1) / asr::RESIZE_TILE_H);
+        bytes += (double)(h * w + ho * wo);
+    }
+    first[n_pages] = tiles;
+    if (tiles > 0x7fffffffLL) return fail(ctx, ASR_ERR_INVALID, "resize_pages: %lld tiles in one call", (long long)tiles);
+    if (!pages_dev || !out_dev) return fail(ctx, ASR_ERR_INVALID, "resize_pages: NULL argument");
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    int rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    if (tab.size() > ctx->resize_ws_bytes) {
+        ASR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->resize_ws) ASR_HIP(ctx, hipFree(ctx->resize_ws));
+        ctx->resize_ws = nullptr; ctx->resize_ws_bytes = 0;
+        ASR_HIP(ctx, hipMalloc(&ctx->resize_ws, tab.size()));
+        ctx->resize_ws_bytes = tab.size();
+    }
+    hipError_t e = hipMemcpyAsync(ctx->resize_ws, tab.data(), tab.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        ProfScope ps(ctx, "resize_pages", 0, 0.0, bytes);
+        e = asr::launch_resize_pages(ctx->stream, (const uint8_t *)pages_dev, (uint8_t *)out_dev,
+                                     (const int64_t *)ctx->resize_ws,
+                                     (const asr::ResizePage *)((const char *)ctx->resize_ws + b_first), n_pages, tiles);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "resize_pages: %s", hipGetErrorString(e));
     return mark_main(ctx);
 }

@@ -265,6 +265,8 @@ struct asr_ctx {
     size_t post_ws_bytes = 0;
     void *resample_ws = nullptr;              // asr_resample_batch_dev: per-recording tables + phase-major taps
     size_t resample_ws_bytes = 0;
+    void *resize_ws = nullptr;                // asr_resize_pages_dev: running tile counts + page table
+    size_t resize_ws_bytes = 0;
     unsigned *topk_tickets = nullptr;         // 1024 last-arriver counters of the top-k call (zero between calls)
     float *unit_ws = nullptr;                 // asr_topk_dev on a large pool: unit-length copy + reciprocal norms of the
     size_t unit_ws_floats = 0;                // pool, rebuilt per call (what an asr_db keeps)

@@ -306,6 +306,26 @@ hipError_t launch_resample_batch(hipStream_t s, const float *in, float *out, con
                                  const int64_t *in_off, const int64_t *in_cnt, const int64_t *out_off,
                                  const int64_t *out_cnt, int n_rec, int64_t total_tiles, int up, int down, int half,
                                  int taps_per_phase, const double *taps, int round_int16);
+// score pages at another resolution (page_resize_kernels.hip): exact integer area resampling, one 64-thread workgroup
+// per tile of RESIZE_TILE_H x RESIZE_TILE_W output pixels of one page.  tile_first (n_pages + 1 running tile counts) and
+// the page table on the device.  A tile stages its source rows in RESIZE_LDS_BYTES of LDS, chunk by chunk; one row of a
+// tile at the ratio RESIZE_MAX_DOWN is 1025 bytes + alignment, so at least 7 rows fit.
+constexpr int RESIZE_TILE_W = 64;
+constexpr int RESIZE_TILE_H = 16;
+constexpr int RESIZE_LDS_BYTES = 8 * 1024;
+constexpr int RESIZE_BATCH = 8;             // 16-byte loads a lane issues before it waits for the first
+constexpr int RESIZE_MAX_DOWN = 16;         // n_in <= RESIZE_MAX_DOWN * n_out per axis
+constexpr int RESIZE_MAX_UP = 4;            // n_out <= RESIZE_MAX_UP * n_in per axis
+constexpr int RESIZE_MAX_DIM = 1 << 24;     // every dimension: tile-relative positions and 255 * w_in stay in 32 bits
+struct ResizePage {
+    int64_t src;            // byte offset of the page in the source buffer
+    int64_t dst;            // byte offset of the resized page in the output buffer
+    int32_t h_in, w_in, h_out, w_out;
+    int32_t tiles_x;        // column tiles of the output: ceil(w_out / RESIZE_TILE_W)
+    int32_t pad;
+};
+hipError_t launch_resize_pages(hipStream_t s, const uint8_t *pages, uint8_t *out, const int64_t *tile_first,
+                               const ResizePage *table, int n_pages, int64_t total_tiles);
 // batch assembly of the training pool: desc_dev holds n x 9 doubles (see piece_vote_kernels.hip)
 hipError_t launch_gather_windows(hipStream_t s, const float *src, const double *desc_dev, int n, int out_h, int out_w,
                                  float *out);

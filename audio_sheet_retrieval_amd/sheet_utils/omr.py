@@ -309,6 +309,49 @@ def unroll_rows(page_shape, systems, system_height=SYSTEM_HEIGHT):
     return rows
 
 
+PAGE_WIDTH = 835            # the width the OMR networks were trained on (the tutorial page is 1181 x 835)
+
+
+def resized_shape(h, w, width=PAGE_WIDTH):
+    """the shape scripts/prepare_umc_data.py:17-22 resizes an h x w scan to: `width` columns, rows in proportion,
+    truncated - its float arithmetic restated"""
+    return int(float(width) / w * h), int(width)
+
+
+def _axis_sums(a, n_out):
+    """a: (n_in, m) int64 -> (n_out, m): row i = sum over j of w(i, j) * a[j] with w the overlap of [i * n_in,
+    (i + 1) * n_in) and [j * n_out, (j + 1) * n_out) - as differences of F(x) = n_out * P[x // n_out] +
+    (x % n_out) * a[x // n_out], P the running sums of a"""
+    n_in = a.shape[0]
+    ext = np.concatenate([a, np.zeros((1,) + a.shape[1:], np.int64)])         # a[n_in] = 0: x = n_in * n_out
+    run = np.concatenate([np.zeros((1,) + a.shape[1:], np.int64), np.cumsum(a, axis=0, dtype=np.int64)])
+    x = np.arange(n_out + 1, dtype=np.int64) * n_in
+    q, r = x // n_out, x % n_out
+    F = n_out * run[q] + r[:, None] * ext[q]
+    return F[1:] - F[:-1]
+
+
+def resize_page_host(page, h_out, w_out):
+    """asr_resize_pages_dev on the host (the definition in include/asr_hip.h): exact integer area resampling of a uint8
+    page to h_out x w_out, in int64, in time proportional to the pixels.  The device returns the same bytes."""
+    page = np.asarray(page)
+    if page.ndim != 2 or page.dtype != np.uint8:
+        raise ValueError("resize_page_host takes a 2-D uint8 page, got %s %s" % (page.dtype, page.shape))
+    h_in, w_in = page.shape
+    h_out, w_out = int(h_out), int(w_out)
+    if min(h_in, w_in, h_out, w_out) < 1:
+        raise ValueError("resize_page_host: %d x %d -> %d x %d" % (h_in, w_in, h_out, w_out))
+    rows = _axis_sums(np.ascontiguousarray(page.T, dtype=np.int64), w_out)    # (w_out, h_in): along the width
+    S = _axis_sums(np.ascontiguousarray(rows.T), h_out)                       # (h_out, w_out): along the height
+    D = h_in * w_in
+    return ((2 * S + D) // (2 * D)).astype(np.uint8)
+
+
+def resize_pages_host(pages, width=PAGE_WIDTH):
+    """every page resized to `width` columns (resized_shape) with resize_page_host"""
+    return [resize_page_host(p, *resized_shape(p.shape[0], p.shape[1], width)) for p in pages]
+
+
 class DevicePages(object):
     """uint8 pages back to back in one device buffer, as asr_seg_predict_dev (IN_U8_RAW) and asr_unroll_systems_dev
     read them: uploaded once, used by both networks and by the unroll."""
@@ -332,6 +375,50 @@ class DevicePages(object):
 
     def free(self):
         self.buf.free()
+
+    def resized(self, width=PAGE_WIDTH):
+        """a new DevicePages on the same engine: every page at `width` columns (resized_shape), resampled on the device
+        in one launch (asr_resize_pages_dev) - nothing is uploaded or downloaded.  A page that has the width already is
+        copied by the same kernel.  This object stays valid; free both."""
+        shapes = [resized_shape(int(h), int(w), width) for h, w in zip(self.heights, self.widths)]
+        for i, (h, w) in enumerate(shapes):
+            if h < 1 or w < 1:
+                raise ValueError("page %d (%d x %d) at width %d has no rows" % (i, self.heights[i], self.widths[i], width))
+        res = DevicePages.__new__(DevicePages)
+        res.engine = self.engine
+        res.heights = np.asarray([h for h, _ in shapes], np.int32)
+        res.widths = np.asarray([w for _, w in shapes], np.int32)
+        res.sizes = res.heights.astype(np.int64) * res.widths
+        res.offsets = np.concatenate([[0], np.cumsum(res.sizes)[:-1]]).astype(np.int64)
+        res.nbytes = int(res.sizes.sum())
+        res.buf = self.engine.alloc(max(res.nbytes, 4))
+        try:
+            self.engine.resize_pages_dev(self.buf.ptr, self.nbytes, self.offsets, self.heights, self.widths, res.offsets,
+                                         res.heights, res.widths, res.buf.ptr, res.nbytes)
+        except Exception:
+            res.buf.free()
+            raise
+        return res
+
+    def download_page(self, i):
+        """page i as a uint8 array on the host"""
+        return self.engine.raw_download(self.buf.ptr + int(self.offsets[i]), (int(self.heights[i]), int(self.widths[i])),
+                                        np.uint8)
+
+    def download(self):
+        """all pages as uint8 arrays on the host, in one copy"""
+        flat = self.buf.download((self.nbytes,), np.uint8) if self.nbytes else np.zeros(0, np.uint8)
+        return [flat[o:o + s].reshape(h, w) for o, s, h, w in zip(self.offsets, self.sizes, self.heights, self.widths)]
+
+
+def resize_pages_dev(engine, pages, width=PAGE_WIDTH):
+    """host pages (2-D uint8 arrays of any sizes) -> a DevicePages holding them at `width` columns: one upload of the
+    raw pages, one launch.  Free it when done."""
+    raw = DevicePages(engine, pages)
+    try:
+        return raw.resized(width)
+    finally:
+        raw.free()
 
 
 def unroll_systems_dev(dev_pages, page_rows, piece_of_page, n_pieces, system_height=SYSTEM_HEIGHT):

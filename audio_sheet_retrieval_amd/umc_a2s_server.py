@@ -5,7 +5,7 @@ umc_a2s_server.py (:178-189):
     python -m audio_sheet_retrieval_amd.umc_a2s_server --model models/mutopia_ccal_cont.py --data_dir <dir> \
         --train_split splits/all_split.yaml --config exp_configs/mutopia_full_aug.yaml \
         --init_sheet_db --full_eval --dump_results [--real_perf] [--n_candidates 25] [--estimate_UV] \
-        --system_params system_params.pkl --bar_params bar_params.pkl [--device_post] [--resample]
+        --system_params system_params.pkl --bar_params bar_params.pkl [--device_post] [--resample] [--page_width 835]
 
 <dir> holds one folder per piece: sheet/*.png (the page scans), score_ppq.* (the synthesised recording) and, for
 --real_perf, 01_performance*.  The pages go through the two segmentation networks (their parameter pickles:
@@ -24,7 +24,10 @@ spectrograms in one call, and strips and spectrograms stay on the device for the
 (piece_identification.detect_scores / detect_performances).  umc_s2a_server.py is the S2A direction of this driver.
 Recordings are read by audio_frontend.load_audio: .wav or .npy at 22050 Hz.  --resample (off by default) reads .wav
 files of any sample rate (audio_frontend.read_audio) and resamples them to 22050 Hz on the device, between the upload
-and the spectrogram launch (asr_resample_batch_dev).
+and the spectrogram launch (asr_resample_batch_dev).  The pages are taken at the resolution the networks were trained on,
+835 pixels wide; --page_width W (none by default; 835 for these networks) accepts scans of any resolution and reduces
+them to W columns on the device, between the upload and the first network (asr_resize_pages_dev: exact area
+resampling, the shape rule of the reference's scripts/prepare_umc_data.py).
 """
 import argparse
 import os
@@ -59,6 +62,9 @@ def _arguments(argv, direction):
                    help="find the systems from the U-Net maps on the device too (asr_systems_from_maps_dev)")
     p.add_argument("--resample", action="store_true",
                    help="accept recordings at any sample rate and resample them on the device (asr_resample_batch_dev)")
+    p.add_argument("--page_width", type=int, default=None,
+                   help="accept page scans of any resolution and resize them to this width on the device "
+                        "(asr_resize_pages_dev); the networks were trained at 835")
     return p.parse_args(argv)
 
 
@@ -75,7 +81,8 @@ def run(argv, direction):
         raise SystemExit("--data_dir: the directory of pieces is required")
     omr = umc.build_recognizer(args.system_params, args.bar_params)
     te_pieces, piece_paths, _, strips = umc.load_umc_sheets(args.data_dir, require_performance=True, omr=omr,
-                                                           return_device=True, device_post=args.device_post)
+                                                           return_device=True, device_post=args.device_post,
+                                                           page_width=args.page_width)
     try:
         dset = os.path.basename(args.data_dir)
         audio_file = "01_performance" if args.real_perf else "score_ppq"

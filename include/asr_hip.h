@@ -710,7 +710,28 @@ int asr_bars_from_map_dev(asr_ctx *ctx, const double *maps_dev, const int32_t *h
  *   checked against both buffer sizes and out_counts[i] against ceil(in_counts[i] * up / down), and up, down >= 1,
  *   taps_per_phase * up >= 2 * half + 1 and the size of a tile's input span (ratios down / up up to 13 fit) are
  *   checked: a violation returns ASR_ERR_INVALID with a message.  Recordings of zero samples and n_recordings == 0 are
- *   valid and write nothing. */
+ *   valid and write nothing.
+ * asr_resize_pages_dev = what scripts/prepare_umc_data.py:17-22 does to a scan before the OMR networks see it (width
+ *   835, height int(835.0 / W * H), cv2.resize), for n_pages pages of any sizes in one launch, between the upload and
+ *   asr_seg_predict_dev.  OpenCV's fixed-point bilinear rule is not restated; the yardstick is this definition, exact
+ *   area resampling (a box filter over each output pixel's footprint), separable, in integers, which
+ *   sheet_utils/omr.resize_page_host restates in numpy and the device reproduces byte for byte:
+ *     axis    n_in source and n_out output pixels, in units of 1 / (n_in * n_out) of the axis: source pixel j covers
+ *             [j * n_out, (j + 1) * n_out), output pixel i covers [i * n_in, (i + 1) * n_in), and the weight w(i, j) is
+ *             the integer length of their overlap; the weights of an output pixel sum to n_in
+ *     sum     S(r, c) = sum over j, k of wy(r, j) * wx(c, k) * src[j, k], an exact integer <= 255 * h_in * w_in (64 bits:
+ *             it passes 2^32 from about 600 dpi on)
+ *     result  out[r, c] = (2 * S + D) / (2 * D), D = h_in * w_in, integer division: the mean rounded, a half goes up
+ *   n_out == n_in reproduces the input, an integer ratio gives the exact block mean, n_out > n_in replicates pixels
+ *   and blends the seams.  Page p: heights[p] x widths[p] uint8, row-major at byte page_offsets[p] of pages_dev
+ *   (pages_bytes = size of that buffer) - the layout asr_seg_predict_dev (in_mode 2) and asr_unroll_systems_dev read,
+ *   rows at any alignment; its out_heights[p] x out_widths[p] result goes to byte out_offsets[p] of out_dev (out_bytes =
+ *   its size) in the same layout.  Bytes of out_dev that belong to no page are left as they are.  The host chooses the
+ *   output shape (the drivers: sheet_utils/omr.resized_shape, the reference's rule).  The page-to-tile table is
+ *   workspace of the context.  Before anything is launched every page and every output is checked against its buffer
+ *   size, and per page: all four dimensions at least 1 and at most 2^24, h_in * w_in < 2^31, and per axis
+ *   n_out / 4 <= n_in <= 16 * n_out (ratios n_in / n_out from 1/4 to 16: what a tile's source rows in LDS are sized
+ *   for).  A violation returns ASR_ERR_INVALID with a message.  n_pages == 0 is valid and writes nothing. */
 int asr_unroll_systems_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
                            const int32_t *heights, const int32_t *widths, int n_pages, const int32_t *systems,
                            int n_systems, int system_height, const int64_t *strip_offsets, const int32_t *strip_widths,
@@ -725,6 +746,9 @@ int asr_resample_batch_dev(asr_ctx *ctx, const float *in_dev, int64_t in_floats,
                            const int64_t *in_counts, const int64_t *out_offsets, const int64_t *out_counts,
                            int n_recordings, int up, int down, const double *taps_phase_major, int taps_per_phase,
                            int half, int round_int16, float *out_dev, int64_t out_floats);
+int asr_resize_pages_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
+                         const int32_t *heights, const int32_t *widths, int n_pages, const int64_t *out_offsets,
+                         const int32_t *out_heights, const int32_t *out_widths, void *out_dev, int64_t out_bytes);
 
 /* ---- device memory (plain pointers; library-owned allocations) ---------- */
 int asr_dev_alloc(asr_ctx *ctx, size_t bytes, void **dptr);
