@@ -39,7 +39,7 @@ EXPORTS = [
     "asr_valid_loss_in", "asr_valid_output_in", "asr_valid_output_in_dev",
     "asr_comm_unique_id", "asr_comm_init", "asr_comm_init_custom", "asr_comm_destroy", "asr_comm_info", "asr_comm_stats", "asr_comm_timing", "asr_comm_library",
     "asr_comm_allreduce_dev", "asr_comm_allgather_dev",
-    "asr_rank_sharded_dev", "asr_slice_windows_dev", "asr_piece_vote_dev", "asr_piece_vote_batch_dev", "asr_track_gate_dev", "asr_track_vote_batch_dev", "asr_gather_windows_dev", "asr_dtw_dev", "asr_dtw_batch_dev", "asr_spectrogram_dev", "asr_debug_tune_report",
+    "asr_rank_sharded_dev", "asr_slice_windows_dev", "asr_piece_vote_dev", "asr_piece_vote_batch_dev", "asr_track_gate_dev", "asr_track_vote_batch_dev", "asr_gather_windows_dev", "asr_dtw_dev", "asr_dtw_batch_dev", "asr_dtw_subseq_batch_dev", "asr_spectrogram_dev", "asr_debug_tune_report",
     "asr_seg_create", "asr_seg_set_window", "asr_seg_destroy", "asr_seg_predict_dev", "asr_systems_from_maps_dev",
     "asr_notes_from_map_dev", "asr_bars_from_map_dev",
     "asr_unroll_systems_dev", "asr_spectrogram_batch_dev", "asr_resample_batch_dev", "asr_resize_pages_dev",
@@ -207,6 +207,8 @@ def load_library(path=None):
         "asr_dtw_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                 POINTER(c_int32), POINTER(c_double)]),
         "asr_dtw_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 7),
+        "asr_dtw_subseq_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64] + [c_void_p] * 4 +
+                                     [c_int, c_int] + [c_void_p] * 5),
         "asr_spectrogram_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_int, c_float, c_float, c_int64, c_int, c_void_p]),
         "asr_unroll_systems_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
@@ -581,6 +583,56 @@ class Engine(object):
             out.append(item)
             o_cell, o_path, o_a, o_b = o_cell + R * C, o_path + R + C, o_a + R, o_b + C
         return out
+
+    def dtw_subseq_batch_dev(self, q_ptr, q_rows, r_ptr, r_rows, q_row, n_q, r_row, n_r, dim, want_pos=True):
+        """asr_dtw_subseq_batch_dev on device buffers: q_ptr (q_rows, dim) / r_ptr (r_rows, dim) float32 code rows;
+        q_row, n_q, r_row, n_r: per pair the first row and the length in either buffer -> (cost float64 [n], start,
+        end, path_len int32 [n], pos: list of int32 [n_q[p]] or None)"""
+        i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
+        q_row, n_q, r_row, n_r = map(i64, (q_row, n_q, r_row, n_r))
+        n = n_q.size
+        if not (q_row.size == r_row.size == n_r.size == n):
+            raise ValueError("dtw_subseq_batch_dev: the per-pair tables differ in length")
+        cost = np.empty(n, np.float64)
+        start, end, ln = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32)
+        pos = np.empty(int(np.maximum(n_q, 0).sum()), np.int32) if want_pos else None
+        self._check(self.lib.asr_dtw_subseq_batch_dev(self.ctx, q_ptr, int(q_rows), r_ptr, int(r_rows), q_row.ctypes.data,
+                                                      n_q.ctypes.data, r_row.ctypes.data, n_r.ctypes.data, n, int(dim),
+                                                      cost.ctypes.data, start.ctypes.data, end.ctypes.data, ln.ctypes.data,
+                                                      pos.ctypes.data if want_pos else None))
+        if want_pos:
+            at = np.concatenate([[0], np.cumsum(n_q)])
+            pos = [pos[at[p]:at[p + 1]].copy() for p in range(n)]
+        return cost, start, end, ln, pos
+
+    def dtw_subseq_batch(self, queries, refs, pairs):
+        """Subsequence DTW (free start and end on the reference axis; include/asr_hip.h: asr_dtw_subseq_batch_dev) of
+        pairs = [(query index, reference index)] over lists of host (n, d) float32 code arrays, each uploaded once
+        -> [(cost, start, end, path_len, pos)] per pair"""
+        queries, refs = [_f32c(a) for a in queries], [_f32c(a) for a in refs]
+        pairs = [(int(a), int(b)) for a, b in pairs]
+        if not pairs:
+            return []
+        if not queries or not refs or queries[0].ndim != 2:
+            raise ValueError("dtw_subseq_batch expects lists of (n,d) arrays")
+        dim = queries[0].shape[1]
+        if any(a.ndim != 2 or a.shape[1] != dim for a in queries + refs):
+            raise ValueError("dtw_subseq_batch expects (n,d) arrays of one d")
+        if any(not (0 <= a < len(queries) and 0 <= b < len(refs)) for a, b in pairs):
+            raise ValueError("dtw_subseq_batch: a pair names a sequence that is not there")
+        nq, nr = np.array([a.shape[0] for a in queries], np.int64), np.array([a.shape[0] for a in refs], np.int64)
+        q0, r0 = np.concatenate([[0], np.cumsum(nq)]), np.concatenate([[0], np.cumsum(nr)])
+        cat_q, cat_r = np.concatenate(queries), np.concatenate(refs)
+        qi, ri = np.array([a for a, _ in pairs]), np.array([b for _, b in pairs])
+        dq = self.alloc(max(cat_q.nbytes, 4)).upload(cat_q)
+        dr = self.alloc(max(cat_r.nbytes, 4)).upload(cat_r)
+        try:
+            cost, start, end, ln, pos = self.dtw_subseq_batch_dev(dq.ptr, cat_q.shape[0], dr.ptr, cat_r.shape[0], q0[qi],
+                                                                  nq[qi], r0[ri], nr[ri], dim)
+        finally:
+            dq.free()
+            dr.free()
+        return [(float(cost[p]), int(start[p]), int(end[p]), int(ln[p]), pos[p]) for p in range(len(pairs))]
 
     def spectrogram_dev(self, samples_ptr, n_samples, frame_size, hop, window, fb_start, fb_len, fb_weights, n_frames,
                         out_ptr, mul=1.0, add=1.0, transposed=True):

@@ -111,3 +111,73 @@ def estimate_alignment_error(true_coords, true_onsets, a2s_mapping):
         if onset in a2s_mapping:
             errors[n] = true_coords[n] - a2s_mapping[int(onset)]
     return errors
+
+
+# ---- subsequence DTW: where in a long reference does a short query lie? (include/asr_hip.h: asr_dtw_subseq_batch_dev)
+
+def subseq_dtw_host(dists):
+    """The definition of asr_dtw_subseq_batch_dev restated in numpy on a float64 distance matrix (query rows x
+    reference columns): A[0][j] = D[0][j], A[i][j] = D[i][j] + fmin(diagonal, fmin(up, left)) with an infinite border;
+    end = first minimum of the last row, cost = A[Q-1][end] / Q; traceback by _traceback's rule (argmin over diagonal,
+    up, left, the first minimum winning) until row 0 -> (cost, start, end, path), path = (rows, columns) in forward
+    order.  The anti-diagonals are evaluated as vectors; every cell is the same sequence of float64 operations in any
+    order of evaluation."""
+    D = np.ascontiguousarray(dists, dtype=np.float64)
+    if D.ndim != 2 or D.shape[0] < 1 or D.shape[1] < 1:
+        raise ValueError("subseq_dtw_host expects a (Q, S) matrix with Q, S >= 1")
+    Q, S = D.shape
+    A = np.full((Q + 1, S + 1), np.inf)                   # A[i + 1][j + 1] = accumulated cost of cell (i, j)
+    A[1, 1:] = D[0]
+    for d in range(1, Q + S - 1):
+        i = np.arange(max(1, d - S + 1), min(d, Q - 1) + 1)
+        j = d - i
+        A[i + 1, j + 1] = D[i, j] + np.fmin(A[i, j], np.fmin(A[i, j + 1], A[i + 1, j]))
+    end = int(np.argmin(A[Q, 1:]))
+    cost = A[Q, end + 1] / Q
+    i, j = Q - 1, end
+    rows, cols = [i], [j]
+    while i > 0:
+        w = int(np.argmin((A[i, j], A[i, j + 1], A[i + 1, j])))     # diagonal, up (i-1, j), left (i, j-1)
+        i -= w != 2
+        j -= w != 1
+        rows.append(i)
+        cols.append(j)
+    return float(cost), j, end, (np.array(rows[::-1], np.int64), np.array(cols[::-1], np.int64))
+
+
+def cosine_dists_host(a, b):
+    """float64 cosine distances of float32 code rows in the library's operation order (csrc/dist64.h): two accumulators
+    over even / odd elements, summed, an odd tail element last; norms = sqrt of the same sum over squares;
+    1 - dot / (|a| |b|) with the quotient clipped to [-1, 1]"""
+    a = np.asarray(a, np.float32).astype(np.float64)
+    b = np.asarray(b, np.float32).astype(np.float64)
+
+    def sum2(p):
+        n = p.shape[-1]
+        a0, a1 = np.zeros(p.shape[:-1]), np.zeros(p.shape[:-1])
+        for k in range(0, n - 1, 2):
+            a0 = a0 + p[..., k]
+            a1 = a1 + p[..., k + 1]
+        return a0 + a1 + p[..., n - 1] if n & 1 else a0 + a1
+
+    na, nb = np.sqrt(sum2(a * a)), np.sqrt(sum2(b * b))
+    dot = np.empty((a.shape[0], b.shape[0]))
+    step = max(1, (1 << 22) // max(1, b.size))
+    for s0 in range(0, a.shape[0], step):                  # products of float32 values are exact in float64
+        dot[s0:s0 + step] = sum2(a[s0:s0 + step, None, :] * b[None, :, :])
+    cos = dot / (na[:, None] * nb[None, :])
+    cos = np.where(np.abs(cos) > 1.0, np.copysign(1.0, cos), cos)
+    return 1.0 - cos
+
+
+def subseq_positions(path, n_q):
+    """pos of asr_dtw_subseq_batch_dev: per query row the smallest reference column the path visits in it (the column
+    of the row's first entry in forward order)"""
+    rows, cols = np.asarray(path[0]), np.asarray(path[1])
+    return cols[first_entries(rows, n_q)].astype(np.int32)
+
+
+def locate_codes_batch(engine, queries, refs, pairs):
+    """Subsequence DTW of pairs = [(query index, reference index)] over lists of (n, d) code arrays in one library
+    call -> [(cost, start, end, path_len, pos)] (Engine.dtw_subseq_batch)"""
+    return engine.dtw_subseq_batch(queries, refs, pairs)

@@ -22,6 +22,15 @@ the last --running_frames such frames ranks the pieces (piece_identification.tra
 prints the first frame at which the target leads and the share of voiced frames at which it leads; --dump_results
 writes the two lists to tracking_<tag>_A2S.yaml.
 
+--locate (A2S only) answers the question between piece identification and whole-piece alignment: given an excerpt,
+where in which score are we?  Per test piece a seeded excerpt of --excerpt_frames frames is cut from its spectrogram;
+the vote names --locate_pieces candidates and a subsequence DTW (free start and end on the score axis) aligns the
+excerpt's windows, one every --step_spec frames, with each candidate's ordered data-base codes
+(piece_identification.locate_scores: one asr_dtw_subseq_batch_dev call for all excerpts and candidates).  Per piece it
+prints the rank of the own piece by vote and by alignment cost and the pixel distance of the found start and end from
+the onset map interpolated at the excerpt's first and last window centres; --dump_results writes them to
+location_<tag>_A2S.yaml.  The error is a report, not a gate.
+
 The microphone and the GUI of the live server, audio decoding (--real_audio) and MSMD loading are not part of this
 implementation.  sheet_audio_server.py is the S2A direction (sheet -> audio) of the same driver.
 """
@@ -32,7 +41,8 @@ import numpy as np
 import yaml
 
 from . import audio2sheet_align
-from .piece_identification import EmbeddingDB, detect_performances, detect_scores, rank_summary, track_scores
+from .piece_identification import (EmbeddingDB, detect_performances, detect_scores, locate_scores, rank_summary,
+                                   track_scores)
 from .utils.data_pools import NO_AUGMENT, AudioScoreRetrievalPool
 
 # per direction: data-base flag, data-base file, data-base view, what a query finds (the reference's summary line)
@@ -70,6 +80,11 @@ def _arguments(argv, direction):
     if direction == "A2S":
         p.add_argument("--track", action="store_true",
                        help="run the live server's running vote over every test piece's spectrogram")
+        p.add_argument("--locate", action="store_true",
+                       help="locate a seeded excerpt of every test piece in the scores of the data base")
+        p.add_argument("--excerpt_frames", type=int, default=400, help="frames of the excerpt (--locate)")
+        p.add_argument("--locate_pieces", type=int, default=5, help="candidates of the vote that are aligned (--locate)")
+        p.add_argument("--step_spec", type=int, default=2, help="frames between the excerpt's windows (--locate)")
     p.add_argument("--seed", type=int, default=23)
     return p.parse_args(argv)
 
@@ -128,6 +143,75 @@ def report_tracking(names, first_lead, lead_share, res_file=None):
     return results
 
 
+def location_file(param_file, direction):
+    """result_file's name with location_ in place of retrieval_"""
+    return param_file.replace("params_", "location_").replace(".pkl", "_%s.yaml") % direction
+
+
+def pool_sheet_columns(pool, n_rows):
+    """the strip x-coordinate of every row of an EmbeddingDB.from_pool data base: the annotated coordinate of the row's
+    (piece, performance, onset) entity, on which its sheet window is centred; None when `pool` does not describe a data
+    base of n_rows rows (then locate_scores applies EmbeddingDB.from_images' rule)"""
+    if int(pool.shape[0]) != n_rows:
+        return None
+    return np.array([pool.o2c_maps[p][f][o][1] for p, f, o in pool.train_entities], np.float64)
+
+
+def cut_excerpts(specs, o2c_maps, excerpt_frames, step_spec, win_w, seed):
+    """per piece a seeded excerpt of (at most) excerpt_frames frames of its first performance -> (excerpts, per piece
+    the onset map's x at the centres of the excerpt's first and last window)"""
+    rng = np.random.RandomState(seed)
+    excerpts, truth = [], []
+    for spec, o2c in zip(specs, o2c_maps):
+        spec, o2c = spec[0], np.asarray(o2c[0], np.float64)
+        n = min(int(excerpt_frames), spec.shape[1])
+        f0 = int(rng.randint(0, spec.shape[1] - n + 1))
+        excerpts.append(np.ascontiguousarray(spec[:, f0:f0 + n]))
+        last = np.arange(0, n - win_w + 1, step_spec)[-1] if n >= win_w else 0
+        centres = np.array([f0 + win_w // 2, f0 + last + win_w // 2], np.float64)
+        truth.append(tuple(float(v) for v in np.interp(centres, o2c[:, 0], o2c[:, 1])))
+    return excerpts, truth
+
+
+def locate(engine, db, pool, names, n_candidates, excerpt_frames, n_pieces, step_spec, seed):
+    """an excerpt of every piece located in the data base -> one dict per piece: name, vote_rank / cost_rank of the own
+    piece among the candidates (0: not among them), start_x / end_x found for it, start_error / end_error in pixels
+    against the onset map (None when the own piece is no candidate)"""
+    excerpts, truth = cut_excerpts(pool.specs, pool.o2c_maps, excerpt_frames, step_spec, int(pool.spec_dim[1]), seed)
+    found = locate_scores(engine, db, excerpts, n_pieces=n_pieces, step_spec=step_spec, n_candidates=n_candidates,
+                          spec_shape=tuple(pool.spec_dim), sheet_columns=pool_sheet_columns(pool, len(db)))
+    out = []
+    for name, cands, (x0, x1) in zip(names, found, truth):
+        entry = dict(name=str(name), vote_rank=0, cost_rank=0, start_x=None, end_x=None, start_error=None, end_error=None)
+        for rank, cand in enumerate(cands):
+            if cand["name"] == name:
+                entry.update(vote_rank=int(cand["vote_rank"]), cost_rank=rank + 1, start_x=float(cand["start_x"]),
+                             end_x=float(cand["end_x"]), start_error=float(abs(cand["start_x"] - x0)),
+                             end_error=float(abs(cand["end_x"] - x1)))
+                break
+        out.append(entry)
+    return out
+
+
+def report_location(entries, res_file=None):
+    for e in entries:
+        if e["cost_rank"]:
+            print("rank by vote %02d, by cost %02d, start off by %6.1f px, end off by %6.1f px  %s"
+                  % (e["vote_rank"], e["cost_rank"], e["start_error"], e["end_error"], e["name"]))
+        else:
+            print("rank by vote --, by cost --, not among the candidates                      %s" % e["name"])
+    hit = [e for e in entries if e["cost_rank"]]
+    if hit:
+        print("own piece first by vote: %d, by cost: %d of %d; median start / end error %.1f / %.1f px"
+              % (sum(e["vote_rank"] == 1 for e in hit), sum(e["cost_rank"] == 1 for e in hit), len(entries),
+                 float(np.median([e["start_error"] for e in hit])), float(np.median([e["end_error"] for e in hit]))))
+    if res_file is not None:
+        with open(res_file, "w") as fp:
+            yaml.dump(entries, fp, default_flow_style=False)
+        print("location of %d pieces written to %s" % (len(entries), res_file))
+    return entries
+
+
 def run(argv, direction):
     d = DIRECTIONS[direction]
     args = _arguments(argv, direction)
@@ -148,6 +232,11 @@ def run(argv, direction):
         print("\nTracking every test piece:")
         return report_tracking(*track(engine, db, pool, data["names"], args.n_candidates, args.running_frames),
                                res_file=tracking_file(param_file, direction) if args.dump_results else None)
+    if getattr(args, "locate", False):
+        print("\nLocating an excerpt of every test piece:")
+        return report_location(locate(engine, db, pool, data["names"], args.n_candidates, args.excerpt_frames,
+                                      args.locate_pieces, args.step_spec, args.seed),
+                               res_file=location_file(param_file, direction) if args.dump_results else None)
     if not args.full_eval:
         raise SystemExit("the live server loop (microphone, GUI) is not part of this implementation; use --full_eval")
 

@@ -203,6 +203,7 @@ void free_ctx_buffers(asr_ctx *ctx) {
     if (ctx->cca_ws) hipFree(ctx->cca_ws);
     if (ctx->topk_ws) hipFree(ctx->topk_ws);
     if (ctx->dtw_ws) hipFree(ctx->dtw_ws);
+    if (ctx->subseq_ws) hipFree(ctx->subseq_ws);
     if (ctx->vote_ws) hipFree(ctx->vote_ws);
     if (ctx->post_ws) hipFree(ctx->post_ws);
     if (ctx->resample_ws) hipFree(ctx->resample_ws);

@@ -667,6 +667,146 @@ int asr_dtw_batch_dev(asr_ctx *ctx, const float *a_dev, const float *b_dev, cons
     return mark_main(ctx);
 }
 
+int asr_dtw_subseq_batch_dev(asr_ctx *ctx, const float *q_dev, int64_t q_rows, const float *r_dev, int64_t r_rows,
+                             const int64_t *q_row, const int64_t *n_q, const int64_t *r_row, const int64_t *n_r,
+                             int n_pairs, int dim, double *cost, int32_t *start, int32_t *end, int32_t *path_len,
+                             int32_t *pos) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_pairs < 0 || dim < 1 || dim > 64 || q_rows < 0 || r_rows < 0)
+        return fail(ctx, ASR_ERR_INVALID, "dtw_subseq: bad sizes n_pairs=%d dim=%d (1..64) q_rows=%lld r_rows=%lld", n_pairs,
+                    dim, (long long)q_rows, (long long)r_rows);
+    if (n_pairs == 0) return ASR_OK;
+    if (!q_dev || !r_dev || !q_row || !n_q || !r_row || !n_r) return fail(ctx, ASR_ERR_INVALID, "dtw_subseq: NULL argument");
+    for (int p = 0; p < n_pairs; ++p) {
+        if (n_q[p] < 1 || n_q[p] > 1024 || n_r[p] < 1 || n_r[p] > 100000 || n_q[p] * (n_r[p] + n_q[p]) >= (1ll << 31))
+            return fail(ctx, ASR_ERR_INVALID, "dtw_subseq: pair %d has bad sizes n_q=%lld (1..1024) n_r=%lld (1..100000)", p,
+                        (long long)n_q[p], (long long)n_r[p]);
+        if (q_row[p] < 0 || q_row[p] > q_rows - n_q[p] || r_row[p] < 0 || r_row[p] > r_rows - n_r[p])
+            return fail(ctx, ASR_ERR_INVALID, "dtw_subseq: pair %d reads rows outside its buffers (q %lld+%lld of %lld, r "
+                        "%lld+%lld of %lld)", p, (long long)q_row[p], (long long)n_q[p], (long long)q_rows,
+                        (long long)r_row[p], (long long)n_r[p], (long long)r_rows);
+    }
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    int rc = ensure_norms(ctx, q_rows, r_rows);
+    if (rc != ASR_OK) return rc;
+    rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    // ASR_DTW_BUDGET_MB: device workspace per chunk of pairs; ASR_DTW_SUBSEQ_LDS_CAP=<bytes> (debug): workgroups whose
+    // staging ring is larger read the reference rows from global memory (exercises that path at small sizes)
+    const size_t budget = (size_t)std::max<int64_t>(dtw_env("ASR_DTW_BUDGET_MB", 4096), 1) << 20;
+    int lds_dev = 0;
+    if (hipDeviceGetAttribute(&lds_dev, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->cfg.device) != hipSuccess)
+        lds_dev = 65536;
+    const size_t lds_limit = (size_t)std::min<int64_t>(lds_dev, dtw_env("ASR_DTW_SUBSEQ_LDS_CAP", 1 << 30));
+
+    // chunks of consecutive pairs whose workspace fits the budget (a pair larger than it gets a chunk of its own):
+    // pair table | direction bytes | cost | start | end | path_len | pos, 256-byte aligned sections
+    struct Chunk { int p0 = 0, n = 0; int64_t dir = 0, rows = 0; size_t o_dir = 0, o_cost = 0, o_start = 0, o_end = 0,
+                   o_len = 0, o_pos = 0, bytes = 0; };
+    auto layout = [](Chunk &c) {
+        size_t o = 0;
+        auto take = [&](size_t bytes) { const size_t at = o; o += dtw_align(bytes); return at; };
+        take((size_t)c.n * sizeof(asr::SubseqPair));
+        c.o_dir = take((size_t)c.dir);
+        c.o_cost = take((size_t)c.n * sizeof(double));
+        c.o_start = take((size_t)c.n * sizeof(int32_t));
+        c.o_end = take((size_t)c.n * sizeof(int32_t));
+        c.o_len = take((size_t)c.n * sizeof(int32_t));
+        c.o_pos = take((size_t)c.rows * sizeof(int32_t));
+        c.bytes = o;
+    };
+    std::vector<Chunk> chunks;
+    Chunk c;
+    for (int p = 0; p < n_pairs; ++p) {
+        Chunk t = c;
+        t.n += 1;
+        t.dir += n_q[p] * (n_r[p] + n_q[p] - 1);
+        t.rows += n_q[p];
+        layout(t);
+        if (t.bytes > budget && c.n > 0) {
+            chunks.push_back(c);
+            Chunk f;
+            f.p0 = p;
+            c = f;
+            --p;
+            continue;
+        }
+        c = t;
+    }
+    chunks.push_back(c);
+    size_t need = 0;
+    for (const Chunk &k : chunks) need = std::max(need, k.bytes);
+    if (need > ctx->subseq_ws_bytes) {
+        rc = sync_all(ctx);
+        if (rc != ASR_OK) return rc;
+        if (ctx->subseq_ws) ASR_HIP(ctx, hipFree(ctx->subseq_ws));
+        ctx->subseq_ws = nullptr; ctx->subseq_ws_bytes = 0;
+        ASR_HIP(ctx, hipMalloc(&ctx->subseq_ws, need));
+        ctx->subseq_ws_bytes = need;
+    }
+
+    double tot_cells = 0;
+    for (int p = 0; p < n_pairs; ++p) tot_cells += (double)n_q[p] * (double)n_r[p];
+    ProfScope ps(ctx, "dtw_subseq", 0, 2.0 * dim * tot_cells, tot_cells);
+    ASR_HIP(ctx, asr::launch_row_norms(ctx->stream, q_dev, q_rows, dim, dim, ctx->norm1));
+    ASR_HIP(ctx, asr::launch_row_norms(ctx->stream, r_dev, r_rows, dim, dim, ctx->norm2));
+    char *ws = (char *)ctx->subseq_ws;
+    int64_t host_pos = 0;
+    std::vector<asr::SubseqPair> desc;
+    for (const Chunk &k : chunks) {
+        // the table is ordered by size class (waves = ceil(n_q / 64)): one launch per class present in the chunk
+        desc.clear();
+        int class_n[17] = {0};
+        std::vector<int64_t> dir_at(k.n), pos_at(k.n);
+        int64_t dir = 0, rows = 0;
+        for (int q = 0; q < k.n; ++q) {
+            const int p = k.p0 + q;
+            dir_at[q] = dir; pos_at[q] = rows;
+            dir += n_q[p] * (n_r[p] + n_q[p] - 1); rows += n_q[p];
+            class_n[(n_q[p] + 63) / 64] += 1;
+        }
+        for (int w = 1; w <= 16; ++w)
+            for (int q = 0; q < k.n && class_n[w] > 0; ++q) {
+                const int p = k.p0 + q;
+                if ((n_q[p] + 63) / 64 != w) continue;
+                asr::SubseqPair P;
+                P.Q = (int32_t)n_q[p]; P.S = (int32_t)n_r[p];
+                P.q_row = q_row[p]; P.r_row = r_row[p];
+                P.dir = dir_at[q]; P.pos = pos_at[q]; P.out = q; P.pad = 0;
+                desc.push_back(P);
+            }
+        asr::SubseqPair *d_pairs = (asr::SubseqPair *)ws;
+        uint8_t *d_dir = (uint8_t *)(ws + k.o_dir);
+        double *d_cost = (double *)(ws + k.o_cost);
+        int32_t *d_start = (int32_t *)(ws + k.o_start), *d_end = (int32_t *)(ws + k.o_end);
+        int32_t *d_len = (int32_t *)(ws + k.o_len), *d_pos = (int32_t *)(ws + k.o_pos);
+        ASR_HIP(ctx, hipMemcpyAsync(d_pairs, desc.data(), desc.size() * sizeof(asr::SubseqPair), hipMemcpyHostToDevice,
+                                    ctx->stream));
+        {
+            ProfScope pk(ctx, "dtw_subseq_wave", 0, 0.0, 0.0);  // the kernels alone (the outer scope has the copies too)
+            int at = 0;
+            for (int w = 1; w <= 16; ++w) {
+                if (class_n[w] == 0) continue;
+                ASR_HIP(ctx, asr::launch_dtw_subseq(ctx->stream, d_pairs + at, class_n[w], w, lds_limit, q_dev,
+                                                    ctx->norm1, r_dev, ctx->norm2, dim, d_dir, d_cost, d_start, d_end,
+                                                    d_len, pos ? d_pos : nullptr));
+                at += class_n[w];
+            }
+        }
+        if (cost) ASR_HIP(ctx, hipMemcpyAsync(cost + k.p0, d_cost, k.n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        if (start)
+            ASR_HIP(ctx, hipMemcpyAsync(start + k.p0, d_start, k.n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        if (end) ASR_HIP(ctx, hipMemcpyAsync(end + k.p0, d_end, k.n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        if (path_len)
+            ASR_HIP(ctx, hipMemcpyAsync(path_len + k.p0, d_len, k.n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        if (pos)
+            ASR_HIP(ctx, hipMemcpyAsync(pos + host_pos, d_pos, k.rows * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        ASR_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the next chunk reuses the workspace; `desc` is rebuilt
+        host_pos += k.rows;
+    }
+    return mark_main(ctx);
+}
+
 int asr_spectrogram_dev(asr_ctx *ctx, const float *samples_dev, int64_t n_samples, int frame_size, double hop,
                         const float *window, const int32_t *fb_start, const int32_t *fb_len, const float *fb_weights,
                         int n_filters, float mul, float add, int64_t n_frames, int transposed, float *out_dev) {

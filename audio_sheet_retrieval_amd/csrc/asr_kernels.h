@@ -219,6 +219,24 @@ hipError_t launch_dtw_batch_traceback(hipStream_t s, const DtwPair *pairs, int n
                                       int32_t *path_a, int32_t *path_b, int32_t *path_len, int32_t *first_a,
                                       int32_t *first_b);
 
+// ---- batched subsequence DTW (dtw_subseq_kernels.hip): distances, wavefront and traceback fused, one workgroup per pair
+struct SubseqPair {
+    int32_t Q, S;          // query rows (one lane each, <= 1024) / reference rows
+    int64_t q_row, r_row;  // first code row in q / r
+    int64_t dir;           // first direction byte: cell (i, j) at (i + j) * Q + i, Q * (S + Q - 1) bytes
+    int64_t pos;           // first entry of the pair's pos (Q entries) in the chunk's array
+    int32_t out;           // index of the pair's cost / start / end / path_len in the chunk's arrays
+    int32_t pad;
+};
+// LDS one workgroup of `waves` waves needs to stage reference rows of `dim` floats (0: dim out of range)
+size_t dtw_subseq_lds_bytes(int waves, int dim);
+// `pairs`: n_pairs entries that all take `waves` = ceil(Q / 64) waves.  lds_limit: LDS one workgroup may use; a
+// workgroup whose staging ring does not fit reads the reference rows from global memory instead (same results).
+// nq / nr: float64 norms of the rows of q / r, indexed like q / r.  pos may be null.
+hipError_t launch_dtw_subseq(hipStream_t s, const SubseqPair *pairs, int n_pairs, int waves, size_t lds_limit,
+                             const float *q, const double *nq, const float *r, const double *nr, int dim, uint8_t *dir,
+                             double *cost, int32_t *start, int32_t *end, int32_t *path_len, int32_t *pos);
+
 // ---- piece-identification vote (audio_sheet_server.py:213-300) -----------------
 hipError_t launch_slice_windows(hipStream_t s, const float *src, int64_t T, int r0, int win_h, int win_w,
                                 const int32_t *starts_dev, int n, float *out);

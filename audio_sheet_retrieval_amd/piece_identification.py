@@ -351,7 +351,7 @@ def window_plan(inputs, win_shape, n_samples, centre_rows):
 
 
 def _detect_batch(engine, db, inputs, view, win_shape, centre_rows, top_k, n_candidates, n_samples, targets,
-                  max_windows):
+                  max_windows, with_ids=False):
     on_device = _is_device(inputs)
     if not on_device:
         inputs = list(inputs)
@@ -396,7 +396,8 @@ def _detect_batch(engine, db, inputs, view, win_shape, centre_rows, top_k, n_can
     for g in range(n_in):
         c = counts[g, :n_out[g]]
         names = [db.id_to_name[int(p)] for p in pieces[g, :n_out[g]]]
-        results.append((names, c.astype(np.float64) / c.sum() if c.size else c.astype(np.float64)))
+        results.append((names, c.astype(np.float64) / c.sum() if c.size else c.astype(np.float64)) +
+                       ((pieces[g, :n_out[g]].copy(),) if with_ids else ()))     # (locate_scores: the piece ids too)
     return (results, ranks, ratios) if targets is not None else results
 
 
@@ -701,3 +702,152 @@ class PieceTracker(object):
         self.n_frames += n
         self.n_voiced += m
         return TrackResult(m_prob, voiced, frames, pieces, counts, n_out, history, db.id_to_name, new_rows)
+
+
+# ---- where in the score is an excerpt?  piece vote, then subsequence DTW against the candidates' ordered codes ----------
+def piece_segments(ids):
+    """{piece id: (first data-base row, number of rows)} of a data base whose `ids` list every piece's rows
+    contiguously (EmbeddingDB.from_images / from_pool do); ValueError otherwise"""
+    ids = np.asarray(ids).reshape(-1)
+    segs = {}
+    if ids.size == 0:
+        return segs
+    cuts = np.flatnonzero(np.diff(ids) != 0) + 1
+    for first, stop in zip(np.concatenate([[0], cuts]), np.concatenate([cuts, [ids.size]])):
+        piece = int(ids[first])
+        if piece in segs:
+            raise ValueError("the data-base rows of piece %d are not contiguous (rows %d.. and %d..): pass `segments`"
+                             % (piece, segs[piece][0], first))
+        segs[piece] = (int(first), int(stop - first))
+    return segs
+
+
+def default_sheet_columns(ids, w_sheet):
+    """strip x-coordinate of every data-base row by EmbeddingDB.from_images' rule: window k of a piece starts at
+    k * (w_sheet // 4), so its centre is at k * (w_sheet // 4) + w_sheet // 2"""
+    ids = np.asarray(ids).reshape(-1)
+    cols = np.zeros(ids.size, np.float64)
+    for first, n in piece_segments(ids).values():
+        cols[first:first + n] = np.arange(n) * (w_sheet // 4) + w_sheet // 2
+    return cols
+
+
+def locate_window_plan(shapes, offsets, win_shape, step_spec):
+    """the query windows of locate_scores: per excerpt the columns np.arange(0, T - w + 1, step_spec), rows 0.. ->
+    (per excerpt its window starts, gather descriptors)"""
+    win_h, win_w = win_shape
+    if step_spec < 1:
+        raise ValueError("step_spec must be >= 1")
+    starts, desc = [], []
+    for i, ((rows, T), off) in enumerate(zip(shapes, offsets)):
+        if T < win_w:
+            raise ValueError("input %d has %d columns, a window needs %d" % (i, T, win_w))
+        if win_h > rows:
+            raise ValueError("input %d has %d rows, a window needs %d" % (i, rows, win_h))
+        st = np.arange(0, T - win_w + 1, step_spec)
+        if len(st) > 1024:
+            raise ValueError("input %d gives %d windows; the subsequence DTW takes queries of at most 1024 (raise "
+                             "step_spec or cut the excerpt)" % (i, len(st)))
+        starts.append(st)
+        desc.append(_identity_desc(off, rows, T, 0, st))
+    return starts, (np.concatenate(desc) if desc else np.zeros((0, 9), np.float64))
+
+
+def _locate(engine, sheet_db, spectrograms, n_pieces, step_spec, n_candidates, n_samples, spec_shape, segments,
+            sheet_columns, max_windows, host):
+    segments = piece_segments(sheet_db.ids) if segments is None else {int(k): (int(v[0]), int(v[1]))
+                                                                      for k, v in dict(segments).items()}
+    for piece, (first, n) in segments.items():
+        if first < 0 or n < 1 or first + n > len(sheet_db):
+            raise ValueError("segment of piece %d (rows %d..%d) leaves the %d rows of the data base"
+                             % (piece, first, first + n, len(sheet_db)))
+    if sheet_columns is None:
+        sheet_columns = default_sheet_columns(sheet_db.ids, int(engine.cfg.w1))
+    sheet_columns = np.asarray(sheet_columns, np.float64).reshape(-1)
+    if sheet_columns.size != len(sheet_db):
+        raise ValueError("%d sheet_columns for %d data-base rows" % (sheet_columns.size, len(sheet_db)))
+    dev, owned = _to_device(engine, spectrograms if _is_device(spectrograms) else list(spectrograms))
+    try:
+        n_in = len(dev.shapes)
+        if n_in == 0:
+            return []
+        votes = _detect_batch(engine, sheet_db, dev, 2, spec_shape, False, n_pieces, n_candidates, n_samples, None,
+                              max_windows, with_ids=True)
+        starts, desc = locate_window_plan(dev.shapes, dev.offsets, spec_shape, step_spec)
+        n_q = np.array([len(st) for st in starts], np.int64)
+        q_at = np.concatenate([[0], np.cumsum(n_q)])
+        n_win = int(n_q.sum())
+        pairs = []                                           # (excerpt, candidate, piece)
+        for e, (_, _, pieces) in enumerate(votes):
+            for c, piece in enumerate(pieces):
+                if int(piece) not in segments:
+                    raise ValueError("piece %d got votes but has no segment" % int(piece))
+                pairs.append((e, c, int(piece)))
+        chunk = max(1, min(n_win, int(max_windows)))
+        d_win = engine.alloc(chunk * spec_shape[0] * spec_shape[1] * 4)
+        d_codes = engine.alloc(max(n_win * 32 * 4, 4))
+        try:
+            embed_windows_dev(engine, 2, dev.buf.ptr, dev.buf.nbytes // 4, desc, spec_shape, d_win, d_codes, chunk)
+            if host:
+                from . import alignment
+                codes = d_codes.download((n_win, 32), np.float32)
+                res = []
+                for e, _, piece in pairs:
+                    first, n = segments[piece]
+                    d = alignment.cosine_dists_host(codes[q_at[e]:q_at[e + 1]], sheet_db.codes[first:first + n])
+                    cost, start, end, path = alignment.subseq_dtw_host(d)
+                    res.append((cost, start, end, alignment.subseq_positions(path, int(n_q[e]))))
+            elif pairs:
+                cost, start, end, _, pos = engine.dtw_subseq_batch_dev(
+                    d_codes.ptr, n_win, sheet_db._d_codes.ptr, len(sheet_db), [q_at[e] for e, _, _ in pairs],
+                    [n_q[e] for e, _, _ in pairs], [segments[p][0] for _, _, p in pairs],
+                    [segments[p][1] for _, _, p in pairs], 32)
+                res = [(float(cost[k]), int(start[k]), int(end[k]), pos[k]) for k in range(len(pairs))]
+            else:
+                res = []
+        finally:
+            d_win.free()
+            d_codes.free()
+    finally:
+        if owned:
+            dev.buf.free()
+    out = [[] for _ in range(n_in)]
+    for (e, c, piece), (cost, start, end, pos) in zip(pairs, res):
+        first = segments[piece][0]
+        names, share, _ = votes[e]
+        out[e].append(dict(name=names[c], votes=float(share[c]), vote_rank=c + 1, cost=float(cost), start_row=int(start), end_row=int(end),
+                           start_x=float(sheet_columns[first + start]), end_x=float(sheet_columns[first + end]),
+                           x=sheet_columns[first + np.asarray(pos, np.int64)]))
+    return [sorted(cands, key=lambda cand: cand["cost"]) for cands in out]     # stable: equal costs keep the vote's order
+
+
+def locate_scores(engine, sheet_db, spectrograms, n_pieces=5, step_spec=2, n_candidates=25, n_samples=100,
+                  spec_shape=(92, 42), segments=None, sheet_columns=None, max_windows=4096):
+    """Where in which score does each excerpt lie?  The piece vote (detect_scores, top_k = n_pieces) names the
+    candidates; every excerpt's windows at columns np.arange(0, T - w + 1, step_spec) are cut and embedded on the
+    device, and one asr_dtw_subseq_batch_dev call aligns every excerpt with the ordered codes of each of its candidates
+    inside the resident data base (free start and end on the score axis, the excerpt consumed completely).
+    segments: {piece id: (first data-base row, rows)}, by default derived from sheet_db.ids, which must list every
+    piece's rows contiguously (ValueError otherwise).  sheet_columns: the strip x-coordinate of every data-base row;
+    by default EmbeddingDB.from_images' rule, window k of a piece at k * (w_sheet // 4) + w_sheet // 2.
+    -> per excerpt its candidates ordered by alignment cost (equal costs keep the vote's order), each a dict of name,
+    votes (normalised), vote_rank (1 = most votes), cost, start_row / end_row (rows of the piece's segment), start_x / end_x and x (one strip
+    coordinate per query window).  `spectrograms`: host arrays or a DeviceArrays handle.  An excerpt gives at most 1024
+    windows."""
+    return _locate(engine, sheet_db, spectrograms, n_pieces, step_spec, n_candidates, n_samples, tuple(spec_shape),
+                   segments, sheet_columns, max_windows, host=False)
+
+
+def locate_score(engine, sheet_db, spectrogram, n_pieces=5, step_spec=2, n_candidates=25, n_samples=100,
+                 spec_shape=(92, 42), segments=None, sheet_columns=None):
+    """locate_scores for one spectrogram -> its candidates"""
+    return locate_scores(engine, sheet_db, [spectrogram], n_pieces, step_spec, n_candidates, n_samples, spec_shape,
+                         segments, sheet_columns)[0]
+
+
+def locate_scores_host(engine, sheet_db, spectrograms, n_pieces=5, step_spec=2, n_candidates=25, n_samples=100,
+                       spec_shape=(92, 42), segments=None, sheet_columns=None, max_windows=4096):
+    """locate_scores with the alignment on the host: the same vote and window codes, downloaded, and per pair
+    alignment.subseq_dtw_host on alignment.cosine_dists_host - what the device path is tested against"""
+    return _locate(engine, sheet_db, spectrograms, n_pieces, step_spec, n_candidates, n_samples, tuple(spec_shape),
+                   segments, sheet_columns, max_windows, host=True)

@@ -369,6 +369,41 @@ int asr_dtw_batch_dev(asr_ctx *ctx, const float *a_dev, const float *b_dev, cons
                       int n_pairs, int dim, double *min_dist, int32_t *path_len, int32_t *path_a, int32_t *path_b,
                       double *dists, int32_t *first_a, int32_t *first_b);
 
+/* ---- batched subsequence DTW: where in a long reference does a short query lie? -----------
+ * For a query of Q code rows and a reference of S code rows let D[i][j] be the float64 cosine distance of query row i
+ * and reference row j in exactly asr_dtw_dev's arithmetic (dot2acc and cos_dist of csrc/dist64.h, row norms as the
+ * DTW path computes them).  The accumulated cost is
+ *     A[0][j] = D[0][j]                                                     (free start on the reference axis)
+ *     A[i][j] = D[i][j] + fmin(A[i-1][j-1], fmin(A[i-1][j], A[i][j-1]))      for i >= 1,
+ *               every out-of-range predecessor = +inf
+ * and from it
+ *     end      = the smallest j that minimises A[Q-1][j] (first minimum);
+ *     cost     = A[Q-1][end] / Q, one correctly rounded float64 division;
+ *     the traceback starts at (Q-1, end) and, while i > 0, picks the predecessor by _traceback's rule (the one of
+ *     asr_dtw_batch_dev): order (diagonal, up (i-1,j), left (i,j-1)), strict <, first minimum wins;
+ *     start    = j when i reaches 0;
+ *     path_len = the cells of the path, both ends included;
+ *     pos[i]   = the smallest j the path visits in row i, i.e. the column of row i's first entry in forward order
+ *                (align_pydtw's projection, from the query side).
+ * The code rows are embeddings: a row of zero norm makes the result unspecified.  Every A value is one fixed sequence
+ * of correctly rounded float64 operations, so the order in which cells are scheduled cannot change a bit.
+ *
+ * q_dev (q_rows, dim) and r_dev (r_rows, dim): float32 code rows on the device; r_dev may be the resident code buffer
+ * of a data base.  q_row / n_q / r_row / n_r: host arrays of n_pairs, each pair's first row and length in either
+ * buffer; pairs may share a query or a reference.  Outputs (host, each may be NULL): cost, start, end, path_len of
+ * n_pairs; pos holds pair p's n_q[p] entries at offset sum_{q<p} n_q[q].  Pairs are independent: neither batch
+ * composition nor order changes a result.
+ * Limits (ASR_ERR_INVALID otherwise, nothing is launched): 1 <= dim <= 64; per pair 1 <= n_q <= 1024,
+ * 1 <= n_r <= 100000, the row ranges inside the two buffers, n_q * (n_r + n_q) < 2^31.  A longer query is
+ * asr_dtw_batch_dev's job.  One workgroup per pair, one lane per query row; no distance or accumulated value is
+ * written to device memory, only one direction byte per cell (n_q * (n_r + n_q - 1) per pair), kept with the pair
+ * table on the context between calls and freed by asr_destroy; a batch above ASR_DTW_BUDGET_MB (default 4096) runs in
+ * chunks of consecutive pairs with identical results. */
+int asr_dtw_subseq_batch_dev(asr_ctx *ctx, const float *q_dev, int64_t q_rows, const float *r_dev, int64_t r_rows,
+                             const int64_t *q_row, const int64_t *n_q, const int64_t *r_row, const int64_t *n_r,
+                             int n_pairs, int dim, double *cost, int32_t *start, int32_t *end,
+                             int32_t *path_len, int32_t *pos);
+
 /* ---- training-pool batch assembly on the device ----------------------
  * AudioScoreRetrievalPool.__getitem__ (utils/data_pools.py:127-228): every sample is a window of one strip (unrolled
  * score image or spectrogram) of a pool that stays resident on the device, with the augmentations of
