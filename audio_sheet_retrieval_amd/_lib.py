@@ -39,7 +39,7 @@ EXPORTS = [
     "asr_valid_loss_in", "asr_valid_output_in", "asr_valid_output_in_dev",
     "asr_comm_unique_id", "asr_comm_init", "asr_comm_init_custom", "asr_comm_destroy", "asr_comm_info", "asr_comm_stats", "asr_comm_timing", "asr_comm_library",
     "asr_comm_allreduce_dev", "asr_comm_allgather_dev",
-    "asr_rank_sharded_dev", "asr_slice_windows_dev", "asr_piece_vote_dev", "asr_piece_vote_batch_dev", "asr_track_gate_dev", "asr_track_vote_batch_dev", "asr_gather_windows_dev", "asr_dtw_dev", "asr_dtw_batch_dev", "asr_dtw_subseq_batch_dev", "asr_spectrogram_dev", "asr_debug_tune_report",
+    "asr_rank_sharded_dev", "asr_slice_windows_dev", "asr_piece_vote_dev", "asr_piece_vote_batch_dev", "asr_track_gate_dev", "asr_track_vote_batch_dev", "asr_gather_windows_dev", "asr_dtw_dev", "asr_dtw_batch_dev", "asr_dtw_subseq_batch_dev", "asr_dtw_follow_batch_dev", "asr_spectrogram_dev", "asr_debug_tune_report",
     "asr_seg_create", "asr_seg_set_window", "asr_seg_destroy", "asr_seg_predict_dev", "asr_systems_from_maps_dev",
     "asr_notes_from_map_dev", "asr_bars_from_map_dev",
     "asr_unroll_systems_dev", "asr_spectrogram_batch_dev", "asr_resample_batch_dev", "asr_resize_pages_dev",
@@ -209,6 +209,8 @@ def load_library(path=None):
         "asr_dtw_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 7),
         "asr_dtw_subseq_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64] + [c_void_p] * 4 +
                                      [c_int, c_int] + [c_void_p] * 5),
+        "asr_dtw_follow_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64] + [c_void_p] * 5 +
+                                     [c_int, c_int, c_void_p, c_void_p, c_int64] + [c_void_p] * 4),
         "asr_spectrogram_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_int, c_float, c_float, c_int64, c_int, c_void_p]),
         "asr_unroll_systems_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
@@ -633,6 +635,88 @@ class Engine(object):
             dq.free()
             dr.free()
         return [(float(cost[p]), int(start[p]), int(end[p]), int(ln[p]), pos[p]) for p in range(len(pairs))]
+
+    def dtw_follow_batch_dev(self, q_ptr, q_rows, r_ptr, r_rows, q_row, n_q, r_row, n_r, rows_before, dim, acc_ptr,
+                             org_ptr, state_len, state_off, want=True):
+        """asr_dtw_follow_batch_dev on device buffers: every pair's state (n_r[p] entries at state_off[p] of the float64
+        buffer acc_ptr and the int32 buffer org_ptr, state_len elements each) advances by the n_q[p] query rows at
+        q_row[p]; rows_before: the rows the state has consumed (0: fresh) -> per pair (cost float64 [n_q[p]], start,
+        pos int32 [n_q[p]]), or None with want=False (the state advances all the same)"""
+        i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
+        q_row, n_q, r_row, n_r, rows_before, state_off = map(i64, (q_row, n_q, r_row, n_r, rows_before, state_off))
+        n = n_q.size
+        if not (q_row.size == r_row.size == n_r.size == rows_before.size == state_off.size == n):
+            raise ValueError("dtw_follow_batch_dev: the per-pair tables differ in length")
+        tot = int(np.maximum(n_q, 0).sum())
+        cost = np.empty(tot, np.float64) if want else None
+        start, pos = (np.empty(tot, np.int32), np.empty(tot, np.int32)) if want else (None, None)
+        self._check(self.lib.asr_dtw_follow_batch_dev(self.ctx, q_ptr, int(q_rows), r_ptr, int(r_rows), q_row.ctypes.data,
+                                                      n_q.ctypes.data, r_row.ctypes.data, n_r.ctypes.data,
+                                                      rows_before.ctypes.data, n, int(dim), acc_ptr, org_ptr,
+                                                      int(state_len), state_off.ctypes.data,
+                                                      cost.ctypes.data if want else None,
+                                                      start.ctypes.data if want else None,
+                                                      pos.ctypes.data if want else None))
+        if not want:
+            return None
+        at = np.concatenate([[0], np.cumsum(n_q)])
+        return [(cost[at[p]:at[p + 1]], start[at[p]:at[p + 1]], pos[at[p]:at[p + 1]]) for p in range(n)]
+
+    def dtw_follow_batch(self, queries, refs, pairs, states=None):
+        """Streaming subsequence DTW (include/asr_hip.h: asr_dtw_follow_batch_dev) of pairs = [(query index, reference
+        index)] over lists of host (n, d) float32 code arrays, each uploaded once.  states: per pair None (fresh) or
+        (acc float64 [S], org int32 [S], rows consumed).  A query longer than 1024 rows runs as consecutive calls.
+        -> [(cost, start, pos, (acc, org, rows))] per pair"""
+        queries, refs = [_f32c(a) for a in queries], [_f32c(a) for a in refs]
+        pairs = [(int(a), int(b)) for a, b in pairs]
+        if not pairs:
+            return []
+        if not queries or not refs or queries[0].ndim != 2:
+            raise ValueError("dtw_follow_batch expects lists of (n,d) arrays")
+        dim = queries[0].shape[1]
+        if any(a.ndim != 2 or a.shape[1] != dim for a in queries + refs):
+            raise ValueError("dtw_follow_batch expects (n,d) arrays of one d")
+        if any(not (0 <= a < len(queries) and 0 <= b < len(refs)) for a, b in pairs):
+            raise ValueError("dtw_follow_batch: a pair names a sequence that is not there")
+        states = [None] * len(pairs) if states is None else list(states)
+        if len(states) != len(pairs):
+            raise ValueError("dtw_follow_batch: one state (or None) per pair")
+        nq, nr = np.array([a.shape[0] for a in queries], np.int64), np.array([a.shape[0] for a in refs], np.int64)
+        q0, r0 = np.concatenate([[0], np.cumsum(nq)]), np.concatenate([[0], np.cumsum(nr)])
+        cat_q, cat_r = np.concatenate(queries), np.concatenate(refs)
+        qi, ri = np.array([a for a, _ in pairs]), np.array([b for _, b in pairs])
+        if (nq[qi] < 1).any():
+            raise ValueError("dtw_follow_batch: an empty query")
+        s_off = np.concatenate([[0], np.cumsum(nr[ri])])
+        acc, org = np.full(int(s_off[-1]), np.nan), np.zeros(int(s_off[-1]), np.int32)
+        before = np.zeros(len(pairs), np.int64)
+        for p, st in enumerate(states):
+            if st is not None and int(st[2]) > 0:
+                a, o = np.asarray(st[0], np.float64), np.asarray(st[1], np.int32)
+                if a.shape != (nr[ri[p]],) or o.shape != a.shape:
+                    raise ValueError("dtw_follow_batch: pair %d's state does not have its reference's length" % p)
+                acc[s_off[p]:s_off[p + 1]], org[s_off[p]:s_off[p + 1]], before[p] = a, o, int(st[2])
+        dq = self.alloc(max(cat_q.nbytes, 4)).upload(cat_q)
+        dr = self.alloc(max(cat_r.nbytes, 4)).upload(cat_r)
+        da, do = self.alloc(max(acc.nbytes, 8)).upload(acc), self.alloc(max(org.nbytes, 4)).upload(org)
+        parts = [[] for _ in pairs]
+        try:
+            for c0 in range(0, int(nq[qi].max()), 1024):
+                live = np.flatnonzero(nq[qi] > c0)
+                n_now = np.minimum(nq[qi][live] - c0, 1024)
+                res = self.dtw_follow_batch_dev(dq.ptr, cat_q.shape[0], dr.ptr, cat_r.shape[0], q0[qi][live] + c0, n_now,
+                                                r0[ri][live], nr[ri][live], before[live] + c0, dim, da.ptr, do.ptr,
+                                                acc.size, s_off[:-1][live])
+                for p, item in zip(live, res):
+                    parts[p].append(item)
+            acc, org = da.download(acc.shape, np.float64), do.download(org.shape, np.int32)
+        finally:
+            for b in (dq, dr, da, do):
+                b.free()
+        return [(np.concatenate([c for c, _, _ in parts[p]]), np.concatenate([s for _, s, _ in parts[p]]),
+                 np.concatenate([e for _, _, e in parts[p]]),
+                 (acc[s_off[p]:s_off[p + 1]].copy(), org[s_off[p]:s_off[p + 1]].copy(), int(before[p] + nq[qi[p]])))
+                for p in range(len(pairs))]
 
     def spectrogram_dev(self, samples_ptr, n_samples, frame_size, hop, window, fb_start, fb_len, fb_weights, n_frames,
                         out_ptr, mul=1.0, add=1.0, transposed=True):

@@ -145,6 +145,44 @@ def subseq_dtw_host(dists):
     return float(cost), j, end, (np.array(rows[::-1], np.int64), np.array(cols[::-1], np.int64))
 
 
+def follow_dtw_host(dists, state=None):
+    """The definition of asr_dtw_follow_batch_dev restated in numpy: the rows of the float64 distance matrix `dists`
+    (B new query rows x S reference columns) continue state = (acc float64 [S], org int32 [S], rows consumed), or start
+    a stream (state None or 0 rows consumed: the first row is the free start).  Every cell carries, beside its
+    accumulated cost, the column at which its best path started - the origin of the predecessor _traceback's rule
+    picks (diagonal, up, left; strict <) - so per row the first minimum gives (cost, start, pos) without a traceback:
+    for every row this is subseq_dtw_host on all rows up to it, whatever the cut into calls.
+    -> (cost float64 [B], start int32 [B], pos int32 [B], new state).  Anti-diagonals are evaluated as vectors."""
+    D = np.ascontiguousarray(dists, dtype=np.float64)
+    if D.ndim != 2 or D.shape[0] < 1 or D.shape[1] < 1:
+        raise ValueError("follow_dtw_host expects a (B, S) matrix with B, S >= 1")
+    B, S = D.shape
+    n0 = 0 if state is None else int(state[2])
+    A = np.full((B + 1, S + 1), np.inf)                   # A[i + 1][j + 1]: cell (i, j); row 0 is the carried row
+    O = np.zeros((B + 1, S + 1), np.int32)
+    if n0 == 0:
+        A[1, 1:], O[1, 1:], first = D[0], np.arange(S), 1
+    else:
+        acc, org = np.asarray(state[0], np.float64), np.asarray(state[1], np.int32)
+        if acc.shape != (S,) or org.shape != (S,):
+            raise ValueError("follow_dtw_host: the state does not have the reference's length")
+        A[0, 1:], O[0, 1:], first = acc, org, 0
+    for d in range(first, B + S - 1):
+        i = np.arange(max(first, d - S + 1), min(d, B - 1) + 1)
+        j = d - i
+        dg, up, lf = A[i, j], A[i, j + 1], A[i + 1, j]
+        take_up = up < dg
+        bst = np.where(take_up, up, dg)
+        o = np.where(take_up, O[i, j + 1], O[i, j])
+        A[i + 1, j + 1] = D[i, j] + np.fmin(dg, np.fmin(up, lf))
+        O[i + 1, j + 1] = np.where(lf < bst, O[i + 1, j], o)
+    rows = np.arange(B)
+    pos = np.argmin(A[1:, 1:], axis=1)
+    cost = A[rows + 1, pos + 1] / (n0 + rows + 1)
+    start = O[rows + 1, pos + 1]
+    return cost, start.astype(np.int32), pos.astype(np.int32), (A[B, 1:].copy(), O[B, 1:].copy(), n0 + B)
+
+
 def cosine_dists_host(a, b):
     """float64 cosine distances of float32 code rows in the library's operation order (csrc/dist64.h): two accumulators
     over even / odd elements, summed, an odd tail element last; norms = sqrt of the same sum over squares;

@@ -31,6 +31,15 @@ prints the rank of the own piece by vote and by alignment cost and the pixel dis
 the onset map interpolated at the excerpt's first and last window centres; --dump_results writes them to
 location_<tag>_A2S.yaml.  The error is a report, not a gate.
 
+--follow (A2S only) is score following, --locate while the recording still streams: per test piece the candidates are
+the top --locate_pieces of the vote on its first performance (detect_scores); the performance is then pushed through a
+piece_identification.ScoreFollower in blocks of --block_frames frames, windows --step_spec frames apart (one
+asr_dtw_follow_batch_dev call per block for all candidates; the session keeps one accumulated row per candidate, so a
+block costs its own windows only and the recording may be of any length).  Per piece it prints whether the own piece is
+a candidate, the share of windows at which it has the least cost, and the median absolute pixel distance of its found
+position from the onset map interpolated at each window's centre; --dump_results writes them to
+following_<tag>_A2S.yaml.  A report, not a gate.
+
 The microphone and the GUI of the live server, audio decoding (--real_audio) and MSMD loading are not part of this
 implementation.  sheet_audio_server.py is the S2A direction (sheet -> audio) of the same driver.
 """
@@ -41,8 +50,8 @@ import numpy as np
 import yaml
 
 from . import audio2sheet_align
-from .piece_identification import (EmbeddingDB, detect_performances, detect_scores, locate_scores, rank_summary,
-                                   track_scores)
+from .piece_identification import (EmbeddingDB, ScoreFollower, detect_performances, detect_scores, locate_scores,
+                                   rank_summary, track_scores)
 from .utils.data_pools import NO_AUGMENT, AudioScoreRetrievalPool
 
 # per direction: data-base flag, data-base file, data-base view, what a query finds (the reference's summary line)
@@ -83,8 +92,12 @@ def _arguments(argv, direction):
         p.add_argument("--locate", action="store_true",
                        help="locate a seeded excerpt of every test piece in the scores of the data base")
         p.add_argument("--excerpt_frames", type=int, default=400, help="frames of the excerpt (--locate)")
-        p.add_argument("--locate_pieces", type=int, default=5, help="candidates of the vote that are aligned (--locate)")
-        p.add_argument("--step_spec", type=int, default=2, help="frames between the excerpt's windows (--locate)")
+        p.add_argument("--locate_pieces", type=int, default=5,
+                       help="candidates of the vote that are aligned (--locate, --follow)")
+        p.add_argument("--step_spec", type=int, default=2, help="frames between the query windows (--locate, --follow)")
+        p.add_argument("--follow", action="store_true",
+                       help="follow every test piece's first performance through the scores of the vote's candidates")
+        p.add_argument("--block_frames", type=int, default=20, help="frames pushed per block (--follow)")
     p.add_argument("--seed", type=int, default=23)
     return p.parse_args(argv)
 
@@ -212,6 +225,61 @@ def report_location(entries, res_file=None):
     return entries
 
 
+def following_file(param_file, direction):
+    """result_file's name with following_ in place of retrieval_"""
+    return param_file.replace("params_", "following_").replace(".pkl", "_%s.yaml") % direction
+
+
+def follow(engine, db, pool, names, n_candidates, n_pieces, step_spec, block_frames):
+    """every piece's first performance streamed through a ScoreFollower against the vote's top n_pieces -> one dict per
+    piece: name, candidate (is the own piece one?), windows, best_share (share of the windows at which the own piece has
+    the least cost), median_error (median |x - truth| in pixels, truth = the onset map at each window's centre frame;
+    None when the own piece is no candidate or no window was completed)"""
+    if block_frames < 1:
+        raise ValueError("block_frames must be >= 1")
+    specs = [spec[0] for spec in pool.specs]
+    win_w = int(pool.spec_dim[1])
+    votes = detect_scores(engine, db, specs, top_k=n_pieces, n_candidates=n_candidates, spec_shape=tuple(pool.spec_dim))
+    out = []
+    for name, spec, o2c, (cands, _) in zip(names, specs, pool.o2c_maps, votes):
+        session = ScoreFollower(engine, db, cands, step_spec=step_spec, spec_shape=tuple(pool.spec_dim),
+                                sheet_columns=pool_sheet_columns(pool, len(db)))
+        try:
+            res = [session.push(spec[:, f:f + block_frames]) for f in range(0, spec.shape[1], block_frames)]
+        finally:
+            session.close()
+        frames = np.concatenate([r.frames for r in res])
+        entry = dict(name=str(name), candidate=name in cands, windows=int(len(frames)), best_share=0.0, median_error=None)
+        if entry["candidate"] and len(frames):
+            own = list(cands).index(name)
+            o2c = np.asarray(o2c[0], np.float64)
+            truth = np.interp(frames + win_w // 2, o2c[:, 0], o2c[:, 1])
+            entry.update(best_share=float(np.mean(np.concatenate([r.best for r in res]) == own)),
+                         median_error=float(np.median(np.abs(np.concatenate([r.x[:, own] for r in res]) - truth))))
+        out.append(entry)
+    return out
+
+
+def report_following(entries, res_file=None):
+    for e in entries:
+        if e["median_error"] is not None:
+            print("own piece a candidate, least cost at %.2f of %5d windows, median off by %6.1f px  %s"
+                  % (e["best_share"], e["windows"], e["median_error"], e["name"]))
+        else:
+            print("own piece %s, %5d windows                                            %s"
+                  % ("a candidate" if e["candidate"] else "not among the candidates", e["windows"], e["name"]))
+    hit = [e for e in entries if e["median_error"] is not None]
+    if hit:
+        print("own piece a candidate: %d of %d; median share of windows with the least cost %.2f, median error %.1f px"
+              % (len(hit), len(entries), float(np.median([e["best_share"] for e in hit])),
+                 float(np.median([e["median_error"] for e in hit]))))
+    if res_file is not None:
+        with open(res_file, "w") as fp:
+            yaml.dump(entries, fp, default_flow_style=False)
+        print("following of %d pieces written to %s" % (len(entries), res_file))
+    return entries
+
+
 def run(argv, direction):
     d = DIRECTIONS[direction]
     args = _arguments(argv, direction)
@@ -237,6 +305,11 @@ def run(argv, direction):
         return report_location(locate(engine, db, pool, data["names"], args.n_candidates, args.excerpt_frames,
                                       args.locate_pieces, args.step_spec, args.seed),
                                res_file=location_file(param_file, direction) if args.dump_results else None)
+    if getattr(args, "follow", False):
+        print("\nFollowing every test piece through the scores:")
+        return report_following(follow(engine, db, pool, data["names"], args.n_candidates, args.locate_pieces,
+                                       args.step_spec, args.block_frames),
+                                res_file=following_file(param_file, direction) if args.dump_results else None)
     if not args.full_eval:
         raise SystemExit("the live server loop (microphone, GUI) is not part of this implementation; use --full_eval")
 

@@ -807,6 +807,117 @@ int asr_dtw_subseq_batch_dev(asr_ctx *ctx, const float *q_dev, int64_t q_rows, c
     return mark_main(ctx);
 }
 
+int asr_dtw_follow_batch_dev(asr_ctx *ctx, const float *q_dev, int64_t q_rows, const float *r_dev, int64_t r_rows,
+                             const int64_t *q_row, const int64_t *n_q, const int64_t *r_row, const int64_t *n_r,
+                             const int64_t *rows_before, int n_pairs, int dim, double *acc_dev, int32_t *org_dev,
+                             int64_t state_len, const int64_t *state_off, double *cost, int32_t *start, int32_t *pos) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_pairs < 0 || dim < 1 || dim > 64 || q_rows < 0 || r_rows < 0 || state_len < 0)
+        return fail(ctx, ASR_ERR_INVALID, "dtw_follow: bad sizes n_pairs=%d dim=%d (1..64) q_rows=%lld r_rows=%lld "
+                    "state_len=%lld", n_pairs, dim, (long long)q_rows, (long long)r_rows, (long long)state_len);
+    if (n_pairs == 0) return ASR_OK;
+    if (!q_dev || !r_dev || !q_row || !n_q || !r_row || !n_r || !rows_before || !acc_dev || !org_dev || !state_off)
+        return fail(ctx, ASR_ERR_INVALID, "dtw_follow: NULL argument");
+    int64_t tot_rows = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        if (n_q[p] < 1 || n_q[p] > 1024 || n_r[p] < 1 || n_r[p] > 100000 || rows_before[p] < 0 ||
+            rows_before[p] >= (1ll << 31) - n_q[p])
+            return fail(ctx, ASR_ERR_INVALID, "dtw_follow: pair %d has bad sizes n_q=%lld (1..1024) n_r=%lld (1..100000) "
+                        "rows_before=%lld (rows_before + n_q < 2^31)", p, (long long)n_q[p], (long long)n_r[p],
+                        (long long)rows_before[p]);
+        if (q_row[p] < 0 || q_row[p] > q_rows - n_q[p] || r_row[p] < 0 || r_row[p] > r_rows - n_r[p])
+            return fail(ctx, ASR_ERR_INVALID, "dtw_follow: pair %d reads rows outside its buffers (q %lld+%lld of %lld, r "
+                        "%lld+%lld of %lld)", p, (long long)q_row[p], (long long)n_q[p], (long long)q_rows,
+                        (long long)r_row[p], (long long)n_r[p], (long long)r_rows);
+        if (state_off[p] < 0 || state_off[p] > state_len - n_r[p])
+            return fail(ctx, ASR_ERR_INVALID, "dtw_follow: pair %d keeps its state outside the buffers (%lld+%lld of %lld)",
+                        p, (long long)state_off[p], (long long)n_r[p], (long long)state_len);
+        tot_rows += n_q[p];
+    }
+    {   // two pairs that share state entries would race
+        std::vector<int> by_off(n_pairs);
+        for (int p = 0; p < n_pairs; ++p) by_off[p] = p;
+        std::sort(by_off.begin(), by_off.end(), [&](int a, int b) { return state_off[a] < state_off[b]; });
+        for (int k = 1; k < n_pairs; ++k) {
+            const int a = by_off[k - 1], b = by_off[k];
+            if (state_off[a] + n_r[a] > state_off[b])
+                return fail(ctx, ASR_ERR_INVALID, "dtw_follow: the states of pairs %d and %d overlap", a, b);
+        }
+    }
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    int rc = ensure_norms(ctx, q_rows, r_rows);
+    if (rc != ASR_OK) return rc;
+    rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    // ASR_DTW_SUBSEQ_LDS_CAP=<bytes> (debug): as in asr_dtw_subseq_batch_dev.  ASR_DTW_BUDGET_MB has nothing to chunk:
+    // the workspace is the pair table and 16 bytes per new query row
+    int lds_dev = 0;
+    if (hipDeviceGetAttribute(&lds_dev, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->cfg.device) != hipSuccess)
+        lds_dev = 65536;
+    const size_t lds_limit = (size_t)std::min<int64_t>(lds_dev, dtw_env("ASR_DTW_SUBSEQ_LDS_CAP", 1 << 30));
+
+    // pair table | cost | start | pos, 256-byte aligned sections
+    const size_t o_cost = dtw_align((size_t)n_pairs * sizeof(asr::FollowPair));
+    const size_t o_start = o_cost + dtw_align((size_t)tot_rows * sizeof(double));
+    const size_t o_pos = o_start + dtw_align((size_t)tot_rows * sizeof(int32_t));
+    const size_t need = o_pos + dtw_align((size_t)tot_rows * sizeof(int32_t));
+    if (need > ctx->subseq_ws_bytes) {
+        rc = sync_all(ctx);
+        if (rc != ASR_OK) return rc;
+        if (ctx->subseq_ws) ASR_HIP(ctx, hipFree(ctx->subseq_ws));
+        ctx->subseq_ws = nullptr; ctx->subseq_ws_bytes = 0;
+        ASR_HIP(ctx, hipMalloc(&ctx->subseq_ws, need));
+        ctx->subseq_ws_bytes = need;
+    }
+
+    double tot_cells = 0;
+    for (int p = 0; p < n_pairs; ++p) tot_cells += (double)n_q[p] * (double)n_r[p];
+    ProfScope ps(ctx, "dtw_follow", 0, 2.0 * dim * tot_cells, 0.0);
+    ASR_HIP(ctx, asr::launch_row_norms(ctx->stream, q_dev, q_rows, dim, dim, ctx->norm1));
+    ASR_HIP(ctx, asr::launch_row_norms(ctx->stream, r_dev, r_rows, dim, dim, ctx->norm2));
+    // the table is ordered by size class (waves = ceil(n_q / 64)): one launch per class present
+    std::vector<asr::FollowPair> desc;
+    desc.reserve(n_pairs);
+    std::vector<int64_t> out_at(n_pairs);
+    int class_n[17] = {0};
+    int64_t rows = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        out_at[p] = rows;
+        rows += n_q[p];
+        class_n[(n_q[p] + 63) / 64] += 1;
+    }
+    for (int w = 1; w <= 16; ++w)
+        for (int p = 0; p < n_pairs && class_n[w] > 0; ++p) {
+            if ((n_q[p] + 63) / 64 != w) continue;
+            asr::FollowPair P;
+            P.B = (int32_t)n_q[p]; P.S = (int32_t)n_r[p];
+            P.q_row = q_row[p]; P.r_row = r_row[p];
+            P.state = state_off[p]; P.out = out_at[p]; P.n0 = (int32_t)rows_before[p]; P.pad = 0;
+            desc.push_back(P);
+        }
+    char *ws = (char *)ctx->subseq_ws;
+    asr::FollowPair *d_pairs = (asr::FollowPair *)ws;
+    double *d_cost = (double *)(ws + o_cost);
+    int32_t *d_start = (int32_t *)(ws + o_start), *d_pos = (int32_t *)(ws + o_pos);
+    ASR_HIP(ctx, hipMemcpyAsync(d_pairs, desc.data(), desc.size() * sizeof(asr::FollowPair), hipMemcpyHostToDevice,
+                                ctx->stream));
+    {
+        ProfScope pk(ctx, "dtw_follow_wave", 0, 0.0, 0.0);      // the kernels alone (the outer scope has the copies too)
+        int at = 0;
+        for (int w = 1; w <= 16; ++w) {
+            if (class_n[w] == 0) continue;
+            ASR_HIP(ctx, asr::launch_dtw_follow(ctx->stream, d_pairs + at, class_n[w], w, lds_limit, q_dev, ctx->norm1,
+                                                r_dev, ctx->norm2, dim, acc_dev, org_dev, d_cost, d_start, d_pos));
+            at += class_n[w];
+        }
+    }
+    if (cost) ASR_HIP(ctx, hipMemcpyAsync(cost, d_cost, tot_rows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (start) ASR_HIP(ctx, hipMemcpyAsync(start, d_start, tot_rows * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (pos) ASR_HIP(ctx, hipMemcpyAsync(pos, d_pos, tot_rows * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    ASR_HIP(ctx, hipStreamSynchronize(ctx->stream));       // `desc` is read by the copy; the outputs are the caller's
+    return mark_main(ctx);
+}
+
 int asr_spectrogram_dev(asr_ctx *ctx, const float *samples_dev, int64_t n_samples, int frame_size, double hop,
                         const float *window, const int32_t *fb_start, const int32_t *fb_len, const float *fb_weights,
                         int n_filters, float mul, float add, int64_t n_frames, int transposed, float *out_dev) {

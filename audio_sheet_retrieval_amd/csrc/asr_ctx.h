@@ -260,7 +260,7 @@ struct asr_ctx {
     void *dtw_ws = nullptr;                   // asr_dtw_batch_dev: one chunk's distances, directions, rings, paths
     size_t dtw_ws_bytes = 0;
     void *subseq_ws = nullptr;                // asr_dtw_subseq_batch_dev: one chunk's pair table, direction bytes, results
-    size_t subseq_ws_bytes = 0;
+    size_t subseq_ws_bytes = 0;               // (asr_dtw_follow_batch_dev keeps its pair table and per-row results here too)
     void *vote_ws = nullptr;                  // asr_piece_vote_batch_dev: results, targets, global-path counters + keys
     size_t vote_ws_bytes = 0;
     void *post_ws = nullptr;                  // asr_systems_from_maps_dev: one chunk of pages' tables, masks and labels

@@ -237,6 +237,24 @@ hipError_t launch_dtw_subseq(hipStream_t s, const SubseqPair *pairs, int n_pairs
                              const float *q, const double *nq, const float *r, const double *nr, int dim, uint8_t *dir,
                              double *cost, int32_t *start, int32_t *end, int32_t *path_len, int32_t *pos);
 
+// ---- streaming subsequence DTW (dtw_follow_kernels.hip): a block of query rows continues a carried row, one workgroup
+// per pair, no per-cell memory
+struct FollowPair {
+    int32_t B, S;          // new query rows (one lane each, <= 1024) / reference rows
+    int64_t q_row, r_row;  // first code row in q / r
+    int64_t state;         // first of the pair's S entries in acc / org
+    int64_t out;           // first of the pair's B entries in cost / start / pos
+    int32_t n0;            // query rows the state has consumed (0: fresh, the state is not read)
+    int32_t pad;
+};
+// as dtw_subseq_lds_bytes (same ring)
+size_t dtw_follow_lds_bytes(int waves, int dim);
+// `pairs`: n_pairs entries that all take `waves` = ceil(B / 64) waves; lds_limit, nq / nr as for launch_dtw_subseq.
+// acc / org: the state buffers, updated in place; the pairs' ranges must not overlap.
+hipError_t launch_dtw_follow(hipStream_t s, const FollowPair *pairs, int n_pairs, int waves, size_t lds_limit,
+                             const float *q, const double *nq, const float *r, const double *nr, int dim, double *acc,
+                             int32_t *org, double *cost, int32_t *start, int32_t *pos);
+
 // ---- piece-identification vote (audio_sheet_server.py:213-300) -----------------
 hipError_t launch_slice_windows(hipStream_t s, const float *src, int64_t T, int r0, int win_h, int win_w,
                                 const int32_t *starts_dev, int n, float *out);

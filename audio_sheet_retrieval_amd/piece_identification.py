@@ -8,6 +8,9 @@ the resident data base, vote histogram and selection (csrc/piece_vote_kernels.hi
 The server's default mode, the running vote of AudioSheetServer.run (:83-211), is track_scores / track_score (whole
 recordings, batched) and PieceTracker (blocks of new frames): music gate and sliding vote in csrc/track_kernels.hip,
 track_score_host the numpy restatement they are tested against.
+
+Where in the score: locate_scores places a finished excerpt (subsequence DTW against the vote's candidates), and
+ScoreFollower / follow_scores follow a stream block by block, the same alignment carried from call to call.
 """
 from __future__ import annotations
 
@@ -753,8 +756,8 @@ def locate_window_plan(shapes, offsets, win_shape, step_spec):
     return starts, (np.concatenate(desc) if desc else np.zeros((0, 9), np.float64))
 
 
-def _locate(engine, sheet_db, spectrograms, n_pieces, step_spec, n_candidates, n_samples, spec_shape, segments,
-            sheet_columns, max_windows, host):
+def _score_tables(engine, sheet_db, segments, sheet_columns):
+    """the checked (segments, sheet_columns) of locate_scores and the follow routes, with their defaults"""
     segments = piece_segments(sheet_db.ids) if segments is None else {int(k): (int(v[0]), int(v[1]))
                                                                       for k, v in dict(segments).items()}
     for piece, (first, n) in segments.items():
@@ -766,6 +769,12 @@ def _locate(engine, sheet_db, spectrograms, n_pieces, step_spec, n_candidates, n
     sheet_columns = np.asarray(sheet_columns, np.float64).reshape(-1)
     if sheet_columns.size != len(sheet_db):
         raise ValueError("%d sheet_columns for %d data-base rows" % (sheet_columns.size, len(sheet_db)))
+    return segments, sheet_columns
+
+
+def _locate(engine, sheet_db, spectrograms, n_pieces, step_spec, n_candidates, n_samples, spec_shape, segments,
+            sheet_columns, max_windows, host):
+    segments, sheet_columns = _score_tables(engine, sheet_db, segments, sheet_columns)
     dev, owned = _to_device(engine, spectrograms if _is_device(spectrograms) else list(spectrograms))
     try:
         n_in = len(dev.shapes)
@@ -851,3 +860,225 @@ def locate_scores_host(engine, sheet_db, spectrograms, n_pieces=5, step_spec=2, 
     alignment.subseq_dtw_host on alignment.cosine_dists_host - what the device path is tested against"""
     return _locate(engine, sheet_db, spectrograms, n_pieces, step_spec, n_candidates, n_samples, tuple(spec_shape),
                    segments, sheet_columns, max_windows, host=True)
+
+
+# ---- where in the score is the music now?  the subsequence DTW carried from block to block (asr_dtw_follow_batch_dev) ----
+class FollowResult(object):
+    """Score following per query window: frames (n,) the first stream column of each window; per window and candidate
+    (n, candidates): cost (float64), row / start_row (rows of the piece's segment where the best path so far ends /
+    started), x / start_x (their strip coordinates); best (n,) the candidate of least cost, the earlier one on equal
+    costs.  pieces: the candidates' piece ids, names: their names."""
+
+    def __init__(self, frames, cost, row, start_row, x, start_x, pieces, names):
+        self.frames, self.cost, self.row, self.start_row, self.x, self.start_x = frames, cost, row, start_row, x, start_x
+        self.best = np.argmin(cost, axis=1).astype(np.int64) if cost.shape[1] else np.zeros(len(frames), np.int64)
+        self.pieces, self.names = list(pieces), list(names)
+
+
+def follow_window_plan(n_before, n_new, win_w, step_spec):
+    """The bookkeeping of a followed stream, whose windows are those at stream columns k * step_spec whatever the
+    block cut: after n_before columns, a block of n_new more completes the windows -> (their stream columns, the
+    stream column from which the session carries on: the next unfinished window's start, or the stream's end when
+    that start lies further on)"""
+    if step_spec < 1 or win_w < 1 or n_before < 0 or n_new < 0:
+        raise ValueError("step_spec and win_w must be >= 1, the column counts >= 0")
+    done = lambda T: 0 if T < win_w else (T - win_w) // step_spec + 1
+    k0, k1, T = done(n_before), done(n_before + n_new), n_before + n_new
+    return np.arange(k0, k1, dtype=np.int64) * step_spec, min(k1 * step_spec, T)
+
+
+def _follow_candidates(sheet_db, pieces, segments):
+    """piece ids of a candidate list of ids or names, each with a segment"""
+    by_name = {v: k for k, v in sheet_db.id_to_name.items()}
+    out = []
+    for piece in pieces:
+        piece = by_name[piece] if isinstance(piece, str) and piece in by_name else piece
+        if isinstance(piece, str) or int(piece) not in segments:
+            raise ValueError("candidate %r is no piece of the data base with a segment" % (piece,))
+        out.append(int(piece))
+    return out
+
+
+def _follow_result(sheet_db, segments, sheet_columns, pieces, frames, per_cand):
+    """FollowResult of per candidate (cost, start, pos) over the windows at `frames`"""
+    n = len(frames)
+    cost = np.zeros((n, len(pieces)), np.float64)
+    row, start_row = np.zeros((n, len(pieces)), np.int32), np.zeros((n, len(pieces)), np.int32)
+    x, start_x = np.zeros((n, len(pieces)), np.float64), np.zeros((n, len(pieces)), np.float64)
+    for c, (piece, (cst, start, pos)) in enumerate(zip(pieces, per_cand)):
+        first = segments[piece][0]
+        cost[:, c], row[:, c], start_row[:, c] = cst, pos, start
+        x[:, c] = sheet_columns[first + np.asarray(pos, np.int64)]
+        start_x[:, c] = sheet_columns[first + np.asarray(start, np.int64)]
+    return FollowResult(np.asarray(frames, np.int64), cost, row, start_row, x, start_x, pieces,
+                        [sheet_db.id_to_name[p] for p in pieces])
+
+
+FOLLOW_MAX_ROWS = 1024      # query rows of one pair of one asr_dtw_follow_batch_dev call
+
+
+class ScoreFollower(object):
+    """Score following as a streaming session, the companion of PieceTracker: push(columns) takes a (bins, n >= 1)
+    block of new spectrogram columns and returns the FollowResult of the windows this block completes - the windows at
+    stream columns k * step_spec, whatever the block cut - against every candidate piece (`pieces`: ids or names, for
+    example PieceTracker's current leaders or detect_scores' top few).  Per window and candidate it is what
+    locate_scores' alignment gives for the stream so far (subsequence DTW, free start and end on the score axis), but
+    a block costs its own rows only: the session keeps, per candidate, the last accumulated row and the path origins
+    in two device buffers (asr_dtw_follow_batch_dev's state; never downloaded in push) and the spectrogram columns from
+    the next unfinished window's start on.  Every block is one gather and one tower call over its windows and one
+    follow call for all candidates (one per 1024 windows).  segments, sheet_columns: as in locate_scores.  close()
+    frees the state."""
+
+    def __init__(self, engine, sheet_db, pieces, step_spec=2, spec_shape=(92, 42), segments=None, sheet_columns=None):
+        if step_spec < 1 or int(step_spec) != step_spec:
+            raise ValueError("step_spec must be an int >= 1")
+        self.engine, self.db, self.step_spec, self.spec_shape = engine, sheet_db, int(step_spec), tuple(spec_shape)
+        self.segments, self.sheet_columns = _score_tables(engine, sheet_db, segments, sheet_columns)
+        self.pieces = _follow_candidates(sheet_db, pieces, self.segments)
+        self._r_row = np.array([self.segments[p][0] for p in self.pieces], np.int64)
+        self._n_r = np.array([self.segments[p][1] for p in self.pieces], np.int64)
+        self._state_off = np.concatenate([[0], np.cumsum(self._n_r)]).astype(np.int64)
+        self._state_len = int(self._state_off[-1])
+        self._d_acc = engine.alloc(max(self._state_len * 8, 8))
+        self._d_org = engine.alloc(max(self._state_len * 4, 4))
+        self.n_columns = 0                                  # stream columns pushed so far
+        self.n_windows = 0                                  # windows followed so far
+        self._col0 = 0                                      # stream column of the first carried column
+        self._carry = np.zeros((self.spec_shape[0], 0), np.float32)
+
+    def close(self):
+        for b in (self._d_acc, self._d_org):
+            if b is not None:
+                b.free()
+        self._d_acc = self._d_org = None
+
+    def state(self):
+        """the downloaded state per candidate: (acc, org, windows followed) - for tests and checkpoints"""
+        acc = self._d_acc.download((self._state_len,), np.float64)
+        org = self._d_org.download((self._state_len,), np.int32)
+        at = self._state_off
+        return [(acc[at[c]:at[c + 1]], org[at[c]:at[c + 1]], self.n_windows) for c in range(len(self.pieces))]
+
+    def push(self, columns):
+        cols = np.ascontiguousarray(columns, dtype=np.float32)
+        win_h, win_w = self.spec_shape
+        if cols.ndim != 2 or cols.shape[0] != win_h or cols.shape[1] < 1:
+            raise ValueError("expected a (%d, n >= 1) block of columns, got shape %r" % (win_h, cols.shape))
+        if self._d_acc is None:
+            raise ValueError("the session is closed")
+        eng, db, C = self.engine, self.db, len(self.pieces)
+        starts, carry_from = follow_window_plan(self.n_columns, cols.shape[1], win_w, self.step_spec)
+        block = np.ascontiguousarray(np.hstack((self._carry, cols)))
+        m = len(starts)
+        per_cand = [(np.zeros(0), np.zeros(0, np.int32), np.zeros(0, np.int32))] * C
+        if m and C:
+            d_src = db.scratch("follow_src", block.nbytes).upload(block)
+            d_win, d_codes = db.scratch("follow_win", m * win_h * win_w * 4), db.scratch("follow_codes", m * 32 * 4)
+            embed_windows_dev(eng, 2, d_src.ptr, block.size, _identity_desc(0, win_h, block.shape[1], 0, starts - self._col0),
+                              self.spec_shape, d_win, d_codes, m)
+            parts = []
+            for c0 in range(0, m, FOLLOW_MAX_ROWS):
+                mm = min(FOLLOW_MAX_ROWS, m - c0)
+                parts.append(eng.dtw_follow_batch_dev(d_codes.ptr, m, db._d_codes.ptr, len(db), [c0] * C, [mm] * C,
+                                                      self._r_row, self._n_r, [self.n_windows + c0] * C, 32,
+                                                      self._d_acc.ptr, self._d_org.ptr, self._state_len,
+                                                      self._state_off[:-1]))
+            per_cand = [tuple(np.concatenate([part[c][k] for part in parts]) for k in range(3)) for c in range(C)]
+        self.n_columns += cols.shape[1]
+        self._carry = np.ascontiguousarray(block[:, carry_from - self._col0:])
+        self._col0 = carry_from
+        self.n_windows += m
+        return _follow_result(db, self.segments, self.sheet_columns, self.pieces, starts, per_cand)
+
+
+def _follow(engine, sheet_db, spectrograms, pieces, step_spec, spec_shape, segments, sheet_columns, max_windows, host):
+    segments, sheet_columns = _score_tables(engine, sheet_db, segments, sheet_columns)
+    if step_spec < 1:
+        raise ValueError("step_spec must be >= 1")
+    win_h, win_w = spec_shape
+    dev, owned = _to_device(engine, spectrograms if _is_device(spectrograms) else list(spectrograms))
+    try:
+        n_in = len(dev.shapes)
+        cands = [_follow_candidates(sheet_db, p, segments) for p in pieces]
+        if len(cands) != n_in:
+            raise ValueError("%d candidate lists for %d recordings" % (len(cands), n_in))
+        if n_in == 0:
+            return []
+        starts, desc = [], []
+        for i, ((rows, T), off) in enumerate(zip(dev.shapes, dev.offsets)):
+            if rows != win_h:
+                raise ValueError("input %d: expected a (%d, frames) array, got shape %r" % (i, win_h, (rows, T)))
+            st = follow_window_plan(0, T, win_w, step_spec)[0]
+            starts.append(st)
+            desc.append(_identity_desc(off, rows, T, 0, st))
+        desc = np.concatenate(desc)
+        n_q = np.array([len(st) for st in starts], np.int64)
+        q_at = np.concatenate([[0], np.cumsum(n_q)])
+        n_win = int(n_q.sum())
+        pairs = [(e, piece) for e in range(n_in) for piece in cands[e]]
+        res = [[] for _ in pairs]
+        bufs = []
+        try:
+            if n_win and pairs:
+                chunk = max(1, min(n_win, int(max_windows)))
+                d_win = engine.alloc(chunk * win_h * win_w * 4)
+                d_codes = engine.alloc(n_win * 32 * 4)
+                bufs += [d_win, d_codes]
+                embed_windows_dev(engine, 2, dev.buf.ptr, dev.buf.nbytes // 4, desc, spec_shape, d_win, d_codes, chunk)
+                if host:
+                    from . import alignment
+                    codes = d_codes.download((n_win, 32), np.float32)
+                    for k, (e, piece) in enumerate(pairs):
+                        if n_q[e]:
+                            first, n = segments[piece]
+                            d = alignment.cosine_dists_host(codes[q_at[e]:q_at[e + 1]], sheet_db.codes[first:first + n])
+                            res[k].append(alignment.follow_dtw_host(d)[:3])
+                else:
+                    n_r = np.array([segments[p][1] for _, p in pairs], np.int64)
+                    r_row = np.array([segments[p][0] for _, p in pairs], np.int64)
+                    q_of = np.array([e for e, _ in pairs], np.int64)
+                    s_off = np.concatenate([[0], np.cumsum(n_r)]).astype(np.int64)
+                    d_acc, d_org = engine.alloc(int(s_off[-1]) * 8), engine.alloc(int(s_off[-1]) * 4)
+                    bufs += [d_acc, d_org]
+                    for c0 in range(0, int(n_q.max()), FOLLOW_MAX_ROWS):
+                        live = np.flatnonzero(n_q[q_of] > c0)
+                        out = engine.dtw_follow_batch_dev(
+                            d_codes.ptr, n_win, sheet_db._d_codes.ptr, len(sheet_db), q_at[q_of[live]] + c0,
+                            np.minimum(n_q[q_of[live]] - c0, FOLLOW_MAX_ROWS), r_row[live], n_r[live],
+                            np.full(len(live), c0, np.int64), 32, d_acc.ptr, d_org.ptr, int(s_off[-1]), s_off[:-1][live])
+                        for k, item in zip(live, out):
+                            res[k].append(item)
+        finally:
+            for b in bufs:
+                b.free()
+    finally:
+        if owned:
+            dev.buf.free()
+    empty = (np.zeros(0), np.zeros(0, np.int32), np.zeros(0, np.int32))
+    results, k = [], 0
+    for e in range(n_in):
+        per_cand = []
+        for _ in cands[e]:
+            per_cand.append(tuple(np.concatenate([part[j] for part in res[k]]) for j in range(3)) if res[k] else empty)
+            k += 1
+        results.append(_follow_result(sheet_db, segments, sheet_columns, cands[e], starts[e], per_cand))
+    return results
+
+
+def follow_scores(engine, sheet_db, spectrograms, pieces, step_spec=2, spec_shape=(92, 42), segments=None,
+                  sheet_columns=None, max_windows=4096):
+    """Score following over whole recordings of any length: `pieces` is one candidate list (ids or names) per
+    recording.  One embedding pass over all windows (columns np.arange(0, T - w + 1, step_spec) of every recording),
+    then ceil(max windows / 1024) asr_dtw_follow_batch_dev calls over all recordings x candidates.  -> one FollowResult
+    per recording, equal to what a ScoreFollower returns over any block cut of it.  A recording shorter than a window
+    gives an empty result."""
+    return _follow(engine, sheet_db, spectrograms, pieces, step_spec, tuple(spec_shape), segments, sheet_columns,
+                   max_windows, host=False)
+
+
+def follow_scores_host(engine, sheet_db, spectrograms, pieces, step_spec=2, spec_shape=(92, 42), segments=None,
+                       sheet_columns=None, max_windows=4096):
+    """follow_scores with the alignment on the host: the same window codes, downloaded, and per pair
+    alignment.follow_dtw_host on alignment.cosine_dists_host - what the device path is tested against"""
+    return _follow(engine, sheet_db, spectrograms, pieces, step_spec, tuple(spec_shape), segments, sheet_columns,
+                   max_windows, host=True)

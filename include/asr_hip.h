@@ -404,6 +404,44 @@ int asr_dtw_subseq_batch_dev(asr_ctx *ctx, const float *q_dev, int64_t q_rows, c
                              int n_pairs, int dim, double *cost, int32_t *start, int32_t *end,
                              int32_t *path_len, int32_t *pos);
 
+/* ---- streaming subsequence DTW: where in the reference is the stream now? -----------------
+ * asr_dtw_subseq_batch_dev's matrix, one block of query rows at a time: the recurrence needs only the last accumulated
+ * row from the past, and when every cell also carries the column at which its best path started, no traceback is
+ * needed.  D[i][j] is the float64 cosine distance in asr_dtw_subseq_batch_dev's arithmetic.  A pair is one stream
+ * against one reference of S rows; its state is acc[S] (float64), org[S] (int32) and the number n0 of query rows it
+ * has consumed.  A call gives the pair B new query rows, global rows n0 .. n0 + B - 1:
+ *     n0 == 0: global row 0 is the free start, A[0][j] = D[0][j], O[0][j] = j; the state is not read and need not be
+ *              initialised;
+ *     n0 > 0:  row n0 - 1 is the state, A[n0-1][j] = acc[j], O[n0-1][j] = org[j];
+ *     every further row: A[i][j] = D[i][j] + fmin(A[i-1][j-1], fmin(A[i-1][j], A[i][j-1])), out-of-range predecessors
+ *              = +inf; w = the first minimum in the order (diagonal, up, left) with strict < (_traceback's rule, the
+ *              direction byte of the subsequence kernel); O[i][j] = O of predecessor w.
+ * Per new row i:
+ *     pos[i]   = the smallest j that minimises A[i][.];
+ *     cost[i]  = A[i][pos[i]] / (i + 1), one correctly rounded float64 division, i global;
+ *     start[i] = O[i][pos[i]].
+ * Afterwards acc and org hold row n0 + B - 1 (updated in place on the device).  For every i this is
+ * asr_dtw_subseq_batch_dev on rows 0..i: end = pos[i], start = start[i], cost = cost[i] - independent of how the rows
+ * were cut into calls.  A row of zero norm or a non-finite value leaves the result unspecified.
+ *
+ * q_dev, q_rows, r_dev, r_rows, q_row, n_q, r_row, n_r as in asr_dtw_subseq_batch_dev (r_dev may be a data base's
+ * resident code buffer; pairs may share query rows and reference rows); rows_before: n0 per pair.  acc_dev / org_dev:
+ * device buffers of state_len elements; pair p's state is n_r[p] entries at state_off[p] of both.  cost, start, pos:
+ * host arrays of sum n_q, pair p's entries at offset sum_{q<p} n_q[q]; each may be NULL, and a call with all three
+ * NULL still advances the state.
+ * Limits (ASR_ERR_INVALID otherwise; nothing is launched and no state is touched): 1 <= dim <= 64; per pair
+ * 1 <= n_q <= 1024, 1 <= n_r <= 100000, 0 <= rows_before, rows_before + n_q < 2^31, the row ranges inside the two
+ * buffers, the state range inside state_len; the state ranges of two pairs of one call must not overlap (they would
+ * race).  A longer block is several calls.  One workgroup per pair, one lane per block row.  There is no per-cell
+ * memory: the workspace (kept on the context, freed by asr_destroy) is the pair table and the three per-row outputs,
+ * 16 bytes per query row, so ASR_DTW_BUDGET_MB has nothing to chunk and is not read.  ASR_DTW_SUBSEQ_LDS_CAP (debug)
+ * applies as in asr_dtw_subseq_batch_dev. */
+int asr_dtw_follow_batch_dev(asr_ctx *ctx, const float *q_dev, int64_t q_rows, const float *r_dev, int64_t r_rows,
+                             const int64_t *q_row, const int64_t *n_q, const int64_t *r_row, const int64_t *n_r,
+                             const int64_t *rows_before, int n_pairs, int dim,
+                             double *acc_dev, int32_t *org_dev, int64_t state_len, const int64_t *state_off,
+                             double *cost, int32_t *start, int32_t *pos);
+
 /* ---- training-pool batch assembly on the device ----------------------
  * AudioScoreRetrievalPool.__getitem__ (utils/data_pools.py:127-228): every sample is a window of one strip (unrolled
  * score image or spectrogram) of a pool that stays resident on the device, with the augmentations of
