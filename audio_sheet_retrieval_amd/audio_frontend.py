@@ -329,3 +329,262 @@ class SpectrogramProcessor(object):
         finally:
             dev.buf.free()
         return [flat[o:o + r * c].reshape(r, c).copy() for o, (r, c) in zip(dev.offsets, dev.shapes)]
+
+    def stream(self, n_streams=1, sample_rate=None, integer=False, window_scale=None):
+        """AudioStream(self, ...): spectrogram columns from audio that arrives block by block"""
+        return AudioStream(self, n_streams, sample_rate, integer, window_scale)
+
+
+# ---- streamed audio: blocks of samples in, the spectrogram columns they complete out ----------------------------------------
+# The integer plan of asr_audio_stream_push_dev (include/asr_hip.h carries the definition).  The resampler's output m reads
+# the inputs j0(m) - (T - 1) .. j0(m), j0(m) = (m * down + half) // up, T = taps_per_phase; taps_per_phase == 0 stands for
+# the front-end's own rate (up == down == 1, y = x, no filter).
+def _stream_final_outputs(n, up, down, half, taps_per_phase):
+    """M(n): how many resampler outputs n input samples make final, j0(m) < n"""
+    if not taps_per_phase:
+        return n
+    num = n * up - half
+    return 0 if num <= 0 else min(-(-num // down), -(-n * up // down))
+
+
+def _stream_complete_frames(m, frame_size, hop):
+    """number of frames i with int(i * hop) + frame_size <= m: an estimate, then the definition"""
+    if m < frame_size:
+        return 0
+    k = int(float(m - frame_size) / hop)
+    while int(float(k) * hop) + frame_size <= m:
+        k += 1
+    while k > 0 and int(float(k - 1) * hop) + frame_size > m:
+        k -= 1
+    return k
+
+
+def _stream_keep_from(next_frame, n, hop, up, down, half, taps_per_phase):
+    s = int(float(next_frame) * hop)
+    j = (s * down + half) // up - (taps_per_phase - 1) if taps_per_phase else s
+    return max(0, min(j, n))
+
+
+def audio_stream_plan(n_before, n_new, final, frame_size, hop, up=1, down=1, half=0, taps_per_phase=0):
+    """-> (first_frame, n_frames, keep_from) of one push of n_new input samples to a stream that has had n_before: the
+    first frame the push emits, how many it emits, and the first input sample the state holds afterwards - what
+    asr_audio_stream_push_dev recomputes and checks.  final: the push flushes the stream (the frames past the last sample,
+    zero padded, up to num_frames of the whole recording).  hop is a float64 and a frame starts at int(i * hop), as on the
+    device; everything else is integer arithmetic."""
+    n_before, n_new, hop = int(n_before), int(n_new), float(hop)
+    n1 = n_before + n_new
+    args = (up, down, half, taps_per_phase)
+    f0 = _stream_complete_frames(_stream_final_outputs(n_before, *args), frame_size, hop)
+    if final:
+        length = -(-n1 * up // down) if taps_per_phase else n1
+        f1 = max(f0, int(np.ceil(length / hop)))
+    else:
+        f1 = _stream_complete_frames(_stream_final_outputs(n1, *args), frame_size, hop)
+    return f0, f1 - f0, _stream_keep_from(f1, n1, hop, *args)
+
+
+def audio_stream_state_len(frame_size, up=1, down=1, taps_per_phase=0):
+    """floats of state a stream needs: n - keep_from never exceeds it, whatever the cut into blocks.
+    Proof.  After n samples let i be the first frame not emitted and s = int(i * hop) its start.  Not emitted means
+    s + frame_size > M(n), so output s + frame_size - 1 is not final: j0(s + frame_size - 1) >= n.  The state starts at
+    keep_from = max(0, j0(s) - (T - 1)) (the clamp to n only empties it), hence
+        n - keep_from <= j0(s + frame_size - 1) - j0(s) + T - 1
+                       = floor((a + (frame_size - 1) * down) / up) - floor(a / up) + T - 1,    a = s * down + half
+                      <= ceil((frame_size - 1) * down / up) + T - 1.
+    At the front-end's own rate j0(m) = m and no tap reaches back: n <= s + frame_size - 1, keep_from = s, frame_size - 1.
+    A flushed stream's next frame starts at or past the end of the recording, which only moves keep_from up.  The bound
+    does not depend on hop or on the block lengths (2047 floats at 22.05 kHz, 4158 at 44.1 kHz, 4526 at 48 kHz, 18103
+    at 192 kHz for frames of 2048)."""
+    if not taps_per_phase:
+        return frame_size - 1
+    return -(-(frame_size - 1) * down // up) + taps_per_phase - 1
+
+
+class resample_stream_host(object):
+    """resample_host for samples that arrive block by block - the numpy restatement of the resampling half of
+    asr_audio_stream_push_dev.  push(block) returns the outputs the block makes final (every input they read has arrived),
+    flush() the remaining ones up to ceil(n * up / down), computed with zeros past the end as resample_host does; the
+    concatenation equals resample_host on the whole recording bit for bit, whatever the cut.  The object carries the
+    input tail the next output still reads."""
+
+    def __init__(self, rate_in, integer=False, rate_out=SAMPLE_RATE):
+        self.up, self.down, self.half, self.taps = resample_plan(rate_in, rate_out)
+        self.integer = bool(integer)
+        self.n_in = 0                                       # input samples so far
+        self.n_out = 0                                      # outputs returned so far
+        self._tail = np.zeros(0, np.float64)                # inputs self._from .. n_in - 1
+        self._from = 0
+        self.flushed = False
+
+    def _outputs(self, m0, m1, x, x_from):
+        """outputs m0 .. m1 - 1 from inputs x = x[x_from .. n_in): ascending taps, float64 product then float64 sum"""
+        up, down, half, hp = self.up, self.down, self.half, self.taps
+        T = hp.shape[1]
+        m = np.arange(m0, m1, dtype=np.int64)
+        c = m * down + half
+        p, j0 = c % up, c // up
+        acc = np.zeros(m.size, np.float64)
+        for t in range(T):
+            j = j0 - t
+            ok = (j >= 0) & (j < self.n_in)
+            acc[ok] = acc[ok] + hp[p[ok], t] * x[j[ok] - x_from]
+        if self.integer:
+            acc = np.clip(np.rint(acc), -32768, 32767)
+        return acc.astype(np.float32)
+
+    def _advance(self, block, m1):
+        x = np.concatenate((self._tail, np.ascontiguousarray(block, dtype=np.float32).ravel().astype(np.float64)))
+        self.n_in = self._from + x.size
+        if m1 is None:
+            m1 = _stream_final_outputs(self.n_in, self.up, self.down, self.half, self.taps.shape[1])
+        y = self._outputs(self.n_out, m1, x, self._from)
+        keep = max(self._from, min(self.n_in, (m1 * self.down + self.half) // self.up - (self.taps.shape[1] - 1)))
+        self._tail, self._from, self.n_out = x[keep - self._from:], keep, m1
+        return y
+
+    def push(self, block):
+        if self.flushed:
+            raise ValueError("the stream has been flushed")
+        return self._advance(block, None)
+
+    def flush(self):
+        if self.flushed:
+            raise ValueError("the stream has been flushed")
+        self.flushed = True
+        return self._advance(np.zeros(0, np.float32), -(-(self._from + self._tail.size) * self.up // self.down))
+
+
+class AudioStream(object):
+    """Spectrogram columns from audio that arrives block by block, for n_streams parallel streams of one sample rate:
+    push(blocks) takes one 1-d array of new samples per stream (empty allowed) and returns per stream the
+    (num_bins, n_i) float32 columns those samples complete; flush() emits the zero-padded last frames and closes the
+    streams.  Whatever the cut into blocks, the concatenated columns of a stream are bit-identical with
+    processor.process(recording, sample_rate, integer) on the whole recording.  sample_rate: the rate of the samples
+    (None: the processor's); integer: they are 16-bit PCM values (read_audio's flag); window_scale: what read_audio
+    returned (None: the processor's).  All streams share rate, integer flag and window scale: one push is one
+    asr_audio_stream_push_dev call (csrc/audio_stream_kernels.hip).  The samples the next frames still read stay on the
+    device (audio_stream_state_len floats per stream); state and upload buffers are allocated once and reused."""
+
+    def __init__(self, processor, n_streams=1, sample_rate=None, integer=False, window_scale=None):
+        if n_streams < 1:
+            raise ValueError("n_streams must be >= 1")
+        self.processor, self.engine, self.n_streams = processor, processor.engine, int(n_streams)
+        self.sample_rate = processor.sample_rate if sample_rate is None else sample_rate
+        self.integer = bool(integer)
+        if self.sample_rate == processor.sample_rate:
+            self.up, self.down, self.half, self.taps, self.taps_per_phase = 1, 1, 0, None, 0
+        else:
+            self.up, self.down, self.half, self.taps = resample_plan(self.sample_rate, processor.sample_rate)
+            self.taps_per_phase = self.taps.shape[1]
+        scale = processor.window_scale if window_scale is None else float(window_scale)
+        self.window = processor.window if scale == processor.window_scale else processor._window(scale)
+        self.state_cap = audio_stream_state_len(processor.frame_size, self.up, self.down, self.taps_per_phase)
+        self.state_floats = self.n_streams * self.state_cap
+        self.state_offsets = np.arange(self.n_streams, dtype=np.int64) * self.state_cap
+        self.n_samples = [0] * self.n_streams               # input samples per stream so far
+        self.n_frames = [0] * self.n_streams                # frames emitted per stream so far
+        self.flushed = [False] * self.n_streams
+        self._d_state = self.engine.alloc(max(4, self.state_floats * 4))
+        self._d_blocks = self._d_out = None
+
+    def _plan(self, s, n_new, final):
+        p = self.processor
+        return audio_stream_plan(self.n_samples[s], n_new, final, p.frame_size, p.hop, self.up, self.down, self.half,
+                                 self.taps_per_phase)
+
+    def _buffer(self, name, nbytes):
+        """the upload / output buffer `name`, grown when a larger push arrives"""
+        buf = getattr(self, name)
+        if buf is None or buf.nbytes < nbytes:
+            if buf is not None:
+                buf.free()
+            buf = self.engine.alloc(max(4, int(nbytes)))
+            setattr(self, name, buf)
+        return buf
+
+    def _push(self, blocks, final, out_buf=None):
+        """one call -> (buffer, offsets, shapes); out_buf None: a buffer of the caller's (push_dev)"""
+        if self._d_state is None:
+            raise ValueError("the AudioStream is closed")
+        if len(blocks) != self.n_streams:
+            raise ValueError("%d blocks for %d streams" % (len(blocks), self.n_streams))
+        blocks = [np.ascontiguousarray(b, dtype=np.float32) for b in blocks]
+        for s, b in enumerate(blocks):
+            if b.ndim != 1:
+                raise ValueError("stream %d: expected a 1-d block of samples, got shape %r" % (s, b.shape))
+            if self.flushed[s] and (b.size or final[s]):
+                raise ValueError("stream %d has been flushed; reset() it before pushing again" % s)
+        counts = np.asarray([b.size for b in blocks], np.int64)
+        b_off = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
+        plans = [self._plan(s, int(counts[s]), final[s]) for s in range(self.n_streams)]
+        first = np.asarray([p[0] for p in plans], np.int64)
+        n_new = np.asarray([p[1] for p in plans], np.int64)
+        nb = self.processor.num_bins
+        o_off = np.concatenate([[0], np.cumsum(n_new * nb)[:-1]]).astype(np.int64)
+        total_in, out_floats = int(counts.sum()), int(n_new.sum()) * nb
+        d_blocks = self._buffer("_d_blocks", total_in * 4)
+        if total_in:
+            d_blocks.upload(np.concatenate(blocks))
+        d_out = self.engine.alloc(max(4, out_floats * 4)) if out_buf is None else self._buffer(out_buf, out_floats * 4)
+        p = self.processor
+        try:
+            self.engine.audio_stream_push_dev(
+                d_blocks.ptr, total_in, b_off, counts, self.n_samples, [1 if f else 0 for f in final], first, n_new, o_off,
+                self.up, self.down, self.taps, self.half, self.integer, self._d_state.ptr, self.state_floats,
+                self.state_offsets, self.state_cap, p.frame_size, p.hop, self.window, p.fb_start, p.fb_len, p.fb_w,
+                d_out.ptr, out_floats, transposed=True)
+        except Exception:
+            if out_buf is None:
+                d_out.free()
+            raise
+        for s in range(self.n_streams):
+            self.n_samples[s] += int(counts[s])
+            self.n_frames[s] += int(n_new[s])
+            self.flushed[s] = self.flushed[s] or bool(final[s])
+        return d_out, [int(o) for o in o_off], [(nb, int(n)) for n in n_new]
+
+    def _download(self, res):
+        d_out, offsets, shapes = res
+        total = sum(r * c for r, c in shapes)
+        flat = d_out.download((total,), np.float32) if total else np.zeros(0, np.float32)
+        return [flat[o:o + r * c].reshape(r, c).copy() for o, (r, c) in zip(offsets, shapes)]
+
+    def push_dev(self, blocks):
+        """push() that leaves the columns on the device -> piece_identification.DeviceArrays (free its buffer)"""
+        from .piece_identification import DeviceArrays
+        return DeviceArrays(*self._push(blocks, [False] * self.n_streams))
+
+    def push(self, blocks):
+        """one 1-d array of new samples per stream -> list of (num_bins, n_i) float32 arrays, the columns they complete"""
+        return self._download(self._push(blocks, [False] * self.n_streams, "_d_out"))
+
+    def _which(self, streams):
+        which = range(self.n_streams) if streams is None else [int(s) for s in streams]
+        for s in which:
+            if not 0 <= s < self.n_streams:
+                raise ValueError("stream %d of %d" % (s, self.n_streams))
+        return which
+
+    def flush(self, streams=None):
+        """the recordings of `streams` (default: all that are open) end here -> list (one entry per stream of the object;
+        an empty array for the others) of their remaining columns, the last frames zero padded as process() pads them.
+        A flushed stream takes no more samples until reset()."""
+        if streams is None:
+            which = [s for s in range(self.n_streams) if not self.flushed[s]]
+        else:
+            which = self._which(streams)
+        final = [s in which for s in range(self.n_streams)]
+        empty = np.zeros(0, np.float32)
+        return self._download(self._push([empty] * self.n_streams, final, "_d_out"))
+
+    def reset(self, streams=None):
+        """`streams` (default: all) start over: the next push is the first of a new recording"""
+        for s in self._which(streams):
+            self.n_samples[s], self.n_frames[s], self.flushed[s] = 0, 0, False
+
+    def close(self):
+        for name in ("_d_state", "_d_blocks", "_d_out"):
+            buf = getattr(self, name)
+            if buf is not None:
+                buf.free()
+            setattr(self, name, None)

@@ -1,8 +1,9 @@
 // C-ABI layer of the UMC drivers' device stages: asr_resize_pages_dev (page scans of any resolution -> pages of the
 // networks' width), asr_unroll_systems_dev (page scans -> unrolled strips), asr_resample_batch_dev (recordings at any
-// rate -> recordings at the front-end's rate) and asr_spectrogram_batch_dev (recordings -> spectrograms);
+// rate -> recordings at the front-end's rate), asr_spectrogram_batch_dev (recordings -> spectrograms) and
+// asr_audio_stream_push_dev (blocks of streamed samples at any rate -> the spectrogram frames they complete);
 // include/asr_hip.h for the contract.  Kernels: page_resize_kernels.hip, umc_kernels.hip, resample_kernels.hip,
-// piece_vote_kernels.hip (spectrogram_batch_kernel).  Every call checks every offset against the buffer sizes the
+// piece_vote_kernels.hip (spectrogram_batch_kernel), audio_stream_kernels.hip.  Every call checks every offset against the buffer sizes the
 // caller states before anything is launched, and returns after the work is done.
 #include "asr_ctx.h"
 
@@ -221,6 +222,226 @@ int asr_resample_batch_dev(asr_ctx *ctx, const float *in_dev, int64_t in_floats,
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "resample_batch: %s", hipGetErrorString(e));
+    return mark_main(ctx);
+}
+
+// ---- asr_audio_stream_push_dev: the host half of the stream's integer plan (audio_frontend.audio_stream_plan restates it)
+namespace {
+
+struct StreamPlan {
+    int up, down, half, T, F; double hop; bool native;
+    int64_t start(int64_t i) const { return (int64_t)((double)i * hop); }
+    // M(n): outputs of the resampler that n input samples make final, j0(m) = (m * down + half) / up < n
+    int64_t final_outputs(int64_t n) const {
+        if (native) return n;
+        const int64_t num = n * up - half;
+        return num <= 0 ? 0 : std::min((num + down - 1) / down, (n * up + down - 1) / down);
+    }
+    int64_t length(int64_t n) const { return native ? n : (n * up + down - 1) / down; }   // of the whole recording
+    // frames i with start(i) + F <= m: an estimate, then the definition
+    int64_t complete_frames(int64_t m) const {
+        if (m < F) return 0;
+        int64_t k = (int64_t)((double)(m - F) / hop);
+        while (start(k) + F <= m) ++k;
+        while (k > 0 && start(k - 1) + F > m) --k;
+        return k;
+    }
+    int64_t keep_from(int64_t next_frame, int64_t n) const {
+        const int64_t s = start(next_frame);
+        const int64_t j = native ? s : (s * down + half) / up - (T - 1);
+        return std::max<int64_t>(0, std::min(j, n));
+    }
+    // n - keep_from never exceeds this (the proof is with audio_frontend.audio_stream_state_len)
+    int64_t state_len() const { return native ? F - 1 : ((int64_t)(F - 1) * down + up - 1) / up + T - 1; }
+};
+
+}  // namespace
+
+int asr_audio_stream_push_dev(asr_ctx *ctx, const float *blocks_dev, int64_t blocks_floats, const int64_t *block_offsets,
+                              const int64_t *block_counts, const int64_t *samples_before, const int32_t *final_flags,
+                              const int64_t *first_frames, const int64_t *n_new_frames, const int64_t *out_offsets,
+                              int n_streams, int up, int down, const double *taps_phase_major, int taps_per_phase,
+                              int half, int round_int16, float *state_dev, int64_t state_floats,
+                              const int64_t *state_offsets, int64_t state_cap, int frame_size, double hop,
+                              const float *window, const int32_t *fb_start, const int32_t *fb_len,
+                              const float *fb_weights, int n_filters, float mul, float add, int transposed,
+                              float *out_dev, int64_t out_floats) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_streams < 0 || blocks_floats < 0 || state_floats < 0 || state_cap < 0 || out_floats < 0 || frame_size < 64 ||
+        frame_size > 8192 || (frame_size & (frame_size - 1)) || !(hop > 0.0) || n_filters < 1 || n_filters > 4096)
+        return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: bad sizes (frame_size must be a power of two in [64, 8192])");
+    if (up < 1 || down < 1)
+        return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: ratio %d / %d (up and down must be at least 1)", up, down);
+    const bool native = !taps_phase_major;
+    if (native && (up != 1 || down != 1))
+        return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: ratio %d / %d without taps (only 1 / 1 is the front-end's "
+                    "own rate)", up, down);
+    if (!native && (half < 0 || taps_per_phase < 1 || (int64_t)taps_per_phase * up < 2 * (int64_t)half + 1))
+        return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: %d taps per phase x %d phases do not hold the %lld taps of "
+                    "half = %d", taps_per_phase, up, 2 * (long long)half + 1, half);
+    if (!window || !fb_start || !fb_len || !fb_weights)
+        return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: NULL argument");
+    std::vector<int32_t> off(n_filters);
+    int64_t total_w = 0;
+    int max_bin = 0;
+    for (int f = 0; f < n_filters; ++f) {
+        if (fb_start[f] < 0 || fb_len[f] < 0 || fb_start[f] + fb_len[f] > frame_size / 2)
+            return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: filter %d covers bins [%d, %d) outside [0, %d)", f,
+                        fb_start[f], fb_start[f] + fb_len[f], frame_size / 2);
+        off[f] = (int32_t)total_w;
+        total_w += fb_len[f];
+        max_bin = std::max(max_bin, fb_start[f] + fb_len[f]);
+    }
+    const StreamPlan plan{up, down, native ? 0 : half, native ? 1 : taps_per_phase, frame_size, hop, native};
+    const int64_t span64 = native ? 0 : ((int64_t)(frame_size - 1) * down + up - 1) / up + taps_per_phase;
+    if (span64 > (int64_t)(asr::AUDIO_STREAM_MAX_LDS / 4) ||
+        asr::audio_stream_lds(frame_size, max_bin, (int)span64) > asr::AUDIO_STREAM_MAX_LDS)
+        return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: ratio %d / %d with %d taps per phase and frames of %d: the "
+                    "input span of a frame (%lld samples) does not fit %zu bytes of LDS", up, down, taps_per_phase,
+                    frame_size, (long long)span64, asr::AUDIO_STREAM_MAX_LDS);
+    if (state_cap < plan.state_len())
+        return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: a state of %lld floats per stream, %lld are needed",
+                    (long long)state_cap, (long long)plan.state_len());
+    if (n_streams == 0) return ASR_OK;
+    if (!block_offsets || !block_counts || !samples_before || !final_flags || !first_frames || !n_new_frames ||
+        !out_offsets || !state_offsets)
+        return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: NULL argument");
+    const int n = n_streams;
+    const size_t b_first = ((size_t)n + 1) * 8, b_rows = (size_t)n * sizeof(asr::StreamRow), b_win = (size_t)frame_size * 4,
+                 b_i = (size_t)n_filters * 4, b_w = (size_t)std::max<int64_t>(total_w, 1) * 4;
+    std::vector<char> tab(b_first + b_rows + b_win + 3 * b_i + b_w);  // frame_first | rows | window | start, len, off | w
+    int64_t *first = (int64_t *)tab.data();
+    asr::StreamRow *rows = (asr::StreamRow *)(tab.data() + b_first);
+    // every index the kernels form stays below n1 * up + (frame_size + 2) * down + half: keep that inside int64
+    const int64_t max_count = (INT64_MAX - half - (int64_t)(frame_size + 2) * down) / up - 1;
+    int64_t total = 0;
+    bool moves = false;
+    std::vector<std::pair<int64_t, int>> ranges(n);
+    for (int i = 0; i < n; ++i) {
+        const int64_t n0 = samples_before[i], cnt = block_counts[i];
+        if (n0 < 0 || cnt < 0 || block_offsets[i] < 0 || cnt > blocks_floats || block_offsets[i] > blocks_floats - cnt)
+            return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: stream %d: block of %lld samples at %lld (after %lld) "
+                        "outside the %lld-float buffer", i, (long long)cnt, (long long)block_offsets[i], (long long)n0,
+                        (long long)blocks_floats);
+        if (n0 > max_count || cnt > max_count - n0)
+            return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: stream %d: %lld + %lld samples x %d overflow", i,
+                        (long long)n0, (long long)cnt, up);
+        if (state_offsets[i] < 0 || state_cap > state_floats || state_offsets[i] > state_floats - state_cap)
+            return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: stream %d: state of %lld floats at %lld outside the "
+                        "%lld-float buffer", i, (long long)state_cap, (long long)state_offsets[i], (long long)state_floats);
+        ranges[i] = {state_offsets[i], i};
+        const int64_t n1 = n0 + cnt;
+        const int64_t f0 = plan.complete_frames(plan.final_outputs(n0));
+        const int64_t f1 = final_flags[i] ? std::max(f0, (int64_t)std::ceil((double)plan.length(n1) / hop))
+                                          : plan.complete_frames(plan.final_outputs(n1));
+        if (first_frames[i] != f0 || n_new_frames[i] != f1 - f0)
+            return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: stream %d: %lld new frames from frame %lld stated, %lld "
+                        "+ %lld samples%s give %lld from %lld", i, (long long)n_new_frames[i], (long long)first_frames[i],
+                        (long long)n0, (long long)cnt, final_flags[i] ? " (flushed)" : "", (long long)(f1 - f0),
+                        (long long)f0);
+        if (out_offsets[i] < 0 || (f1 - f0) > out_floats / n_filters ||
+            out_offsets[i] > out_floats - (f1 - f0) * (int64_t)n_filters)
+            return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: stream %d: %lld frames at %lld outside the %lld-float "
+                        "output", i, (long long)(f1 - f0), (long long)out_offsets[i], (long long)out_floats);
+        asr::StreamRow &r = rows[i];
+        r.n0 = n0; r.n1 = n1;
+        r.keep0 = n0 > 0 ? plan.keep_from(f0, n0) : 0;
+        r.keep1 = plan.keep_from(f1, n1);
+        r.first_frame = f0; r.n_new = f1 - f0;
+        r.y_len = plan.length(n1);
+        r.block_off = block_offsets[i]; r.state_off = state_offsets[i]; r.out_off = out_offsets[i];
+        if (r.keep1 < r.keep0 || r.n1 - r.keep1 > state_cap || r.n0 - r.keep0 > state_cap)
+            return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: stream %d: the state would hold samples %lld .. %lld "
+                        "(before: from %lld) in %lld floats", i, (long long)r.keep1, (long long)r.n1, (long long)r.keep0,
+                        (long long)state_cap);
+        moves = moves || cnt > 0 || r.keep1 != r.keep0;
+        first[i] = total;
+        total += f1 - f0;
+    }
+    first[n] = total;
+    std::sort(ranges.begin(), ranges.end());
+    for (int i = 1; i < n; ++i)
+        if (ranges[i].first < ranges[i - 1].first + state_cap)
+            return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: the states of streams %d and %d overlap (%lld floats at "
+                        "%lld and at %lld)", ranges[i - 1].second, ranges[i].second, (long long)state_cap,
+                        (long long)ranges[i - 1].first, (long long)ranges[i].first);
+    if (total > 0x7fffffffLL)
+        return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: %lld frames in one call", (long long)total);
+    if (total == 0 && !moves) return ASR_OK;
+    if (!blocks_dev || !state_dev || (total && !out_dev))
+        return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: NULL argument");
+    char *t = tab.data() + b_first + b_rows;
+    memcpy(t, window, b_win);
+    memcpy(t + b_win, fb_start, b_i);
+    memcpy(t + b_win + b_i, fb_len, b_i);
+    memcpy(t + b_win + 2 * b_i, off.data(), b_i);
+    if (total_w) memcpy(t + b_win + 3 * b_i, fb_weights, (size_t)total_w * 4);
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    int rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    if (tab.size() > ctx->stream_ws_bytes) {
+        ASR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->stream_ws) ASR_HIP(ctx, hipFree(ctx->stream_ws));
+        ctx->stream_ws = nullptr; ctx->stream_ws_bytes = 0;
+        ASR_HIP(ctx, hipMalloc(&ctx->stream_ws, tab.size()));
+        ctx->stream_ws_bytes = tab.size();
+    }
+    // the taps stay on the device from call to call: a stream pushes the same table every time (82 KB at 48 kHz)
+    const size_t n_taps = native ? 0 : (size_t)up * taps_per_phase;
+    if (n_taps && (ctx->stream_taps_host.size() != n_taps ||
+                   memcmp(ctx->stream_taps_host.data(), taps_phase_major, n_taps * 8) != 0)) {
+        ASR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->stream_taps) ASR_HIP(ctx, hipFree(ctx->stream_taps));
+        ctx->stream_taps = nullptr; ctx->stream_taps_host.clear();
+        ASR_HIP(ctx, hipMalloc((void **)&ctx->stream_taps, n_taps * 8));
+        ASR_HIP(ctx, hipMemcpy(ctx->stream_taps, taps_phase_major, n_taps * 8, hipMemcpyHostToDevice));
+        ctx->stream_taps_host.assign(taps_phase_major, taps_phase_major + n_taps);
+    }
+    char *d = (char *)ctx->stream_ws;
+    const int64_t *d_first = (const int64_t *)d;
+    const asr::StreamRow *d_rows = (const asr::StreamRow *)(d + b_first);
+    const float *d_win = (const float *)(d + b_first + b_rows);
+    const int32_t *d_start = (const int32_t *)(d + b_first + b_rows + b_win), *d_len = d_start + n_filters,
+                  *d_off = d_len + n_filters;
+    const float *d_w = (const float *)(d + b_first + b_rows + b_win + 3 * b_i);
+    hipError_t e = hipMemcpyAsync(d, tab.data(), tab.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && total) {
+        const asr::StreamResample r{up, down, plan.half, plan.T, (int)span64, round_int16 ? 1 : 0,
+                                    native ? nullptr : ctx->stream_taps};
+        ProfScope ps(ctx, "audio_stream_frames", 0,
+                     (4.0 * frame_size * (double)max_bin + (native ? 0.0 : 2.0 * taps_per_phase * frame_size)) * (double)total,
+                     4.0 * (double)(native ? frame_size : span64) * (double)total);
+        // fewer frames than CUs: split a frame's filters over workgroups of about 192 DFT bins each (a lane then sums one
+        // bin, not three), balanced by the filters' bin counts, as long as every part of every frame still finds a CU
+        asr::StreamParts parts{};
+        const int64_t want = std::min<int64_t>({(int64_t)asr::STREAM_MAX_PARTS, (int64_t)(max_bin + 191) / 192,
+                                                (int64_t)ctx->num_cus / total, (int64_t)n_filters});
+        const char *env = getenv("ASR_STREAM_PARTS");                   // debug: force the number of parts (1 .. 8)
+        const int n_parts = (int)std::max<int64_t>(1, env ? std::min<int64_t>({(int64_t)atoi(env), (int64_t)asr::STREAM_MAX_PARTS,
+                                                                               (int64_t)n_filters}) : want);
+        parts.n = n_parts;
+        int f = 0;
+        for (int p = 0; p < n_parts; ++p) {
+            parts.f[p] = f;
+            const int64_t upto = total_w * (p + 1) / n_parts;           // weights (= bins read) up to the end of part p
+            while (f < n_filters && (p == n_parts - 1 || off[f] + fb_len[f] <= upto || f == parts.f[p])) ++f;
+            parts.k0[p] = parts.k1[p] = 0;
+            for (int q = parts.f[p]; q < f; ++q) {
+                if (q == parts.f[p] || fb_start[q] < parts.k0[p]) parts.k0[p] = fb_start[q];
+                parts.k1[p] = std::max(parts.k1[p], fb_start[q] + fb_len[q]);
+            }
+        }
+        parts.f[n_parts] = n_filters;
+        e = asr::launch_audio_stream_frames(ctx->stream, blocks_dev, state_dev, d_first, d_rows, n, total, r, parts, d_win,
+                                            frame_size, hop, max_bin, d_start, d_len, d_off, d_w, n_filters, mul, add,
+                                            out_dev, transposed);
+    }
+    if (e == hipSuccess && moves) {
+        ProfScope ps(ctx, "audio_stream_carry", 0, 0.0, 8.0 * (double)plan.state_len() * n);
+        e = asr::launch_audio_stream_carry(ctx->stream, blocks_dev, state_dev, d_rows, n);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "audio_stream_push: %s", hipGetErrorString(e));
     return mark_main(ctx);
 }
 

@@ -269,6 +269,10 @@ struct asr_ctx {
     size_t resample_ws_bytes = 0;
     void *resize_ws = nullptr;                // asr_resize_pages_dev: running tile counts + page table
     size_t resize_ws_bytes = 0;
+    void *stream_ws = nullptr;                // asr_audio_stream_push_dev: running frame counts, stream rows, window, filters
+    size_t stream_ws_bytes = 0;
+    double *stream_taps = nullptr;            // ... and the phase-major taps of the last call, kept while they stay the same
+    std::vector<double> stream_taps_host;
     unsigned *topk_tickets = nullptr;         // 1024 last-arriver counters of the top-k call (zero between calls)
     float *unit_ws = nullptr;                 // asr_topk_dev on a large pool: unit-length copy + reciprocal norms of the
     size_t unit_ws_floats = 0;                // pool, rebuilt per call (what an asr_db keeps)

@@ -342,6 +342,34 @@ hipError_t launch_resample_batch(hipStream_t s, const float *in, float *out, con
                                  const int64_t *in_off, const int64_t *in_cnt, const int64_t *out_off,
                                  const int64_t *out_cnt, int n_rec, int64_t total_tiles, int up, int down, int half,
                                  int taps_per_phase, const double *taps, int round_int16);
+// spectrogram columns from streamed blocks (audio_stream_kernels.hip): one workgroup per new frame stages the frame's input
+// span from [state | block], resamples its frame_size samples into LDS and runs the frame arithmetic; then one workgroup
+// per stream slides the inputs the next frame reads to the front of the state.  One row per stream, on the device:
+struct StreamRow {
+    int64_t n0, n1;             // input samples of the stream before / after the call
+    int64_t keep0, keep1;       // first input sample the state holds before / after the call (n0 == 0: keep0 = 0)
+    int64_t first_frame, n_new; // the call's frames
+    int64_t y_len;              // ceil(n1 * up / down): samples at the front-end's rate from here on are zero
+    int64_t block_off, state_off, out_off;      // in floats
+};
+struct StreamResample {
+    int up, down, half, taps_per_phase, span, round_int16;
+    const double *taps;         // phase-major, on the device; nullptr: the front-end's own rate, y = x
+};
+// a frame's filters split over n workgroups: part p computes filters f[p] .. f[p + 1] - 1 and DFT bins k0[p] .. k1[p] - 1
+constexpr int STREAM_MAX_PARTS = 8;
+struct StreamParts { int n; int f[STREAM_MAX_PARTS + 1], k0[STREAM_MAX_PARTS], k1[STREAM_MAX_PARTS]; };
+constexpr size_t AUDIO_STREAM_MAX_LDS = 160 * 1024;
+// input samples one frame reads: ceil((frame_size - 1) * down / up) + taps_per_phase
+int audio_stream_span(int frame_size, int up, int down, int taps_per_phase);
+size_t audio_stream_lds(int frame_size, int max_bin, int span);
+hipError_t launch_audio_stream_frames(hipStream_t s, const float *blocks, const float *state, const int64_t *frame_first,
+                                      const StreamRow *rows, int n_streams, int64_t total_frames, const StreamResample &r,
+                                      const StreamParts &parts, const float *window, int frame_size, double hop, int max_bin,
+                                      const int32_t *fb_start, const int32_t *fb_len, const int32_t *fb_off,
+                                      const float *fb_w, int nf, float mul, float add, float *out, int transposed);
+hipError_t launch_audio_stream_carry(hipStream_t s, const float *blocks, float *state, const StreamRow *rows,
+                                     int n_streams);
 // score pages at another resolution (page_resize_kernels.hip): exact integer area resampling, one 64-thread workgroup
 // per tile of RESIZE_TILE_H x RESIZE_TILE_W output pixels of one page.  tile_first (n_pages + 1 running tile counts) and
 // the page table on the device.  A tile stages its source rows in RESIZE_LDS_BYTES of LDS, chunk by chunk; one row of a

@@ -9,6 +9,7 @@
 //                          repeated arg-max.  Ties: the LARGER piece id first (what reversing a stable ascending
 //                          sort gives; the reference's quicksort leaves ties undefined).
 #include "asr_kernels.h"
+#include "spectrogram_frame.h"
 
 namespace asr {
 
@@ -126,69 +127,9 @@ hipError_t launch_gather_windows(hipStream_t s, const float *src, const double *
 }  // namespace asr
 
 // ---- audio front-end ---------------------------------------------------------------------
-// The madmom chain of the reference (tutorials/Embedding Tutorial.ipynb cell 28; msmd.midi_parser.processor):
-// FramedSignal(frame_size 2048, fps 20, origin 'future') -> |STFT| with a Hann window -> LogarithmicFilterbank
-// (16 bands/octave, 30..6000 Hz: 92 triangular filters) -> log10(1 + x).  One workgroup per frame: windowed frame
-// and a 2048-entry twiddle table in LDS, direct DFT of the bins the filterbank touches (<= 558 of 1024: 2.3 MFLOP
-// per frame - an FFT would not pay), magnitudes in LDS, filterbank + logarithm.
+// The arithmetic of a frame (spectrogram_frame, spectrogram_twiddles, SpecArgs) is in spectrogram_frame.h, shared with the
+// streamed front-end (audio_stream_kernels.hip).
 namespace asr {
-
-struct SpecArgs {
-    const float *samples; int64_t n_samples;
-    const float *window;            // [frame_size]
-    int frame_size; double hop;
-    int max_bin;                    // DFT bins 0 .. max_bin-1 are needed
-    const int32_t *fb_start, *fb_len, *fb_off;   // per filter: first bin, number of bins, offset into fb_w
-    const float *fb_w; int nf;
-    float mul, add;
-    float *out; int64_t n_frames; int transposed;      // out: (n_frames, nf) or (nf, n_frames)
-};
-
-// twiddle table of the workgroup: tc[t] = cos(2 pi t / F), ts[t] = sin(2 pi t / F)
-__device__ __forceinline__ void spectrogram_twiddles(int F, float *tc, float *ts) {
-    for (int t = threadIdx.x; t < F; t += 256) {
-        double s, c;
-        sincospi(2.0 * (double)t / (double)F, &s, &c);
-        tc[t] = (float)c; ts[t] = (float)s;
-    }
-}
-
-// one frame of one recording (samples[0 .. n_samples), output of n_frames frames at out), by the whole workgroup: the
-// only place the arithmetic of a frame is written down - spectrogram_kernel and spectrogram_batch_kernel both call it,
-// which is what makes the batched result bit-identical with the single one
-__device__ __forceinline__ void spectrogram_frame(const SpecArgs &a, const float *__restrict__ samples, int64_t n_samples,
-                                                  int64_t frame, float *__restrict__ out, int64_t n_frames, float *x,
-                                                  const float *tc, const float *ts, float *mag) {
-    const int F = a.frame_size;
-    const int tid = threadIdx.x;
-    const int64_t start = (int64_t)((double)frame * a.hop);        // int(index * hop_size), origin 'future'
-    __syncthreads();
-    for (int t = tid; t < F; t += 256) {
-        const int64_t i = start + t;
-        x[t] = (i < n_samples ? samples[i] : 0.0f) * a.window[t];
-    }
-    __syncthreads();
-    for (int k = tid; k < a.max_bin; k += 256) {
-        float re = 0.0f, im = 0.0f;
-        int idx = 0;
-        for (int n = 0; n < F; ++n) {
-            re = fmaf(x[n], tc[idx], re);
-            im = fmaf(-x[n], ts[idx], im);
-            idx = (idx + k) & (F - 1);                              // (k * n) mod F, F a power of two
-        }
-        mag[k] = sqrtf(re * re + im * im);
-    }
-    __syncthreads();
-    for (int f = tid; f < a.nf; f += 256) {
-        const float *w = a.fb_w + a.fb_off[f];
-        const int b0 = a.fb_start[f];
-        float s = 0.0f;
-        for (int q = 0; q < a.fb_len[f]; ++q) s = fmaf(mag[b0 + q], w[q], s);
-        const float v = log10f(a.mul * s + a.add);
-        if (a.transposed) out[(int64_t)f * n_frames + frame] = v;
-        else out[frame * a.nf + f] = v;
-    }
-}
 
 __global__ __launch_bounds__(256) void spectrogram_kernel(SpecArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sl[];
@@ -196,7 +137,8 @@ __global__ __launch_bounds__(256) void spectrogram_kernel(SpecArgs a) {
     float *x = sl, *tc = sl + F, *ts = sl + 2 * F, *mag = sl + 3 * F;
     spectrogram_twiddles(F, tc, ts);
     for (int64_t frame = blockIdx.x; frame < a.n_frames; frame += gridDim.x)
-        spectrogram_frame(a, a.samples, a.n_samples, frame, a.out, a.n_frames, x, tc, ts, mag);
+        spectrogram_frame(a, a.samples, 0, a.n_samples, frame, a.out, frame, a.n_frames, x, tc, ts, mag, 0, a.nf, 0,
+                          a.max_bin);
 }
 
 // many recordings in one launch (asr_spectrogram_batch_dev): the frames of all recordings are numbered through,
@@ -220,8 +162,9 @@ __global__ __launch_bounds__(256) void spectrogram_batch_kernel(SpecArgs a, Spec
             if (b.frame_first[mid] <= g) lo = mid; else hi = mid - 1;
         }
         const int64_t n_frames = b.frame_first[lo + 1] - b.frame_first[lo];
-        spectrogram_frame(a, a.samples + b.sample_off[lo], b.sample_cnt[lo], g - b.frame_first[lo], a.out + b.out_off[lo],
-                          n_frames, x, tc, ts, mag);
+        const int64_t frame = g - b.frame_first[lo];
+        spectrogram_frame(a, a.samples + b.sample_off[lo], 0, b.sample_cnt[lo], frame, a.out + b.out_off[lo], frame,
+                          n_frames, x, tc, ts, mag, 0, a.nf, 0, a.max_bin);
     }
 }
 

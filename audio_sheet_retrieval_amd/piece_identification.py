@@ -7,7 +7,8 @@ the resident data base, vote histogram and selection (csrc/piece_vote_kernels.hi
 
 The server's default mode, the running vote of AudioSheetServer.run (:83-211), is track_scores / track_score (whole
 recordings, batched) and PieceTracker (blocks of new frames): music gate and sliding vote in csrc/track_kernels.hip,
-track_score_host the numpy restatement they are tested against.
+track_score_host the numpy restatement they are tested against.  live_track_scores starts one stage earlier, at blocks of
+audio samples (audio_frontend.AudioStream -> PieceTracker).
 
 Where in the score: locate_scores places a finished excerpt (subsequence DTW against the vote's candidates), and
 ScoreFollower / follow_scores follow a stream block by block, the same alignment carried from call to call.
@@ -705,6 +706,71 @@ class PieceTracker(object):
         self.n_frames += n
         self.n_voiced += m
         return TrackResult(m_prob, voiced, frames, pieces, counts, n_out, history, db.id_to_name, new_rows)
+
+
+def _concat_track_results(parts, id_to_name, top_k, n_candidates):
+    """the TrackResults of consecutive blocks of one recording as one (frames: indices within the recording)"""
+    if not parts:
+        z = np.zeros((0, top_k), np.int32)
+        return TrackResult(np.zeros(0, np.float32), np.zeros(0, bool), np.zeros(0, np.int64), z, z, np.zeros(0, np.int32),
+                           np.zeros(0, np.int64), id_to_name, np.zeros((0, n_candidates), np.int32))
+    first = np.concatenate([[0], np.cumsum([len(r.m_prob) for r in parts])])
+    cat = lambda name: np.concatenate([getattr(r, name) for r in parts])
+    return TrackResult(cat("m_prob"), cat("voiced"), np.concatenate([r.frames + first[i] for i, r in enumerate(parts)]),
+                       cat("pieces"), cat("counts"), cat("n_out"), cat("history"), id_to_name, cat("idx"))
+
+
+def live_track_scores(engine, sheet_db, processor, recordings, sample_rates, block_samples, levels=None, top_k=5,
+                      n_candidates=5, running_frames=100, spec_shape=(92, 42), integer=None, window_scales=None):
+    """The live server from the samples on: every recording (mono samples at sample_rates[i]) is cut into blocks of
+    block_samples input samples (an int, or one per recording) and pushed block by block through an
+    audio_frontend.AudioStream - all recordings of one (rate, integer, window scale) group as parallel streams of one
+    object, one launch per round of blocks - and each stream's new columns go to its own PieceTracker.  A recording
+    that ends is flushed.  -> one TrackResult per recording, the fields of its blocks concatenated (frames: indices
+    within the recording; idx included); equal to track_scores on processor.process_many(recordings, ...) at the same
+    levels.  levels: per recording the normaliser of the music gate; None takes spec.sum(axis=0).max() of the finished
+    spectrogram, as track_scores does - which means computing that spectrogram first: a real stream cannot, and must be
+    given a level."""
+    from .audio_frontend import AudioStream
+    recs = [np.ascontiguousarray(r, dtype=np.float32).ravel() for r in recordings]
+    n = len(recs)
+    rates = list(sample_rates)
+    flags = [False] * n if integer is None else [bool(f) for f in integer]
+    scales = [processor.window_scale] * n if window_scales is None else [float(w) for w in window_scales]
+    steps = [int(block_samples)] * n if np.ndim(block_samples) == 0 else [int(b) for b in block_samples]
+    if not (len(rates) == len(flags) == len(scales) == len(steps) == n):
+        raise ValueError("%d recordings: %d sample rates, %d integer flags, %d window scales, %d block lengths" %
+                         (n, len(rates), len(flags), len(scales), len(steps)))
+    if any(b < 1 for b in steps):
+        raise ValueError("block_samples must be >= 1")
+    if levels is None:
+        levels = [spec.sum(axis=0).max() if spec.shape[1] else 0.0
+                  for spec in processor.process_many(recs, scales, rates, flags)]
+    if len(levels) != n:
+        raise ValueError("%d levels for %d recordings" % (len(levels), n))
+    parts = [[] for _ in recs]
+    for key in sorted(set(zip(rates, flags, scales))):
+        sel = [i for i in range(n) if (rates[i], flags[i], scales[i]) == key]
+        trackers = [PieceTracker(engine, sheet_db, levels[i], top_k, n_candidates, running_frames, spec_shape) for i in sel]
+        stream = AudioStream(processor, len(sel), key[0], key[1], key[2])
+        try:
+            pos = [0] * len(sel)
+            while not all(stream.flushed):
+                blocks = []
+                for k, i in enumerate(sel):
+                    blocks.append(recs[i][pos[k]:pos[k] + steps[i]])
+                    pos[k] += blocks[-1].size
+                results = [stream.push(blocks)]
+                ended = [k for k, i in enumerate(sel) if pos[k] >= recs[i].size and not stream.flushed[k]]
+                if ended:
+                    results.append(stream.flush(ended))
+                for columns in results:
+                    for k, i in enumerate(sel):
+                        if columns[k].shape[1]:
+                            parts[i].append(trackers[k].push(columns[k]))
+        finally:
+            stream.close()
+    return [_concat_track_results(p, sheet_db.id_to_name, top_k, n_candidates) for p in parts]
 
 
 # ---- where in the score is an excerpt?  piece vote, then subsequence DTW against the candidates' ordered codes ----------

@@ -6,6 +6,7 @@ umc_a2s_server.py (:178-189):
         --train_split splits/all_split.yaml --config exp_configs/mutopia_full_aug.yaml \
         --init_sheet_db --full_eval --dump_results [--real_perf] [--n_candidates 25] [--estimate_UV] \
         --system_params system_params.pkl --bar_params bar_params.pkl [--device_post] [--resample] [--page_width 835]
+        [--live [--block_ms 100] [--running_frames 100]]
 
 <dir> holds one folder per piece: sheet/*.png (the page scans), score_ppq.* (the synthesised recording) and, for
 --real_perf, 01_performance*.  The pages go through the two segmentation networks (their parameter pickles:
@@ -28,6 +29,14 @@ and the spectrogram launch (asr_resample_batch_dev).  The pages are taken at the
 835 pixels wide; --page_width W (none by default; 835 for these networks) accepts scans of any resolution and reduces
 them to W columns on the device, between the upload and the first network (asr_resize_pages_dev: exact area
 resampling, the shape rule of the reference's scripts/prepare_umc_data.py).
+
+--live (A2S only, off by default) runs the reference's default mode, the running vote of AudioSheetServer.run, on the
+recordings as a sound card would deliver them: every queried piece's recording is read at its own rate
+(audio_frontend.read_audio), cut into blocks of --block_ms milliseconds and streamed through
+piece_identification.live_track_scores (AudioStream: asr_audio_stream_push_dev, then PieceTracker).  Per piece it prints
+the first frame at which the piece leads and the share of voiced frames at which it leads
+(audio_sheet_server.report_tracking); --dump_results writes umc_tracking_<tag>_<dset>_A2S[_real].yaml.  The level of the
+music gate is taken from the finished spectrogram, as --track of audio_sheet_server does; a microphone has to be given one.
 """
 import argparse
 import os
@@ -36,8 +45,8 @@ import numpy as np
 
 from . import audio2sheet_align
 from .audio_frontend import SpectrogramProcessor
-from .audio_sheet_server import common_arguments, report_ranks
-from .piece_identification import EmbeddingDB, detect_performances, detect_scores
+from .audio_sheet_server import TRACK_TOP_K, common_arguments, report_ranks, report_tracking
+from .piece_identification import EmbeddingDB, detect_performances, detect_scores, live_track_scores
 from .sheet_utils import umc
 
 # per direction: data-base flag, data-base file, data-base view
@@ -65,7 +74,42 @@ def _arguments(argv, direction):
     p.add_argument("--page_width", type=int, default=None,
                    help="accept page scans of any resolution and resize them to this width on the device "
                         "(asr_resize_pages_dev); the networks were trained at 835")
+    if direction == "A2S":
+        p.add_argument("--live", action="store_true",
+                       help="stream every recording block by block through the running vote (live_track_scores)")
+        p.add_argument("--block_ms", type=float, default=100.0, help="milliseconds of audio per block (--live)")
+        p.add_argument("--running_frames", type=int, default=100,
+                       help="voiced frames in the history of the running vote (--live)")
     return p.parse_args(argv)
+
+
+def tracking_file(param_file, dset, real_perf=False):
+    """result_file's name with umc_tracking_ in place of umc_retrieval_"""
+    return result_file(param_file, dset, "A2S", real_perf).replace("umc_retrieval_", "umc_tracking_", 1)
+
+
+def live_track(engine, db, processor, piece_paths, names, audio_file, n_candidates, running_frames, block_ms):
+    """the recordings of `piece_paths`, streamed in blocks of block_ms milliseconds -> (names, first_lead, lead_share) as
+    audio_sheet_server.track"""
+    from .audio_frontend import read_audio
+    recs, scales, rates, integer = [], [], [], []
+    for piece_path in piece_paths:
+        samples, scale, rate, is_int = read_audio(umc.get_performance_audio_path(piece_path, audio_file))
+        recs.append(samples)
+        scales.append(scale)
+        rates.append(rate)
+        integer.append(is_int)
+    steps = [max(1, int(round(rate * block_ms / 1000.0))) for rate in rates]
+    results = live_track_scores(engine, db, processor, recs, rates, steps, None, top_k=TRACK_TOP_K,
+                                n_candidates=n_candidates, running_frames=running_frames, integer=integer,
+                                window_scales=scales)
+    ids = {name: i for i, name in db.id_to_name.items()}
+    first_lead, lead_share = [], []
+    for name, res in zip(names, results):
+        leads = (res.n_out > 0) & (res.pieces[:, 0] == ids.get(name, -2)) if len(res.frames) else np.zeros(0, bool)
+        first_lead.append(int(res.frames[np.argmax(leads)]) if leads.any() else -1)
+        lead_share.append(float(leads.mean()) if leads.size else 0.0)
+    return names, first_lead, lead_share
 
 
 def result_file(param_file, dset, direction, real_perf=False):
@@ -101,7 +145,7 @@ def run(argv, direction):
             print("Loading spectrograms ...")
             queried = list(range(len(te_pieces)))
         specs = umc.load_specs([piece_paths[i] for i in queried], audio_file, processor, return_device=True,
-                               resample=args.resample)
+                               resample=args.resample or getattr(args, "live", False))
         try:
             if args.init_db:
                 print("Initializing %s db ..." % ("sheet music" if direction == "A2S" else "audio"))
@@ -114,6 +158,13 @@ def run(argv, direction):
                 db.save(d["db_file"])
             else:
                 db = EmbeddingDB.load(engine, d["db_file"])
+            if getattr(args, "live", False):
+                print("\nStreaming every recording through the running vote:")
+                names = [te_pieces[i] for i in queried]
+                return report_tracking(*live_track(engine, db, processor, [piece_paths[i] for i in queried], names,
+                                                   audio_file, args.n_candidates, args.running_frames, args.block_ms),
+                                       res_file=tracking_file(param_file, dset, args.real_perf) if args.dump_results
+                                       else None)
             if not args.full_eval:
                 return []
             print("\nRunning full evaluation:")

@@ -784,6 +784,46 @@ int asr_bars_from_map_dev(asr_ctx *ctx, const double *maps_dev, const int32_t *h
  *   taps_per_phase * up >= 2 * half + 1 and the size of a tile's input span (ratios down / up up to 13 fit) are
  *   checked: a violation returns ASR_ERR_INVALID with a message.  Recordings of zero samples and n_recordings == 0 are
  *   valid and write nothing.
+ * asr_audio_stream_push_dev = asr_resample_batch_dev followed by asr_spectrogram_batch_dev for recordings that arrive
+ *   block by block: for n_streams streams of one input rate, one call takes a block of new input samples per stream and
+ *   writes the spectrogram frames those samples complete; the input samples that later frames still read stay on the
+ *   device, in a buffer the caller owns.
+ *     sequences  x_s[0 .. N) is every input sample stream s has been given so far; N0 = samples_before[s] (the host keeps
+ *                count), N1 = N0 + block_counts[s].  y_s[m] is output m of asr_resample_batch_dev's definition on x_s with
+ *                the same up, down, half, taps_phase_major, taps_per_phase, round_int16.  Output m is final once
+ *                (m * down + half) / up < N: every input it reads has arrived.  M(N) = max(0, ceil((N * up - half) / down)),
+ *                capped at ceil(N * up / down), is the number of final outputs.  up == down == 1 with taps_phase_major ==
+ *                NULL is the front-end's own rate: y = x, M(N) = N, no filter (taps_per_phase, half, round_int16 unused).
+ *     frames     frame i is asr_spectrogram_dev's frame i on y_s, starting at (int64)((double)i * hop).  A stream that is
+ *                not flushed (final[s] == 0) has emitted frame i once start + frame_size <= M(N1): no zero is invented
+ *                for a sample that has not arrived.  A flushed stream (final[s] != 0) takes y_s as the whole recording,
+ *                of length ceil(N1 * up / down) and zero beyond, and emits every remaining frame up to
+ *                ceil(length / hop) (SpectrogramProcessor.num_frames).  The host does not push to a flushed stream again.
+ *     property   whatever the cut into calls, the concatenation of a stream's outputs is bit-identical with
+ *                asr_spectrogram_batch_dev on asr_resample_batch_dev of the whole recording; before the flush the outputs
+ *                are a prefix of it.
+ *     state      stream s owns floats state_offsets[s] .. + state_cap of state_dev (state_floats = size of that buffer).
+ *                After a call it holds input samples keep_from .. N1 - 1, keep_from = the first input the next frame not
+ *                yet emitted reads: (start_next * down + half) / up - (taps_per_phase - 1), clamped to [0, N1]
+ *                (start_next at the front-end's own rate).  It is read where N0 > 0 and rewritten in place by the call,
+ *                on the device, after the frames; N0 == 0 is a reset and does not read it.  N1 - keep_from never exceeds
+ *                ceil((frame_size - 1) * down / up) + taps_per_phase - 1 (frame_size - 1 at the front-end's own rate:
+ *                2047 floats at 22.05 kHz, 4158 at 44.1 kHz, 4526 at 48 kHz), whatever the block lengths;
+ *                state_cap must be at least that (audio_frontend.audio_stream_state_len).
+ *     arguments  block s: block_counts[s] floats (0 is valid) at float block_offsets[s] of blocks_dev (blocks_floats = size
+ *                of that buffer).  first_frames[s] / n_new_frames[s]: the first frame this call emits and how many - the
+ *                host needs them for out_offsets (audio_frontend.audio_stream_plan); the library recomputes both from
+ *                samples_before, block_counts and final, and a mismatch is an error.  The frames go to float
+ *                out_offsets[s] of out_dev (out_floats = its size) as (n_filters, n_new_frames[s]) if transposed else
+ *                (n_new_frames[s], n_filters); floats that belong to no stream are left as they are.  window, fb_start,
+ *                fb_len, fb_weights, mul, add: as asr_spectrogram_batch_dev.
+ *   Before anything is launched: every block, state and output range is checked against its buffer, no two state ranges
+ *   may overlap, state_cap against the bound above, frame_size (a power of two in [64, 8192]) and the filter bank as in
+ *   asr_spectrogram_batch_dev, the resampler arguments as in asr_resample_batch_dev, the frame counts, and the LDS a
+ *   frame's input span needs at this ratio against the 160 KB of a workgroup.  A violation returns ASR_ERR_INVALID with a
+ *   message; a failing call touches no state and writes no output.  n_streams == 0 and all-empty blocks are valid and
+ *   write nothing.  One workgroup per new frame resamples the frame's own samples (overlapping frames resample the
+ *   samples they share once each), then one workgroup per stream slides the state.
  * asr_resize_pages_dev = what scripts/prepare_umc_data.py:17-22 does to a scan before the OMR networks see it (width
  *   835, height int(835.0 / W * H), cv2.resize), for n_pages pages of any sizes in one launch, between the upload and
  *   asr_seg_predict_dev.  OpenCV's fixed-point bilinear rule is not restated; the yardstick is this definition, exact
@@ -819,6 +859,15 @@ int asr_resample_batch_dev(asr_ctx *ctx, const float *in_dev, int64_t in_floats,
                            const int64_t *in_counts, const int64_t *out_offsets, const int64_t *out_counts,
                            int n_recordings, int up, int down, const double *taps_phase_major, int taps_per_phase,
                            int half, int round_int16, float *out_dev, int64_t out_floats);
+int asr_audio_stream_push_dev(asr_ctx *ctx, const float *blocks_dev, int64_t blocks_floats, const int64_t *block_offsets,
+                              const int64_t *block_counts, const int64_t *samples_before, const int32_t *final,
+                              const int64_t *first_frames, const int64_t *n_new_frames, const int64_t *out_offsets,
+                              int n_streams, int up, int down, const double *taps_phase_major, int taps_per_phase,
+                              int half, int round_int16, float *state_dev, int64_t state_floats,
+                              const int64_t *state_offsets, int64_t state_cap, int frame_size, double hop,
+                              const float *window, const int32_t *fb_start, const int32_t *fb_len,
+                              const float *fb_weights, int n_filters, float mul, float add, int transposed,
+                              float *out_dev, int64_t out_floats);
 int asr_resize_pages_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
                          const int32_t *heights, const int32_t *widths, int n_pages, const int64_t *out_offsets,
                          const int32_t *out_heights, const int32_t *out_widths, void *out_dev, int64_t out_bytes);
