@@ -43,7 +43,7 @@ EXPORTS = [
     "asr_seg_create", "asr_seg_set_window", "asr_seg_destroy", "asr_seg_predict_dev", "asr_systems_from_maps_dev",
     "asr_notes_from_map_dev", "asr_bars_from_map_dev",
     "asr_unroll_systems_dev", "asr_spectrogram_batch_dev", "asr_resample_batch_dev", "asr_resize_pages_dev",
-    "asr_audio_stream_push_dev",
+    "asr_audio_stream_push_dev", "asr_skew_estimate_dev", "asr_deskew_pages_dev",
     "asr_opt_state_size", "asr_get_opt_state", "asr_set_opt_state", "asr_debug_train_tensor", "asr_cca_train_debug",
 ]
 
@@ -223,6 +223,10 @@ def load_library(path=None):
                                            c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int64]),
         "asr_resize_pages_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_int64]),
+        "asr_skew_estimate_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                          c_void_p, c_void_p]),
+        "asr_deskew_pages_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                         c_int, c_void_p, c_int64]),
         "asr_audio_stream_push_dev": (c_int, [c_void_p, c_void_p, c_int64] + [c_void_p] * 7 + [c_int, c_int, c_int,
                                               c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64,
                                               c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
@@ -828,6 +832,40 @@ class Engine(object):
         self._check(self.lib.asr_resize_pages_dev(
             self.ctx, pages_ptr, int(pages_bytes), page_offsets.ctypes.data, heights.ctypes.data, widths.ctypes.data, n,
             out_offsets.ctypes.data, out_heights.ctypes.data, out_widths.ctypes.data, out_ptr, int(out_bytes)))
+
+    def skew_estimate_dev(self, pages_ptr, pages_bytes, page_offsets, heights, widths, max_slope=64, return_scores=False):
+        """the slope of the staves of every uint8 page, in 1/1024 pixel per pixel, from the projection profiles of the
+        slopes -max_slope .. max_slope in one call (asr_skew_estimate_dev; the pages as resize_pages_dev reads them).
+        -> int32 (n,); with return_scores also the int64 (n, 2 * max_slope + 1) scores, slope k in column k + max_slope.
+        The integers of sheet_utils.omr.estimate_skew_host / skew_scores_host per page"""
+        page_offsets = np.ascontiguousarray(page_offsets, dtype=np.int64)
+        heights = np.ascontiguousarray(heights, dtype=np.int32)
+        widths = np.ascontiguousarray(widths, dtype=np.int32)
+        n = heights.size
+        if not (page_offsets.size == widths.size == n):
+            raise ValueError("skew_estimate_dev: the per-page tables differ in length")
+        max_slope = int(max_slope)
+        slopes = np.zeros(n, np.int32)
+        scores = np.zeros((n, 2 * max(max_slope, 0) + 1), np.int64) if return_scores else None
+        self._check(self.lib.asr_skew_estimate_dev(
+            self.ctx, pages_ptr, int(pages_bytes), page_offsets.ctypes.data, heights.ctypes.data, widths.ctypes.data, n,
+            max_slope, slopes.ctypes.data, scores.ctypes.data if return_scores else None))
+        return (slopes, scores) if return_scores else slopes
+
+    def deskew_pages_dev(self, pages_ptr, pages_bytes, page_offsets, heights, widths, slopes, out_ptr, out_bytes, fill=255):
+        """every uint8 page sheared by its slope (1/1024 pixel per pixel) in one launch (asr_deskew_pages_dev): the
+        result of page i goes to byte page_offsets[i] of the buffer at out_ptr, in the shape of the page.  Byte for byte
+        sheet_utils.omr.shear_page_host per page"""
+        page_offsets = np.ascontiguousarray(page_offsets, dtype=np.int64)
+        heights = np.ascontiguousarray(heights, dtype=np.int32)
+        widths = np.ascontiguousarray(widths, dtype=np.int32)
+        slopes = np.ascontiguousarray(slopes, dtype=np.int32)
+        n = heights.size
+        if not (page_offsets.size == widths.size == slopes.size == n):
+            raise ValueError("deskew_pages_dev: the per-page tables differ in length")
+        self._check(self.lib.asr_deskew_pages_dev(
+            self.ctx, pages_ptr, int(pages_bytes), page_offsets.ctypes.data, heights.ctypes.data, widths.ctypes.data, n,
+            slopes.ctypes.data, int(fill), out_ptr, int(out_bytes)))
 
     def unroll_systems_dev(self, pages_ptr, pages_bytes, page_offsets, heights, widths, systems, system_height,
                            strip_offsets, strip_widths, strips_ptr, strips_floats):

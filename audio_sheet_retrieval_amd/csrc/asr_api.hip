@@ -208,6 +208,7 @@ void free_ctx_buffers(asr_ctx *ctx) {
     if (ctx->post_ws) hipFree(ctx->post_ws);
     if (ctx->resample_ws) hipFree(ctx->resample_ws);
     if (ctx->resize_ws) hipFree(ctx->resize_ws);
+    if (ctx->skew_ws) hipFree(ctx->skew_ws);
     if (ctx->stream_ws) hipFree(ctx->stream_ws);
     if (ctx->stream_taps) hipFree(ctx->stream_taps);
     if (ctx->topk_tickets) hipFree(ctx->topk_tickets);

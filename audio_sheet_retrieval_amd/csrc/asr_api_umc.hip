@@ -5,6 +5,8 @@
 // include/asr_hip.h for the contract.  Kernels: page_resize_kernels.hip, umc_kernels.hip, resample_kernels.hip,
 // piece_vote_kernels.hip (spectrogram_batch_kernel), audio_stream_kernels.hip.  Every call checks every offset against the buffer sizes the
 // caller states before anything is launched, and returns after the work is done.
+// asr_skew_estimate_dev / asr_deskew_pages_dev (the slope of a scan's staves and its correction, before the resize):
+// page_deskew_kernels.hip.
 #include "asr_ctx.h"
 
 int asr_unroll_systems_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
@@ -512,5 +514,181 @@ int asr_resize_pages_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_byte
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "resize_pages: %s", hipGetErrorString(e));
+    return mark_main(ctx);
+}
+
+namespace {
+
+// the shared checks of the two skew calls; on failure the message is set and the code returned
+int skew_check_pages(asr_ctx *ctx, const char *who, int64_t pages_bytes, const int64_t *page_offsets, const int32_t *heights,
+                     const int32_t *widths, int n_pages) {
+    for (int p = 0; p < n_pages; ++p) {
+        const int64_t h = heights[p], w = widths[p];
+        if (h < 1 || w < 1 || h > asr::SKEW_MAX_DIM || w > asr::SKEW_MAX_DIM)
+            return fail(ctx, ASR_ERR_INVALID, "%s: page %d: %lld x %lld (every dimension must lie in [1, %d])", who, p,
+                        (long long)h, (long long)w, asr::SKEW_MAX_DIM);
+        if (page_offsets[p] < 0 || h * w > pages_bytes || page_offsets[p] > pages_bytes - h * w)
+            return fail(ctx, ASR_ERR_INVALID, "%s: page %d (%lld x %lld at %lld) outside the %lld-byte buffer", who, p,
+                        (long long)h, (long long)w, (long long)page_offsets[p], (long long)pages_bytes);
+    }
+    return ASR_OK;
+}
+
+int skew_ws_reserve(asr_ctx *ctx, size_t bytes) {
+    if (bytes <= ctx->skew_ws_bytes) return ASR_OK;
+    ASR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->skew_ws) ASR_HIP(ctx, hipFree(ctx->skew_ws));
+    ctx->skew_ws = nullptr; ctx->skew_ws_bytes = 0;
+    ASR_HIP(ctx, hipMalloc(&ctx->skew_ws, bytes));
+    ctx->skew_ws_bytes = bytes;
+    return ASR_OK;
+}
+
+size_t skew_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+}  // namespace
+
+int asr_skew_estimate_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
+                          const int32_t *heights, const int32_t *widths, int n_pages, int max_slope, int32_t *slopes,
+                          int64_t *scores) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_pages < 0 || pages_bytes < 0) return fail(ctx, ASR_ERR_INVALID, "skew_estimate: bad sizes");
+    if (max_slope < 0 || max_slope > asr::SKEW_MAX_SLOPE)
+        return fail(ctx, ASR_ERR_INVALID, "skew_estimate: max_slope %d outside [0, %d]", max_slope, asr::SKEW_MAX_SLOPE);
+    if (n_pages == 0) return ASR_OK;
+    if (!page_offsets || !heights || !widths || !slopes || !pages_dev)
+        return fail(ctx, ASR_ERR_INVALID, "skew_estimate: NULL argument");
+    int rc = skew_check_pages(ctx, "skew_estimate", pages_bytes, page_offsets, heights, widths, n_pages);
+    if (rc != ASR_OK) return rc;
+    const int K = max_slope, n_slopes = 2 * K + 1;
+    // chunks of whole pages whose profiles fit ASR_OMR_BUDGET_MB (at least one page each)
+    const char *env = getenv("ASR_OMR_BUDGET_MB");
+    const size_t budget = (size_t)std::max<int64_t>(env && *env ? atoll(env) : 4096, 1) << 20;
+    struct Chunk { int first, n; size_t prof_bytes; int64_t tiles; size_t first_at; };
+    std::vector<Chunk> chunks;
+    std::vector<asr::SkewPage> table(n_pages);
+    std::vector<int64_t> first;                                    // per chunk: n + 1 running tile counts
+    double bytes = 0.0;
+    for (int p = 0; p < n_pages; ++p) {
+        const int h = heights[p], w = widths[p];
+        asr::SkewPage &r = table[p];
+        r.src = page_offsets[p];
+        r.h = h; r.w = w;
+        r.tiles_x = (w + asr::SKEW_TILE_W - 1) / asr::SKEW_TILE_W;
+        r.dm = (K * (w - 1) + 1024) >> 11;
+        r.len = h + 2 * r.dm;
+        const size_t prof_bytes = (size_t)n_slopes * r.len * sizeof(uint32_t);
+        if (chunks.empty() || chunks.back().prof_bytes + prof_bytes > budget) {
+            if (!chunks.empty()) first.push_back(chunks.back().tiles);
+            chunks.push_back({p, 0, 0, 0, first.size()});
+        }
+        Chunk &c = chunks.back();
+        r.prof = (int64_t)(c.prof_bytes / sizeof(uint32_t));
+        first.push_back(c.tiles);
+        c.n += 1;
+        c.prof_bytes += prof_bytes;
+        c.tiles += (int64_t)r.tiles_x * ((h + asr::SKEW_TILE_H - 1) / asr::SKEW_TILE_H);
+        r.pad = 0;
+        bytes += (double)h * w;
+    }
+    first.push_back(chunks.back().tiles);
+    size_t max_prof = 0;
+    for (const Chunk &c : chunks) {
+        if (c.tiles > 0x7fffffffLL) return fail(ctx, ASR_ERR_INVALID, "skew_estimate: %lld tiles in one chunk", (long long)c.tiles);
+        max_prof = std::max(max_prof, c.prof_bytes);
+    }
+    // workspace: running tile counts | page table (one upload) | scores | slopes | profiles of one chunk
+    const size_t b_first = first.size() * sizeof(int64_t), b_table = table.size() * sizeof(asr::SkewPage);
+    const size_t o_table = b_first, o_scores = skew_align(o_table + b_table),
+                 o_slopes = o_scores + (size_t)n_pages * n_slopes * sizeof(int64_t),
+                 o_prof = skew_align(o_slopes + (size_t)n_pages * sizeof(int32_t)), total = o_prof + max_prof;
+    std::vector<char> blob(o_table + b_table);
+    memcpy(blob.data(), first.data(), b_first);
+    memcpy(blob.data() + o_table, table.data(), b_table);
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    rc = skew_ws_reserve(ctx, total);
+    if (rc != ASR_OK) return rc;
+    char *ws = (char *)ctx->skew_ws;
+    int64_t *d_scores = (int64_t *)(ws + o_scores);
+    int32_t *d_slopes = (int32_t *)(ws + o_slopes);
+    uint32_t *d_prof = (uint32_t *)(ws + o_prof);
+    hipError_t e = hipMemcpyAsync(ws, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream);
+    for (size_t i = 0; i < chunks.size() && e == hipSuccess; ++i) {
+        const Chunk &c = chunks[i];
+        const asr::SkewPage *d_table = (const asr::SkewPage *)(ws + o_table) + c.first;
+        e = hipMemsetAsync(d_prof, 0, c.prof_bytes, ctx->stream);
+        if (e == hipSuccess) {
+            ProfScope ps(ctx, "skew_profiles", 0, 0.0, bytes / chunks.size());
+            e = asr::launch_skew_profiles(ctx->stream, (const uint8_t *)pages_dev, (const int64_t *)ws + c.first_at, d_table,
+                                          c.n, c.tiles, K, d_prof);
+        }
+        if (e == hipSuccess) {
+            ProfScope ps(ctx, "skew_scores", 0, 0.0, (double)c.prof_bytes);
+            e = asr::launch_skew_scores(ctx->stream, d_table, c.n, K, d_prof, d_scores + (size_t)c.first * n_slopes,
+                                        d_slopes + c.first);
+        }
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(slopes, d_slopes, (size_t)n_pages * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && scores)
+        e = hipMemcpyAsync(scores, d_scores, (size_t)n_pages * n_slopes * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "skew_estimate: %s", hipGetErrorString(e));
+    return mark_main(ctx);
+}
+
+int asr_deskew_pages_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
+                         const int32_t *heights, const int32_t *widths, int n_pages, const int32_t *slopes, int fill,
+                         void *out_dev, int64_t out_bytes) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_pages < 0 || pages_bytes < 0 || out_bytes < 0) return fail(ctx, ASR_ERR_INVALID, "deskew_pages: bad sizes");
+    if (fill < 0 || fill > 255) return fail(ctx, ASR_ERR_INVALID, "deskew_pages: fill %d outside [0, 255]", fill);
+    if (n_pages == 0) return ASR_OK;
+    if (!page_offsets || !heights || !widths || !slopes || !pages_dev || !out_dev)
+        return fail(ctx, ASR_ERR_INVALID, "deskew_pages: NULL argument");
+    int rc = skew_check_pages(ctx, "deskew_pages", pages_bytes, page_offsets, heights, widths, n_pages);
+    if (rc != ASR_OK) return rc;
+    const char *in0 = (const char *)pages_dev, *out0 = (const char *)out_dev;
+    if (in0 < out0 + out_bytes && out0 < in0 + pages_bytes)
+        return fail(ctx, ASR_ERR_INVALID, "deskew_pages: the output buffer overlaps the pages");
+    const size_t b_first = ((size_t)n_pages + 1) * sizeof(int64_t);
+    std::vector<char> tab(b_first + (size_t)n_pages * sizeof(asr::DeskewPage));   // tile_first (n + 1) | page table
+    int64_t *first = (int64_t *)tab.data();
+    asr::DeskewPage *table = (asr::DeskewPage *)(tab.data() + b_first);
+    int64_t tiles = 0;
+    double bytes = 0.0;
+    for (int p = 0; p < n_pages; ++p) {
+        const int64_t h = heights[p], w = widths[p];
+        if (slopes[p] < -asr::SKEW_MAX_SLOPE || slopes[p] > asr::SKEW_MAX_SLOPE)
+            return fail(ctx, ASR_ERR_INVALID, "deskew_pages: page %d: slope %d outside [-%d, %d]", p, slopes[p],
+                        asr::SKEW_MAX_SLOPE, asr::SKEW_MAX_SLOPE);
+        if (h * w > out_bytes || page_offsets[p] > out_bytes - h * w)
+            return fail(ctx, ASR_ERR_INVALID, "deskew_pages: output %d (%lld x %lld at %lld) outside the %lld-byte buffer", p,
+                        (long long)h, (long long)w, (long long)page_offsets[p], (long long)out_bytes);
+        asr::DeskewPage &r = table[p];
+        r.off = page_offsets[p];
+        r.h = (int32_t)h; r.w = (int32_t)w; r.k = slopes[p];
+        r.tiles_x = (int32_t)((w + asr::DESKEW_TILE_W - 1) / asr::DESKEW_TILE_W);
+        first[p] = tiles;
+        tiles += (int64_t)r.tiles_x * ((h + asr::DESKEW_TILE_H - 1) / asr::DESKEW_TILE_H);
+        bytes += 2.0 * (double)(h * w);
+    }
+    first[n_pages] = tiles;
+    if (tiles > 0x7fffffffLL) return fail(ctx, ASR_ERR_INVALID, "deskew_pages: %lld tiles in one call", (long long)tiles);
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    rc = skew_ws_reserve(ctx, tab.size());
+    if (rc != ASR_OK) return rc;
+    hipError_t e = hipMemcpyAsync(ctx->skew_ws, tab.data(), tab.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        ProfScope ps(ctx, "deskew_pages", 0, 0.0, bytes);
+        e = asr::launch_deskew_pages(ctx->stream, (const uint8_t *)pages_dev, (uint8_t *)out_dev,
+                                     (const int64_t *)ctx->skew_ws,
+                                     (const asr::DeskewPage *)((const char *)ctx->skew_ws + b_first), n_pages, tiles, fill);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "deskew_pages: %s", hipGetErrorString(e));
     return mark_main(ctx);
 }

@@ -269,6 +269,8 @@ struct asr_ctx {
     size_t resample_ws_bytes = 0;
     void *resize_ws = nullptr;                // asr_resize_pages_dev: running tile counts + page table
     size_t resize_ws_bytes = 0;
+    void *skew_ws = nullptr;                  // asr_skew_estimate_dev / asr_deskew_pages_dev: tables, profiles, scores
+    size_t skew_ws_bytes = 0;
     void *stream_ws = nullptr;                // asr_audio_stream_push_dev: running frame counts, stream rows, window, filters
     size_t stream_ws_bytes = 0;
     double *stream_taps = nullptr;            // ... and the phase-major taps of the last call, kept while they stay the same

@@ -390,6 +390,41 @@ struct ResizePage {
 };
 hipError_t launch_resize_pages(hipStream_t s, const uint8_t *pages, uint8_t *out, const int64_t *tile_first,
                                const ResizePage *table, int n_pages, int64_t total_tiles);
+// skew of scanned pages (page_deskew_kernels.hip; include/asr_hip.h carries the definition).  Estimate: one 1024-thread
+// workgroup per tile of SKEW_TILE_H rows x SKEW_TILE_W columns of one page keeps the tile's row prefix sums of the ink
+// in LDS and adds, for every slope, the tile's share of the profile to the page's profiles in global memory (uint32
+// atomics; integer addition commutes).  Then one workgroup per (page, slope) squares and sums a profile, and one thread
+// per page picks the slope in the visiting order.
+constexpr int SKEW_TILE_H = 32;
+constexpr int SKEW_TILE_W = 448;            // a tile's prefix sums: 32 x 449 uint32 (the pitch is odd: no bank conflicts)
+constexpr int SKEW_WAVES = 16;              // waves of a tile's workgroup: each takes every sixteenth slope
+constexpr int SKEW_MAX_SLOPE = 128;
+constexpr int SKEW_MAX_DIM = 16384;
+struct SkewPage {
+    int64_t src;            // byte offset of the page in the source buffer
+    int64_t prof;           // first uint32 of the page's (2 * max_slope + 1) x len profiles in the profile workspace
+    int32_t h, w;
+    int32_t tiles_x;        // column tiles: ceil(w / SKEW_TILE_W)
+    int32_t dm;             // d_max_slope(w - 1), the largest |d|: profile row r is kept at index r + dm
+    int32_t len;            // h + 2 * dm
+    int32_t pad;
+};
+hipError_t launch_skew_profiles(hipStream_t s, const uint8_t *pages, const int64_t *tile_first, const SkewPage *table,
+                                int n_pages, int64_t total_tiles, int max_slope, uint32_t *prof);
+hipError_t launch_skew_scores(hipStream_t s, const SkewPage *table, int n_pages, int max_slope, const uint32_t *prof,
+                              int64_t *scores, int32_t *slopes);
+// Correction: one 256-thread workgroup per tile of DESKEW_TILE_H rows x DESKEW_TILE_W columns of one output page, one
+// column per thread; both shears in one pass (the intermediate pixel is rounded to uint8 as the definition says).
+constexpr int DESKEW_TILE_H = 8;
+constexpr int DESKEW_TILE_W = 256;
+struct DeskewPage {
+    int64_t off;            // byte offset of the page in the source buffer and of its result in the output buffer
+    int32_t h, w;
+    int32_t k;              // slope, in 1/1024
+    int32_t tiles_x;        // column tiles: ceil(w / DESKEW_TILE_W)
+};
+hipError_t launch_deskew_pages(hipStream_t s, const uint8_t *pages, uint8_t *out, const int64_t *tile_first,
+                               const DeskewPage *table, int n_pages, int64_t total_tiles, int fill);
 // batch assembly of the training pool: desc_dev holds n x 9 doubles (see piece_vote_kernels.hip)
 hipError_t launch_gather_windows(hipStream_t s, const float *src, const double *desc_dev, int n, int out_h, int out_w,
                                  float *out);

@@ -352,6 +352,98 @@ def resize_pages_host(pages, width=PAGE_WIDTH):
     return [resize_page_host(p, *resized_shape(p.shape[0], p.shape[1], width)) for p in pages]
 
 
+MAX_SLOPE = 128             # the largest slope of asr_skew_estimate_dev / asr_deskew_pages_dev, in 1/1024 pixel per pixel
+
+
+def _uint8_page(page, who):
+    page = np.asarray(page)
+    if page.ndim != 2 or page.dtype != np.uint8 or page.size == 0:
+        raise ValueError("%s takes a 2-D uint8 page, got %s %s" % (who, page.dtype, page.shape))
+    return page
+
+
+def skew_scores_host(page, max_slope=64):
+    """asr_skew_estimate_dev's scores on the host (the definition in include/asr_hip.h): int64 (2 * max_slope + 1,),
+    slope k at k + max_slope - the sum of squares of the projection profile of the ink along lines of slope k / 1024.
+    d_k is constant over runs of columns, so a profile is built from differences of the rows' running sums, one per
+    (row, run), not from one add per pixel.  The device returns the same integers."""
+    page = _uint8_page(page, "skew_scores_host")
+    K = int(max_slope)
+    if not 0 <= K <= MAX_SLOPE:
+        raise ValueError("skew_scores_host: max_slope %d outside [0, %d]" % (K, MAX_SLOPE))
+    h, w = page.shape
+    run = np.zeros((w + 1, h), np.int64)                                      # run[i]: ink of the first i columns, per row
+    np.cumsum(255 - page.T.astype(np.int64), axis=0, out=run[1:])
+    x = np.arange(w, dtype=np.int64)
+    scores = np.zeros(2 * K + 1, np.int64)
+    for k in range(-K, K + 1):
+        d = (k * (2 * x - (w - 1)) + 1024) >> 11
+        starts = np.flatnonzero(np.concatenate([[True], d[1:] != d[:-1]]))
+        ends = np.concatenate([starts[1:], [w]])
+        strips = run[ends] - run[starts]                                      # (runs, h): the ink of a run, per row
+        shifts = d[starts]
+        dm = int(np.abs(shifts).max())
+        P = np.zeros(h + 2 * dm, np.int64)                                    # P[r + dm], r = y - d
+        for j, dj in enumerate(shifts):
+            P[dm - dj:dm - dj + h] += strips[j]
+        scores[k + K] = np.dot(P, P)
+    return scores
+
+
+def pick_slope(scores):
+    """the slope of largest score: the candidates in the order 0, -1, +1, -2, +2, ..., replaced only on strict >"""
+    scores = np.asarray(scores)
+    K = (scores.size - 1) // 2
+    best, top = 0, scores[K]
+    for m in range(1, K + 1):
+        for k in (-m, m):
+            if scores[k + K] > top:
+                best, top = k, scores[k + K]
+    return best
+
+
+def estimate_skew_host(page, max_slope=64):
+    """the slope of the staves of a scanned page in 1/1024 pixel per pixel, as asr_skew_estimate_dev returns it: shearing
+    the page by it (shear_page_host) makes them horizontal.  0 for a blank or ambiguous page."""
+    return pick_slope(skew_scores_host(page, max_slope))
+
+
+def shear_page_host(page, k, fill=255):
+    """asr_deskew_pages_dev on the host (the definition in include/asr_hip.h): the page sheared by slope k / 1024 down
+    its columns, then by -k / 1024 along its rows - a rotation up to a scale of 1 - (k / 1024)^2 - in integers, each pass
+    rounded to uint8, `fill` outside the page.  The shape stays; k = 0 is the identity.  The device returns the same
+    bytes."""
+    page = _uint8_page(page, "shear_page_host")
+    k, fill = int(k), int(fill)
+    if abs(k) > MAX_SLOPE or not 0 <= fill <= 255:
+        raise ValueError("shear_page_host: slope %d (at most %d) / fill %d (0 .. 255)" % (k, MAX_SLOPE, fill))
+    h, w = page.shape
+    x, y = np.arange(w, dtype=np.int64), np.arange(h, dtype=np.int64)
+    t = k * (2 * x - (w - 1))
+    q = t >> 11
+    f = t - 2048 * q
+    top, bottom = max(0, int(-q.min())), max(0, int(q.max()) + 1)
+    I = np.full((top + h + bottom, w), fill, np.int64)
+    I[top:top + h] = page
+    rows = y[:, None] + q[None, :] + top
+    A = ((2048 - f) * np.take_along_axis(I, rows, axis=0) + f * np.take_along_axis(I, rows + 1, axis=0) + 1024) >> 11
+    u = -k * (2 * y - (h - 1))
+    p = u >> 11
+    g = (u - 2048 * p)[:, None]
+    left, right = max(0, int(-p.min())), max(0, int(p.max()) + 1)
+    Ap = np.full((h, left + w + right), fill, np.int64)
+    Ap[:, left:left + w] = A
+    cols = x[None, :] + p[:, None] + left
+    out = ((2048 - g) * np.take_along_axis(Ap, cols, axis=1) + g * np.take_along_axis(Ap, cols + 1, axis=1) + 1024) >> 11
+    return out.astype(np.uint8)
+
+
+def deskew_page_host(page, max_slope=64, fill=255):
+    """-> (the page sheared by its estimated slope, the slope): estimate_skew_host, then shear_page_host"""
+    k = estimate_skew_host(page, max_slope)
+    return shear_page_host(page, k, fill), k
+
+
 class DevicePages(object):
     """uint8 pages back to back in one device buffer, as asr_seg_predict_dev (IN_U8_RAW) and asr_unroll_systems_dev
     read them: uploaded once, used by both networks and by the unroll."""
@@ -400,6 +492,32 @@ class DevicePages(object):
             raise
         return res
 
+    def deskewed(self, max_slope=64, slopes=None, fill=255):
+        """a new DevicePages on the same engine: every page sheared so that its staves lie horizontal, in the shape it
+        has (asr_skew_estimate_dev - the slopes -max_slope .. max_slope, in 1/1024 - then asr_deskew_pages_dev; with
+        `slopes` those are applied and nothing is estimated).  The result carries the slopes as .slopes (int32); nothing
+        else is uploaded or downloaded.  This object stays valid; free both."""
+        if slopes is None:
+            slopes = self.engine.skew_estimate_dev(self.buf.ptr, self.nbytes, self.offsets, self.heights, self.widths,
+                                                   max_slope)
+        slopes = np.ascontiguousarray(slopes, dtype=np.int32)
+        if slopes.shape != (len(self),):
+            raise ValueError("%d slopes for %d pages" % (slopes.size, len(self)))
+        res = DevicePages.__new__(DevicePages)
+        res.engine = self.engine
+        res.heights, res.widths, res.sizes, res.offsets = self.heights.copy(), self.widths.copy(), self.sizes.copy(), \
+            self.offsets.copy()
+        res.nbytes = self.nbytes
+        res.slopes = slopes
+        res.buf = self.engine.alloc(max(res.nbytes, 4))
+        try:
+            self.engine.deskew_pages_dev(self.buf.ptr, self.nbytes, self.offsets, self.heights, self.widths, slopes,
+                                         res.buf.ptr, res.nbytes, fill)
+        except Exception:
+            res.buf.free()
+            raise
+        return res
+
     def download_page(self, i):
         """page i as a uint8 array on the host"""
         return self.engine.raw_download(self.buf.ptr + int(self.offsets[i]), (int(self.heights[i]), int(self.widths[i])),
@@ -417,6 +535,16 @@ def resize_pages_dev(engine, pages, width=PAGE_WIDTH):
     raw = DevicePages(engine, pages)
     try:
         return raw.resized(width)
+    finally:
+        raw.free()
+
+
+def deskew_pages_dev(engine, pages, max_slope=64, slopes=None, fill=255):
+    """host pages (2-D uint8 arrays of any sizes) -> a DevicePages holding them straightened (DevicePages.deskewed), with
+    the slopes as .slopes: one upload of the raw pages.  Free it when done."""
+    raw = DevicePages(engine, pages)
+    try:
+        return raw.deskewed(max_slope, slopes, fill)
     finally:
         raw.free()
 

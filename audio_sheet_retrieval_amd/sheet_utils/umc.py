@@ -1,6 +1,7 @@
 """load_umc_sheets of umc_a2s_server.py / umc_s2a_server.py: unrolled sheets of every piece under a data directory
 (<piece>/sheet/*.png), with the systems of all pages detected in one device call per network - and, with
-return_device, unrolled in one more (the strips stay on the device for the data base and the queries).  load_specs /
+return_device, unrolled in one more (the strips stay on the device for the data base and the queries).  load_umc_scans:
+the same for flat-bed scans, straightened and resized on the device first.  load_specs /
 get_performance_audio_path: the recordings of the pieces (umc_a2s_server.py:28-45)."""
 from __future__ import print_function
 
@@ -10,9 +11,9 @@ import os
 import numpy as np
 
 from audio_sheet_retrieval_amd.sheet_utils import bar_detector, note_detector, system_detector
-from audio_sheet_retrieval_amd.sheet_utils.omr import (IN_U8_RAW, SYSTEM_HEIGHT, DevicePages, OpticalMusicRecognizer,
-                                                       SegmentationNetwork, imread_gray, unroll_rows,
-                                                       unroll_systems_dev, unwrap_systems)
+from audio_sheet_retrieval_amd.sheet_utils.omr import (IN_U8_RAW, PAGE_WIDTH, SYSTEM_HEIGHT, DevicePages,
+                                                       OpticalMusicRecognizer, SegmentationNetwork, imread_gray,
+                                                       unroll_rows, unroll_systems_dev, unwrap_systems)
 
 OKBLUE, ENDC = "\033[94m", "\033[0m"       # utils/plotting.BColors
 
@@ -91,6 +92,14 @@ class _PagesOnDevice(object):
         return self._host[i]
 
 
+def _next_stage(dev_pages, stage):
+    """stage(dev_pages) -> the next DevicePages; the one it was made from is freed, also when the stage fails"""
+    try:
+        return stage(dev_pages)
+    finally:
+        dev_pages.free()
+
+
 def load_umc_sheets(data_dir, require_performance=False, omr=None, system_params=None, bar_params=None, device=0,
                     return_device=False, device_post=False, page_width=None):
     """ load unwarpped sheets
@@ -109,6 +118,25 @@ def load_umc_sheets(data_dir, require_performance=False, omr=None, system_params
     host route they are downloaded once for unwrap_systems; with return_device a resized page comes to the host only
     where the post-processing reads it there (device_post=False: every page; device_post=True: a page the device does
     not decide).  None: the pages are taken as they are."""
+    return _load_sheets(data_dir, require_performance, omr, system_params, bar_params, device, return_device, device_post,
+                        page_width, False, 0)
+
+
+def load_umc_scans(data_dir, require_performance=False, omr=None, system_params=None, bar_params=None, device=0,
+                   return_device=False, device_post=False, page_width=PAGE_WIDTH, deskew=True, max_slope=64):
+    """load_umc_sheets for flat-bed scans: pages of any resolution whose staves need not be horizontal.  The raw pages
+    are uploaded once; with deskew the slope of every page is estimated among -max_slope .. max_slope (in 1/1024 pixel
+    per pixel) and the page sheared by it on the device (DevicePages.deskewed: asr_skew_estimate_dev,
+    asr_deskew_pages_dev), then the pages are reduced to page_width columns (DevicePages.resized; None: left at their
+    size) - the area resize after the shear takes the interpolation blur away again.  Everything downstream reads the
+    result on the device, as in load_umc_sheets; the return values are the same."""
+    return _load_sheets(data_dir, require_performance, omr, system_params, bar_params, device, return_device, device_post,
+                        page_width, deskew, max_slope)
+
+
+def _load_sheets(data_dir, require_performance, omr, system_params, bar_params, device, return_device, device_post,
+                 page_width, deskew, max_slope):
+    """the body of load_umc_sheets / load_umc_scans"""
     if omr is None:
         omr = build_recognizer(system_params, bar_params, device=device)
 
@@ -136,10 +164,14 @@ def load_umc_sheets(data_dir, require_performance=False, omr=None, system_params
     # every page of every piece: one call per network (prepare_image on the device)
     all_pages = [I for _, _, pages in jobs for I in pages]
     dev_pages = None
-    if page_width is not None and all_pages:
-        from audio_sheet_retrieval_amd.sheet_utils.omr import _engine, resize_pages_dev
+    if (page_width is not None or deskew) and all_pages:
+        from audio_sheet_retrieval_amd.sheet_utils.omr import _engine
         engine = omr.system_detector.engine or _engine(omr.system_detector.device)
-        dev_pages = resize_pages_dev(engine, all_pages, page_width)
+        dev_pages = DevicePages(engine, all_pages)              # upload raw, then deskew, then resize
+        if deskew:
+            dev_pages = _next_stage(dev_pages, lambda pages: pages.deskewed(max_slope))
+        if page_width is not None:
+            dev_pages = _next_stage(dev_pages, lambda pages: pages.resized(page_width))
     if return_device:
         return _unroll_on_device(omr, jobs, all_pages, device_post=device_post, dev_pages=dev_pages)
     detect = omr.detect_systems_pages_dev if device_post else omr.detect_systems_pages

@@ -6,7 +6,7 @@ umc_a2s_server.py (:178-189):
         --train_split splits/all_split.yaml --config exp_configs/mutopia_full_aug.yaml \
         --init_sheet_db --full_eval --dump_results [--real_perf] [--n_candidates 25] [--estimate_UV] \
         --system_params system_params.pkl --bar_params bar_params.pkl [--device_post] [--resample] [--page_width 835]
-        [--live [--block_ms 100] [--running_frames 100]]
+        [--deskew] [--live [--block_ms 100] [--running_frames 100]]
 
 <dir> holds one folder per piece: sheet/*.png (the page scans), score_ppq.* (the synthesised recording) and, for
 --real_perf, 01_performance*.  The pages go through the two segmentation networks (their parameter pickles:
@@ -28,7 +28,9 @@ files of any sample rate (audio_frontend.read_audio) and resamples them to 22050
 and the spectrogram launch (asr_resample_batch_dev).  The pages are taken at the resolution the networks were trained on,
 835 pixels wide; --page_width W (none by default; 835 for these networks) accepts scans of any resolution and reduces
 them to W columns on the device, between the upload and the first network (asr_resize_pages_dev: exact area
-resampling, the shape rule of the reference's scripts/prepare_umc_data.py).
+resampling, the shape rule of the reference's scripts/prepare_umc_data.py).  --deskew (off by default; with or without
+--page_width) takes flat-bed scans whose staves are not horizontal: the slope of every page is estimated and the page
+sheared by it on the device, between the upload and the resize (sheet_utils/umc.load_umc_scans).
 
 --live (A2S only, off by default) runs the reference's default mode, the running vote of AudioSheetServer.run, on the
 recordings as a sound card would deliver them: every queried piece's recording is read at its own rate
@@ -74,6 +76,9 @@ def _arguments(argv, direction):
     p.add_argument("--page_width", type=int, default=None,
                    help="accept page scans of any resolution and resize them to this width on the device "
                         "(asr_resize_pages_dev); the networks were trained at 835")
+    p.add_argument("--deskew", action="store_true",
+                   help="estimate the slope of every page's staves and straighten the page on the device, before the "
+                        "resize (asr_skew_estimate_dev, asr_deskew_pages_dev; sheet_utils/umc.load_umc_scans)")
     if direction == "A2S":
         p.add_argument("--live", action="store_true",
                        help="stream every recording block by block through the running vote (live_track_scores)")
@@ -124,9 +129,14 @@ def run(argv, direction):
     if args.data_dir is None:
         raise SystemExit("--data_dir: the directory of pieces is required")
     omr = umc.build_recognizer(args.system_params, args.bar_params)
-    te_pieces, piece_paths, _, strips = umc.load_umc_sheets(args.data_dir, require_performance=True, omr=omr,
-                                                           return_device=True, device_post=args.device_post,
-                                                           page_width=args.page_width)
+    if args.deskew:
+        te_pieces, piece_paths, _, strips = umc.load_umc_scans(args.data_dir, require_performance=True, omr=omr,
+                                                               return_device=True, device_post=args.device_post,
+                                                               page_width=args.page_width, deskew=True)
+    else:
+        te_pieces, piece_paths, _, strips = umc.load_umc_sheets(args.data_dir, require_performance=True, omr=omr,
+                                                               return_device=True, device_post=args.device_post,
+                                                               page_width=args.page_width)
     try:
         dset = os.path.basename(args.data_dir)
         audio_file = "01_performance" if args.real_perf else "score_ppq"

@@ -844,7 +844,35 @@ int asr_bars_from_map_dev(asr_ctx *ctx, const double *maps_dev, const int32_t *h
  *   workspace of the context.  Before anything is launched every page and every output is checked against its buffer
  *   size, and per page: all four dimensions at least 1 and at most 2^24, h_in * w_in < 2^31, and per axis
  *   n_out / 4 <= n_in <= 16 * n_out (ratios n_in / n_out from 1/4 to 16: what a tile's source rows in LDS are sized
- *   for).  A violation returns ASR_ERR_INVALID with a message.  n_pages == 0 is valid and writes nothing. */
+ *   for).  A violation returns ASR_ERR_INVALID with a message.  n_pages == 0 is valid and writes nothing.
+ * asr_skew_estimate_dev / asr_deskew_pages_dev = straightening a scan whose staves are not horizontal, between the upload
+ *   and asr_resize_pages_dev.  The reference has no such stage; the yardstick is this definition, all in integers, which
+ *   sheet_utils/omr.skew_scores_host / estimate_skew_host / shear_page_host restate in numpy and the device reproduces
+ *   exactly.  Pages are uint8, dark ink on light paper, in the layout of asr_resize_pages_dev.  A slope k is an integer in
+ *   units of 1/1024 pixel per pixel; >> is the arithmetic shift (floor division).
+ *     profile   t_k(x) = k * (2 * x - (W - 1)), in 1/2048 pixel; d_k(x) = (t_k(x) + 1024) >> 11;
+ *               P_k[r] = sum over all pixels (y, x) with y - d_k(x) == r of (255 - page[y][x]), r over every value that
+ *               occurs (no pixel is dropped); score_k = sum over r of P_k[r]^2 in int64 (P fits 32 bits, the score stays
+ *               below 2^59)
+ *     estimate  the k in [-max_slope, max_slope] of largest score; the candidates are visited in the order 0, -1, +1, -2,
+ *               +2, ... and one replaces the best only on strict >: a blank or ambiguous page gives 0
+ *     shear     by slope k with fill in 0 .. 255, two passes, each rounded to uint8.  Vertical: q = t_k(x) >> 11,
+ *               f = t_k(x) - 2048 * q, A[y][x] = ((2048 - f) * I(y + q, x) + f * I(y + q + 1, x) + 1024) >> 11 with
+ *               I(r, x) = page[r][x] inside the page and fill outside.  Horizontal: u(y) = -k * (2 * y - (H - 1)),
+ *               p = u >> 11, g = u - 2048 * p, out[y][x] = ((2048 - g) * A(y, x + p) + g * A(y, x + p + 1) + 1024) >> 11
+ *               with A = fill outside its columns.  k = 0 is the identity; the output has the input's shape; shearing by
+ *               the estimate straightens the page (the two shears are a rotation up to a scale of 1 - s^2).
+ *   asr_skew_estimate_dev: all pages and all slopes in one call.  slopes: host int32[n_pages].  scores: host
+ *   int64[n_pages * (2 * max_slope + 1)], the score of slope k of page p at p * (2 * max_slope + 1) + k + max_slope, or
+ *   NULL.  d_k is constant over runs of about 1024 / |k| columns, so a profile costs two reads of a row's prefix sums per
+ *   (row, run), not one add per pixel.  The profiles are workspace of the context; batches whose profiles exceed
+ *   ASR_OMR_BUDGET_MB (default 4096) run in chunks of whole pages with identical results.
+ *   asr_deskew_pages_dev: page p sheared by slopes[p] (host int32[n_pages]) goes to the same byte offset of out_dev
+ *   (out_bytes = its size), which must not overlap pages_dev.  Bytes of out_dev that belong to no page are left as they
+ *   are.
+ *   Both: rows at any alignment.  Before anything is launched: 1 <= H, W <= 16384, 0 <= max_slope <= 128,
+ *   |slopes[p]| <= 128, 0 <= fill <= 255, and every page inside the buffers.  A violation returns ASR_ERR_INVALID with a
+ *   message and writes nothing.  n_pages == 0 is valid and writes nothing. */
 int asr_unroll_systems_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
                            const int32_t *heights, const int32_t *widths, int n_pages, const int32_t *systems,
                            int n_systems, int system_height, const int64_t *strip_offsets, const int32_t *strip_widths,
@@ -871,6 +899,12 @@ int asr_audio_stream_push_dev(asr_ctx *ctx, const float *blocks_dev, int64_t blo
 int asr_resize_pages_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
                          const int32_t *heights, const int32_t *widths, int n_pages, const int64_t *out_offsets,
                          const int32_t *out_heights, const int32_t *out_widths, void *out_dev, int64_t out_bytes);
+int asr_skew_estimate_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
+                          const int32_t *heights, const int32_t *widths, int n_pages, int max_slope, int32_t *slopes,
+                          int64_t *scores);
+int asr_deskew_pages_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
+                         const int32_t *heights, const int32_t *widths, int n_pages, const int32_t *slopes, int fill,
+                         void *out_dev, int64_t out_bytes);
 
 /* ---- device memory (plain pointers; library-owned allocations) ---------- */
 int asr_dev_alloc(asr_ctx *ctx, size_t bytes, void **dptr);
