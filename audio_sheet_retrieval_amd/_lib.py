@@ -42,7 +42,7 @@ EXPORTS = [
     "asr_rank_sharded_dev", "asr_slice_windows_dev", "asr_piece_vote_dev", "asr_piece_vote_batch_dev", "asr_track_gate_dev", "asr_track_vote_batch_dev", "asr_gather_windows_dev", "asr_dtw_dev", "asr_dtw_batch_dev", "asr_dtw_subseq_batch_dev", "asr_dtw_follow_batch_dev", "asr_spectrogram_dev", "asr_debug_tune_report",
     "asr_seg_create", "asr_seg_set_window", "asr_seg_destroy", "asr_seg_predict_dev", "asr_systems_from_maps_dev",
     "asr_notes_from_map_dev", "asr_bars_from_map_dev",
-    "asr_unroll_systems_dev", "asr_spectrogram_batch_dev", "asr_resample_batch_dev", "asr_resize_pages_dev",
+    "asr_unroll_systems_dev", "asr_spectrogram_batch_dev", "asr_spectrogram_fft_batch_dev", "asr_resample_batch_dev", "asr_resize_pages_dev",
     "asr_audio_stream_push_dev", "asr_skew_estimate_dev", "asr_deskew_pages_dev",
     "asr_opt_state_size", "asr_get_opt_state", "asr_set_opt_state", "asr_debug_train_tensor", "asr_cca_train_debug",
 ]
@@ -219,6 +219,9 @@ def load_library(path=None):
         "asr_spectrogram_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                               c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
                                               c_float, c_int, c_void_p, c_int64]),
+        "asr_spectrogram_fft_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                                  c_float, c_float, c_int, c_void_p, c_int64]),
         "asr_resample_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                            c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int64]),
         "asr_resize_pages_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
@@ -737,11 +740,9 @@ class Engine(object):
                                                  fb_start.ctypes.data, fb_len.ctypes.data, fb_weights.ctypes.data,
                                                  fb_start.size, mul, add, n_frames, 1 if transposed else 0, out_ptr))
 
-    def spectrogram_batch_dev(self, samples_ptr, samples_floats, sample_offsets, sample_counts, n_frames, out_offsets,
-                              frame_size, hop, window, fb_start, fb_len, fb_weights, out_ptr, out_floats, mul=1.0,
-                              add=1.0, transposed=True):
-        """spectrogram_dev for many recordings of one concatenated sample buffer in one launch
-        (asr_spectrogram_batch_dev); per recording bit-identical with spectrogram_dev on it alone"""
+    def _spectrogram_batch(self, fn, samples_ptr, samples_floats, sample_offsets, sample_counts, n_frames, out_offsets,
+                           frame_size, hop, window, fb_start, fb_len, fb_weights, out_ptr, out_floats, mul, add, transposed):
+        """the argument marshalling asr_spectrogram_batch_dev and asr_spectrogram_fft_batch_dev (fn) share"""
         i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
         sample_offsets, sample_counts, n_frames, out_offsets = map(i64, (sample_offsets, sample_counts, n_frames,
                                                                          out_offsets))
@@ -752,11 +753,30 @@ class Engine(object):
         fb_start = np.ascontiguousarray(fb_start, np.int32)
         fb_len = np.ascontiguousarray(fb_len, np.int32)
         fb_weights = np.ascontiguousarray(fb_weights, np.float32)
-        self._check(self.lib.asr_spectrogram_batch_dev(
+        self._check(fn(
             self.ctx, samples_ptr, int(samples_floats), sample_offsets.ctypes.data, sample_counts.ctypes.data,
             n_frames.ctypes.data, out_offsets.ctypes.data, n, frame_size, hop, window.ctypes.data, fb_start.ctypes.data,
             fb_len.ctypes.data, fb_weights.ctypes.data, fb_start.size, mul, add, 1 if transposed else 0, out_ptr,
             int(out_floats)))
+
+    def spectrogram_batch_dev(self, samples_ptr, samples_floats, sample_offsets, sample_counts, n_frames, out_offsets,
+                              frame_size, hop, window, fb_start, fb_len, fb_weights, out_ptr, out_floats, mul=1.0,
+                              add=1.0, transposed=True):
+        """spectrogram_dev for many recordings of one concatenated sample buffer in one launch
+        (asr_spectrogram_batch_dev); per recording bit-identical with spectrogram_dev on it alone"""
+        self._spectrogram_batch(self.lib.asr_spectrogram_batch_dev, samples_ptr, samples_floats, sample_offsets,
+                                sample_counts, n_frames, out_offsets, frame_size, hop, window, fb_start, fb_len,
+                                fb_weights, out_ptr, out_floats, mul, add, transposed)
+
+    def spectrogram_fft_batch_dev(self, samples_ptr, samples_floats, sample_offsets, sample_counts, n_frames, out_offsets,
+                                  frame_size, hop, window, fb_start, fb_len, fb_weights, out_ptr, out_floats, mul=1.0,
+                                  add=1.0, transposed=True):
+        """spectrogram_batch_dev with the magnitudes from a real-input FFT (asr_spectrogram_fft_batch_dev; frame_size
+        2048 only): within float32 rounding of the DFT, not bit-identical with spectrogram_batch_dev; per recording
+        bit-identical whatever else is in the call, in either layout"""
+        self._spectrogram_batch(self.lib.asr_spectrogram_fft_batch_dev, samples_ptr, samples_floats, sample_offsets,
+                                sample_counts, n_frames, out_offsets, frame_size, hop, window, fb_start, fb_len,
+                                fb_weights, out_ptr, out_floats, mul, add, transposed)
 
     def resample_batch_dev(self, in_ptr, in_floats, in_offsets, in_counts, out_offsets, out_counts, up, down,
                            taps_phase_major, half, round_int16, out_ptr, out_floats):

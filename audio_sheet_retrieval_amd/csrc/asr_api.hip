@@ -207,6 +207,7 @@ void free_ctx_buffers(asr_ctx *ctx) {
     if (ctx->vote_ws) hipFree(ctx->vote_ws);
     if (ctx->post_ws) hipFree(ctx->post_ws);
     if (ctx->resample_ws) hipFree(ctx->resample_ws);
+    if (ctx->specfft_ws) hipFree(ctx->specfft_ws);
     if (ctx->resize_ws) hipFree(ctx->resize_ws);
     if (ctx->skew_ws) hipFree(ctx->skew_ws);
     if (ctx->stream_ws) hipFree(ctx->stream_ws);

@@ -5,6 +5,8 @@
 // include/asr_hip.h for the contract.  Kernels: page_resize_kernels.hip, umc_kernels.hip, resample_kernels.hip,
 // piece_vote_kernels.hip (spectrogram_batch_kernel), audio_stream_kernels.hip.  Every call checks every offset against the buffer sizes the
 // caller states before anything is launched, and returns after the work is done.
+// asr_spectrogram_fft_batch_dev (asr_spectrogram_batch_dev's spectrograms with the magnitudes from a real-input FFT):
+// spectrogram_fft_kernels.hip.
 // asr_skew_estimate_dev / asr_deskew_pages_dev (the slope of a scan's staves and its correction, before the resize):
 // page_deskew_kernels.hip.
 #include "asr_ctx.h"
@@ -144,6 +146,116 @@ int asr_spectrogram_batch_dev(asr_ctx *ctx, const float *samples_dev, int64_t sa
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     (void)hipFree(buf);
     if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "spectrogram_batch: %s", hipGetErrorString(e));
+    return mark_main(ctx);
+}
+
+// the twiddle table of spectrogram_fft_kernels.hip: exp(-2 pi i t / 2048) as (cos, -sin), t = 0 .. 2047, float32 rounded
+// from float64 - the one place it is computed.  The quadrant is taken out first so that the multiples of pi / 2 are exact.
+static const std::vector<float> &specfft_twiddles() {
+    static const std::vector<float> table = [] {
+        std::vector<float> tw(2 * 2048);
+        const double kPi = 3.14159265358979323846;
+        for (int t = 0; t < 2048; ++t) {
+            const int quad = t >> 9, r = t & 511;
+            const double c = cos(2.0 * kPi * r / 2048.0), s = sin(2.0 * kPi * r / 2048.0);
+            const double cs[4][2] = {{c, s}, {-s, c}, {-c, -s}, {s, -c}};    // cos, sin of the angle + quad * pi / 2
+            tw[2 * t] = (float)cs[quad][0];
+            tw[2 * t + 1] = (float)-cs[quad][1];
+        }
+        return tw;
+    }();
+    return table;
+}
+
+int asr_spectrogram_fft_batch_dev(asr_ctx *ctx, const float *samples_dev, int64_t samples_floats,
+                                  const int64_t *sample_offsets, const int64_t *sample_counts, const int64_t *n_frames,
+                                  const int64_t *out_offsets, int n_recordings, int frame_size, double hop,
+                                  const float *window, const int32_t *fb_start, const int32_t *fb_len,
+                                  const float *fb_weights, int n_filters, float mul, float add, int transposed,
+                                  float *out_dev, int64_t out_floats) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_recordings < 0 || samples_floats < 0 || out_floats < 0 || !(hop > 0.0) || n_filters < 1 || n_filters > 4096)
+        return fail(ctx, ASR_ERR_INVALID, "spectrogram_fft_batch: bad sizes");
+    if (frame_size != 2048)
+        return fail(ctx, ASR_ERR_INVALID, "spectrogram_fft_batch: frame_size %d (the FFT route has frames of 2048 samples; "
+                    "asr_spectrogram_batch_dev takes the others)", frame_size);
+    if (n_recordings == 0) return ASR_OK;
+    if (!sample_offsets || !sample_counts || !n_frames || !out_offsets)
+        return fail(ctx, ASR_ERR_INVALID, "spectrogram_fft_batch: NULL argument");
+    // one host image of everything the launch reads besides the samples:
+    // frame_first (n + 1) | sample_off | sample_cnt | out_off | window | fb_start | fb_len | fb_off | weights
+    const size_t n_tab = (size_t)4 * n_recordings + 1;
+    std::vector<int64_t> tab(n_tab);
+    int64_t *first = tab.data(), *s_off = first + n_recordings + 1, *s_cnt = s_off + n_recordings,
+            *o_off = s_cnt + n_recordings;
+    int64_t total = 0;
+    for (int i = 0; i < n_recordings; ++i) {
+        if (sample_counts[i] < 0 || n_frames[i] < 0 || sample_offsets[i] < 0 || out_offsets[i] < 0 ||
+            sample_counts[i] > samples_floats || sample_offsets[i] > samples_floats - sample_counts[i] ||
+            n_frames[i] > out_floats / n_filters || out_offsets[i] > out_floats - n_frames[i] * (int64_t)n_filters)
+            return fail(ctx, ASR_ERR_INVALID, "spectrogram_fft_batch: recording %d (%lld samples at %lld, %lld frames at "
+                        "%lld) outside its buffers (%lld / %lld floats)", i, (long long)sample_counts[i],
+                        (long long)sample_offsets[i], (long long)n_frames[i], (long long)out_offsets[i],
+                        (long long)samples_floats, (long long)out_floats);
+        first[i] = total;
+        s_off[i] = sample_offsets[i];
+        s_cnt[i] = sample_counts[i];
+        o_off[i] = out_offsets[i];
+        total += n_frames[i];
+    }
+    first[n_recordings] = total;
+    if (total == 0) return ASR_OK;
+    if (!samples_dev || !window || !fb_start || !fb_len || !fb_weights || !out_dev)
+        return fail(ctx, ASR_ERR_INVALID, "spectrogram_fft_batch: NULL argument");
+    std::vector<int32_t> off(n_filters);
+    int64_t total_w = 0;
+    for (int f = 0; f < n_filters; ++f) {
+        if (fb_start[f] < 0 || fb_len[f] < 0 || fb_start[f] > 1024 || fb_len[f] > 1024 - fb_start[f])
+            return fail(ctx, ASR_ERR_INVALID, "spectrogram_fft_batch: filter %d covers bins [%d, %d) outside [0, 1024)", f,
+                        fb_start[f], fb_start[f] + fb_len[f]);
+        off[f] = (int32_t)total_w;
+        total_w += fb_len[f];
+    }
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    int rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    const std::vector<float> &tw = specfft_twiddles();
+    const size_t b_tw = tw.size() * 4, b_tab = n_tab * 8, b_win = (size_t)2048 * 4, b_i = (size_t)n_filters * 4,
+                 b_w = (size_t)total_w * 4, b_call = b_tab + b_win + 3 * b_i + b_w, need = b_tw + b_call;
+    if (need > ctx->specfft_ws_bytes) {
+        ASR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->specfft_ws) ASR_HIP(ctx, hipFree(ctx->specfft_ws));
+        ctx->specfft_ws = nullptr; ctx->specfft_ws_bytes = 0;
+        const size_t bytes = need + need / 2;                       // growing recording tables do not reallocate each time
+        ASR_HIP(ctx, hipMalloc(&ctx->specfft_ws, bytes));
+        ctx->specfft_ws_bytes = bytes;
+        ASR_HIP(ctx, hipMemcpy(ctx->specfft_ws, tw.data(), b_tw, hipMemcpyHostToDevice));
+    }
+    std::vector<char> image(b_call);
+    memcpy(image.data(), tab.data(), b_tab);
+    memcpy(image.data() + b_tab, window, b_win);
+    memcpy(image.data() + b_tab + b_win, fb_start, b_i);
+    memcpy(image.data() + b_tab + b_win + b_i, fb_len, b_i);
+    memcpy(image.data() + b_tab + b_win + 2 * b_i, off.data(), b_i);
+    if (b_w) memcpy(image.data() + b_tab + b_win + 3 * b_i, fb_weights, b_w);
+    char *d_call = (char *)ctx->specfft_ws + b_tw;                  // 8-byte aligned: b_tw, b_tab and b_win are multiples of 8
+    const int64_t *d_tab = (const int64_t *)d_call;
+    const float *d_win = (const float *)(d_call + b_tab);
+    const int32_t *d_start = (const int32_t *)(d_call + b_tab + b_win), *d_len = d_start + n_filters,
+                  *d_off = d_len + n_filters;
+    const float *d_w = (const float *)(d_call + b_tab + b_win + 3 * b_i);
+    hipError_t e = hipMemcpyAsync(d_call, image.data(), b_call, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        // 5 passes of 1024 complex values at about 8.5 FLOP per value, the post-pass, the filterbank
+        ProfScope ps(ctx, "spectrogram_fft_batch", 0, (5.0 * 1024 * 8.5 + 1024 * 16.0 + 2.0 * total_w) * (double)total,
+                     4.0 * hop * (double)total);
+        e = asr::launch_spectrogram_fft_batch(ctx->stream, samples_dev, d_tab, d_tab + n_recordings + 1,
+                                              d_tab + 2 * n_recordings + 1, d_tab + 3 * n_recordings + 1, n_recordings,
+                                              total, (const float *)ctx->specfft_ws, d_win, hop, d_start, d_len, d_off,
+                                              d_w, n_filters, mul, add, out_dev, transposed);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "spectrogram_fft_batch: %s", hipGetErrorString(e));
     return mark_main(ctx);
 }
 

@@ -267,6 +267,8 @@ struct asr_ctx {
     size_t post_ws_bytes = 0;
     void *resample_ws = nullptr;              // asr_resample_batch_dev: per-recording tables + phase-major taps
     size_t resample_ws_bytes = 0;
+    void *specfft_ws = nullptr;               // asr_spectrogram_fft_batch_dev: the twiddle table (written when the workspace
+    size_t specfft_ws_bytes = 0;              // is allocated), then per call the recording tables, window and filters
     void *resize_ws = nullptr;                // asr_resize_pages_dev: running tile counts + page table
     size_t resize_ws_bytes = 0;
     void *skew_ws = nullptr;                  // asr_skew_estimate_dev / asr_deskew_pages_dev: tables, profiles, scores

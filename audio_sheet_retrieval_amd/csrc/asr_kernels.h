@@ -320,6 +320,15 @@ hipError_t launch_spectrogram_batch(hipStream_t s, const float *samples, const i
                                     int64_t total_frames, const float *window, int frame_size, double hop, int max_bin,
                                     const int32_t *fb_start, const int32_t *fb_len, const int32_t *fb_off, const float *fb_w,
                                     int nf, float mul, float add, float *out, int transposed);
+// the batched spectrogram with the magnitudes from a real-input FFT (spectrogram_fft_kernels.hip; frame_size 2048 only):
+// the per-recording tables as launch_spectrogram_batch; twiddles: 2048 (cos, -sin) pairs of exp(-2 pi i t / 2048),
+// float32 rounded from float64; window: the 2048 floats, 8-byte aligned.  Magnitudes equal to the DFT's within float32
+// rounding; per recording bit-identical whatever else is in the launch
+hipError_t launch_spectrogram_fft_batch(hipStream_t s, const float *samples, const int64_t *frame_first,
+                                        const int64_t *sample_off, const int64_t *sample_cnt, const int64_t *out_off,
+                                        int n_rec, int64_t total_frames, const float *twiddles, const float *window,
+                                        double hop, const int32_t *fb_start, const int32_t *fb_len, const int32_t *fb_off,
+                                        const float *fb_w, int nf, float mul, float add, float *out, int transposed);
 // unrolled score strips (umc_kernels.hip): one row of the table per staff system, offsets resolved by the host
 struct UnrollSystem {
     int64_t src;            // byte offset of (r0, c0) in the uint8 page buffer

@@ -79,13 +79,19 @@ def _arguments(argv, direction):
     p.add_argument("--deskew", action="store_true",
                    help="estimate the slope of every page's staves and straighten the page on the device, before the "
                         "resize (asr_skew_estimate_dev, asr_deskew_pages_dev; sheet_utils/umc.load_umc_scans)")
+    p.add_argument("--fast_dft", action="store_true",
+                   help="compute the spectrograms' magnitudes with an FFT (asr_spectrogram_fft_batch_dev; "
+                        "SpectrogramProcessor(dft=\"fft\")): the same spectrograms to float32 rounding, not bit for bit")
     if direction == "A2S":
         p.add_argument("--live", action="store_true",
                        help="stream every recording block by block through the running vote (live_track_scores)")
         p.add_argument("--block_ms", type=float, default=100.0, help="milliseconds of audio per block (--live)")
         p.add_argument("--running_frames", type=int, default=100,
                        help="voiced frames in the history of the running vote (--live)")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.fast_dft and getattr(args, "live", False):
+        p.error("--fast_dft with --live: the streamed front-end computes the direct DFT only")
+    return args
 
 
 def tracking_file(param_file, dset, real_perf=False):
@@ -141,7 +147,7 @@ def run(argv, direction):
         dset = os.path.basename(args.data_dir)
         audio_file = "01_performance" if args.real_perf else "score_ppq"
         engine, param_file = audio2sheet_align.load_network(args.model, args.estimate_UV, args.train_split, args.config)
-        processor = SpectrogramProcessor(engine)
+        processor = SpectrogramProcessor(engine, dft="fft" if args.fast_dft else "direct")
         if direction == "A2S":
             # a piece without the recording is left out of the ranks
             queried = []

@@ -760,6 +760,26 @@ int asr_bars_from_map_dev(asr_ctx *ctx, const double *maps_dev, const int32_t *h
  *   (n_frames[i], n_filters).  Every recording's output is bit-identical with asr_spectrogram_dev on it alone: a frame
  *   is computed by the same device code, only the frame-to-recording lookup is added.  Recordings of zero samples /
  *   zero frames and n_recordings == 0 are valid and write nothing.
+ * asr_spectrogram_fft_batch_dev = asr_spectrogram_batch_dev, same arguments and layouts, with the magnitudes taken from
+ *   a real-input FFT in float32 instead of the direct DFT (csrc/spectrogram_fft_kernels.hip; about 80 times fewer
+ *   operations).  The definition:
+ *     frame      frame i of a recording starts at sample (int64)((double)i * hop) and has frame_size samples; samples past
+ *                the end of the frame's own recording read as zero, also when another recording follows immediately in
+ *                the buffer; sample t of the frame is multiplied by window[t] in float32
+ *     magnitude  of bins 0 .. frame_size / 2 - 1: equal to the DFT's within float32 rounding, summation order unspecified
+ *     result     filter f: s = sum of magnitude[fb_start[f] + q] * fb_weights[...][q] in ascending q (fmaf), then
+ *                log10f(mul * s + add), as asr_spectrogram_dev
+ *     tolerance  against the same chain in float64 (float64 product of sample and float32 window, float64 FFT, float64
+ *                filterbank with the float32 weights, float64 log10) the result deviates by at most 1e-4, and by no
+ *                more than asr_spectrogram_batch_dev's does on the same input (tests/test_gpu_spectrogram_fft.py)
+ *     bit for bit  a recording's output does not depend on which other recordings are in the call, on their order or
+ *                on `transposed` (the two layouts are exact transposes), and repeated calls agree.  It is NOT
+ *                bit-identical with asr_spectrogram_batch_dev or asr_audio_stream_push_dev.
+ *   Checked before anything is launched: everything asr_spectrogram_batch_dev checks, frame_size == 2048 (the
+ *   reference's only value) and every filter inside bins 0 .. 1023.  A violation returns ASR_ERR_INVALID with a message
+ *   and launches nothing.  n_recordings == 0 and recordings of zero samples or zero frames are valid and write nothing;
+ *   floats of out_dev that belong to no recording are left as they are.  The twiddle table (float32 rounded from
+ *   float64, computed once on the host) and the per-call tables are workspace of the context.
  * asr_resample_batch_dev = what madmom's SignalProcessor(sample_rate=22050) has its decoder do to a recording at
  *   another rate, for n_recordings recordings of one input rate in one launch, between the upload and
  *   asr_spectrogram_batch_dev.  The reference's resampler (ffmpeg's) is not restated; the yardstick is this definition,
@@ -883,6 +903,12 @@ int asr_spectrogram_batch_dev(asr_ctx *ctx, const float *samples_dev, int64_t sa
                               const float *window, const int32_t *fb_start, const int32_t *fb_len,
                               const float *fb_weights, int n_filters, float mul, float add, int transposed,
                               float *out_dev, int64_t out_floats);
+int asr_spectrogram_fft_batch_dev(asr_ctx *ctx, const float *samples_dev, int64_t samples_floats,
+                                  const int64_t *sample_offsets, const int64_t *sample_counts, const int64_t *n_frames,
+                                  const int64_t *out_offsets, int n_recordings, int frame_size, double hop,
+                                  const float *window, const int32_t *fb_start, const int32_t *fb_len,
+                                  const float *fb_weights, int n_filters, float mul, float add, int transposed,
+                                  float *out_dev, int64_t out_floats);
 int asr_resample_batch_dev(asr_ctx *ctx, const float *in_dev, int64_t in_floats, const int64_t *in_offsets,
                            const int64_t *in_counts, const int64_t *out_offsets, const int64_t *out_counts,
                            int n_recordings, int up, int down, const double *taps_phase_major, int taps_per_phase,
