@@ -39,6 +39,7 @@
 #include "repack_elems.inl"
 #include "wino_tile_order.h"
 #include "wino_weight_layout.h"
+#include "wino_lds_weight_layout.h"
 
 // conv3x3_winog, per-item A/B switches of round 19 (results are the same bits either way; ASR_WINOG_DENSEW, the dense
 // weight layout of the NT = 2 builds, lives in wino_weight_layout.h)
@@ -171,7 +172,13 @@ __global__ __launch_bounds__(64 * (WAVES + PW), MINW) void conv3x3_wino(WinoArgs
     constexpr bool REM = (CIN % 8) != 0;   // one more k-step on the last 4 channels
     constexpr int NCH = NB / KB;
     constexpr int WROW = NTW * 16;
-    constexpr int WS = NTW == 2 ? 48 : WROW;     // LDS row stride of the weights (32 would alias lane groups on banks)
+    // weights in LDS (wino_lds_weight_layout.h): dense - every operand read is one aligned 64-bit read at an immediate
+    // offset from one base register - or, in the producer builds, row-major with stride WS
+    constexpr bool DENSE = wino_lw_dense(NTW, PW);
+    constexpr int WS = wino_lw_row_stride(NTW);  // row-major form (32 would alias lane groups on banks)
+    constexpr int WLDS = wino_lw_lds_floats(CIN, NTW, DENSE);
+    constexpr int RPK = wino_lw_reads_per_kstep(NTW);      // dense form: 64-bit reads per k-step
+    constexpr int WDR = NTW == 2 ? 4 : 2;        // dense form: reads in flight ahead of their MFMAs (4 positions' worth)
     constexpr int C4 = CIN / 4;
     constexpr int T = 64 * (WAVES + PW);
     static_assert(NB % KB == 0, "chunking must divide the channel blocks");
@@ -191,12 +198,20 @@ __global__ __launch_bounds__(64 * (WAVES + PW), MINW) void conv3x3_wino(WinoArgs
     if (first >= last) return;
 
     // ---- the transformed weights of this n-group, once: 16*KS*4 rows of WROW floats
+#pragma unroll 1
     for (int i = tid; i < 16 * KS * 4 * (WROW / 4); i += T) {
         const int row = i / (WROW / 4), q = i - row * (WROW / 4);
         const int col = ng * WROW + q * 4;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (col < a.coutp) v = *reinterpret_cast<const float4 *>(a.wpk + (size_t)row * a.coutp + col);
-        *reinterpret_cast<float4 *>(w_lds + row * WS + q * 4) = v;
+        if constexpr (DENSE) {
+            w_lds[wino_lw_stage_off(NTW, true, row, q * 4)] = v.x;
+            w_lds[wino_lw_stage_off(NTW, true, row, q * 4 + 1)] = v.y;
+            w_lds[wino_lw_stage_off(NTW, true, row, q * 4 + 2)] = v.z;
+            w_lds[wino_lw_stage_off(NTW, true, row, q * 4 + 3)] = v.w;
+        } else {
+            *reinterpret_cast<float4 *>(w_lds + wino_lw_stage_off(NTW, false, row, q * 4)) = v;
+        }
     }
     // ---- which chunks of a region's patch this thread moves (the same for every region): offset from the region's
     // first output pixel in global memory and (row, column) for the border test; -1 marks padding chunks.  The copy
@@ -302,7 +317,7 @@ __global__ __launch_bounds__(64 * (WAVES + PW), MINW) void conv3x3_wino(WinoArgs
     };
     // ---- producer waves: block 1 of one region's patch (output pixels [-1, R+1) of the region) into `buf`.  A lane
     // takes patch pixels ptid, ptid + 64 PW, ...; pixels outside the image are block 2's zero padding.
-    float *tab255 = w_lds + 16 * KS * 4 * WS;                      // uint8 input: the exact quotients v / 255
+    float *tab255 = w_lds + WLDS;                      // uint8 input: the exact quotients v / 255
     auto produce = [&](int region, float *buf) {
         if constexpr (PW > 0) {
         const int ptid = tid - 64 * WAVES;
@@ -382,9 +397,9 @@ __global__ __launch_bounds__(64 * (WAVES + PW), MINW) void conv3x3_wino(WinoArgs
         a_row[i] = (2 * tyy + i) * RPf + 2 * txx * CSf + ((tyy + (i >> 1)) & 1) * 4;
     const int a_pair = (g >> 1) * 4 + (g & 1) * 2;       // block t: channels 8t + 2g, 8t + 2g + 1
     const int a_rem = NB * 8 + g;                        // remainder k-step: channel 8*NB + g
-    const float *w_lane = w_lds + g * WS + n;
+    const float *w_lane = w_lds + wino_lw_lane_off(NTW, DENSE, g, n);
     // B operand q of a run of k-steps: k-step q / (16 NTW), position (q / NTW) % 16, n-tile q % NTW
-    auto wq_off = [](int q) { return ((q / (16 * NTW)) * 16 + (q / NTW) % 16) * 4 * WS + (q % NTW) * 16; };
+    auto wq_off = [](int q) { return wino_lw_rowmajor_off(NTW, q / (16 * NTW), (q / NTW) % 16, q % NTW); };
     // accumulator element r of this lane belongs to tile 4g + r of the M-tile: its coordinates (in tiles) and the
     // offset of its output (pooled: one pixel; else the tile's top-left pixel) from the M-tile's output origin
     int ey[4], ex[4], eoff[4];
@@ -505,6 +520,32 @@ __global__ __launch_bounds__(64 * (WAVES + PW), MINW) void conv3x3_wino(WinoArgs
                         dp[i][0][c] = psub(t0, t2); dp[i][1][c] = padd(t1, t2); dp[i][2][c] = psub(t2, t1); dp[i][3][c] = psub(t1, t3);
                     }
                 }
+                if constexpr (DENSE) {
+                    // B operands as 64-bit reads (two n-tiles of a position, or positions 2j and 2j + 1) in a rolling
+                    // window WDR reads ahead of their MFMAs; plain loads between scheduling barriers, so the compiler
+                    // counts lgkmcnt itself and neither sinks the reads nor pairs them into ds_read2_b64
+                    constexpr int NR = 2 * KB * RPK;
+                    const int r0 = ch * NR;
+                    float2w wv[NR + WDR];
+#pragma unroll
+                    for (int r = 0; r < WDR; ++r)
+                        wv[r] = *reinterpret_cast<const float2w *>(w_lane + wino_lw_read_off(r0 + r));
+#pragma unroll
+                    for (int r = 0; r < NR; ++r) {
+                        wv[r + WDR] = (ASR_WINOG_ABL & 16) ? wv[r]
+                                      : (r + WDR < NR) ? *reinterpret_cast<const float2w *>(w_lane + wino_lw_read_off(r0 + r + WDR))
+                                                       : float2w{0.f, 0.f};
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int e = 0; e < 2; ++e) {
+                            const int c = wino_lw_read_kstep(NTW, r), p = wino_lw_read_pos(NTW, r, e);
+                            const int nt = wino_lw_read_ntile(NTW, e);
+                            acc[p][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(dp[p >> 2][p & 3][c >> 1][c & 1], wv[r][e],
+                                                                              acc[p][nt], 0, 0, 0);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                } else {
                 // B operands in a rolling window WD ahead of their MFMA, pinned against the compiler's sinking
                 // (see conv3x3_winog)
                 constexpr int WQ = 2 * KB * 16 * NTW, WD = 4 * NTW;
@@ -526,6 +567,7 @@ __global__ __launch_bounds__(64 * (WAVES + PW), MINW) void conv3x3_wino(WinoArgs
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
+                }
             } else {
                 float dsg[4][4];
 #pragma unroll
@@ -542,12 +584,32 @@ __global__ __launch_bounds__(64 * (WAVES + PW), MINW) void conv3x3_wino(WinoArgs
                     const float t0 = dsg[i][0], t1 = dsg[i][1], t2 = dsg[i][2], t3 = dsg[i][3];
                     dsg[i][0] = t0 - t2; dsg[i][1] = t1 + t2; dsg[i][2] = t2 - t1; dsg[i][3] = t1 - t3;
                 }
+                if constexpr (DENSE) {
+                    constexpr int r0 = 2 * NB * RPK;
+                    float2w wv[RPK + WDR];
 #pragma unroll
-                for (int p = 0; p < 16; ++p)
+                    for (int r = 0; r < WDR; ++r)
+                        wv[r] = *reinterpret_cast<const float2w *>(w_lane + wino_lw_read_off(r0 + r));
 #pragma unroll
-                    for (int nt = 0; nt < NTW; ++nt)
-                        acc[p][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                            dsg[p >> 2][p & 3], w_lane[((2 * NB * 16 + p) * 4) * WS + nt * 16], acc[p][nt], 0, 0, 0);
+                    for (int r = 0; r < RPK; ++r) {
+                        wv[r + WDR] = (r + WDR < RPK) ? *reinterpret_cast<const float2w *>(w_lane + wino_lw_read_off(r0 + r + WDR))
+                                                      : float2w{0.f, 0.f};
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int e = 0; e < 2; ++e) {
+                            const int p = wino_lw_read_pos(NTW, r, e), nt = wino_lw_read_ntile(NTW, e);
+                            acc[p][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(dsg[p >> 2][p & 3], wv[r][e], acc[p][nt], 0, 0, 0);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                } else {
+#pragma unroll
+                    for (int p = 0; p < 16; ++p)
+#pragma unroll
+                        for (int nt = 0; nt < NTW; ++nt)
+                            acc[p][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                                dsg[p >> 2][p & 3], w_lane[wino_lw_rowmajor_off(NTW, 2 * NB, p, nt)], acc[p][nt], 0, 0, 0);
+                }
             }
         }
 
@@ -1303,7 +1365,7 @@ static void enumerate_wino(int vi, int H, int W, int lds_budget, std::vector<Con
     const WinoVariant &v = g_wino[vi];
     const int nt = (v.cout + 15) / 16;
     const int ngroups = (nt + v.ntw - 1) / v.ntw;
-    const int w_bytes = 16 * v.cin * (v.ntw == 2 ? 48 : v.ntw * 16) * 4;
+    const int w_bytes = wino_lw_lds_floats(v.cin, v.ntw, wino_lw_dense(v.ntw, v.pw)) * 4;
     static const int shapes[4][2] = {{2, 8}, {4, 4}, {8, 2}, {16, 1}};      // MY even: row origins are multiples of 4
     const int ty_img = (H + 1) / 2, tx_img = (W + 1) / 2;       // winograd tiles covering the image
     for (const auto &sh : shapes) {
