@@ -45,6 +45,7 @@ EXPORTS = [
     "asr_unroll_systems_dev", "asr_spectrogram_batch_dev", "asr_spectrogram_fft_batch_dev", "asr_resample_batch_dev", "asr_resize_pages_dev",
     "asr_audio_stream_push_dev", "asr_skew_estimate_dev", "asr_deskew_pages_dev",
     "asr_opt_state_size", "asr_get_opt_state", "asr_set_opt_state", "asr_debug_train_tensor", "asr_cca_train_debug",
+    "asr_debug_train_candidate",
 ]
 
 
@@ -252,6 +253,8 @@ def load_library(path=None):
         "asr_set_opt_state": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32]),
         "asr_debug_train_tensor": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int64, i64p]),
         "asr_cca_train_debug": (c_int, [c_void_p, c_void_p, c_void_p, c_int64] + [c_void_p] * 7),
+        "asr_debug_train_candidate": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,
+                                              c_int64, c_void_p, c_void_p, c_void_p, c_int64]),
     }
     for name, (res, args) in proto.items():
         fn = getattr(lib, name)      # AttributeError if the .so lacks a declared symbol
@@ -1462,6 +1465,41 @@ class Engine(object):
         self._check(self.lib.asr_debug_train_tensor(self.ctx, kinds[kind], view, index, batch, out.ctypes.data,
                                                     n.value, byref(n)))
         return out
+
+    def debug_train_candidate(self, view, block, kind, index, a=None, b=None, batch=None):
+        """asr_debug_train_candidate: candidate `index` of the training tuner's list for 3x3 block `block` (1..7) of
+        `view`, alone, from NaN-filled outputs.  kind 0: a = x (n,H,W,cin) -> z; 1: a = dz (n,H,W,cout) -> dx; 2: a = x,
+        b = dz -> dW (cout,cin,3,3).  An index past the end raises AsrError (ASR_ERR_INVALID, "... has <n> candidates").
+        Returns a dict: out, launched, desc, family, variant, tile (TH, TW), work_items, workgroups, shape (H, W, cin,
+        cout) and, for kind 0, stats_rows, mu, inv_std.  a = None: nothing runs - the description of the candidate for
+        a batch of `batch` samples, without out / launched / statistics."""
+        info = np.zeros(12, np.int32)
+        desc = ctypes.create_string_buffer(128)
+        n = int(batch) if a is None else np.shape(a)[0]
+        self._check(self.lib.asr_debug_train_candidate(self.ctx, view, block, kind, index, n, None, None, None, 0, None,
+                                                       info.ctypes.data, desc, 128))             # the block's shapes
+        h, w, cin, cout = (int(v) for v in info[8:12])
+        if a is None:
+            return dict(desc=desc.value.decode(), family=("direct", "winog", "wino", "wino4")[int(info[4])],
+                        variant=int(info[5]), tile=(int(info[6]), int(info[7])), work_items=int(info[2]),
+                        workgroups=int(info[3]), shape=(h, w, cin, cout))
+        a = _f32c(a)
+        b = _f32c(b) if b is not None else None
+        if a.shape != (n, h, w, cout if kind == 1 else cin) or (kind == 2 and (b is None or b.shape != (n, h, w, cout))):
+            raise ValueError("debug_train_candidate: kind %d of a %d->%d block on %dx%d maps, got %s%s" %
+                             (kind, cin, cout, h, w, a.shape, "" if b is None else " and %s" % (b.shape,)))
+        out = np.empty((n, h, w, cout) if kind == 0 else (n, h, w, cin) if kind == 1 else (cout, cin, 3, 3), np.float32)
+        stats = np.full(2 * cout, np.nan, np.float32)
+        self._check(self.lib.asr_debug_train_candidate(self.ctx, view, block, kind, index, n, a.ctypes.data,
+                                                       b.ctypes.data if b is not None else None, out.ctypes.data,
+                                                       out.size, stats.ctypes.data, info.ctypes.data, desc, 128))
+        res = dict(out=out, launched=bool(info[0]), desc=desc.value.decode(),
+                   family=("direct", "winog", "wino", "wino4")[int(info[4])], variant=int(info[5]),
+                   tile=(int(info[6]), int(info[7])), work_items=int(info[2]), workgroups=int(info[3]),
+                   shape=(h, w, cin, cout))
+        if kind == 0:
+            res.update(stats_rows=int(info[1]), mu=stats[:cout], inv_std=stats[cout:])
+        return res
 
     def cca_train_debug(self, H1, H2, cca_in, backward=True):
         H1, H2 = _f32c(H1), _f32c(H2)

@@ -26,6 +26,47 @@ int train_repack(asr_ctx *ctx) {
 // step's own buffers at the step's batch size, the model's pick included; ~0.3 s once per asr_train_begin.
 // ASR_AUTOTUNE=0 keeps the model's picks.  All candidates are the same kernels with other tile parameters: same results
 // up to the float32 summation order of the Winograd transforms.
+//
+// The candidate lists are built in ONE place, for the tuner and for asr_debug_train_candidate (which runs one candidate
+// alone against NaN-filled outputs, so that the tests compare every schedule the tuner can pick with float64): a
+// schedule added here is tested, a schedule the tests do not see cannot be picked.
+const char *conv_family(int variant) {
+    return variant >= 4000 ? "wino4" : variant >= 3500 ? "winog" : variant >= 3000 ? "wino" : "direct";
+}
+
+// dir 0: the forward convolution x[b] -> z[b]; 1: the data gradient dz -> dx.  The model's plan first; a direct plan has
+// nothing to choose from and stays alone.
+void train_conv_candidates(asr_ctx *ctx, int t, int b, int dir, std::vector<asr::ConvPlan> *cands) {
+    const LayerGeom &g = ctx->tw[t].g[b];
+    const TrainTower &tt = ctx->train->tw[t];
+    const asr::ConvPlan &plan = dir ? tt.dplan[b] : tt.fplan[b];
+    cands->push_back(plan);
+    if (plan.variant < 3000) return;
+    const int cin = dir ? g.cout : g.cin, cout = dir ? g.cin : g.cout;
+    asr::conv_candidates_wino_raw(cin, cout, g.H, g.W, 2, cands);
+    // F(4x4) FORWARD builds only under ASR_POOL_TIES_FIRST.  The "every tied element" rule compares activations
+    // for equality, and what makes the device's ties the reference's (Theano's CorrMM gives equal patches equal
+    // outputs) is that an F(2x2) output depends on its own 3x3 patch only: a uniform or axis-constant patch takes
+    // the exact path through the one non-zero transform position whatever else its tile holds.  An F(4x4) output
+    // also carries rounding noise from the two tile columns / rows beyond its patch - measured on pages with
+    // large white areas: 11 % / 4 % of the pooling windows of blocks 6 / 8 lost ties float64 has (1e-6 with
+    // F(2x2)).  Data gradients are not compared: they keep their F(4x4) builds.
+    if (dir == 1 || ctx->cfg.pool_ties == ASR_POOL_TIES_FIRST)
+        asr::conv_candidates_wino4_raw(cin, cout, g.H, g.W, cands, dir);
+}
+
+// the weight gradient: the planner's tiling against the next-cheapest tile shapes of its model, those whose partial
+// sums fit the tower's buffer (the planner's own pick, first in the list, always does: train_alloc sized the buffer by
+// it).  *listed (may be null): the length of the list before that filter.
+void train_wgrad_candidates(asr_ctx *ctx, int t, int b, std::vector<asr::WgradPlan> *wc, int *listed = nullptr) {
+    const LayerGeom &g = ctx->tw[t].g[b];
+    std::vector<asr::WgradPlan> all;
+    asr::wgrad_candidates(g.cin, g.cout, g.H, g.W, ctx->num_cus, 6, &all);
+    if (listed) *listed = (int)all.size();
+    for (const asr::WgradPlan &c : all)
+        if (asr::wgrad_partial_floats(c) <= ctx->train->tw[t].wpartial_floats) wc->push_back(c);
+}
+
 int tune_train_plans(asr_ctx *ctx, int B) {
     // (read at every asr_train_begin, not latched: a caller that switches the tuner off for one engine gets that)
     const bool on = !(getenv("ASR_AUTOTUNE") && getenv("ASR_AUTOTUNE")[0] == '0') &&
@@ -76,19 +117,9 @@ int tune_train_plans(asr_ctx *ctx, int B) {
             for (int dir = 0; dir < 2 && rc == ASR_OK; ++dir) {          // 0: forward x[b] -> z[b]; 1: data gradient dz -> dB
                 asr::ConvPlan &plan = dir ? tt.dplan[b] : tt.fplan[b];
                 if (plan.variant < 3000) continue;                       // direct schedule: nothing to choose from
-                const int cin = dir ? g.cout : g.cin, cout = dir ? g.cin : g.cout;
+                const int cin = dir ? g.cout : g.cin;
                 std::vector<asr::ConvPlan> cands;
-                cands.push_back(plan);
-                asr::conv_candidates_wino_raw(cin, cout, g.H, g.W, 2, &cands);
-                // F(4x4) FORWARD builds only under ASR_POOL_TIES_FIRST.  The "every tied element" rule compares activations
-                // for equality, and what makes the device's ties the reference's (Theano's CorrMM gives equal patches equal
-                // outputs) is that an F(2x2) output depends on its own 3x3 patch only: a uniform or axis-constant patch takes
-                // the exact path through the one non-zero transform position whatever else its tile holds.  An F(4x4) output
-                // also carries rounding noise from the two tile columns / rows beyond its patch - measured on pages with
-                // large white areas: 11 % / 4 % of the pooling windows of blocks 6 / 8 lost ties float64 has (1e-6 with
-                // F(2x2)).  Data gradients are not compared: they keep their F(4x4) builds.
-                if (dir == 1 || ctx->cfg.pool_ties == ASR_POOL_TIES_FIRST)
-                    asr::conv_candidates_wino4_raw(cin, cout, g.H, g.W, &cands, dir);
+                train_conv_candidates(ctx, t, b, dir, &cands);
                 const float *in = dir ? tt.dz : tt.x[b];
                 const float *w = dir ? tt.wdgrad[b] : tw.w_dev[b];
                 float *out = dir ? tt.dB : tt.z[b];
@@ -138,8 +169,7 @@ int tune_train_plans(asr_ctx *ctx, int B) {
                     ms *= (c == 0) ? 0.99f : 1.0f;                                    // ties go to the model's pick
                     if (dbg)
                         fprintf(stderr, "[asr] train tune v%d conv%d %s %s#%d tile %dx%d x%d: %.4f ms\n", t + 1, b + 1,
-                                dir ? "dgrad" : "fwd", cands[c].variant >= 4000 ? "wino4" : cands[c].variant >= 3500 ? "winog" : "wino",
-                                cands[c].variant,
+                                dir ? "dgrad" : "fwd", conv_family(cands[c].variant), cands[c].variant,
                                 cands[c].TH, cands[c].TW, cands[c].NI, ms / 2);
                     if (ms < best_ms) { best_ms = ms; best = (int)c; }
                 }
@@ -149,38 +179,38 @@ int tune_train_plans(asr_ctx *ctx, int B) {
                     cache_append("t1", k);
                 }
             }
-            // the weight gradient: the planner's tiling against the next-cheapest tile shapes of its model
+            // the weight gradient (train_wgrad_candidates; tilings whose partial sums do not fit are not in `wc`, `listed`
+            // counts them too: a lone candidate is not timed)
             if (rc == ASR_OK) {
                 std::vector<asr::WgradPlan> wc;
-                asr::wgrad_candidates(g.cin, g.cout, g.H, g.W, ctx->num_cus, 6, &wc);
+                int listed = 0;
+                train_wgrad_candidates(ctx, t, b, &wc, &listed);
                 int best = -1;
                 float best_ms = 1e30f;
                 for (auto &c : t2)
                     if (c.k[0] == nf && c.k[1] == t + 1 && c.k[2] == b && c.k[3] == g.H && c.k[4] == g.W && c.k[5] == B)
                         for (size_t q = 0; q < wc.size(); ++q)
                             if (wc[q].variant == c.k[6] && wc[q].TH == c.k[7] && wc[q].TW == c.k[8] &&
-                                wc[q].lds_bytes == c.k[9] && wc[q].grid_cap == c.k[10] &&
-                                asr::wgrad_partial_floats(wc[q]) <= tt.wpartial_floats)
+                                wc[q].lds_bytes == c.k[9] && wc[q].grid_cap == c.k[10])
                                 best = (int)q;
                 if (best >= 0) {
                     tt.wplan[b] = wc[best];
                     if (dbg) fprintf(stderr, "[asr] train tune v%d conv%d wgrad from cache\n", t + 1, b + 1);
                     continue;
                 }
-                if (wc.size() > 1 && cache && ctx->comm && ctx->comm->world > 1 && ctx->comm->rank != 0) {
+                if (listed > 1 && cache && ctx->comm && ctx->comm->world > 1 && ctx->comm->rank != 0) {
                     rc = fail(ctx, ASR_ERR_STATE, "train tuner: rank %d found no weight-gradient schedule for view %d conv%d in "
                               "the job's tune cache %s - rank 0 times, the other ranks read", ctx->comm->rank, t + 1, b + 1, cache);
                     break;
                 }
                 // defined operands for every candidate (x[b] was filled above only when the forward plan is Winograd)
-                if (wc.size() > 1 &&
+                if (listed > 1 &&
                     (hipMemsetD32Async((hipDeviceptr_t)tt.x[b], 0x3f000000, (size_t)B * g.H * g.W * g.cin, st) != hipSuccess ||
                      hipMemsetD32Async((hipDeviceptr_t)tt.dz, 0x3f000000, (size_t)B * g.H * g.W * g.cout, st) != hipSuccess)) {
                     rc = fail(ctx, ASR_ERR_HIP, "tune_train_plans: memset");
                     break;
                 }
-                for (size_t c = 0; c < wc.size() && wc.size() > 1; ++c) {
-                    if (asr::wgrad_partial_floats(wc[c]) > tt.wpartial_floats) continue;
+                for (size_t c = 0; c < wc.size() && listed > 1; ++c) {
                     hipError_t e = asr::launch_wgrad(st, wc[c], tt.x[b], tt.dz, B, tt.wpartial, pg(T, 45 * t + 5 * b));
                     if (e == hipSuccess) e = hipEventRecord(e0, st);
                     for (int r = 0; r < 2 && e == hipSuccess; ++r)
@@ -210,7 +240,9 @@ int tune_train_plans(asr_ctx *ctx, int B) {
     return rc;
 }
 
-int build_repack_table(asr_ctx *ctx, bool all4 = false) {
+// all4: the F(4x4) copies wherever a RAW F(4x4) build exists (the tuner is about to time them); all2: the F(2x2) copies
+// of every block too (asr_debug_train_candidate runs schedules of families the plans do not use)
+int build_repack_table(asr_ctx *ctx, bool all4 = false, bool all2 = false) {
     TrainState &T = *ctx->train;
     std::vector<asr::RepackDesc> descs;
     for (int t = 0; t < 2; ++t) {
@@ -231,8 +263,8 @@ int build_repack_table(asr_ctx *ctx, bool all4 = false) {
                 d.wfwd = tw.w_dev[b];
                 d.wdgrad = T.tw[t].wdgrad[b];
                 // Winograd-domain copies only where the training step's own plans use them
-                if (T.tw[t].fplan[b].variant >= 3000) d.wino_fwd = tw.w_dev[b] + asr::conv_wpack_floats(g.cin, g.cout);
-                if (T.tw[t].dplan[b].variant >= 3000)
+                if (all2 || T.tw[t].fplan[b].variant >= 3000) d.wino_fwd = tw.w_dev[b] + asr::conv_wpack_floats(g.cin, g.cout);
+                if (all2 || T.tw[t].dplan[b].variant >= 3000)
                     d.wino_dgrad = T.tw[t].wdgrad[b] + asr::conv_wpack_floats(g.cout, g.cin);
                 // F(4x4) copies: while the tuner has not run (`all4`) wherever a RAW F(4x4) build exists, afterwards only
                 // where a plan uses one
@@ -654,7 +686,7 @@ int train_forward_block(asr_ctx *ctx, int t, int B, int b, int phase) {
                                                    fuse_stats ? stab : nullptr, &srows, train_recompute1() ? 1 : 0));
             else if (b < 8)
                 ASR_HIP(ctx, launch_conv_any(ctx, st, tt.fplan[b], tt.x[b], tw.w_dev[b], nullptr, tt.z[b], B, nullptr,
-                                             fuse_stats ? stab : nullptr, &srows, own_table));
+                                             fuse_stats ? stab : nullptr, &srows));
             else ASR_HIP(ctx, asr::launch_conv1x1_raw(st, tt.x[8], pm(T, base), tt.z[8], rows, g.cin));
             if (!fuse_stats) srows = 0;
         }
@@ -902,7 +934,7 @@ int train_backward_block(asr_ctx *ctx, int t, int B, int b, int phase, BwdState 
             }
             int prow = 0;
             ASR_HIP(ctx, launch_conv_any(ctx, st, tt.dplan[b], dz, tt.wdgrad[b], nullptr, dB, B, nullptr,
-                                         bf.z ? tt.fstats : nullptr, &prow, true, bf.z ? &bf : nullptr));
+                                         bf.z ? tt.fstats : nullptr, &prow, bf.z ? &bf : nullptr));
             S.pre_rows = bf.z ? prow : 0;           // 0: this plan writes no sums (direct-form build) - the reduce pass runs
             std::swap(dA, dB);
         }
@@ -1600,6 +1632,115 @@ int asr_debug_train_tensor(asr_ctx *ctx, int kind, int view, int index, int64_t 
         return ASR_OK;
     }
     ASR_HIP(ctx, hipMemcpy(out, src, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return ASR_OK;
+}
+
+// One candidate of the training tuner's lists (train_conv_candidates / train_wgrad_candidates) alone, through the
+// production launcher, on the training state's own buffers: outputs, statistics table and partial sums start as 0xff
+// bytes (NaN), so whatever the schedule does not write shows.  Header: include/asr_hip.h.
+int asr_debug_train_candidate(asr_ctx *ctx, int view, int block, int kind, int index, int64_t batch, const float *a,
+                              const float *b, float *out, int64_t cap, float *stats, int32_t *info, char *desc,
+                              int64_t desc_cap) {
+    if (!ctx || !info || !desc || desc_cap < 1) return ASR_ERR_INVALID;
+    if (!ctx->train) return fail(ctx, ASR_ERR_STATE, "debug_train_candidate: no training state");
+    const bool query = !out;                                  // the candidate's description and the shapes only
+    TrainState &T = *ctx->train;
+    if (view < 1 || view > 2 || block < 1 || block > 7 || kind < 0 || kind > 2)
+        return fail(ctx, ASR_ERR_INVALID, "debug_train_candidate: view %d block %d kind %d", view, block, kind);
+    if (batch < 1 || batch > T.B) return fail(ctx, ASR_ERR_INVALID, "debug_train_candidate: batch %lld (1..%d)", (long long)batch, T.B);
+    if (!query && (!a || (kind == 2 && !b))) return fail(ctx, ASR_ERR_INVALID, "debug_train_candidate: kind %d needs %s", kind, kind == 2 ? "x and dz" : "its input");
+    if (!query && kind == 0 && !stats) return fail(ctx, ASR_ERR_INVALID, "debug_train_candidate: the forward kind needs a statistics buffer");
+    const int t = view - 1, n = (int)batch;
+    Tower &tw = ctx->tw[t];
+    TrainTower &tt = T.tw[t];
+    const LayerGeom &g = tw.g[block];
+    std::vector<asr::ConvPlan> cands;
+    std::vector<asr::WgradPlan> wc;
+    if (kind == 2) train_wgrad_candidates(ctx, t, block, &wc);
+    else train_conv_candidates(ctx, t, block, kind, &cands);
+    const int listed = (int)(kind == 2 ? wc.size() : cands.size());
+    if (index < 0 || index >= listed)
+        return fail(ctx, ASR_ERR_INVALID, "debug_train_candidate: index %d, the list of view %d block %d kind %d has %d candidates",
+                    index, view, block, kind, listed);
+    const size_t px = (size_t)n * g.H * g.W;
+    const size_t n_out = kind == 0 ? px * g.cout : kind == 1 ? px * g.cin : (size_t)9 * g.cin * g.cout;
+    if (!query && cap < (int64_t)n_out)
+        return fail(ctx, ASR_ERR_INVALID, "debug_train_candidate: buffer too small (%lld < %lld)", (long long)cap, (long long)n_out);
+    const int srows_max = std::max(asr::conv_wino_stats_rows_max(ctx->num_cus), asr::conv_wino4_stats_rows_max(ctx->num_cus));
+    if (g.cout > tw.g[7].cout) return fail(ctx, ASR_ERR_STATE, "debug_train_candidate: statistics table too small for block %d", block + 1);
+    for (int i = 0; i < 12; ++i) info[i] = 0;
+    info[8] = g.H; info[9] = g.W; info[10] = g.cin; info[11] = g.cout;
+    if (kind == 2) {
+        const asr::WgradPlan &p = wc[index];
+        snprintf(desc, (size_t)desc_cap, "wgrad variant %d tile %dx%d lds %d, %d workgroups", p.variant, p.TH, p.TW, p.lds_bytes, p.grid_cap);
+        asr::wgrad_launch_shape(p, n, &info[2], &info[3]);
+        info[4] = asr::wgrad_is_wino(p) ? 2 : 0;
+        info[5] = p.variant; info[6] = p.TH; info[7] = p.TW;
+    } else {
+        const asr::ConvPlan &p = cands[index];
+        snprintf(desc, (size_t)desc_cap, "%s#%d tile %dx%d x%d", conv_family(p.variant), p.variant, p.TH, p.TW, p.NI);
+        if (p.variant >= 4000) asr::conv_wino4_launch_shape(p, n, ctx->num_cus, &info[2], &info[3]);
+        else if (p.variant >= 3000) asr::conv_wino_launch_shape(p, n, ctx->num_cus, &info[2], &info[3]);
+        info[4] = p.variant >= 4000 ? 3 : p.variant >= 3500 ? 1 : p.variant >= 3000 ? 2 : 0;
+        info[5] = p.variant; info[6] = p.TH; info[7] = p.TW;
+    }
+    if (query) return ASR_OK;
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    int rc = sync_all(ctx);
+    if (rc != ASR_OK) return rc;
+    hipStream_t st = ctx->stream;
+    // every Winograd-domain copy a candidate could read, from the master as it is now; the table of the step's own
+    // plans comes back below, and so does the flag (the copies written here are never older than those they replace)
+    const bool stale = ctx->wino_stale;
+    rc = build_repack_table(ctx, true, true);
+    if (rc == ASR_OK) rc = train_repack(ctx);
+    float *sdev = nullptr;
+    hipError_t e = hipSuccess;
+    bool refused = false;
+    if (rc == ASR_OK) {
+        float *gslot = pg(T, 45 * t + 5 * block);
+        float *res = kind == 0 ? tt.z[block] : kind == 1 ? tt.dB : gslot;
+        e = hipMemsetAsync(res, 0xff, n_out * sizeof(float), st);
+        if (kind != 1 && e == hipSuccess)
+            e = hipMemcpyAsync(tt.x[block], a, px * g.cin * sizeof(float), hipMemcpyHostToDevice, st);
+        if (kind != 0 && e == hipSuccess)
+            e = hipMemcpyAsync(tt.dz, kind == 1 ? a : b, px * g.cout * sizeof(float), hipMemcpyHostToDevice, st);
+        if (kind == 0) {
+            if (e == hipSuccess) e = hipMemsetAsync(tt.partial, 0xff, (size_t)srows_max * 2 * g.cout * sizeof(double), st);
+            if (e == hipSuccess) e = hipMalloc((void **)&sdev, (size_t)2 * g.cout * sizeof(float));
+            if (e == hipSuccess) e = hipMemsetAsync(sdev, 0xff, (size_t)2 * g.cout * sizeof(float), st);
+        }
+        if (kind == 2 && e == hipSuccess) e = hipMemsetAsync(tt.wpartial, 0xff, tt.wpartial_floats * sizeof(float), st);
+        if (e == hipSuccess) {
+            // a candidate that cannot launch is the tuner's "skip it", reported and not an error
+            hipError_t le;
+            int srows = 0;
+            if (kind == 0) le = launch_conv_any(ctx, st, cands[index], tt.x[block], tw.w_dev[block], nullptr, tt.z[block], n, nullptr, tt.partial, &srows);
+            else if (kind == 1) le = launch_conv_any(ctx, st, cands[index], tt.dz, tt.wdgrad[block], nullptr, tt.dB, n);
+            else le = asr::launch_wgrad(st, wc[index], tt.x[block], tt.dz, n, tt.wpartial, gslot);
+            if (le != hipSuccess) { (void)hipGetLastError(); refused = true; }
+            info[1] = srows;
+            if (!refused && kind == 0 && srows > 0)          // as train_forward_block finishes the table, without the running values
+                e = asr::launch_bn_stats_final(st, tt.partial, srows, (int64_t)px, g.cout, sdev, nullptr, nullptr, 1e-4f, 0.1f,
+                                               nullptr, tt.sums, nullptr, false, nullptr);
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(out, res, n_out * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (kind == 0 && e == hipSuccess) e = hipMemcpyAsync(stats, sdev, (size_t)2 * g.cout * sizeof(float), hipMemcpyDeviceToHost, st);
+        // the gradient slots are all-zero between steps (the tuner leaves them so too)
+        if (kind == 2) {
+            const hipError_t ez = hipMemsetAsync(gslot, 0, n_out * sizeof(float), st);
+            if (e == hipSuccess) e = ez;
+        }
+        const hipError_t es = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = es;
+        (void)hipFree(sdev);
+    }
+    const int rc2 = build_repack_table(ctx);
+    ctx->wino_stale = stale;
+    if (rc != ASR_OK) return rc;
+    if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "debug_train_candidate: %s", hipGetErrorString(e));
+    if (rc2 != ASR_OK) return rc2;
+    info[0] = refused ? 0 : 1;
     return ASR_OK;
 }
 

@@ -97,8 +97,10 @@ void conv_candidates_wino(int cin, int cout, int pool, int H, int W, int max_cou
 // f1: plans with fuse1 set (block 1 evaluated inside by producer waves) read the raw input instead of `in`
 hipError_t launch_conv_wino(hipStream_t s, const ConvPlan &p, const float *in, const float *wino_wpk,
                             const float *bnp, float *out, int N, int num_cus, double *stats = nullptr,
-                            int *stats_rows = nullptr, const Fuse1Args *f1 = nullptr, bool stats_clean = false,
-                            const BnBwdFuse *bf = nullptr);
+                            int *stats_rows = nullptr, const Fuse1Args *f1 = nullptr, const BnBwdFuse *bf = nullptr);
+// what launch_conv_wino launches for plan p on N images: its work items (M-tiles of 16 tiles in the global-A form,
+// regions in the LDS-patch form) and its workgroups along x (each repeated per group of n-tiles)
+void conv_wino_launch_shape(const ConvPlan &p, int N, int num_cus, int *items, int *grid_x);
 void conv_candidates_wino_fused(int cin, int cout, int pool, int H, int W, int max_count, std::vector<ConvPlan> *out);
 const char *conv_wino_symbol(const ConvPlan &p, int in_mode);
 int conv_wino_stats_rows_max(int num_cus);
@@ -113,7 +115,9 @@ void conv_candidates_wino_raw(int cin, int cout, int H, int W, int max_count, st
 void conv_candidates_wino4(int cin, int cout, int pool, int H, int W, std::vector<ConvPlan> *out);
 hipError_t launch_conv_wino4(hipStream_t s, const ConvPlan &p, const float *in, const float *wino4_wpk,
                              const float *bnp, float *out, int N, int num_cus, double *stats = nullptr,
-                             int *stats_rows = nullptr, bool stats_clean = false, const BnBwdFuse *bf = nullptr);
+                             int *stats_rows = nullptr, const BnBwdFuse *bf = nullptr);
+// M-tiles and workgroups along x of launch_conv_wino4 for plan p on N images
+void conv_wino4_launch_shape(const ConvPlan &p, int N, int num_cus, int *items, int *grid_x);
 // RAW (training) builds of conv3x3_wino4s: candidates of the training step's tuner for a block's forward convolution
 // (cin, cout; dgrad = 0: only with ASR_TRAIN_WINO4=1, see conv_wino4_kernels.hip) or data gradient (cout, cin; dgrad =
 // 1); their statistics table has one row per workgroup
@@ -551,6 +555,9 @@ struct WgradPlan {
 bool plan_wgrad(int cin, int cout, int H, int W, int num_cus, WgradPlan *p);
 void wgrad_candidates(int cin, int cout, int H, int W, int num_cus, int max_count, std::vector<WgradPlan> *out);
 size_t wgrad_partial_floats(const WgradPlan &p);
+// tiles and workgroups of launch_wgrad for plan p on N images; whether p is a Winograd-domain form
+void wgrad_launch_shape(const WgradPlan &p, int N, int *items, int *grid);
+bool wgrad_is_wino(const WgradPlan &p);
 hipError_t launch_wgrad(hipStream_t s, const WgradPlan &p, const float *x, const float *dz, int N, float *partial,
                         float *dW);
 int conv1_wgrad_blocks();

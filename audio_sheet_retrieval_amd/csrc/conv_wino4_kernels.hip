@@ -865,10 +865,32 @@ void conv_candidates_wino4_raw(int cin, int cout, int H, int W, std::vector<Conv
 bool conv_wino4_is_raw(const ConvPlan &p) { return p.variant >= 4000 && g_wino4[p.variant - 4000].raw != 0; }
 int conv_wino4_stats_rows_max(int num_cus) { return num_cus; }
 
-// stats / stats_rows: RAW builds only (see launch_conv_wino)
+// specialised builds: one workgroup (producer + a consumer per n-tile) per CU, an M-tile at a time each, a multiple of 8
+// workgroups for the XCD-aware walk; the others are persistent, the chip's workgroup slots shared by the n-tile groups
+static int wino4_grid(const ConvPlan &p, const Wino4Variant &v, int total, int num_cus, int *groups_out) {
+    if (v.spec) {
+        const int slices = v.slice ? p.cout / v.slice : 1;
+        int grid = std::min(total, std::max(1, num_cus * std::max(1, p.blocks_per_cu) / slices));
+        if (grid >= 8) grid &= ~7;
+        *groups_out = slices;
+        return grid;
+    }
+    const int ntiles = (p.cout + 15) / 16;
+    const int waves = p.threads / 64;
+    const int slots = std::max(1, num_cus * std::max(1, p.blocks_per_cu) / ntiles);
+    *groups_out = ntiles;
+    return std::min((total + waves - 1) / waves, slots);
+}
+
+void conv_wino4_launch_shape(const ConvPlan &p, int N, int num_cus, int *items, int *grid_x) {
+    int groups = 0;
+    *items = (N * p.tiles_y * p.tiles_x + 15) / 16;
+    *grid_x = *items ? wino4_grid(p, g_wino4[p.variant - 4000], *items, num_cus, &groups) : 0;
+}
+
+// stats / stats_rows: RAW builds only (see launch_conv_wino: no memset, every workgroup of the launch stores its row)
 hipError_t launch_conv_wino4(hipStream_t s, const ConvPlan &p, const float *in, const float *wpk, const float *bnp,
-                             float *out, int N, int num_cus, double *stats, int *stats_rows, bool stats_clean,
-                             const BnBwdFuse *bf) {
+                             float *out, int N, int num_cus, double *stats, int *stats_rows, const BnBwdFuse *bf) {
     const Wino4Variant &v = g_wino4[p.variant - 4000];
     Wino4Args a;
     // the branch-free epilogue needs every byte offset of the output below its sentinel (p.epi: ASR_WINO4_EPI)
@@ -884,25 +906,18 @@ hipError_t launch_conv_wino4(hipStream_t s, const ConvPlan &p, const float *in, 
     if (a.total == 0) return hipSuccess;
     if (v.spec) {
         if ((double)N * p.H * p.W * p.cin * 4.0 >= 4294967296.0) return hipErrorInvalidValue;   // 32-bit byte offsets
-        // one workgroup (producer + a consumer per n-tile) per CU, an M-tile at a time each; a multiple of 8 workgroups
-        // for the XCD-aware walk
-        const int slices = v.slice ? p.cout / v.slice : 1;
-        int grid = std::min(a.total, std::max(1, num_cus * std::max(1, p.blocks_per_cu) / slices));
-        if (grid >= 8) grid &= ~7;
+        int slices = 0;
+        const int grid = wino4_grid(p, v, a.total, num_cus, &slices);
         if (v.raw && stats) {                                 // (workgroups without M-tiles write zeros into their row: no memset)
             a.stats = stats;
             if (bf) a.bf = *bf;
-            (void)stats_clean;
             if (stats_rows) *stats_rows = grid;
         }
         hipLaunchKernelGGL(v.kernel, dim3(grid, slices), dim3(p.threads), p.lds_bytes, s, a);
         return hipGetLastError();
     }
-    const int ntiles = a.coutp / 16;
-    const int waves = p.threads / 64;
-    // persistent: the chip's workgroup slots are shared by the n-tile groups
-    const int slots = std::max(1, num_cus * std::max(1, p.blocks_per_cu) / ntiles);
-    const int grid = std::min((a.total + waves - 1) / waves, slots);
+    int ntiles = 0;
+    const int grid = wino4_grid(p, v, a.total, num_cus, &ntiles);
     hipLaunchKernelGGL(v.kernel, dim3(grid, ntiles), dim3(p.threads), p.lds_bytes, s, a);
     return hipGetLastError();
 }

@@ -1616,11 +1616,47 @@ void conv_candidates_wino_raw(int cin, int cout, int H, int W, int max_count, st
     }
 }
 
-// stats (RAW plans only, may be null): partial table of the outputs' per-channel sums, [rows][2][C_out] float64, zeroed
-// here (waves without work leave their row untouched); *stats_rows receives the number of rows
+// the launch grids: global-A form - `total` M-tiles over workgroups of `waves` waves, a multiple of 8 workgroups for the
+// kernel's XCD-aware walk (blocks b, b + 8 share an XCD); LDS-patch form - persistent, as many workgroups as fit on the
+// chip at once, each with a contiguous range of `per` regions
+static int winog_grid(const ConvPlan &p, const WinoGVariant &v, int total, int num_cus, int *ngroups_out) {
+    const int waves = p.threads / 64;
+    const int ngroups = ((p.cout + 15) / 16 + v.nt - 1) / v.nt;
+    const int slots = std::max(1, num_cus * std::max(1, p.blocks_per_cu) / ngroups);
+    int grid = std::min((total + waves - 1) / waves, slots);
+    if (grid >= 8) grid &= ~7;
+    *ngroups_out = ngroups;
+    return grid;
+}
+static int wino_grid(const ConvPlan &p, int ntw, int total, int num_cus, int *ngroups_out, int *per_out) {
+    const int nt = (p.cout + 15) / 16;
+    const int ngroups = (nt + ntw - 1) / ntw;
+    const int slots = std::max(1, num_cus * std::max(1, p.blocks_per_cu) / ngroups);
+    const int per = (total + slots - 1) / slots;
+    *ngroups_out = ngroups;
+    *per_out = per;
+    return (total + per - 1) / per;
+}
+
+void conv_wino_launch_shape(const ConvPlan &p, int N, int num_cus, int *items, int *grid_x) {
+    int ngroups = 0, per = 0;
+    *items = *grid_x = 0;
+    if (p.variant >= 3500) {
+        *items = (N * p.tiles_y * p.tiles_x + 15) / 16;
+        if (*items) *grid_x = winog_grid(p, g_winog[p.variant - 3500], *items, num_cus, &ngroups);
+    } else {
+        *items = N * p.tiles_y * p.tiles_x;
+        if (*items) *grid_x = wino_grid(p, g_wino[p.variant - 3000].ntw, *items, num_cus, &ngroups, &per);
+    }
+}
+
+// stats (RAW plans only, may be null): partial table of the outputs' per-channel sums, [rows][2][C_out] float64;
+// *stats_rows receives the number of rows.  No memset here or in the caller: EVERY wave of the launch stores its row,
+// zeros if it had no work, so whatever the table held before (it shares its memory with other reductions) is gone from
+// rows [0, *stats_rows) when the kernel ends
 hipError_t launch_conv_wino(hipStream_t s, const ConvPlan &p, const float *in, const float *wpk, const float *bnp,
                             float *out, int N, int num_cus, double *stats, int *stats_rows, const Fuse1Args *f1,
-                            bool stats_clean, const BnBwdFuse *bf) {
+                            const BnBwdFuse *bf) {
     if (p.variant >= 3500) {
         const WinoGVariant &v = g_winog[p.variant - 3500];
         WinoGArgs a;
@@ -1636,16 +1672,11 @@ hipError_t launch_conv_wino(hipStream_t s, const ConvPlan &p, const float *in, c
                                   (unsigned)p.OH * (unsigned)p.OW * (unsigned)p.cout))
             return hipErrorInvalidValue;
         const int waves = p.threads / 64;
-        const int ngroups = (a.coutp / 16 + v.nt - 1) / v.nt;
-        const int slots = std::max(1, num_cus * std::max(1, p.blocks_per_cu) / ngroups);
-        int grid = std::min((a.total + waves - 1) / waves, slots);
-        if (grid >= 8) grid &= ~7;           // a multiple of 8: the kernel's XCD-aware walk (blocks b, b + 8 share an XCD)
+        int ngroups = 0;
+        const int grid = winog_grid(p, v, a.total, num_cus, &ngroups);
         a.stats = v.raw ? stats : nullptr;
         a.bf = (bf && a.stats) ? *bf : BnBwdFuse{nullptr, nullptr, nullptr};
-        if (a.stats) {
-            (void)stats_clean;               // every wave of the launch writes its row (zeros without work): no memset
-            if (stats_rows) *stats_rows = grid * waves;
-        }
+        if (a.stats && stats_rows) *stats_rows = grid * waves;
         hipLaunchKernelGGL(v.kernel, dim3(grid, ngroups), dim3(p.threads), p.lds_bytes, s, a);
         return hipGetLastError();
     }
@@ -1666,12 +1697,8 @@ hipError_t launch_conv_wino(hipStream_t s, const ConvPlan &p, const float *in, c
     a.C4P = p.c4p; a.RP = p.rp;
     a.total = N * p.tiles_y * p.tiles_x;
     if (a.total == 0) return hipSuccess;
-    const int nt = a.coutp / 16;
-    const int ngroups = (nt + v.ntw - 1) / v.ntw;
-    // persistent: as many workgroups as fit on the chip at once, each with a contiguous range of regions
-    const int slots = std::max(1, num_cus * std::max(1, p.blocks_per_cu) / ngroups);
-    a.per = (a.total + slots - 1) / slots;
-    const int grid_x = (a.total + a.per - 1) / a.per;
+    int ngroups = 0;
+    const int grid_x = wino_grid(p, v.ntw, a.total, num_cus, &ngroups, &a.per);
     a.stats = v.raw ? stats : nullptr;
     a.bf = (bf && a.stats) ? *bf : BnBwdFuse{nullptr, nullptr, nullptr};
     if (a.stats) {

@@ -1533,12 +1533,19 @@ void wgrad_candidates(int cin, int cout, int H, int W, int num_cus, int max_coun
 
 size_t wgrad_partial_floats(const WgradPlan &p) { return (size_t)p.grid_cap * 9 * p.cin * p.cout; }
 
+void wgrad_launch_shape(const WgradPlan &p, int N, int *items, int *grid) {
+    *items = N * p.tiles_y * p.tiles_x;
+    *grid = std::max(1, std::min(*items, p.grid_cap));
+}
+bool wgrad_is_wino(const WgradPlan &p) { return g_wgrad[p.variant].wino > 0; }
+
 hipError_t launch_wgrad(hipStream_t s, const WgradPlan &p, const float *x, const float *dz, int N, float *partial,
                         float *dW) {
     WgradArgs a;
     a.x = x; a.dz = dz; a.partial = partial; a.N = N; a.H = p.H; a.W = p.W; a.TH = p.TH; a.TW = p.TW;
-    a.tiles_y = p.tiles_y; a.tiles_x = p.tiles_x; a.total_tiles = N * p.tiles_y * p.tiles_x;
-    const int grid = std::max(1, std::min(a.total_tiles, p.grid_cap));
+    a.tiles_y = p.tiles_y; a.tiles_x = p.tiles_x;
+    int grid = 0;
+    wgrad_launch_shape(p, N, &a.total_tiles, &grid);
     const WgradVariant &wv = g_wgrad[p.variant];
     const int threads = wv.wino > 0 ? 64 * wv.wino : wv.wm > 0 ? 64 * wv.wm * wv.wk : wv.taps_waves > 0 ? 64 * wv.taps_waves : 576;
     hipLaunchKernelGGL(g_wgrad[p.variant].kernel, dim3(grid), dim3(threads), p.lds_bytes, s, a);

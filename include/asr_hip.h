@@ -649,6 +649,27 @@ int asr_debug_train_tensor(asr_ctx *ctx, int kind, int view, int index, int64_t 
 int asr_cca_train_debug(asr_ctx *ctx, const float *H1, const float *H2, int64_t batch,
                         const float *cca_in, float *cca_out, float *loss_corr,
                         float *lv1, float *lv2, float *dH1, float *dH2);
+/* test aid: ONE candidate of the lists asr_train_begin's tuner times for a 3x3 block (`block` 1..7 = conv2..conv8 of
+ * `view`), alone, through the production launcher, on host arrays (NHWC, `batch` <= the training state's batch size):
+ *   kind 0 forward convolution   a = x (batch,H,W,cin)            -> out = z (batch,H,W,cout), stats = [mu | inv_std]
+ *        1 data gradient         a = dz (batch,H,W,cout)          -> out = dx (batch,H,W,cin)
+ *        2 weight gradient       a = x, b = dz                    -> out = dW (cout,cin,3,3), the parameter's layout
+ * `index` counts into the tuner's own list (the model's plan first); past its end the call fails with
+ * ASR_ERR_INVALID and a message that ends in "has <length> candidates".  The output buffer, the BatchNorm statistics
+ * table (kind 0), the partial sums and the gradient slot (kind 2) are filled with 0xff bytes first, so an element or a
+ * table row the schedule does not write comes back as NaN; every Winograd-domain weight copy is rebuilt from the device
+ * master before the launch.  kind 0, when the schedule gathers the statistics itself (info[1] > 0): the table is
+ * finished as the training step does (eps 1e-4) into stats (2*cout floats; NaN otherwise).
+ * out = NULL: nothing runs, info [2..11] and desc alone are filled (a caller sizes and checks its arrays by them).
+ *   info (12 values): [0] 1 launched / 0 the launcher refused the schedule (the tuner skips such a candidate; out is
+ *   NaN), [1] rows of the statistics table the launcher reported, [2] work items (M-tiles of 16 tiles; regions for the
+ *   LDS-patch Winograd form; tiles for kind 2), [3] workgroups along x, [4] family 0 direct / 1 winog (global-A F(2x2))
+ *   / 2 wino (LDS-patch F(2x2); kind 2: the Winograd-domain weight gradient) / 3 wino4 (F(4x4)), [5] variant,
+ *   [6] [7] the plan's TH, TW, [8..11] the block's H, W, cin, cout.  desc: one line in the tuner's ASR_DEBUG format, e.g. "winog#3515 tile 2x32 x16".
+ * Afterwards the gradient slot is zero again and plans, parameters, Adam state and the repack table are as before. */
+int asr_debug_train_candidate(asr_ctx *ctx, int view, int block, int kind, int index, int64_t batch,
+                              const float *a, const float *b, float *out, int64_t cap, float *stats,
+                              int32_t *info, char *desc, int64_t desc_cap);
 
 /* ---- staff-system detection (sheet_utils/omr.py, system_detector.py, bar_detector.py) ----------------
  * One U-Net of SegmentationNetwork (system_detector.build_model(), bar_detector's graph at its own input size) as a
