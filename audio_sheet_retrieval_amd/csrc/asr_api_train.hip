@@ -784,8 +784,6 @@ int train_forward_towers(asr_ctx *ctx, int B) {
 struct BwdState {
     float *dA, *dB;                 // gradients wrt block outputs (rotating)
     bool wg_pending[2];
-    int pre_rows = 0;               // > 0: the data gradient that wrote dA also left the BatchNorm-backward sums of the block
-                                    // about to be processed in the tower's statistics table (asr::BnBwdFuse), that many rows
 };
 
 // the end of a tower's backward pass (block 9, global pooling); phases as in train_forward_block
@@ -861,13 +859,10 @@ int train_backward_block(asr_ctx *ctx, int t, int B, int b, int phase, BwdState 
                                                       tt.partial, tt.sums, pg(T, base + 1), pg(T, base + 2), B, g.H, g.W,
                                                       g.cout, ex));
             else {
-            const int pre = (phase != 2) ? S.pre_rows : 0;
-            S.pre_rows = 0;
             ASR_HIP(ctx, asr::launch_bn_bwd(st, tt.z[b], (b == 0 && fuse1) ? nullptr : dz, dA, tt.stats[b], pm(T, base + 2), pm(T, base + 1),
                                             tt.partial, tt.sums, pg(T, base + 1), pg(T, base + 2), B, g.H, g.W, g.cout,
                                             g.pool, 1, ex, tt.zsel[b], tt.ztie[b],
-                                            ctx->cfg.pool_ties == ASR_POOL_TIES_FIRST ? 1 : 0, tt.ticket,
-                                            pre > 0 ? tt.fstats : nullptr, pre, pre > 0 ? tt.fstats + tt.fstats_doubles : nullptr));
+                                            ctx->cfg.pool_ties == ASR_POOL_TIES_FIRST ? 1 : 0, tt.ticket));
             }
         }
         ctx->exch.phase = 0;
@@ -913,29 +908,10 @@ int train_backward_block(asr_ctx *ctx, int t, int B, int b, int phase, BwdState 
             snprintf(name, sizeof name, "train_dgrad_conv%d", b + 1);
             ProfScope ps(ctx, name, view, 2.0 * rows * 9.0 * g.cin * g.cout, 4.0 * rows * (g.cin + g.cout),
                          tt.dplan[b].symbol);
-            // The data gradient of block b writes dL/d(output of block b-1): it can run the REDUCE pass of that block's
-            // BatchNorm backward in its epilogue (asr::BnBwdFuse: reads z[b-1] - pooled blocks: zsel[b-1] - at the index of
-            // every value it stores), so that bn_bwd_reduce_kernel and its re-read of the gradient leave the main stream's
-            // chain.  Built, parity-green under both pooling rules - and measured
-            // SLOWER: batch 512 update 12.36 ms against 10.57 ms with the separate pass.  The epilogue's loads of z
-            // are used at once by a wave that has nothing else to issue (1-2 workgroups per CU): +70 % on the data
-            // gradients, against 1.25 ms of HBM-bound reduce passes that mostly hide under the other stream's MFMA
-            // kernels anyway.  Off by default (ASR_TRAIN_BNB_FUSE=1 switches it on; kept for a prefetching epilogue).
-            // (round 6: compiled out unless the library is built with -DASR_BNB_FUSE_BUILD=1, see asr_kernels.h)
-            static const bool bnb_fuse = ASR_BNB_FUSE_BUILD && (getenv("ASR_TRAIN_BNB_FUSE") && getenv("ASR_TRAIN_BNB_FUSE")[0] == '1') &&
-                                         (getenv("ASR_TRAIN_FUSED_REDUCE") && getenv("ASR_TRAIN_FUSED_REDUCE")[0] == '1');
-            const LayerGeom &gp = tw.g[b - 1];
-            asr::BnBwdFuse bf{nullptr, nullptr, nullptr};
-            if (bnb_fuse && !ex && b >= 2 && 2 * gp.cout <= 256 && (!gp.pool || tt.zsel[b - 1]) &&
-                (!gp.pool || ctx->cfg.pool_ties == ASR_POOL_TIES_FIRST || tt.ztie[b - 1])) {
-                bf.z = gp.pool ? tt.zsel[b - 1] : tt.z[b - 1];
-                bf.tie = (gp.pool && ctx->cfg.pool_ties == ASR_POOL_TIES_ALL) ? tt.ztie[b - 1] : nullptr;
-                bf.cst = tt.stats[b - 1];
-            }
-            int prow = 0;
-            ASR_HIP(ctx, launch_conv_any(ctx, st, tt.dplan[b], dz, tt.wdgrad[b], nullptr, dB, B, nullptr,
-                                         bf.z ? tt.fstats : nullptr, &prow, bf.z ? &bf : nullptr));
-            S.pre_rows = bf.z ? prow : 0;           // 0: this plan writes no sums (direct-form build) - the reduce pass runs
+            // (Running the REDUCE pass of block b-1's BatchNorm backward in this kernel's epilogue was built, measured
+            // slower - batch 512 update 12.36 ms against 10.57 ms - and removed: docs/MEASUREMENT_LOG.md, "Round 5: the
+            // training step, measured" and "Round 6".)
+            ASR_HIP(ctx, launch_conv_any(ctx, st, tt.dplan[b], dz, tt.wdgrad[b], nullptr, dB, B));
             std::swap(dA, dB);
         }
         if (wgrad_late && b >= 1) {

@@ -389,7 +389,7 @@ int rank_check(asr_ctx *ctx, int64_t n1, int64_t ld1, int64_t n2, int64_t ld2, i
 // towers (asr_api.hip) <-> training step and collectives (asr_api_train.hip)
 hipError_t launch_conv_any(asr_ctx *ctx, hipStream_t st, const asr::ConvPlan &p, const float *in, const float *w,
                            const float *bn, float *out, int n, const asr::Fuse1Args *f1 = nullptr, double *stats = nullptr,
-                           int *stats_rows = nullptr, const asr::BnBwdFuse *bf = nullptr);
+                           int *stats_rows = nullptr);
 int tune_cache_tag();
 void free_train(asr_ctx *ctx);
 void free_comm(asr_ctx *ctx);

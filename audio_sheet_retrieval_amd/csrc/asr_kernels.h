@@ -14,37 +14,6 @@ namespace asr {
 // these values for EQUALITY, so all of them must round the same way whatever the compiler would have contracted.
 __device__ __forceinline__ float bn_affine(float v, float mu, float sc, float be) { return __fmaf_rn(v - mu, sc, be); }
 
-// A data-gradient convolution can carry the REDUCE pass of the BatchNorm backward of the block whose output gradient it
-// writes (round 5): per output element dA it reads that block's raw conv output z at the same index (pooled blocks: the
-// selected raw value zsel, which has the pooled shape of dA) and accumulates sum dy and sum dy*xhat with dy = dA *
-// ELU'(y) (* the tie multiplicity), y by bn_affine - into the same per-wave float64 partial table the forward kernels
-// use for the statistics.  bn_bwd_reduce_kernel then does not run for that block: one read of dA and one launch less.
-// Round 6: compiled OUT by default.  The form was built for the three Winograd families, is parity-green under both
-// pooling rules and runs the batch-512 update 1.8 ms SLOWER (12.36 against 10.57 ms: the epilogue's loads are consumed at
-// once by waves that have nothing else to issue) - and the four per-channel constants it keeps live across the M-tile loop
-// pushed the RAW builds of conv3x3_winog / conv3x3_wino / conv3x3_wino4s over their register budget (68-136 bytes of
-// scratch per lane, spill stores in every prologue).  -DASR_BNB_FUSE_BUILD=1 (tools/build_variant.sh) brings the path and
-// its switch ASR_TRAIN_BNB_FUSE=1 back for experiments.
-#ifndef ASR_BNB_FUSE_BUILD
-#define ASR_BNB_FUSE_BUILD 0
-#endif
-struct BnBwdFuse {
-    const float *z;          // (N,H,W,C) raw output, or (N,H/2,W/2,C) selected raw values of a pooled block
-    const uint8_t *tie;      // pooled + "every tied element": (N,H/2,W/2,C/4) two bits per channel = ties - 1; else null
-    const float *cst;        // the block's statistics buffer: [mu | inv_std | gamma*inv_std | beta] x C
-};
-__device__ __forceinline__ void bnb_acc(float dA, float zz, float mult, float mu, float sc, float be, float istd, float &t1,
-                                        float &t2) {
-    const float y = bn_affine(zz, mu, sc, be);
-    const float dact = y <= 0.0f ? __expf(y) : 1.0f;           // ELU'(y) = exp(y) for y <= 0 (blocks 1..8 all carry ELU)
-    const float dy = dA * dact * mult;
-    t1 += dy;
-    t2 = fmaf(dy, (zz - mu) * istd, t2);
-}
-__device__ __forceinline__ float bnb_mult(const uint8_t *tie, size_t e) {
-    return tie ? (float)(((tie[e >> 2] >> (2 * (e & 3))) & 3u) + 1u) : 1.0f;
-}
-
 // ---- first block: conv3x3 (C_in = 1) + BN + ELU, prepare() folded in -------
 // in_mode: ASR_IN_* of asr_hip.h.  Hraw/Wraw: raw sheet size; H/W: network
 // resolution (= raw, or raw/2 when rsz).  w: [COUT][9] correlation-form taps,
@@ -97,7 +66,7 @@ void conv_candidates_wino(int cin, int cout, int pool, int H, int W, int max_cou
 // f1: plans with fuse1 set (block 1 evaluated inside by producer waves) read the raw input instead of `in`
 hipError_t launch_conv_wino(hipStream_t s, const ConvPlan &p, const float *in, const float *wino_wpk,
                             const float *bnp, float *out, int N, int num_cus, double *stats = nullptr,
-                            int *stats_rows = nullptr, const Fuse1Args *f1 = nullptr, const BnBwdFuse *bf = nullptr);
+                            int *stats_rows = nullptr, const Fuse1Args *f1 = nullptr);
 // what launch_conv_wino launches for plan p on N images: its work items (M-tiles of 16 tiles in the global-A form,
 // regions in the LDS-patch form) and its workgroups along x (each repeated per group of n-tiles)
 void conv_wino_launch_shape(const ConvPlan &p, int N, int num_cus, int *items, int *grid_x);
@@ -115,7 +84,7 @@ void conv_candidates_wino_raw(int cin, int cout, int H, int W, int max_count, st
 void conv_candidates_wino4(int cin, int cout, int pool, int H, int W, std::vector<ConvPlan> *out);
 hipError_t launch_conv_wino4(hipStream_t s, const ConvPlan &p, const float *in, const float *wino4_wpk,
                              const float *bnp, float *out, int N, int num_cus, double *stats = nullptr,
-                             int *stats_rows = nullptr, const BnBwdFuse *bf = nullptr);
+                             int *stats_rows = nullptr);
 // M-tiles and workgroups along x of launch_conv_wino4 for plan p on N images
 void conv_wino4_launch_shape(const ConvPlan &p, int N, int num_cus, int *items, int *grid_x);
 // RAW (training) builds of conv3x3_wino4s: candidates of the training step's tuner for a block's forward convolution
@@ -534,11 +503,7 @@ hipError_t launch_bn_bwd(hipStream_t s, const float *z, float *dz, const float *
                          const float *gamma, const float *beta, double *partial, double *sums, float *dbeta,
                          float *dgamma, int N, int H, int W, int C, int pool, int elu, const Exchange *ex = nullptr,
                          const float *zsel = nullptr, const uint8_t *ztie = nullptr, int ties_first = 0,
-                         unsigned *ticket = nullptr, double *pre_partial = nullptr, int pre_rows = 0,
-                         double *pre_staged = nullptr);
-// pre_partial / pre_rows (> 0) / pre_staged: the reduce pass already ran inside the data-gradient convolution that wrote
-// `dout` (BnBwdFuse): its per-wave partial table (the zero-between-uses statistics table) is reduced, the reduce kernel
-// is skipped.  Needs ticket.
+                         unsigned *ticket = nullptr);
 // One launch for "column sums of a partial table [nb][cols] (float64) + what follows": workgroup b sums rows 32b .. 32b+31
 // into a staged row behind the table, the LAST workgroup to arrive (atomic ticket, reset to 0 for the next use) sums the
 // staged rows in fixed order - deterministic for a given nb - and finishes.  mode 0: BatchNorm statistics (mu, inv_std,

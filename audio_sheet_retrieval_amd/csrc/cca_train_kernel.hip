@@ -91,12 +91,9 @@ __device__ void eigh_spd(CcaScratch &S, const double *Min, double *w, double *Vo
         cca_set_identity(S.V, tid, nt);
     }
     __syncthreads();
-    // ASR_CCA_NOV (default 1, round 6): the Jacobi iteration does not carry V - see cca_hestenes_wave_on<false>; the
-    // eigenvectors are W's columns over their norms.  0: V accumulated by the rotations as in rounds 2-5.
-#ifndef ASR_CCA_NOV
-#define ASR_CCA_NOV 1
-#endif
-    const bool nov = ASR_CCA_NOV && ASR_CCA_WAVE && reg >= 1e-6f;      // uniform
+    // Round 6: the Jacobi iteration does not carry V - see cca_hestenes_wave_on<false>; the eigenvectors are W's
+    // columns over their norms.  (Without a regulariser V is accumulated by the rotations as in rounds 2-5.)
+    const bool nov = reg >= 1e-6f;      // uniform
     if (nov) cca_hestenes_wave<false>(S, tid);
     else cca_hestenes_fast(S, tid);
     for (int j = tid; j < D; j += nt) {

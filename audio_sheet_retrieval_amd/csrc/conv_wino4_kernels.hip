@@ -49,7 +49,6 @@ struct Wino4Args {
     int tiles;             // tiles in the launch
     int total;             // M-tiles in the launch = ceil(tiles / 16)
     double *stats;         // RAW builds of conv3x3_wino4s, may be null: per-workgroup [sum | sum of squares] of the outputs
-    BnBwdFuse bf;          // RAW + stats, bf.z != null: the sums are those of a BatchNorm backward instead (asr_kernels.h)
     int epi;               // conv3x3_wino4s, non-RAW: 1 = rows-full M-tiles take the branch-free epilogue (ASR_WINO4_EPI;
                            // last, so that the other builds read their arguments where they did)
 };
@@ -358,9 +357,6 @@ __global__ __launch_bounds__(64 * (PW + (SLICE + 15) / 16), 1) void conv3x3_wino
     // (Round 2 had [m][g][2]: the 16 lanes of a write group sat 32 bytes apart on 4 bank pairs, a 4-way conflict, 16
     // LDS cycles per store instead of 6; the reads 2-way.  SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE was 0.74.)
     float *vlane = vbuf + (g * 32 + 2 * m);
-#ifdef ASR_WINO4_OLD_V
-    vlane = vbuf + (m * 8 + 2 * g);
-#endif
 
     if (producer) {
         // the 36 patch pixels of this lane's tile as 32-bit BYTE offsets from the tensor base (the launcher admits
@@ -463,12 +459,6 @@ __global__ __launch_bounds__(64 * (PW + (SLICE + 15) / 16), 1) void conv3x3_wino
     float bmean = (!RAW && ch_ok) ? a.bnp[chn] : 0.f;
     float bscale = (!RAW && ch_ok) ? a.bnp[a.coutp + chn] : 1.f;
     float bbeta = (!RAW && ch_ok) ? a.bnp[2 * a.coutp + chn] : 0.f;
-    float bistd = 0.f;                                        // BatchNorm-backward sums (a.bf): mu, gamma*inv_std, beta, inv_std
-    const bool bnb = ASR_BNB_FUSE_BUILD && RAW && a.stats && a.bf.z != nullptr;
-    if (bnb && ch_ok) {
-        bmean = a.bf.cst[chn]; bistd = a.bf.cst[COUT + chn];
-        bscale = a.bf.cst[2 * COUT + chn]; bbeta = a.bf.cst[3 * COUT + chn];
-    }
     double st1 = 0.0, st2 = 0.0;                              // RAW + a.stats: sums of this lane's channel
     // the output tensor as a raw buffer (stride 0) for the branch-free epilogue; the launcher sets a.epi only when
     // num_records is below the sentinel offset
@@ -702,12 +692,7 @@ __global__ __launch_bounds__(64 * (PW + (SLICE + 15) / 16), 1) void conv3x3_wino
                     for (int r = 0; r < 4; ++r) {
                         if (i >= (ee[r] & 0xff) || j >= (ee[r] >> 8)) continue;
                         const float res = RAW ? y[j][r] : elu_fastq((y[j][r] - bmean) * bscale + bbeta);
-                        if (RAW) {
-                            if (bnb) {
-                                const size_t e = (size_t)eo[r] + (size_t)(i * a.W + j) * COUT + chn;
-                                bnb_acc(res, a.bf.z[e], bnb_mult(a.bf.tie, e), bmean, bscale, bbeta, bistd, rs1, rs2);
-                            } else { rs1 += res; rs2 = fmaf(res, res, rs2); }
-                        }
+                        if (RAW) { rs1 += res; rs2 = fmaf(res, res, rs2); }
                         if (ASR_WINO4_ABL & 32) asm volatile("" ::"v"(res));
                         else a.out[(size_t)eo[r] + (size_t)(i * a.W + j) * COUT + chn] = res;
                     }
@@ -890,13 +875,12 @@ void conv_wino4_launch_shape(const ConvPlan &p, int N, int num_cus, int *items, 
 
 // stats / stats_rows: RAW builds only (see launch_conv_wino: no memset, every workgroup of the launch stores its row)
 hipError_t launch_conv_wino4(hipStream_t s, const ConvPlan &p, const float *in, const float *wpk, const float *bnp,
-                             float *out, int N, int num_cus, double *stats, int *stats_rows, const BnBwdFuse *bf) {
+                             float *out, int N, int num_cus, double *stats, int *stats_rows) {
     const Wino4Variant &v = g_wino4[p.variant - 4000];
     Wino4Args a;
     // the branch-free epilogue needs every byte offset of the output below its sentinel (p.epi: ASR_WINO4_EPI)
     a.epi = (p.epi && v.spec && !v.raw && wino4_fast_epilogue_admitted(N, p.OH, p.OW, p.cout)) ? 1 : 0;
     a.stats = nullptr;
-    a.bf = BnBwdFuse{nullptr, nullptr, nullptr};
     a.in = in; a.wpk = wpk; a.bnp = bnp; a.out = out;
     a.N = N; a.H = p.H; a.W = p.W; a.OH = p.OH; a.OW = p.OW;
     a.ty_img = p.tiles_y; a.tx_img = p.tiles_x;
@@ -910,7 +894,6 @@ hipError_t launch_conv_wino4(hipStream_t s, const ConvPlan &p, const float *in, 
         const int grid = wino4_grid(p, v, a.total, num_cus, &slices);
         if (v.raw && stats) {                                 // (workgroups without M-tiles write zeros into their row: no memset)
             a.stats = stats;
-            if (bf) a.bf = *bf;
             if (stats_rows) *stats_rows = grid;
         }
         hipLaunchKernelGGL(v.kernel, dim3(grid, slices), dim3(p.threads), p.lds_bytes, s, a);

@@ -41,13 +41,6 @@
 #include "wino_weight_layout.h"
 #include "wino_lds_weight_layout.h"
 
-// conv3x3_winog, per-item A/B switches of round 19 (results are the same bits either way; ASR_WINOG_DENSEW, the dense
-// weight layout of the NT = 2 builds, lives in wino_weight_layout.h)
-#ifndef ASR_WINOG_NOCOPY
-#define ASR_WINOG_NOCOPY 1   // 1: the column pass of the input transform reads the loaded patch where it landed and the
-                             // next loads go out behind it; 0: copy the patch first, loads before the transform
-#endif
-
 #ifndef ASR_WINOG_ABL
 #define ASR_WINOG_ABL 0      // timing experiments only (wrong results).  LDS form: 1 = no patch DMA after the first region,
                              // 16 = no B reads, 32 = no A (patch) reads, 64 = no stores; global-A form: 2 = no input loads
@@ -59,13 +52,6 @@ namespace asr {
 
 typedef float floatx4w __attribute__((ext_vector_type(4)));
 typedef float float2w __attribute__((ext_vector_type(2)));
-
-#ifndef ASR_WINO_ASMREAD
-#define ASR_WINO_ASMREAD 1     // 0: the patch reads as plain loads (the compiler pairs them into ds_read2_b64)
-#endif
-#ifndef ASR_WINO_BUFDMA
-#define ASR_WINO_BUFDMA 1      // 0: round 2's pointer form of the LDS-DMA (A/B timing: tools/ab_build.sh)
-#endif
 
 struct WinoArgs {
     const float *in;       // (N,H,W,CIN)
@@ -82,7 +68,6 @@ struct WinoArgs {
     int total;             // regions in the launch
     int per;               // regions per workgroup (contiguous range)
     double *stats;         // RAW only, may be null: per-wave [sum | sum of squares] of the outputs, [row][2][C_out]
-    BnBwdFuse bf;          // RAW + stats, bf.z != null: the sums are those of a BatchNorm backward instead (asr_kernels.h)
     // producer-wave builds (PW > 0): block 1 is evaluated into the LDS patch, `in` is unused
     const void *raw;       // raw view-1 / view-2 input (N,1,Hraw,Wraw): uint8 or float32
     const float *w1;       // block 1: [C][9] correlation-form taps
@@ -91,42 +76,15 @@ struct WinoArgs {
 
 // a - b on vector types.  (Tried: spelling it as v_pk_add_f32 with neg modifiers in inline asm, because the compiler
 // expands a packed fsub into scalar v_sub_f32 - 55 fewer VALU instructions per M-tile, no measurable time, dropped.)
-#ifndef ASR_WINO_PKADD
-#define ASR_WINO_PKADD 1     // 0: spell the transform adds as scalar v_add_f32 / v_sub_f32 (measured: 1 % SLOWER, see padd)
-#endif
-__device__ __forceinline__ float ssub(float a, float b) {
-    float r;
-    asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float2w psub(float2w a, float2w b) {
-    if (ASR_WINO_PKADD) return a - b;
-    return float2w{ssub(a[0], b[0]), ssub(a[1], b[1])};
-}
-__device__ __forceinline__ floatx4w psub(floatx4w a, floatx4w b) {
-    if (ASR_WINO_PKADD) return a - b;
-    return floatx4w{ssub(a[0], b[0]), ssub(a[1], b[1]), ssub(a[2], b[2]), ssub(a[3], b[3])};
-}
+__device__ __forceinline__ float2w psub(float2w a, float2w b) { return a - b; }
+__device__ __forceinline__ floatx4w psub(floatx4w a, floatx4w b) { return a - b; }
 // a + b on vector types.  The compiler lowers vector fadd / fsub to v_pk_add_f32, which MI355X_MICROARCH.md lists as
 // an anti-lever beside bf16 MFMAs (2 v_pk_add_f32 per MFMA gap: +26 cycles against 2 scalar adds).  Measured here
-// (round 2, tools/ab_flags.sh, -DASR_WINO_PKADD=0: every transform add as a scalar instruction the SLP vectoriser
-// cannot re-pack): the scalar form is 1 % SLOWER on every Winograd layer (conv2 0.725 -> 0.732 ms, conv6 0.474 ->
-// 0.485) - the fp32 MFMA occupies the vector pipe either way, so what counts is the instruction count.  Packed stays.
-__device__ __forceinline__ float sadd(float a, float b) {
-    float r;
-    asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float2w padd(float2w a, float2w b) {
-    if (ASR_WINO_PKADD) return a + b;
-    return float2w{sadd(a[0], b[0]), sadd(a[1], b[1])};
-}
-__device__ __forceinline__ floatx4w padd(floatx4w a, floatx4w b) {
-    if (ASR_WINO_PKADD) return a + b;
-    return floatx4w{sadd(a[0], b[0]), sadd(a[1], b[1]), sadd(a[2], b[2]), sadd(a[3], b[3])};
-}
-
-__device__ float4 g_wino_zero[4];       // zero block the border lanes of the LDS-DMA read
+// (round 2): every transform add as a scalar instruction is 1 % SLOWER on every Winograd layer (conv2 0.725 -> 0.732 ms,
+// conv6 0.474 -> 0.485) - the fp32 MFMA occupies the vector pipe either way, so what counts is the instruction count.
+// Packed stays; the scalar form is removed.
+__device__ __forceinline__ float2w padd(float2w a, float2w b) { return a + b; }
+__device__ __forceinline__ floatx4w padd(floatx4w a, floatx4w b) { return a + b; }
 
 // BatchNorm statistics of a RAW convolution, gathered where the outputs are produced (train-mode forward,
 // train_fwd_kernels.hip): every lane (g, n) keeps float64 sums of the values and squares it wrote for channel
@@ -214,10 +172,10 @@ __global__ __launch_bounds__(64 * (WAVES + PW), MINW) void conv3x3_wino(WinoArgs
         }
     }
     // ---- which chunks of a region's patch this thread moves (the same for every region): offset from the region's
-    // first output pixel in global memory and (row, column) for the border test; -1 marks padding chunks.  The copy
-    // itself is an LDS-DMA (global_load_lds_dwordx4): no data registers, the wave's 64 x 16 B land contiguously in
-    // LDS, and every lane picks its own source - that is how the padded, shifted layout is produced.  Lanes outside
-    // the image (and padding) read a zero block
+    // first output pixel in global memory (bytes) and (row, column) for the border test; -1 marks padding chunks.  The
+    // copy itself is an LDS-DMA (buffer_load_dwordx4 ... lds): no data registers, the wave's 64 x 16 B land contiguously
+    // in LDS, and every lane gives its own offset - that is how the padded, shifted layout is produced.  Lanes outside
+    // the image (and padding) get zeros from the buffer's range check (see fetch)
     constexpr int RMAXE = PW > 0 ? 1 : RMAX;
     int st_g[RMAXE], st_rc[RMAXE];
     if constexpr (PW == 0) {
@@ -228,11 +186,7 @@ __global__ __launch_bounds__(64 * (WAVES + PW), MINW) void conv3x3_wino(WinoArgs
             const int xs = f - r * a.RP - ((r >> 1) & 1);
             const int px = xs / C4P, c = xs - px * C4P;
             const bool real = r < LH && xs >= 0 && px < LW && c < C4;
-#if ASR_WINO_BUFDMA
             st_g[k] = real ? (((r - 1) * a.W + (px - 1)) * CIN + c * 4) * 4 : (int)0x80000000;      // BYTES; padding: out of range
-#else
-            st_g[k] = ((r - 1) * a.W + (px - 1)) * CIN + c * 4;
-#endif
             st_rc[k] = real ? (r << 16) | px : -1;
         }
     }
@@ -243,7 +197,6 @@ __global__ __launch_bounds__(64 * (WAVES + PW), MINW) void conv3x3_wino(WinoArgs
         const int ty = rest % a.tiles_y;
         const int img = rest / a.tiles_y;
         const int Y0 = ty * a.RY, X0 = tx * a.RX;
-#if ASR_WINO_BUFDMA
         // Round 3: the copy as BUFFER loads (buffer_load_dwordx4 ... lds) through a descriptor of THIS image: a chunk's
         // address is "region offset (scalar) + this thread's constant" - one v_add per copy instead of a 64-bit
         // pointer, two selects and the border tests - and the hardware's range check supplies the zeros: rows above
@@ -286,32 +239,6 @@ __global__ __launch_bounds__(64 * (WAVES + PW), MINW) void conv3x3_wino(WinoArgs
                 const int x = X0 - 1 + (st_rc[k] & 0xffff);
                 dma(k, (st_rc[k] >= 0 && (unsigned)x < (unsigned)a.W) ? st_g[k] + roff : (int)0x80000000);
             }
-            return;
-        }
-#endif
-        const float *gbase = a.in + (((int64_t)img * a.H + Y0) * a.W + X0) * CIN;
-        if (!(ASR_WINOG_ABL & 512) && Y0 >= 1 && Y0 + LH - 1 <= a.H && X0 >= 1 && X0 + LW - 1 <= a.W) {
-            // patch and halo inside the image (most regions): no border tests - they are ~15 vector instructions per
-            // copy, which the fp32 MFMAs of the same SIMD do not overlap
-#pragma unroll
-            for (int k = 0; k < RMAX; ++k) {
-                if ((k * T + wave * 64) * 4 >= buf_floats) break;          // wave-uniform: nothing left for this wave
-                const float *src = st_rc[k] >= 0 ? gbase + st_g[k] : reinterpret_cast<const float *>(g_wino_zero);
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                                 (__attribute__((address_space(3))) void *)(buf + (k * T + wave * 64) * 4),
-                                                 16, 0, 0);
-            }
-            return;
-        }
-#pragma unroll
-        for (int k = 0; k < RMAX; ++k) {
-            if ((k * T + wave * 64) * 4 >= buf_floats) break;              // wave-uniform: nothing left for this wave
-            const int y = Y0 - 1 + (st_rc[k] >> 16), x = X0 - 1 + (st_rc[k] & 0xffff);
-            const bool ok = st_rc[k] >= 0 && y >= 0 && y < a.H && x >= 0 && x < a.W;
-            const float *src = ok ? gbase + st_g[k] : reinterpret_cast<const float *>(g_wino_zero);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                             (__attribute__((address_space(3))) void *)(buf + (k * T + wave * 64) * 4),
-                                             16, 0, 0);
         }
         }
     };
@@ -380,9 +307,7 @@ __global__ __launch_bounds__(64 * (WAVES + PW), MINW) void conv3x3_wino(WinoArgs
         if (producer) produce(first, lds);
     } else {
         fetch(first, lds);
-#if ASR_WINO_BUFDMA
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
     }
     __syncthreads();
 
@@ -419,17 +344,6 @@ __global__ __launch_bounds__(64 * (WAVES + PW), MINW) void conv3x3_wino(WinoArgs
         bscale[nt] = ok ? a.bnp[a.coutp + ch] : 1.f;
         bbeta[nt] = ok ? a.bnp[2 * a.coutp + ch] : 0.f;
     }
-    float bistd[NTW];                        // BatchNorm-backward sums (a.bf): mu, gamma*inv_std, beta, inv_std per channel
-    const bool bnb = ASR_BNB_FUSE_BUILD && RAW && a.stats && a.bf.z != nullptr;
-#pragma unroll
-    for (int nt = 0; nt < NTW; ++nt) {
-        const int ch = ng * WROW + nt * 16 + n;
-        bistd[nt] = 0.f;
-        if (bnb && ch < COUT) {
-            bmean[nt] = a.bf.cst[ch]; bistd[nt] = a.bf.cst[COUT + ch];
-            bscale[nt] = a.bf.cst[2 * COUT + ch]; bbeta[nt] = a.bf.cst[3 * COUT + ch];
-        }
-    }
 
     double st1[NTW], st2[NTW];               // RAW + a.stats: running sums of this lane's channel(s)
 #pragma unroll
@@ -464,7 +378,6 @@ __global__ __launch_bounds__(64 * (WAVES + PW), MINW) void conv3x3_wino(WinoArgs
             if (ch < NCH) {
                 // KB channel blocks: per patch pixel one b64 read = the operands of two k-steps, transformed together
                 float2w dp[4][4][KB];
-#if ASR_WINO_ASMREAD
                 // The patch reads as explicit ds_read_b64: the compiler pairs neighbouring reads into ds_read2_b64, which
                 // this LDS serves at half the rate of two ds_read_b64 (8 cycles against 2 + 2, MI355X_MICROARCH.md) and
                 // in 16-lane groups on 32 banks - not the 32-lane / 64-bank pattern the patch layout is planned for
@@ -497,16 +410,6 @@ __global__ __launch_bounds__(64 * (WAVES + PW), MINW) void conv3x3_wino(WinoArgs
                                        "+v"(dp[2][0][c]), "+v"(dp[2][1][c]), "+v"(dp[2][2][c]), "+v"(dp[2][3][c]),
                                        "+v"(dp[3][0][c]), "+v"(dp[3][1][c]), "+v"(dp[3][2][c]), "+v"(dp[3][3][c]));
                 }
-#else
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-#pragma unroll
-                        for (int c = 0; c < KB; ++c)
-                            dp[i][j][c] = (ASR_WINOG_ABL & 32) ? float2w{(float)i, (float)j}
-                                                               : *reinterpret_cast<const float2w *>(ap + a_row[i] + j * CSf + (ch * KB + c) * 8 + a_pair);
-#endif
 #pragma unroll
                 for (int c = 0; c < KB; ++c) {
 #pragma unroll
@@ -652,19 +555,8 @@ __global__ __launch_bounds__(64 * (WAVES + PW), MINW) void conv3x3_wino(WinoArgs
                         const float v11 = RAW ? y11[r] : elu_fastw((y11[r] - bmean[nt]) * bscale[nt] + bbeta[nt]);
                         o[0] = v00; o[COUT] = v01; o[rstride] = v10; o[rstride + COUT] = v11;
                         if (RAW && a.stats) {
-                            if (bnb) {
-                                const size_t e = (size_t)(o - a.out);
-                                const float *zp = a.bf.z + e;
-                                float t1 = 0.f, t2 = 0.f;
-                                bnb_acc(v00, zp[0], bnb_mult(a.bf.tie, e), bmean[nt], bscale[nt], bbeta[nt], bistd[nt], t1, t2);
-                                bnb_acc(v01, zp[COUT], bnb_mult(a.bf.tie, e + COUT), bmean[nt], bscale[nt], bbeta[nt], bistd[nt], t1, t2);
-                                bnb_acc(v10, zp[rstride], bnb_mult(a.bf.tie, e + rstride), bmean[nt], bscale[nt], bbeta[nt], bistd[nt], t1, t2);
-                                bnb_acc(v11, zp[rstride + COUT], bnb_mult(a.bf.tie, e + rstride + COUT), bmean[nt], bscale[nt], bbeta[nt], bistd[nt], t1, t2);
-                                st1[nt] += (double)t1; st2[nt] += (double)t2;
-                            } else {
                             st1[nt] += (double)((v00 + v01) + (v10 + v11));
                             st2[nt] += (double)((v00 * v00 + v01 * v01) + (v10 * v10 + v11 * v11));
-                            }
                         }
                     }
                 }
@@ -695,28 +587,15 @@ __global__ __launch_bounds__(64 * (WAVES + PW), MINW) void conv3x3_wino(WinoArgs
                     if (y1) o[rstride] = v10;
                     if (y1 && x1) o[rstride + COUT] = v11;
                     if (RAW && a.stats) {
-                        if (bnb) {
-                            const size_t e = (size_t)(o - a.out);
-                            const float *zp = a.bf.z + e;
-                            float t1 = 0.f, t2 = 0.f;
-                            bnb_acc(v00, zp[0], bnb_mult(a.bf.tie, e), bmean[nt], bscale[nt], bbeta[nt], bistd[nt], t1, t2);
-                            if (x1) bnb_acc(v01, zp[COUT], bnb_mult(a.bf.tie, e + COUT), bmean[nt], bscale[nt], bbeta[nt], bistd[nt], t1, t2);
-                            if (y1) bnb_acc(v10, zp[rstride], bnb_mult(a.bf.tie, e + rstride), bmean[nt], bscale[nt], bbeta[nt], bistd[nt], t1, t2);
-                            if (y1 && x1) bnb_acc(v11, zp[rstride + COUT], bnb_mult(a.bf.tie, e + rstride + COUT), bmean[nt], bscale[nt], bbeta[nt], bistd[nt], t1, t2);
-                            st1[nt] += (double)t1; st2[nt] += (double)t2;
-                        } else {
                         const float w01 = x1 ? v01 : 0.f, w10 = y1 ? v10 : 0.f, w11 = (y1 && x1) ? v11 : 0.f;
                         st1[nt] += (double)((v00 + w01) + (w10 + w11));
                         st2[nt] += (double)((v00 * v00 + w01 * w01) + (w10 * w10 + w11 * w11));
-                        }
                     }
                 }
             }
         }
     }
-#if ASR_WINO_BUFDMA
     if constexpr (PW == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the copies above are invisible to the compiler's counters
-#endif
     __syncthreads();      // the next region's patch is in place (LDS-DMA drained / producers done), this buffer is free
     }
     if (RAW && a.stats)
@@ -745,7 +624,6 @@ struct WinoGArgs {
     int total;             // M-tiles in the launch = ceil(tiles / 16)
     WinoTileOrder ord;     // tile list order: strips of 1, 2, 4 or 8 tile rows, column-major inside (wino_tile_order.h)
     double *stats;         // RAW only, may be null: per-wave [sum | sum of squares] of the outputs, [row][2][C_out]
-    BnBwdFuse bf;          // RAW + stats, bf.z != null: the sums are those of a BatchNorm backward instead (asr_kernels.h)
 };
 
 template <int CIN, int COUT, bool POOL, int NT, int WAVES, int MINW, bool RAW>
@@ -823,17 +701,6 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void conv3x3_winog(WinoGArgs a) {
         bmean[nt] = ok ? a.bnp[ch] : 0.f;
         bscale[nt] = ok ? a.bnp[a.coutp + ch] : 1.f;
         bbeta[nt] = ok ? a.bnp[2 * a.coutp + ch] : 0.f;
-    }
-    float bistd[NT];                         // BatchNorm-backward sums (a.bf): mu, gamma*inv_std, beta, inv_std per channel
-    const bool bnb = ASR_BNB_FUSE_BUILD && RAW && a.stats && a.bf.z != nullptr;
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const int ch = ng * WROW + nt * 16 + n;
-        bistd[nt] = 0.f;
-        if (bnb && ch < COUT) {
-            bmean[nt] = a.bf.cst[ch]; bistd[nt] = a.bf.cst[COUT + ch];
-            bscale[nt] = a.bf.cst[2 * COUT + ch]; bbeta[nt] = a.bf.cst[3 * COUT + ch];
-        }
     }
 
     // Which M-tiles this wave owns.  Blocks b and b + 8 share an XCD (observed placement; correctness does not depend
@@ -1033,10 +900,10 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void conv3x3_winog(WinoGArgs a) {
                     load_first();
                 }
             };
-#if ASR_WINOG_NOCOPY
             // The column pass reads the patch where the loads put it (border M-tiles: the selected values) and the
             // next loads into the same registers go out behind it, 16 packed adds later than they could: copying
-            // the patch aside first, only to free `nxt` that much earlier, was 16 v_mov_b64 per block.
+            // the patch aside first, only to free `nxt` that much earlier, was 16 v_mov_b64 per block (measured and
+            // removed: docs/MEASUREMENT_LOG.md, Round 19).
             auto columns = [&](auto sel) {                 // B^T d
                 // (a real branch on the wave-uniform `interior`: merged into one body, every block of every M-tile
                 // pays the 32 selects of the border form)
@@ -1064,34 +931,6 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void conv3x3_winog(WinoGArgs a) {
                 flush();
             }
             load_next();
-#else
-            if (interior) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) dp[i][j] = nxt[i][j];
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        dp[i][j] = ((okm_cur >> (i * 4 + j)) & 1u) ? nxt[i][j] : float2w{0.f, 0.f};
-            }
-            if (t == 0 && have_pend) {
-                // dp holds block 0: its loads have landed, nothing else is outstanding - the previous M-tile's
-                // stores go out now and retire under this block's MFMAs
-                asm volatile("" ::"v"(dp[3][3]));
-                flush();
-            }
-            load_next();
-            if (!(ASR_WINOG_ABL & 8)) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {              // columns: B^T d
-                const float2w d0 = dp[0][j], d1 = dp[1][j], d2 = dp[2][j], d3 = dp[3][j];
-                dp[0][j] = psub(d0, d2); dp[1][j] = padd(d1, d2); dp[2][j] = psub(d2, d1); dp[3][j] = psub(d1, d3);
-            }
-            }
-#endif
             if (!(ASR_WINOG_ABL & 8)) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {              // rows: (B^T d) B
@@ -1208,24 +1047,10 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void conv3x3_winog(WinoGArgs a) {
                     pend[nt][r][PV - 1] = RAW ? y11[r] : elu_fastw((y11[r] - bmean[nt]) * bscale[nt] + bbeta[nt]);
                     if (RAW && a.stats) {
                         const int f = pend_flags[r];
-                        if (bnb) {
-                            if ((f & 1) && ng * WROW + nt * 16 + n < COUT) {
-                                const size_t e = (size_t)pend_off[r] + ng * WROW + nt * 16 + n;
-                                const float *zp = a.bf.z + e;
-                                const int rstride = a.W * COUT;
-                                float t1 = 0.f, t2 = 0.f;
-                                bnb_acc(y00[r], zp[0], bnb_mult(a.bf.tie, e), bmean[nt], bscale[nt], bbeta[nt], bistd[nt], t1, t2);
-                                if ((f & 3) == 3) bnb_acc(y01[r], zp[COUT], bnb_mult(a.bf.tie, e + COUT), bmean[nt], bscale[nt], bbeta[nt], bistd[nt], t1, t2);
-                                if ((f & 5) == 5) bnb_acc(y10[r], zp[rstride], bnb_mult(a.bf.tie, e + rstride), bmean[nt], bscale[nt], bbeta[nt], bistd[nt], t1, t2);
-                                if ((f & 7) == 7) bnb_acc(y11[r], zp[rstride + COUT], bnb_mult(a.bf.tie, e + rstride + COUT), bmean[nt], bscale[nt], bbeta[nt], bistd[nt], t1, t2);
-                                gst1[nt] += (double)t1; gst2[nt] += (double)t2;
-                            }
-                        } else {
                         const float w00 = (f & 1) ? y00[r] : 0.f, w01 = ((f & 3) == 3) ? y01[r] : 0.f;
                         const float w10 = ((f & 5) == 5) ? y10[r] : 0.f, w11 = ((f & 7) == 7) ? y11[r] : 0.f;
                         gst1[nt] += (double)((w00 + w01) + (w10 + w11));
                         gst2[nt] += (double)((w00 * w00 + w01 * w01) + (w10 * w10 + w11 * w11));
-                        }
                     }
                 }
             }
@@ -1655,8 +1480,7 @@ void conv_wino_launch_shape(const ConvPlan &p, int N, int num_cus, int *items, i
 // zeros if it had no work, so whatever the table held before (it shares its memory with other reductions) is gone from
 // rows [0, *stats_rows) when the kernel ends
 hipError_t launch_conv_wino(hipStream_t s, const ConvPlan &p, const float *in, const float *wpk, const float *bnp,
-                            float *out, int N, int num_cus, double *stats, int *stats_rows, const Fuse1Args *f1,
-                            const BnBwdFuse *bf) {
+                            float *out, int N, int num_cus, double *stats, int *stats_rows, const Fuse1Args *f1) {
     if (p.variant >= 3500) {
         const WinoGVariant &v = g_winog[p.variant - 3500];
         WinoGArgs a;
@@ -1675,7 +1499,6 @@ hipError_t launch_conv_wino(hipStream_t s, const ConvPlan &p, const float *in, c
         int ngroups = 0;
         const int grid = winog_grid(p, v, a.total, num_cus, &ngroups);
         a.stats = v.raw ? stats : nullptr;
-        a.bf = (bf && a.stats) ? *bf : BnBwdFuse{nullptr, nullptr, nullptr};
         if (a.stats && stats_rows) *stats_rows = grid * waves;
         hipLaunchKernelGGL(v.kernel, dim3(grid, ngroups), dim3(p.threads), p.lds_bytes, s, a);
         return hipGetLastError();
@@ -1700,7 +1523,6 @@ hipError_t launch_conv_wino(hipStream_t s, const ConvPlan &p, const float *in, c
     int ngroups = 0;
     const int grid_x = wino_grid(p, v.ntw, a.total, num_cus, &ngroups, &a.per);
     a.stats = v.raw ? stats : nullptr;
-    a.bf = (bf && a.stats) ? *bf : BnBwdFuse{nullptr, nullptr, nullptr};
     if (a.stats) {
         const int rows = grid_x * (p.threads / 64);
         // (no memset: every consumer wave of every workgroup stores its row at the end of the kernel, and grid_x holds

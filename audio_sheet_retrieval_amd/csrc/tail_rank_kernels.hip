@@ -319,15 +319,9 @@ typedef float floatx4_r __attribute__((ext_vector_type(4)));
 // once per workgroup.  Accuracy, tools/mfma_bf16x3_probe.hip on the MI355X (16.7 M pairs of unit vectors: one sign - sum
 // |x_i y_i| = 1 -, alternating signs, near neighbours, one-hot, random): max |dot - float64| 2.1e-7, the fp32 MFMA's
 // on the same pairs 3.2e-7 - the 3e-6 that the filters' proofs assume holds with the same margin.  NaN rows stay NaN
-// (a quiet NaN keeps its top mantissa bit in bf16).  ASR_TF_BF3=0 at compile time: the fp32 MFMAs.
-#ifndef ASR_TF_BF3
-#define ASR_TF_BF3 1
-#endif
-// ASR_TF_BF2: two planes instead of three where a wider error bound is affordable (see TF_EPS_BF2 at the top-k filter):
-// 1 = the top-k filter, 2 = also the counting ranking (fused and stand-alone, band RF_BAND_BF2), 0 = three planes
-#ifndef ASR_TF_BF2
-#define ASR_TF_BF2 2
-#endif
+// (a quiet NaN keeps its top mantissa bit in bf16).
+// Two planes instead of three where a wider error bound is affordable (see TF_EPS_BF2 at the top-k filter): the top-k
+// filter and the counting ranking (fused and stand-alone, band RF_BAND_BF2).
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef float floatx2_t __attribute__((ext_vector_type(2)));
@@ -383,17 +377,15 @@ __global__ __launch_bounds__(256) void rank_count_kernel(
         for (int j = 0; j < 8; ++j) bq[u][j] = lv1[qi[u] * 32 + 8 * g + j];
         nq[u] = norm1[qi[u]]; ds[u] = dstar[qi[u]]; js[u] = jstar[qi[u]];
         rq[u] = (float)(1.0 / nq[u]);
-        constexpr float band = (ASR_TF_BF3 && ASR_TF_BF2 > 1) ? RF_BAND_BF2 : RF_BAND;
+        constexpr float band = RF_BAND_BF2;
         lo_t[u] = (float)ds[u] - band; hi_t[u] = (float)ds[u] + band;
         less[u] = 0; eq[u] = 0; eqb[u] = 0;
     }
-    // the products on the bf16 MFMA as an exact three-plane split (split_bf3 above; raw rows: the error is relative to
-    // |q| |x| like the fp32 MFMA's and is scaled by the same reciprocal norms)
-    Bf3 qb[ASR_TF_BF3 ? QG : 1];
-    if (ASR_TF_BF3) {
+    // the products on the bf16 MFMA from the two upper planes of the split (split_bf3 above, band RF_BAND_BF2; raw
+    // rows: the error is relative to |q| |x| like the fp32 MFMA's and is scaled by the same reciprocal norms)
+    Bf3 qb[QG];
 #pragma unroll
-        for (int u = 0; u < QG; ++u) qb[u] = split_bf3(bq[u]);
-    }
+    for (int u = 0; u < QG; ++u) qb[u] = split_bf3(bq[u]);
     for (int64_t tb = t_lo + wave; tb < t_hi; tb += 8) {          // two tiles per wave and iteration
         float4 a0[2], a1[2];
         float rn[2][4];
@@ -420,26 +412,13 @@ __global__ __launch_bounds__(256) void rank_count_kernel(
             const int64_t tile = tb + 4 * r;
             if (tile >= t_hi) continue;
             const float af[8] = {a0[r].x, a0[r].y, a0[r].z, a0[r].w, a1[r].x, a1[r].y, a1[r].z, a1[r].w};
-            Bf3 ab;
-            if (ASR_TF_BF3) ab = split_bf3(af);
+            const Bf3 ab = split_bf3(af);
 #pragma unroll
             for (int u = 0; u < QG; ++u) {
                 floatx4_r acc = {0.f, 0.f, 0.f, 0.f};
-                if (ASR_TF_BF3 && ASR_TF_BF2 > 1) {
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab.p2, qb[u].p1, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab.p1, qb[u].p2, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab.p1, qb[u].p1, acc, 0, 0, 0);
-                } else if (ASR_TF_BF3) {
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab.p3, qb[u].p1, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab.p1, qb[u].p3, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab.p2, qb[u].p2, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab.p2, qb[u].p1, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab.p1, qb[u].p2, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab.p1, qb[u].p1, acc, 0, 0, 0);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j], bq[u][j], acc, 0, 0, 0);
-                }
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab.p2, qb[u].p1, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab.p1, qb[u].p2, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab.p1, qb[u].p1, acc, 0, 0, 0);
                 // per distance: one multiply, one fused multiply-add, two compares; the items past the end of the pool
                 // (last tile only) are cut off by `lim`, computed once per tile, and the exact path is entered only when
                 // some lane of the wave is inside the band (the 64-bit index tests and three-way branches per distance
@@ -813,16 +792,13 @@ __global__ __launch_bounds__(256) void rnorm_f32_kernel(const double *__restrict
 typedef float floatx4_t __attribute__((ext_vector_type(4)));
 
 // Which 8 of a row's 32 dimensions lane (item nn, k group g) of an A / B fragment holds.  The contraction index may be
-// permuted freely as long as both operands use the same map.  ASR_TF_HALFROW=1 (round 6): dims 4g..4g+3 and 16+4g..16+4g+3 -
+// permuted freely as long as both operands use the same map.  Since round 6: dims 4g..4g+3 and 16+4g..16+4g+3 -
 // the first float4 load of a wave then covers the FIRST 64 bytes of each of its 16 rows and the second load the other
-// 64, i.e. 16 whole 64-byte requests per instruction; with dims 8g..8g+7 (=0, rounds 3-5) each instruction took the
+// 64, i.e. 16 whole 64-byte requests per instruction; with dims 8g..8g+7 (rounds 3-5, removed) each instruction took the
 // even / odd 16-byte pieces of all 32 half-lines - twice the requests for the same bytes.
-#ifndef ASR_TF_HALFROW
-#define ASR_TF_HALFROW 1
-#endif
-__device__ __forceinline__ int tf_dim(int g, int j) { return ASR_TF_HALFROW ? (j < 4 ? 4 * g + j : 12 + 4 * g + j) : 8 * g + j; }
-constexpr int TF_A0 = ASR_TF_HALFROW ? 4 : 8;      // float offset of a lane's first float4 = TF_A0 * g
-constexpr int TF_A1 = ASR_TF_HALFROW ? 4 : 1;      // its second float4, in float4 units from the first
+__device__ __forceinline__ int tf_dim(int g, int j) { return j < 4 ? 4 * g + j : 12 + 4 * g + j; }
+constexpr int TF_A0 = 4;      // float offset of a lane's first float4 = TF_A0 * g
+constexpr int TF_A1 = 4;      // its second float4, in float4 units from the first
 
 #if defined(ASR_TF_ABL) && (ASR_TF_ABL & 4)          // trace build (tools/ab_topk_abl.sh 4): per-workgroup time stamps
 __device__ unsigned long long g_tf_trace[8192 * 8];
@@ -917,12 +893,11 @@ __global__ __launch_bounds__(TF_THREADS, 2) void topk_filter_kernel(
         for (int j = 0; j < 8; ++j) bq[u][j] = NORM ? qs[qi * 32 + tf_dim(g, j)] * rq[u] : qs[qi * 32 + tf_dim(g, j)];
         less[u] = 0;
     }
-    constexpr bool BF3 = NORM && ASR_TF_BF3;
-    constexpr bool BF2 = BF3 && ASR_TF_BF2 && (!RANK || ASR_TF_BF2 > 1);     // (ASR_TF_BF2=2: the fused ranking too, band 5.5e-5)
+    constexpr bool BF2 = NORM;        // unit rows: two bf16 planes (the fused ranking too, band 5.5e-5); raw rows: fp32 MFMAs
     constexpr float RFB = BF2 ? RF_BAND_BF2 : RF_BAND;        // the fused ranking's band: >= the error bound of d~
     constexpr float EPSF = BF2 ? TF_EPS_BF2 : TF_EPS;
-    Bf3 qb[BF3 ? QG : 1];
-    if constexpr (BF3) {
+    Bf3 qb[BF2 ? QG : 1];
+    if constexpr (BF2) {
 #pragma unroll
         for (int u = 0; u < QG; ++u) qb[u] = split_bf3(bq[u]);
     }
@@ -1019,16 +994,13 @@ __global__ __launch_bounds__(TF_THREADS, 2) void topk_filter_kernel(
     // wait for every older load (vmcnt counts in order), i.e. for the prefetched next group as well.
     // tiles per wave and group.  (Round 4: two for four query groups - "they hold a tile's registers four times as long".
     // Round 5, with half the MFMAs per tile: 2 / 3 / 4 tiles - 64 x 2 M 0.115 / 0.111 / 0.113 ms, 512 x 2 M 0.529 / 0.510 /
-    // 0.501, 4096 x 2 M fused 4.04 / - / 3.90, 1024 x 250 k 0.221 / 0.219 / 0.221; -DASR_TF_TPW4=2 builds the old form)
+    // 0.501, 4096 x 2 M fused 4.04 / - / 3.90, 1024 x 250 k 0.221 / 0.219 / 0.221)
     // Round 6, after the straight-line tile loop: 4 / 6 / 8 tiles - 64 x 2 M 0.1077-0.1100 / 0.1060-0.1070 / 0.125 ms,
     // 512 x 2 M 0.485 / 0.471 / 0.512, 1024 x 250 k 0.215 / 0.212 / 0.234 (eight: the register budget of two workgroups
     // per CU is gone) - six.
-#ifndef ASR_TF_TPW4
-#define ASR_TF_TPW4 6
-#endif
     // (the fused-ranking build keeps four: its triggered path exists once per unrolled tile, and with six copies the
     // 4096 x 2 M fused call went from 3.61 to 6.45 ms - instruction cache)
-    constexpr int TPW = QG == 4 ? (RANK ? 4 : ASR_TF_TPW4) : 4, GT = 4 * TPW;
+    constexpr int TPW = QG == 4 ? (RANK ? 4 : 6) : 4, GT = 4 * TPW;
     auto load_group = [&](int64_t tg, float4 (&a0)[TPW], float4 (&a1)[TPW], float4 (&rn)[TPW]) {
 #pragma unroll
         for (int r = 0; r < TPW; ++r) {
@@ -1054,7 +1026,7 @@ __global__ __launch_bounds__(TF_THREADS, 2) void topk_filter_kernel(
                           const float (&ch_r)[RANK ? QG : 1]) {
         const int64_t it0 = tile * 16 + 4 * g;                   // C: lane (g, nn) holds items it0 + rr against query 16u + nn
         Bf3 ab;
-        if constexpr (BF3) ab = split_bf3(af);                  // once per tile, shared by the query groups
+        if constexpr (BF2) ab = split_bf3(af);                  // once per tile, shared by the query groups
         // the accumulators of all query groups first: QG independent chains of MFMAs issue back to back (inside one
         // chain every MFMA waits for the previous one's result), then the epilogues
         floatx4_t accs[QG];
@@ -1067,19 +1039,6 @@ __global__ __launch_bounds__(TF_THREADS, 2) void topk_filter_kernel(
         }
 #else
         if constexpr (BF2) {
-#pragma unroll
-            for (int u = 0; u < QG; ++u) accs[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab.p2, qb[u].p1, accs[u], 0, 0, 0);
-#pragma unroll
-            for (int u = 0; u < QG; ++u) accs[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab.p1, qb[u].p2, accs[u], 0, 0, 0);
-#pragma unroll
-            for (int u = 0; u < QG; ++u) accs[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab.p1, qb[u].p1, accs[u], 0, 0, 0);
-        } else if constexpr (BF3) {
-#pragma unroll
-            for (int u = 0; u < QG; ++u) accs[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab.p3, qb[u].p1, accs[u], 0, 0, 0);
-#pragma unroll
-            for (int u = 0; u < QG; ++u) accs[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab.p1, qb[u].p3, accs[u], 0, 0, 0);
-#pragma unroll
-            for (int u = 0; u < QG; ++u) accs[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab.p2, qb[u].p2, accs[u], 0, 0, 0);
 #pragma unroll
             for (int u = 0; u < QG; ++u) accs[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab.p2, qb[u].p1, accs[u], 0, 0, 0);
 #pragma unroll
@@ -1172,12 +1131,8 @@ __global__ __launch_bounds__(TF_THREADS, 2) void topk_filter_kernel(
         // prefetched next group as soon as the first tile of this one is scored.  Unrolled, tile r waits for its own two
         // loads only.  Rolled / unrolled: 64 x 2 M 0.111 / 0.107 ms, 1024 x 250 k 0.221 / 0.214, 512 x 2 M 0.501 / 0.473,
         // 1024 x 65 k 0.119 / 0.114, fused 4096 x 2 M 3.90 / 3.66 (the fused build's triggered path exists four times now:
-        // still inside the instruction cache).  -DASR_TF_UNROLL=0: the rolled loop everywhere, =1: only without the ranking.
-#ifndef ASR_TF_UNROLL
-#define ASR_TF_UNROLL 2
-#endif
-#if ASR_TF_UNROLL
-        if constexpr ((!RANK || ASR_TF_UNROLL > 1) && NORM) {
+        // still inside the instruction cache).  The raw-row builds keep the rolled loop.
+        if constexpr (NORM) {
 #pragma unroll
             for (int r = 0; r < TPW; ++r) {
                 const int64_t tile = tg + r * 4 + wave;
@@ -1189,7 +1144,6 @@ __global__ __launch_bounds__(TF_THREADS, 2) void topk_filter_kernel(
             }
             return;
         }
-#endif
 #pragma unroll 1
         for (int r = 0; r < TPW; ++r) {
             const int64_t tile = tg + r * 4 + wave;

@@ -27,14 +27,9 @@
 #define ASR_LWLAY_HD inline constexpr
 #endif
 
-// -DASR_WINO_DENSEW=0 builds the row-major form everywhere (the A/B leg of the measurement log)
-#ifndef ASR_WINO_DENSEW
-#define ASR_WINO_DENSEW 1
-#endif
-
 namespace asr {
 
-ASR_LWLAY_HD bool wino_lw_dense(int ntw, int pw) { return ASR_WINO_DENSEW && pw == 0 && (ntw == 1 || ntw == 2); }
+ASR_LWLAY_HD bool wino_lw_dense(int ntw, int pw) { return pw == 0 && (ntw == 1 || ntw == 2); }
 
 // row stride of the row-major form
 ASR_LWLAY_HD int wino_lw_row_stride(int ntw) { return ntw == 2 ? 48 : 16 * ntw; }

@@ -25,14 +25,9 @@
 #define ASR_WLAY_HD inline constexpr
 #endif
 
-// -DASR_WINOG_DENSEW=0 builds the row-major form everywhere (the A/B leg of the measurement log)
-#ifndef ASR_WINOG_DENSEW
-#define ASR_WINOG_DENSEW 1
-#endif
-
 namespace asr {
 
-ASR_WLAY_HD bool wino_w_dense(int cin, int nt) { return ASR_WINOG_DENSEW && nt == 2 && cin % 8 == 0; }
+ASR_WLAY_HD bool wino_w_dense(int cin, int nt) { return nt == 2 && cin % 8 == 0; }
 
 // row stride of the row-major form
 ASR_WLAY_HD int wino_w_row_stride(int nt) { return nt == 2 ? 48 : 16 * nt; }

@@ -409,8 +409,8 @@ def test_training_schedule_switches_compute_the_same_step(tmp_path):
                      # round 6: the tower gates (the sheet tower's block b waits for the spectrogram tower's; measured
                      # no faster, off by default) only add stream waits
                      ("tower_gates", dict(ASR_TRAIN_GATE_FWD="1", ASR_TRAIN_GATE_BWD="0"))):
-        # (the BatchNorm-backward sums from the data gradient's epilogue - round 5, 1.8 ms slower - are compiled out of the
-        # default build since round 6: asr_kernels.h, ASR_BNB_FUSE_BUILD; its two variants of this list went with it)
+        # (the BatchNorm-backward sums from the data gradient's epilogue - round 5, 1.8 ms slower - were compiled out in
+        # round 6 and have since been removed from the sources; its two variants of this list went with it)
         got = run(tag, **env)
         assert abs(got["losses"][0] - ref["losses"][0]) <= 2e-6, (tag, got["losses"], ref["losses"])
         assert np.abs(got["losses"] - ref["losses"]).max() <= 2e-4, (tag, got["losses"], ref["losses"])   # Adam spreads the noise

@@ -66,7 +66,7 @@ def test_the_jacobi_routine_is_compiled_with_the_registers_it_needs(tmp_path):
 def test_the_raw_winograd_builds_of_the_training_step_do_not_spill_into_their_loops(tmp_path):
     """The switched-off BatchNorm-backward epilogue of round 5 kept four per-channel constants live across the M-tile
     loops of every RAW (training) Winograd build: 68-136 bytes of scratch per lane, 0.2 ms of the batch-512 update.  It
-    is compiled out by default (ASR_BNB_FUSE_BUILD); the RAW builds of conv3x3_wino and conv3x3_wino4s use no scratch at
+    was compiled out in round 6 and has since been removed; the RAW builds of conv3x3_wino and conv3x3_wino4s use no scratch at
     all, the two-waves-per-SIMD RAW builds of conv3x3_winog at most three reloads per M-tile, and the dominant inference
     kernels none that is waited for at once."""
     w = _functions(_listing(tmp_path, "conv_wino_kernels"))
