@@ -44,6 +44,7 @@ EXPORTS = [
     "asr_notes_from_map_dev", "asr_bars_from_map_dev",
     "asr_unroll_systems_dev", "asr_spectrogram_batch_dev", "asr_spectrogram_fft_batch_dev", "asr_resample_batch_dev", "asr_resize_pages_dev",
     "asr_audio_stream_push_dev", "asr_skew_estimate_dev", "asr_deskew_pages_dev",
+    "asr_track_stream_gate_dev", "asr_track_stream_vote_dev",
     "asr_opt_state_size", "asr_get_opt_state", "asr_set_opt_state", "asr_debug_train_tensor", "asr_cca_train_debug",
     "asr_debug_train_candidate",
 ]
@@ -205,6 +206,10 @@ def load_library(path=None):
         "asr_track_gate_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int] + [c_void_p] * 5 + [c_int] + [c_void_p] * 3),
         "asr_track_vote_batch_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                              c_void_p, c_int64, c_int32, c_int, c_void_p, c_void_p, c_void_p]),
+        "asr_track_stream_gate_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int] + [c_void_p] * 4 + [c_int, c_int, c_void_p,
+                                              c_int64, c_void_p, c_void_p, c_int64] + [c_void_p] * 3),
+        "asr_track_stream_vote_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int,
+                                              c_void_p, c_int64, c_int32, c_int, c_void_p, c_int64] + [c_void_p] * 4),
         "asr_gather_windows_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p]),
         "asr_dtw_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                 POINTER(c_int32), POINTER(c_double)]),
@@ -525,6 +530,50 @@ class Engine(object):
         self._check(self.lib.asr_track_vote_batch_dev(self.ctx, idx_ptr, n_rows, n, ptr(first), ptr(count), ptr(emit),
                                                       n_candidates, running_frames, ids_ptr, n_db, n_pieces, top_k,
                                                       ptr(pieces), ptr(counts), ptr(n_out)))
+        return pieces, counts, n_out
+
+    def track_stream_gate_dev(self, cols_ptr, cols_floats, col_off, n_new, frames_before, level, bins, width, tail_ptr,
+                              tail_floats, tail_off, win_ptr, win_cap):
+        """the music gate and the windows of the voiced frames for parallel streams whose last width - 1 columns stay on
+        the device (asr_track_stream_gate_dev): stream s brings n_new[s] columns as a (bins, n_new[s]) block at float
+        col_off[s] of the buffer at cols_ptr and has frames_before[s] frames behind it; its tail at float tail_off[s] of
+        the buffer at tail_ptr is updated in place.  -> (m_prob float32, voiced bool, n_voiced int32 per stream); the
+        per-frame arrays hold the streams one after the other, and the windows of the voiced frames stand in that order
+        at win_ptr (room for win_cap windows)."""
+        new = np.ascontiguousarray(n_new, dtype=np.int32)
+        n = new.size
+        off = np.ascontiguousarray(col_off, dtype=np.int64)
+        before = np.ascontiguousarray(frames_before, dtype=np.int64)
+        lvl = np.ascontiguousarray(level, dtype=np.float32)
+        t_off = np.ascontiguousarray(tail_off, dtype=np.int64)
+        if new.ndim != 1 or not (off.shape == before.shape == lvl.shape == t_off.shape == (n,)):
+            raise ValueError("track_stream_gate_dev: the per-stream tables differ in length")
+        total = int(np.maximum(new, 0).sum())
+        m_prob, voiced, n_voiced = np.empty(total, np.float32), np.empty(total, np.uint8), np.zeros(n, np.int32)
+        self._check(self.lib.asr_track_stream_gate_dev(
+            self.ctx, cols_ptr, int(cols_floats), n, off.ctypes.data, new.ctypes.data, before.ctypes.data, lvl.ctypes.data,
+            int(bins), int(width), tail_ptr, int(tail_floats), t_off.ctypes.data, win_ptr, int(win_cap),
+            m_prob.ctypes.data, voiced.ctypes.data, n_voiced.ctypes.data))
+        return m_prob, voiced.astype(bool), n_voiced
+
+    def track_stream_vote_dev(self, idx_ptr, n_rows, row_count, voiced_before, n_candidates, running_frames, ids_ptr, n_db,
+                              n_pieces, top_k, hist_ptr, hist_len, hist_off):
+        """the sliding vote for parallel streams whose history stays on the device (asr_track_stream_vote_dev): stream s
+        owns row_count[s] consecutive rows of the (n_rows, n_candidates) index table at idx_ptr and has voiced_before[s]
+        voiced frames behind it; its ring of running_frames - 1 rows at entry hist_off[s] of the buffer at hist_ptr is
+        updated in place.  -> (pieces (n_rows, top_k) int32, counts (n_rows, top_k) int32, n_out (n_rows,) int32)."""
+        count = np.ascontiguousarray(row_count, dtype=np.int32)
+        n = count.size
+        before = np.ascontiguousarray(voiced_before, dtype=np.int64)
+        h_off = None if hist_off is None else np.ascontiguousarray(hist_off, dtype=np.int64)
+        if count.ndim != 1 or before.shape != (n,) or (h_off is not None and h_off.shape != (n,)):
+            raise ValueError("track_stream_vote_dev: the per-stream tables differ in length")
+        e, k = max(int(n_rows), 0), max(int(top_k), 0)
+        pieces, counts, n_out = np.empty((e, k), np.int32), np.empty((e, k), np.int32), np.empty(e, np.int32)
+        self._check(self.lib.asr_track_stream_vote_dev(
+            self.ctx, idx_ptr, int(n_rows), n, count.ctypes.data, before.ctypes.data, int(n_candidates),
+            int(running_frames), ids_ptr, int(n_db), int(n_pieces), int(top_k), hist_ptr, int(hist_len),
+            None if h_off is None else h_off.ctypes.data, pieces.ctypes.data, counts.ctypes.data, n_out.ctypes.data))
         return pieces, counts, n_out
 
     def dtw(self, a, b, want_dists=True):

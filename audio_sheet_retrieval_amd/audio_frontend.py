@@ -656,13 +656,21 @@ class AudioStream(object):
         """the recordings of `streams` (default: all that are open) end here -> list (one entry per stream of the object;
         an empty array for the others) of their remaining columns, the last frames zero padded as process() pads them.
         A flushed stream takes no more samples until reset()."""
+        return self._download(self._flush(streams, "_d_out"))
+
+    def flush_dev(self, streams=None):
+        """flush() that leaves the columns on the device -> piece_identification.DeviceArrays (free its buffer)"""
+        from .piece_identification import DeviceArrays
+        return DeviceArrays(*self._flush(streams))
+
+    def _flush(self, streams, out_buf=None):
         if streams is None:
             which = [s for s in range(self.n_streams) if not self.flushed[s]]
         else:
             which = self._which(streams)
         final = [s in which for s in range(self.n_streams)]
         empty = np.zeros(0, np.float32)
-        return self._download(self._push([empty] * self.n_streams, final, "_d_out"))
+        return self._push([empty] * self.n_streams, final, out_buf)
 
     def reset(self, streams=None):
         """`streams` (default: all) start over: the next push is the first of a new recording"""

@@ -26,7 +26,8 @@ FLAGS = BASE_FLAGS + ["-I", INCLUDE] + EXTRA_FLAGS
 # tracking loop's music gate compares bits, and so does the resampler's float64 polyphase sum, so no fused
 # multiply-adds there
 FILE_FLAGS = {"omr_post_kernels.hip": ["-ffp-contract=off"], "omr_detect_kernels.hip": ["-ffp-contract=off"],
-              "track_kernels.hip": ["-ffp-contract=off"], "resample_kernels.hip": ["-ffp-contract=off"]}
+              "track_kernels.hip": ["-ffp-contract=off"], "track_stream_kernels.hip": ["-ffp-contract=off"],
+              "resample_kernels.hip": ["-ffp-contract=off"]}
 
 
 def sources():

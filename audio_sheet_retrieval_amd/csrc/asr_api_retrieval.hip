@@ -1234,6 +1234,187 @@ int asr_track_vote_batch_dev(asr_ctx *ctx, const int32_t *idx_dev, int64_t n_row
     return mark_main(ctx);
 }
 
+// ---- the running vote for parallel streams, state on the device (track_stream_kernels.hip) --------------------------
+// true when the slices [off[s], off[s] + len) do not all lie inside [0, total) or two of them overlap
+static bool track_slices_bad(const int64_t *off, int n, int64_t len, int64_t total) {
+    std::vector<int64_t> sorted(off, off + n);
+    std::sort(sorted.begin(), sorted.end());
+    for (int s = 0; s < n; ++s) {
+        if (sorted[s] < 0 || sorted[s] > total || len > total - sorted[s]) return true;
+        if (s > 0 && sorted[s] - sorted[s - 1] < len) return true;
+    }
+    return false;
+}
+
+int asr_track_stream_gate_dev(asr_ctx *ctx, const float *cols_dev, int64_t cols_floats, int n_streams,
+                              const int64_t *col_off, const int32_t *n_new, const int64_t *frames_before,
+                              const float *level, int bins, int width, float *tail_dev, int64_t tail_floats,
+                              const int64_t *tail_off, float *win_dev, int64_t win_cap, float *m_prob, uint8_t *voiced,
+                              int32_t *n_voiced) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_streams < 1 || bins < 1 || width < 8 || width > 128 || cols_floats < 0 || tail_floats < 0 || win_cap < 0)
+        return fail(ctx, ASR_ERR_INVALID, "asr_track_stream_gate_dev: bad sizes n_streams=%d bins=%d width=%d (8..128)",
+                    n_streams, bins, width);
+    if (!col_off || !n_new || !frames_before || !level || !tail_dev || !tail_off || !n_voiced)
+        return fail(ctx, ASR_ERR_INVALID, "asr_track_stream_gate_dev: NULL argument");
+    std::vector<asr::TrackStreamRec> recs(n_streams);
+    int64_t total = 0, total_ext = 0;
+    for (int s = 0; s < n_streams; ++s) {
+        if (n_new[s] < 0 || frames_before[s] < 0 || col_off[s] < 0 || col_off[s] > cols_floats ||
+            (int64_t)bins * n_new[s] > cols_floats - col_off[s])
+            return fail(ctx, ASR_ERR_INVALID,
+                        "asr_track_stream_gate_dev: stream %d (%d x %d at %lld, %lld frames before) lies outside the "
+                        "%lld-float buffer", s, bins, n_new[s], (long long)col_off[s], (long long)frames_before[s],
+                        (long long)cols_floats);
+        asr::TrackStreamRec &R = recs[s];
+        R.col_off = col_off[s]; R.tail_off = tail_off[s]; R.frames_before = frames_before[s];
+        R.first = total; R.ext_first = total_ext; R.n_new = n_new[s]; R.level = level[s];
+        total += n_new[s];
+        if (n_new[s] > 0) total_ext += (int64_t)(width - 1) + n_new[s];
+        if (total > INT32_MAX / 2) return fail(ctx, ASR_ERR_INVALID, "asr_track_stream_gate_dev: more than 2^30 - 1 frames");
+    }
+    if (track_slices_bad(tail_off, n_streams, (int64_t)bins * (width - 1), tail_floats))
+        return fail(ctx, ASR_ERR_INVALID,
+                    "asr_track_stream_gate_dev: a tail (%d x %d) lies outside the %lld-float buffer or two tails overlap",
+                    bins, width - 1, (long long)tail_floats);
+    if (total > win_cap)
+        return fail(ctx, ASR_ERR_INVALID, "asr_track_stream_gate_dev: %lld new frames for %lld windows", (long long)total,
+                    (long long)win_cap);
+    if (total > 0 && (!cols_dev || !win_dev || !m_prob || !voiced))
+        return fail(ctx, ASR_ERR_INVALID, "asr_track_stream_gate_dev: NULL argument");
+    if (total == 0) {
+        memset(n_voiced, 0, (size_t)n_streams * sizeof(int32_t));
+        return ASR_OK;
+    }
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    int rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    // results (one download): m_prob | n_voiced | voiced; then the stream table, the column sums and the window slots
+    const size_t T = (size_t)total, o_nv = T * 4, o_voiced = o_nv + (size_t)n_streams * 4, res_bytes = o_voiced + T;
+    const size_t o_recs = dtw_align(res_bytes), o_colsum = dtw_align(o_recs + recs.size() * sizeof(asr::TrackStreamRec));
+    const size_t o_slot = dtw_align(o_colsum + (size_t)total_ext * 4);
+    rc = track_ws(ctx, o_slot + (T + 1) * 4);
+    if (rc != ASR_OK) return rc;
+    char *ws = (char *)ctx->vote_ws;
+    ASR_HIP(ctx, hipMemcpyAsync(ws + o_recs, recs.data(), recs.size() * sizeof(asr::TrackStreamRec), hipMemcpyHostToDevice,
+                                ctx->stream));
+    asr::TrackStreamGateArgs a;
+    a.cols = cols_dev; a.tail = tail_dev; a.recs = (const asr::TrackStreamRec *)(ws + o_recs); a.n_streams = n_streams;
+    a.total_frames = total; a.total_ext = total_ext; a.bins = bins; a.width = width;
+    a.colsum = (float *)(ws + o_colsum); a.slot = (int32_t *)(ws + o_slot); a.win = win_dev;
+    a.m_prob = (float *)ws; a.voiced = (uint8_t *)(ws + o_voiced); a.n_voiced = (int32_t *)(ws + o_nv);
+    {
+        ProfScope ps(ctx, "track_stream_gate", 0, 0.0, 4.0 * (double)total_ext * bins);
+        ASR_HIP(ctx, asr::launch_track_stream_gate(ctx->stream, a));
+    }
+    {   // bytes: every new frame voiced
+        ProfScope ps(ctx, "track_stream_windows", 0, 0.0, 4.0 * (double)total * bins * width);
+        ASR_HIP(ctx, asr::launch_track_stream_windows(ctx->stream, a));
+    }
+    std::vector<char> host(res_bytes);
+    ASR_HIP(ctx, hipMemcpyAsync(host.data(), ws, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    ASR_HIP(ctx, hipStreamSynchronize(ctx->stream));    // (also: `recs` was read by the upload)
+    memcpy(m_prob, host.data(), T * 4);
+    memcpy(n_voiced, host.data() + o_nv, (size_t)n_streams * 4);
+    memcpy(voiced, host.data() + o_voiced, T);
+    return mark_main(ctx);
+}
+
+int asr_track_stream_vote_dev(asr_ctx *ctx, const int32_t *idx_dev, int64_t n_rows, int n_streams,
+                              const int32_t *row_count, const int64_t *voiced_before, int n_candidates,
+                              int running_frames, const int32_t *ids_dev, int64_t n_db, int32_t n_pieces, int top_k,
+                              int32_t *hist_dev, int64_t hist_len, const int64_t *hist_off, int32_t *pieces,
+                              int32_t *counts, int32_t *n_out) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_streams < 1 || n_rows < 0 || n_rows > INT32_MAX || top_k < 1 || top_k > 64 || n_candidates < 1 ||
+        running_frames < 1 || n_db < n_candidates || n_db > INT32_MAX || n_pieces < 1 || n_pieces > (1 << 30) ||
+        n_rows > (INT64_MAX / 4) / n_candidates || hist_len < 0 ||
+        (int64_t)(running_frames - 1) > (INT64_MAX / 4) / n_candidates)
+        return fail(ctx, ASR_ERR_INVALID,
+                    "asr_track_stream_vote_dev: bad sizes n_rows=%lld n_streams=%d n_candidates=%d running_frames=%d "
+                    "n_db=%lld n_pieces=%d top_k=%d (1..64)", (long long)n_rows, n_streams, n_candidates, running_frames,
+                    (long long)n_db, n_pieces, top_k);
+    const int64_t keep = running_frames - 1, slice = keep * n_candidates;
+    if (!row_count || !voiced_before || (keep > 0 && (!hist_dev || !hist_off)))
+        return fail(ctx, ASR_ERR_INVALID, "asr_track_stream_vote_dev: NULL argument");
+    const int64_t seg_frames = std::max<int64_t>(1, dtw_env("ASR_TRACK_SEG_FRAMES", 64));
+    std::vector<asr::TrackStreamSeg> segs;
+    std::vector<asr::TrackStreamKeep> keeps;
+    int64_t row0 = 0;
+    for (int s = 0; s < n_streams; ++s) {
+        if (row_count[s] < 0 || voiced_before[s] < 0 || row_count[s] > n_rows - row0 ||
+            voiced_before[s] > INT64_MAX / 2)
+            return fail(ctx, ASR_ERR_INVALID, "asr_track_stream_vote_dev: stream %d: %d rows from row %lld of %lld, %lld before",
+                        s, row_count[s], (long long)row0, (long long)n_rows, (long long)voiced_before[s]);
+        const int64_t off = keep > 0 ? hist_off[s] : 0;
+        for (int64_t f = 0; f < row_count[s]; f += seg_frames) {
+            asr::TrackStreamSeg S;
+            S.row0 = row0; S.v0 = voiced_before[s] + f; S.vb = voiced_before[s]; S.hist_off = off;
+            S.n = (int32_t)std::min<int64_t>(seg_frames, row_count[s] - f); S.pad = 0;
+            segs.push_back(S);
+        }
+        if (keep > 0 && row_count[s] > 0) {
+            asr::TrackStreamKeep K;
+            K.row0 = row0; K.vb = voiced_before[s]; K.hist_off = off; K.n_new = row_count[s]; K.pad = 0;
+            keeps.push_back(K);
+        }
+        row0 += row_count[s];
+    }
+    if (row0 != n_rows)
+        return fail(ctx, ASR_ERR_INVALID, "asr_track_stream_vote_dev: the row counts add up to %lld, not n_rows=%lld",
+                    (long long)row0, (long long)n_rows);
+    if (keep > 0 && track_slices_bad(hist_off, n_streams, slice, hist_len))
+        return fail(ctx, ASR_ERR_INVALID,
+                    "asr_track_stream_vote_dev: a history (%lld x %d) lies outside the %lld entries or two overlap",
+                    (long long)keep, n_candidates, (long long)hist_len);
+    if (n_rows == 0) return ASR_OK;
+    if (!idx_dev || !ids_dev || !pieces || !counts || !n_out)
+        return fail(ctx, ASR_ERR_INVALID, "asr_track_stream_vote_dev: NULL argument");
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    int rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+
+    // the debug switches and the workspace bound of asr_track_vote_batch_dev
+    const int64_t lds_pieces = std::min<int64_t>(asr::TRACK_LDS_PIECES, dtw_env("ASR_TRACK_LDS_PIECES", 1 << 30));
+    const bool global_path = n_pieces > lds_pieces;
+    const size_t budget = (size_t)std::max<int64_t>(dtw_env("ASR_VOTE_BUDGET_MB", 1024), 1) << 20;
+    int64_t grid = std::min<int64_t>((int64_t)segs.size(), 65536);
+    if (global_path) grid = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(grid, 4096), budget / ((size_t)n_pieces * 4)));
+
+    // results block (one download): pieces | counts (n_rows x top_k) | n_out; then the two tables and the counters
+    const size_t E = (size_t)n_rows, EK = E * (size_t)top_k;
+    const size_t o_counts = EK * 4, o_nout = 2 * EK * 4, res_bytes = o_nout + E * 4;
+    const size_t o_segs = dtw_align(res_bytes), o_keeps = dtw_align(o_segs + segs.size() * sizeof(asr::TrackStreamSeg));
+    const size_t o_hist = dtw_align(o_keeps + keeps.size() * sizeof(asr::TrackStreamKeep));
+    rc = track_ws(ctx, o_hist + (global_path ? (size_t)grid * n_pieces * 4 : 0));
+    if (rc != ASR_OK) return rc;
+    char *ws = (char *)ctx->vote_ws;
+    ASR_HIP(ctx, hipMemcpyAsync(ws + o_segs, segs.data(), segs.size() * sizeof(asr::TrackStreamSeg), hipMemcpyHostToDevice,
+                                ctx->stream));
+    if (!keeps.empty())
+        ASR_HIP(ctx, hipMemcpyAsync(ws + o_keeps, keeps.data(), keeps.size() * sizeof(asr::TrackStreamKeep),
+                                    hipMemcpyHostToDevice, ctx->stream));
+    {
+        ProfScope ps(ctx, "track_stream_vote", 0, 0.0, 4.0 * (double)n_rows * n_candidates + 8.0 * (double)EK);
+        asr::TrackStreamVoteArgs a;
+        a.idx = idx_dev; a.segs = (const asr::TrackStreamSeg *)(ws + o_segs); a.n_segs = (int64_t)segs.size();
+        a.n_rows = n_rows; a.keeps = (const asr::TrackStreamKeep *)(ws + o_keeps); a.n_keep = (int)keeps.size();
+        a.n_candidates = n_candidates; a.running_frames = running_frames;
+        a.ids = ids_dev; a.n_db = n_db; a.n_pieces = n_pieces; a.top_k = top_k;
+        a.ring = hist_dev;
+        a.pieces = (int32_t *)ws; a.counts = (int32_t *)(ws + o_counts); a.n_out = (int32_t *)(ws + o_nout);
+        a.hist_ws = (int32_t *)(ws + o_hist);
+        ASR_HIP(ctx, asr::launch_track_stream_vote(ctx->stream, a, (int)grid, global_path));
+    }
+    std::vector<char> host(res_bytes);
+    ASR_HIP(ctx, hipMemcpyAsync(host.data(), ws, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    ASR_HIP(ctx, hipStreamSynchronize(ctx->stream));    // (also: the tables were read by the uploads)
+    memcpy(pieces, host.data(), EK * 4);
+    memcpy(counts, host.data() + o_counts, EK * 4);
+    memcpy(n_out, host.data() + o_nout, E * 4);
+    return mark_main(ctx);
+}
+
 int asr_topk(asr_ctx *ctx, const float *db, int64_t n_db, int64_t ld_db, const float *q, int64_t n_q, int64_t ld_q,
              int dim, int k, int64_t idx_offset, int32_t *idx, double *dist) {
     if (!ctx) return ASR_ERR_INVALID;

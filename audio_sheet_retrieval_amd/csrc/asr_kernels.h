@@ -278,6 +278,42 @@ struct TrackVoteArgs {
 };
 hipError_t launch_track_vote(hipStream_t s, const TrackVoteArgs &a, int grid, bool global_path);
 
+// ---- the same loop for parallel streams with carried device state (track_stream_kernels.hip) ----
+// gate: stream s brings n_new columns as a (bins, n_new) row-major block at float col_off of cols; its state is the
+// (bins, width - 1) row-major block at tail_off of tail (not read with frames_before == 0).  first = its first entry in
+// the per-frame arrays, ext_first = its first entry in colsum, which holds the width - 1 + n_new column sums of
+// [tail | new] for every stream with n_new > 0.  slot (total_frames + 1): the exclusive running count of voiced frames
+// = the window a voiced frame writes; win = total voiced windows (bins x width).  All pointers on the device.
+struct TrackStreamRec {
+    int64_t col_off, tail_off, frames_before, first, ext_first;
+    int32_t n_new; float level;
+};
+struct TrackStreamGateArgs {
+    const float *cols; float *tail; const TrackStreamRec *recs; int n_streams; int64_t total_frames, total_ext;
+    int bins, width;
+    float *colsum; int32_t *slot;       // workspace: total_ext floats / total_frames + 1 counts
+    float *win;
+    float *m_prob; uint8_t *voiced; int32_t *n_voiced;
+};
+hipError_t launch_track_stream_gate(hipStream_t s, const TrackStreamGateArgs &a);       // column sums, gate, slots
+hipError_t launch_track_stream_windows(hipStream_t s, const TrackStreamGateArgs &a);    // windows, then the tails
+// vote: one wave per segment = voiced frames v0 .. v0 + n - 1 (counted over the stream's life) of a stream with vb
+// voiced frames before this call, whose new rows start at row row0 of idx; frame v >= vb is row row0 + v - vb (its
+// output row too), an earlier one slot v mod (running_frames - 1) of the ring at hist_off of ring.  After the votes the
+// last min(n_new, running_frames - 1) new rows of every stream in `keeps` (n_keep entries) are stored in their slots.
+struct TrackStreamSeg { int64_t row0, v0, vb, hist_off; int32_t n, pad; };
+struct TrackStreamKeep { int64_t row0, vb, hist_off; int32_t n_new, pad; };
+struct TrackStreamVoteArgs {
+    const int32_t *idx; const TrackStreamSeg *segs; int64_t n_segs; int64_t n_rows;
+    const TrackStreamKeep *keeps; int n_keep;
+    int n_candidates, running_frames;
+    const int32_t *ids; int64_t n_db; int32_t n_pieces; int top_k;
+    int32_t *ring;
+    int32_t *pieces, *counts, *n_out;
+    int32_t *hist_ws;
+};
+hipError_t launch_track_stream_vote(hipStream_t s, const TrackStreamVoteArgs &a, int grid, bool global_path);
+
 // autotuner self-check (ASR_TUNE_VERIFY=1): deterministic input pattern, max |a - b| as float bits
 hipError_t launch_fill_pattern(hipStream_t s, float *p, int64_t n);
 hipError_t launch_max_abs_diff(hipStream_t s, const float *a, const float *b, int64_t n, uint32_t *out_bits);

@@ -24,13 +24,13 @@
 // outside [0, n_pieces) is ignored, as asr_piece_vote_batch_dev ignores it.
 #pragma clang fp contract(off)
 #include "asr_kernels.h"
+#include "track_shared.h"
 
 namespace asr {
 
 namespace {
 
 constexpr int GATE_THREADS = 256;
-constexpr int TRACK_THREADS = 64;      // one wave: the slide is a chain of small steps, barriers would dominate it
 
 // recording of concatenated frame g: the last r with recs[r].first <= g
 __device__ __forceinline__ int track_rec_of(const TrackRec *__restrict__ recs, int n_rec, int64_t g) {
@@ -89,46 +89,16 @@ __global__ __launch_bounds__(GATE_THREADS) void track_gate_kernel(TrackGateArgs 
     const int64_t c0 = g - R.first - (w - 1);                  // first column of the window (negative: zeros)
     const float *cs = a.colsum + R.first;
     auto elem = [&](int j) { const int64_t c = c0 + j; return c >= 0 ? cs[c] : 0.0f; };
-    float r[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = elem(j);
-    const int full = w - (w & 7);
-    for (int i = 8; i < full; i += 8) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] = r[j] + elem(i + j);
-    }
-    float s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (int i = full; i < w; ++i) s = s + elem(i);
-    float m = __fdiv_rn(s, (float)w);
-    m = __fdiv_rn(m, __fmul_rn(a.level[ri], 0.15f));
-    if (m == m) m = fminf(fmaxf(m, 0.0f), 1.0f);
+    const float m = track_music_prob(elem, w, a.level[ri]);
     a.m_prob[g] = m;
     a.voiced[g] = (m > 0.5f && R.frame0 + (g - R.first) >= (int64_t)w) ? 1 : 0;
 }
 
 // ---- sliding vote ----------------------------------------------------------------------------------------------------
-template <bool GLOBAL>
-__device__ __forceinline__ void hist_add(int32_t *h, int32_t p, int32_t d) {
-    if (GLOBAL) __hip_atomic_fetch_add(h + p, d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else atomicAdd(h + p, d);
-}
-// the global counters are read where the atomics work, past the vector cache: a line fetched before a later atomic
-// would still hold the old count
-template <bool GLOBAL>
-__device__ __forceinline__ int32_t hist_get(const int32_t *h, int32_t p) {
-    return GLOBAL ? __hip_atomic_load(h + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : h[p];
-}
-
 // the n_candidates entries of table row `row` vote with weight d
 template <bool GLOBAL>
 __device__ __forceinline__ void track_vote_row(const TrackVoteArgs &a, int32_t *hist, int64_t row, int32_t d) {
-    const int32_t *e = a.idx + row * a.n_candidates;
-    for (int c = threadIdx.x; c < a.n_candidates; c += TRACK_THREADS) {
-        const int32_t j = e[c];
-        if (j < 0 || j >= a.n_db) continue;
-        const int32_t p = a.ids[j];
-        if (p >= 0 && p < a.n_pieces) hist_add<GLOBAL>(hist, p, d);
-    }
+    track_vote_entries<GLOBAL>(a.idx + row * a.n_candidates, a.n_candidates, a.ids, a.n_db, a.n_pieces, hist, d);
 }
 
 template <bool GLOBAL>
@@ -150,26 +120,7 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_vote_kernel(TrackVoteArgs
             __syncthreads();
             const int64_t o = S.out0 + (f - S.f0);
             int32_t *op = a.pieces + o * a.top_k, *oc = a.counts + o * a.top_k;
-            unsigned long long prev = ~0ull;
-            int n = 0;
-            while (n < a.top_k) {
-                unsigned long long best = 0;
-                for (int p = lane; p < a.n_pieces; p += TRACK_THREADS) {
-                    const int32_t c = hist_get<GLOBAL>(hist, p);
-                    const unsigned long long key = c > 0 ? ((unsigned long long)(uint32_t)c << 32) | (uint32_t)p : 0;
-                    if (key < prev && key > best) best = key;
-                }
-                for (int off = 32; off > 0; off >>= 1) {
-                    const unsigned long long other = __shfl_xor(best, off);
-                    if (other > best) best = other;
-                }
-                if (best == 0) break;                     // fewer voted pieces than top_k
-                if (lane == 0) { op[n] = (int32_t)(uint32_t)best; oc[n] = (int32_t)(best >> 32); }
-                prev = best;
-                ++n;
-            }
-            for (int r = n + lane; r < a.top_k; r += TRACK_THREADS) { op[r] = -1; oc[r] = 0; }
-            if (lane == 0) a.n_out[o] = n;
+            track_emit_topk<GLOBAL>(hist, a.n_pieces, a.top_k, op, oc, a.n_out + o);
             __syncthreads();                              // the next frame's atomics come after this frame's reads
         }
         if (GLOBAL) {                                     // leave the slice zeroed: take back what is still counted

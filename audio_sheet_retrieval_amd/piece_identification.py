@@ -708,6 +708,162 @@ class PieceTracker(object):
         return TrackResult(m_prob, voiced, frames, pieces, counts, n_out, history, db.id_to_name, new_rows)
 
 
+class PieceTrackerBank(object):
+    """PieceTracker for len(levels) parallel streams in one object, with every stream's state on the device: the last
+    w - 1 columns of all streams in one buffer and the top-k rows of their last running_frames - 1 voiced frames in
+    another (a ring per stream), both updated in place by the two calls of csrc/track_stream_kernels.hip.
+    push(columns) takes one (bins, n_i >= 0) block per stream - host arrays, or the DeviceArrays handle of
+    AudioStream.push_dev, which it does not free - and returns one TrackResult per stream, equal field for field to
+    what a PieceTracker of that stream returns for the block (an empty result where n_i == 0).  One round is one
+    asr_track_stream_gate_dev call, one tower and one top-k call over the voiced windows of all streams, one
+    asr_track_stream_vote_dev call and one download of the new index rows, whatever the number of streams; a round of
+    more than max_windows new frames is cut along the frames into several, which changes no result.  The work buffers
+    (windows, codes, index rows, distances) are allocated once and grown when a larger round arrives."""
+
+    def __init__(self, engine, sheet_db, levels, top_k=5, n_candidates=5, running_frames=100, spec_shape=(92, 42),
+                 max_windows=4096):
+        _track_check(top_k, n_candidates, running_frames, max_windows)
+        if n_candidates > len(sheet_db):
+            raise ValueError("n_candidates=%d for a data base of %d codes" % (n_candidates, len(sheet_db)))
+        self.levels = np.ascontiguousarray(levels, dtype=np.float32)
+        if self.levels.ndim != 1 or self.levels.size < 1:
+            raise ValueError("levels: expected one gate level per stream (at least one), got shape %r" % (self.levels.shape,))
+        self.engine, self.db, self.n_streams = engine, sheet_db, int(self.levels.size)
+        self.top_k, self.n_candidates, self.running_frames = int(top_k), int(n_candidates), int(running_frames)
+        self.spec_shape, self.max_windows = tuple(spec_shape), int(max_windows)
+        self.n_frames = [0] * self.n_streams                # frames pushed so far, per stream
+        self.n_voiced = [0] * self.n_streams                # voiced frames so far, per stream
+        win_h, win_w = self.spec_shape
+        tail, ring = win_h * (win_w - 1), (self.running_frames - 1) * self.n_candidates
+        self._tail_off = np.arange(self.n_streams, dtype=np.int64) * tail
+        self._hist_off = np.arange(self.n_streams, dtype=np.int64) * ring
+        self._tail_floats, self._hist_len = self.n_streams * tail, self.n_streams * ring
+        self._d_tail = engine.alloc(max(4, self._tail_floats * 4))                      # running_spec[:, 1:] (:92) per stream
+        self._d_hist = engine.alloc(self._hist_len * 4) if ring else None
+        self._work = {}
+        #: a dict here receives the seconds per stage (gate / embed / topk / vote / rows; synchronises after every stage)
+        self.stages = None
+
+    def _buffer(self, name, nbytes):
+        """the work buffer `name`, grown when a larger round arrives"""
+        buf = self._work.get(name)
+        if buf is None or buf.nbytes < nbytes:
+            if buf is not None:
+                buf.free()
+            buf = self._work[name] = self.engine.alloc(max(4, int(nbytes)))
+        return buf
+
+    def _round(self, cols_ptr, cols_floats, col_off, n_new):
+        """one round of (bins, n_new[s]) blocks at float col_off[s] of the device buffer -> one TrackResult per stream"""
+        import time
+        eng, db, C = self.engine, self.db, self.n_candidates
+        win_h, win_w = self.spec_shape
+        total = int(sum(n_new))
+        d_win = self._buffer("win", total * win_h * win_w * 4)
+
+        def timed(name, fn, *args):
+            if self.stages is None:
+                return fn(*args)
+            t0 = time.perf_counter()
+            out = fn(*args)
+            eng.sync()
+            self.stages[name] = self.stages.get(name, 0.0) + time.perf_counter() - t0
+            return out
+        m_prob, voiced, n_voiced = timed("gate", eng.track_stream_gate_dev, cols_ptr, cols_floats, col_off, n_new,
+                                         self.n_frames, self.levels, win_h, win_w, self._d_tail.ptr, self._tail_floats,
+                                         self._tail_off, d_win.ptr, total)
+        m = int(n_voiced.sum())
+        pieces = counts = np.zeros((0, self.top_k), np.int32)
+        n_out, idx = np.zeros(0, np.int32), np.zeros((0, C), np.int32)
+        if m:
+            d_codes, d_idx = self._buffer("codes", m * 32 * 4), self._buffer("idx", m * C * 4)
+            d_dist = self._buffer("dist", m * C * 8)
+            if (eng.cfg.h2, eng.cfg.w2) != (win_h, win_w):
+                eng.set_input_size(2, win_h, win_w)
+            timed("embed", eng.embed_view2_dev, d_win.ptr, m, d_codes.ptr)
+            timed("topk", db.topk_dev, d_codes.ptr, m, C, d_idx.ptr, d_dist.ptr)
+            pieces, counts, n_out = timed(
+                "vote", eng.track_stream_vote_dev, d_idx.ptr, m, n_voiced, self.n_voiced, C, self.running_frames,
+                db._d_ids.ptr, len(db), db.n_pieces, self.top_k, self._d_hist.ptr if self._d_hist is not None else None,
+                self._hist_len, self._hist_off)
+            idx = timed("rows", d_idx.download, (m, C), np.int32)
+        results, f0, r0 = [], 0, 0
+        for s in range(self.n_streams):
+            f1, r1 = f0 + int(n_new[s]), r0 + int(n_voiced[s])
+            history = _history_lengths(self.n_voiced[s], r1 - r0, C, self.running_frames)
+            results.append(TrackResult(m_prob[f0:f1], voiced[f0:f1], np.flatnonzero(voiced[f0:f1]), pieces[r0:r1],
+                                       counts[r0:r1], n_out[r0:r1], history, db.id_to_name, idx[r0:r1]))
+            self.n_frames[s] += f1 - f0
+            self.n_voiced[s] += r1 - r0
+            f0, r0 = f1, r1
+        return results
+
+    def push(self, columns):
+        if self._d_tail is None:
+            raise ValueError("the PieceTrackerBank is closed")
+        win_h, win_w = self.spec_shape
+        if _is_device(columns):
+            buf, offsets, shapes = columns
+            offsets, shapes = [int(o) for o in offsets], [tuple(int(v) for v in shp) for shp in shapes]
+            if len(offsets) != len(shapes):
+                raise ValueError("device handle: %d offsets for %d shapes" % (len(offsets), len(shapes)))
+        else:
+            cols = [np.ascontiguousarray(c, dtype=np.float32) for c in columns]
+            shapes = [c.shape for c in cols]
+        if len(shapes) != self.n_streams:
+            raise ValueError("%d blocks for %d streams" % (len(shapes), self.n_streams))
+        for s, shp in enumerate(shapes):
+            if len(shp) != 2 or shp[0] != win_h:
+                raise ValueError("stream %d: expected a (%d, n >= 0) block of columns, got shape %r" % (s, win_h, shp))
+        n_new = [int(shp[1]) for shp in shapes]
+        total = sum(n_new)
+        if not _is_device(columns):
+            offsets = [int(o) for o in np.concatenate([[0], np.cumsum([c.size for c in cols])[:-1]])]
+            buf = self._buffer("cols", total * win_h * 4)
+            if total:
+                buf.upload(np.concatenate([c.ravel() for c in cols]))
+        src_floats = buf.nbytes // 4
+        if total <= self.max_windows:
+            return self._round(buf.ptr, src_floats, offsets, n_new)
+        # cut along the frames: every round takes the next columns of each stream, max_windows in all; a column range of
+        # a row-major block is not one, so the gather call repacks it
+        parts, done = [[] for _ in shapes], [0] * self.n_streams
+        d_cut = self._buffer("cut", self.max_windows * win_h * 4)
+        while sum(done) < total:
+            room, take = self.max_windows, []
+            for s in range(self.n_streams):
+                take.append(min(n_new[s] - done[s], room))
+                room -= take[-1]
+            cut_off = [int(o) for o in np.concatenate([[0], np.cumsum(take)[:-1]]) * win_h]
+            for s in range(self.n_streams):
+                if take[s]:
+                    self.engine.gather_windows_dev(buf.ptr, src_floats,
+                                                   _identity_desc(offsets[s], win_h, n_new[s], 0, [done[s]]), win_h, take[s],
+                                                   d_cut.offset(cut_off[s] * 4))
+                    done[s] += take[s]
+            for s, r in enumerate(self._round(d_cut.ptr, d_cut.nbytes // 4, cut_off, take)):
+                if take[s]:
+                    parts[s].append(r)
+        return [_concat_track_results(p, self.db.id_to_name, self.top_k, self.n_candidates) for p in parts]
+
+    def reset(self, streams=None):
+        """`streams` (default: all) start over: the next push is the first of a new recording.  Only the counters are
+        zeroed - the calls do not read the state of a stream without frames."""
+        which = range(self.n_streams) if streams is None else [int(s) for s in streams]
+        for s in which:
+            if not 0 <= s < self.n_streams:
+                raise ValueError("stream %d of %d" % (s, self.n_streams))
+        for s in which:
+            self.n_frames[s], self.n_voiced[s] = 0, 0
+
+    def close(self):
+        for buf in [self._d_tail, self._d_hist] + list(self._work.values()):
+            if buf is not None:
+                buf.free()
+        self._d_tail = self._d_hist = None
+        self._work = {}
+
+
 def _concat_track_results(parts, id_to_name, top_k, n_candidates):
     """the TrackResults of consecutive blocks of one recording as one (frames: indices within the recording)"""
     if not parts:
@@ -721,7 +877,8 @@ def _concat_track_results(parts, id_to_name, top_k, n_candidates):
 
 
 def live_track_scores(engine, sheet_db, processor, recordings, sample_rates, block_samples, levels=None, top_k=5,
-                      n_candidates=5, running_frames=100, spec_shape=(92, 42), integer=None, window_scales=None):
+                      n_candidates=5, running_frames=100, spec_shape=(92, 42), integer=None, window_scales=None,
+                      batched=False):
     """The live server from the samples on: every recording (mono samples at sample_rates[i]) is cut into blocks of
     block_samples input samples (an int, or one per recording) and pushed block by block through an
     audio_frontend.AudioStream - all recordings of one (rate, integer, window scale) group as parallel streams of one
@@ -730,7 +887,8 @@ def live_track_scores(engine, sheet_db, processor, recordings, sample_rates, blo
     within the recording; idx included); equal to track_scores on processor.process_many(recordings, ...) at the same
     levels.  levels: per recording the normaliser of the music gate; None takes spec.sum(axis=0).max() of the finished
     spectrogram, as track_scores does - which means computing that spectrogram first: a real stream cannot, and must be
-    given a level."""
+    given a level.  batched=True: the columns of a group stay on the device (AudioStream.push_dev / flush_dev) and one
+    PieceTrackerBank takes the place of the group's trackers - the same results, a fixed number of calls per round."""
     from .audio_frontend import AudioStream
     recs = [np.ascontiguousarray(r, dtype=np.float32).ravel() for r in recordings]
     n = len(recs)
@@ -751,8 +909,22 @@ def live_track_scores(engine, sheet_db, processor, recordings, sample_rates, blo
     parts = [[] for _ in recs]
     for key in sorted(set(zip(rates, flags, scales))):
         sel = [i for i in range(n) if (rates[i], flags[i], scales[i]) == key]
-        trackers = [PieceTracker(engine, sheet_db, levels[i], top_k, n_candidates, running_frames, spec_shape) for i in sel]
+        bank, trackers = None, []
+        if batched:
+            bank = PieceTrackerBank(engine, sheet_db, [levels[i] for i in sel], top_k, n_candidates, running_frames,
+                                    spec_shape)
+        else:
+            trackers = [PieceTracker(engine, sheet_db, levels[i], top_k, n_candidates, running_frames, spec_shape)
+                        for i in sel]
         stream = AudioStream(processor, len(sel), key[0], key[1], key[2])
+
+        def track_dev(handle):
+            try:
+                for k, r in enumerate(bank.push(handle)):
+                    if len(r.m_prob):
+                        parts[sel[k]].append(r)
+            finally:
+                handle.buf.free()
         try:
             pos = [0] * len(sel)
             while not all(stream.flushed):
@@ -760,6 +932,12 @@ def live_track_scores(engine, sheet_db, processor, recordings, sample_rates, blo
                 for k, i in enumerate(sel):
                     blocks.append(recs[i][pos[k]:pos[k] + steps[i]])
                     pos[k] += blocks[-1].size
+                if batched:
+                    track_dev(stream.push_dev(blocks))
+                    ended = [k for k, i in enumerate(sel) if pos[k] >= recs[i].size and not stream.flushed[k]]
+                    if ended:
+                        track_dev(stream.flush_dev(ended))
+                    continue
                 results = [stream.push(blocks)]
                 ended = [k for k, i in enumerate(sel) if pos[k] >= recs[i].size and not stream.flushed[k]]
                 if ended:
@@ -770,6 +948,8 @@ def live_track_scores(engine, sheet_db, processor, recordings, sample_rates, blo
                             parts[i].append(trackers[k].push(columns[k]))
         finally:
             stream.close()
+            if bank is not None:
+                bank.close()
     return [_concat_track_results(p, sheet_db.id_to_name, top_k, n_candidates) for p in parts]
 
 

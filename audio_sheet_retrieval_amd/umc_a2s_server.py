@@ -6,7 +6,7 @@ umc_a2s_server.py (:178-189):
         --train_split splits/all_split.yaml --config exp_configs/mutopia_full_aug.yaml \
         --init_sheet_db --full_eval --dump_results [--real_perf] [--n_candidates 25] [--estimate_UV] \
         --system_params system_params.pkl --bar_params bar_params.pkl [--device_post] [--resample] [--page_width 835]
-        [--deskew] [--live [--block_ms 100] [--running_frames 100]]
+        [--deskew] [--live [--bank] [--block_ms 100] [--running_frames 100]]
 
 <dir> holds one folder per piece: sheet/*.png (the page scans), score_ppq.* (the synthesised recording) and, for
 --real_perf, 01_performance*.  The pages go through the two segmentation networks (their parameter pickles:
@@ -39,6 +39,8 @@ piece_identification.live_track_scores (AudioStream: asr_audio_stream_push_dev, 
 the first frame at which the piece leads and the share of voiced frames at which it leads
 (audio_sheet_server.report_tracking); --dump_results writes umc_tracking_<tag>_<dset>_A2S[_real].yaml.  The level of the
 music gate is taken from the finished spectrogram, as --track of audio_sheet_server does; a microphone has to be given one.
+--bank (with --live) tracks all recordings of one sample rate with one piece_identification.PieceTrackerBank, whose
+state stays on the device (live_track_scores(batched=True)): the same printout and the same file.
 """
 import argparse
 import os
@@ -85,12 +87,17 @@ def _arguments(argv, direction):
     if direction == "A2S":
         p.add_argument("--live", action="store_true",
                        help="stream every recording block by block through the running vote (live_track_scores)")
+        p.add_argument("--bank", action="store_true",
+                       help="--live with one PieceTrackerBank per sample rate in place of a PieceTracker per recording: "
+                            "the trackers' state stays on the device (live_track_scores(batched=True))")
         p.add_argument("--block_ms", type=float, default=100.0, help="milliseconds of audio per block (--live)")
         p.add_argument("--running_frames", type=int, default=100,
                        help="voiced frames in the history of the running vote (--live)")
     args = p.parse_args(argv)
     if args.fast_dft and getattr(args, "live", False):
         p.error("--fast_dft with --live: the streamed front-end computes the direct DFT only")
+    if getattr(args, "bank", False) and not args.live:
+        p.error("--bank needs --live: it chooses how the streamed recordings are tracked")
     return args
 
 
@@ -99,7 +106,8 @@ def tracking_file(param_file, dset, real_perf=False):
     return result_file(param_file, dset, "A2S", real_perf).replace("umc_retrieval_", "umc_tracking_", 1)
 
 
-def live_track(engine, db, processor, piece_paths, names, audio_file, n_candidates, running_frames, block_ms):
+def live_track(engine, db, processor, piece_paths, names, audio_file, n_candidates, running_frames, block_ms,
+               batched=False):
     """the recordings of `piece_paths`, streamed in blocks of block_ms milliseconds -> (names, first_lead, lead_share) as
     audio_sheet_server.track"""
     from .audio_frontend import read_audio
@@ -113,7 +121,7 @@ def live_track(engine, db, processor, piece_paths, names, audio_file, n_candidat
     steps = [max(1, int(round(rate * block_ms / 1000.0))) for rate in rates]
     results = live_track_scores(engine, db, processor, recs, rates, steps, None, top_k=TRACK_TOP_K,
                                 n_candidates=n_candidates, running_frames=running_frames, integer=integer,
-                                window_scales=scales)
+                                window_scales=scales, batched=batched)
     ids = {name: i for i, name in db.id_to_name.items()}
     first_lead, lead_share = [], []
     for name, res in zip(names, results):
@@ -178,7 +186,8 @@ def run(argv, direction):
                 print("\nStreaming every recording through the running vote:")
                 names = [te_pieces[i] for i in queried]
                 return report_tracking(*live_track(engine, db, processor, [piece_paths[i] for i in queried], names,
-                                                   audio_file, args.n_candidates, args.running_frames, args.block_ms),
+                                                   audio_file, args.n_candidates, args.running_frames, args.block_ms,
+                                                   batched=args.bank),
                                        res_file=tracking_file(param_file, dset, args.real_perf) if args.dump_results
                                        else None)
             if not args.full_eval:

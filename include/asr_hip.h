@@ -322,6 +322,60 @@ int asr_track_vote_batch_dev(asr_ctx *ctx, const int32_t *idx_dev, int64_t n_row
                              const int32_t *ids_dev, int64_t n_db, int32_t n_pieces, int top_k, int32_t *pieces,
                              int32_t *counts, int32_t *n_out);
 
+/* ---- the running vote for n_streams parallel live streams, state on the device (track_stream_kernels.hip) ------------
+ * The two calls above, per round of new columns, for streams that arrive block by block.  Like asr_dtw_follow_batch_dev
+ * and asr_audio_stream_push_dev they keep a stream's state in the caller's device buffers and update it in place; the
+ * counters the host knows anyway (frames_before, voiced_before) are arguments, and a counter of 0 means "new stream: the
+ * state is not read and need not be initialised".  Between the two calls the caller runs asr_embed_view2_dev and
+ * asr_topk_db_dev over the windows of all streams.  All streams of a call share bins, width, n_candidates and
+ * running_frames.
+ *
+ * asr_track_stream_gate_dev: stream s brings n_new[s] >= 0 new columns as a (bins, n_new[s]) float32 row-major block at
+ *   float col_off[s] of cols_dev (cols_floats floats; asr_audio_stream_push_dev's transposed output).  Its state is the
+ *   (bins, width - 1) row-major block at float tail_off[s] of tail_dev (tail_floats floats): the last width - 1 columns
+ *   of the stream so far, zeros where it had not started (running_spec[:, 1:], :92, :110).  With frames_before[s] == 0
+ *   the tail counts as zeros and is not read.
+ *     m_prob, voiced (host; sum(n_new) each, in stream order): per new frame what asr_track_gate_dev returns for the
+ *       recording [tail | new] with norm = level[s] and frame0 = frames_before[s] - (width - 1), without its first
+ *       width - 1 entries - the same float32 operations in the same order (column sums row after row, the
+ *       eight-accumulator mean, the two divisions, the clip, m_prob > 0.5 and frame >= width).
+ *     win_dev (device, win_cap windows of bins x width floats): the window (1, bins, width) = columns i - width + 1 .. i
+ *       of the stream of every voiced frame i, ordered by stream and then by frame - an order fixed by a count and a
+ *       scan, not by atomics; nothing is written past the last window.  n_voiced (host, n_streams): windows per stream.
+ *   Afterwards the tail of every stream with n_new[s] > 0 holds the last width - 1 columns of [tail | new]; a stream
+ *   with n_new[s] == 0 is left untouched.  ASR_ERR_INVALID before anything is launched and with no state touched:
+ *   width outside 8..128, bins < 1, n_streams < 1, a negative n_new or frames_before, a block outside cols_floats, a
+ *   tail outside tail_floats, two tails that overlap, sum(n_new) > win_cap.  Four launches whatever n_streams is: the
+ *   column sums, the gate with the window numbering (one workgroup), the windows (one workgroup per voiced frame, rows
+ *   of width floats written coalesced, [tail | new] read through the cache), and behind them the tails (one workgroup
+ *   per stream: a chunk's sources are read before a barrier and the chunk written after it).
+ *
+ * asr_track_stream_vote_dev: idx_dev = (n_rows x n_candidates) int32 data-base indices, the new rows of all streams
+ *   (what asr_topk_db_dev wrote for win_dev); stream s owns row_count[s] >= 0 consecutive rows in stream order,
+ *   sum(row_count) = n_rows.  Its state is (running_frames - 1) x n_candidates int32 at hist_off[s] of hist_dev
+ *   (hist_len entries), a ring: the row of the stream's v-th voiced frame (v from 0) lives in slot
+ *   v mod (running_frames - 1); voiced_before[s] = the voiced frames before this call, so the slots of the last
+ *   min(voiced_before, running_frames - 1) frames are valid.  With voiced_before[s] == 0 the ring is not read;
+ *   running_frames == 1 has no history and hist_dev / hist_off may be NULL.
+ *     pieces / counts (host, n_rows x top_k), n_out (n_rows): per new row what asr_track_vote_batch_dev returns for the
+ *       table [ring rows in frame order | new rows] with emit_from = the number of ring rows: the same order
+ *       (count << 32 | piece), -1 / 0 padding, ignored invalid entries and limits; counters in LDS up to 4096 pieces,
+ *       in the workspace above; ASR_TRACK_SEG_FRAMES / ASR_TRACK_LDS_PIECES / ASR_VOTE_BUDGET_MB as there.
+ *   Afterwards the ring holds the rows of the last running_frames - 1 voiced frames: a launch behind all votes of the
+ *   call stores the last min(row_count, running_frames - 1) new rows.  ASR_ERR_INVALID before anything is launched and
+ *   with no state touched: the size limits of asr_track_vote_batch_dev, n_streams < 1, a negative row_count or
+ *   voiced_before, sum(row_count) != n_rows, a ring outside hist_len, two rings that overlap. */
+int asr_track_stream_gate_dev(asr_ctx *ctx, const float *cols_dev, int64_t cols_floats, int n_streams,
+                              const int64_t *col_off, const int32_t *n_new, const int64_t *frames_before,
+                              const float *level, int bins, int width, float *tail_dev, int64_t tail_floats,
+                              const int64_t *tail_off, float *win_dev, int64_t win_cap, float *m_prob, uint8_t *voiced,
+                              int32_t *n_voiced);
+int asr_track_stream_vote_dev(asr_ctx *ctx, const int32_t *idx_dev, int64_t n_rows, int n_streams,
+                              const int32_t *row_count, const int64_t *voiced_before, int n_candidates,
+                              int running_frames, const int32_t *ids_dev, int64_t n_db, int32_t n_pieces, int top_k,
+                              int32_t *hist_dev, int64_t hist_len, const int64_t *hist_off, int32_t *pieces,
+                              int32_t *counts, int32_t *n_out);
+
 /* ---- audio front-end -------------------------------------------------
  * The madmom chain the reference feeds its spectrogram tower with (tutorials/Embedding Tutorial.ipynb cell 28,
  * msmd.midi_parser.processor; audio_sheet_server.py:632,678 `processor.process(audio_file).T`):
