@@ -45,6 +45,7 @@ EXPORTS = [
     "asr_unroll_systems_dev", "asr_spectrogram_batch_dev", "asr_spectrogram_fft_batch_dev", "asr_resample_batch_dev", "asr_resize_pages_dev",
     "asr_audio_stream_push_dev", "asr_skew_estimate_dev", "asr_deskew_pages_dev",
     "asr_track_stream_gate_dev", "asr_track_stream_vote_dev",
+    "asr_follow_stream_windows_dev", "asr_follow_stream_log_dev",
     "asr_opt_state_size", "asr_get_opt_state", "asr_set_opt_state", "asr_debug_train_tensor", "asr_cca_train_debug",
     "asr_debug_train_candidate",
 ]
@@ -210,6 +211,10 @@ def load_library(path=None):
                                               c_int64, c_void_p, c_void_p, c_int64] + [c_void_p] * 3),
         "asr_track_stream_vote_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int,
                                               c_void_p, c_int64, c_int32, c_int, c_void_p, c_int64] + [c_void_p] * 4),
+        "asr_follow_stream_windows_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int] + [c_void_p] * 3 +
+                                          [c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+        "asr_follow_stream_log_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int,
+                                              c_void_p, c_int64, c_void_p]),
         "asr_gather_windows_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p]),
         "asr_dtw_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                 POINTER(c_int32), POINTER(c_double)]),
@@ -575,6 +580,43 @@ class Engine(object):
             int(running_frames), ids_ptr, int(n_db), int(n_pieces), int(top_k), hist_ptr, int(hist_len),
             None if h_off is None else h_off.ctypes.data, pieces.ctypes.data, counts.ctypes.data, n_out.ctypes.data))
         return pieces, counts, n_out
+
+    def follow_stream_windows_dev(self, cols_ptr, cols_floats, col_off, n_new, cols_before, bins, width, step, tail_ptr,
+                                  tail_floats, tail_off, win_ptr, win_cap):
+        """the query windows of score following for parallel streams whose last width - 1 columns stay on the device
+        (asr_follow_stream_windows_dev): stream s brings n_new[s] columns as a (bins, n_new[s]) block at float col_off[s]
+        of the buffer at cols_ptr and has cols_before[s] columns behind it; the windows that begin at its columns
+        k * step and end in this block are written to win_ptr (room for win_cap windows) in stream order, and its tail
+        at float tail_off[s] of the buffer at tail_ptr is updated in place.  -> n_win int32 per stream"""
+        new = np.ascontiguousarray(n_new, dtype=np.int32)
+        n = new.size
+        off = np.ascontiguousarray(col_off, dtype=np.int64)
+        before = np.ascontiguousarray(cols_before, dtype=np.int64)
+        t_off = np.ascontiguousarray(tail_off, dtype=np.int64)
+        if new.ndim != 1 or not (off.shape == before.shape == t_off.shape == (n,)):
+            raise ValueError("follow_stream_windows_dev: the per-stream tables differ in length")
+        n_win = np.zeros(n, np.int32)
+        self._check(self.lib.asr_follow_stream_windows_dev(
+            self.ctx, cols_ptr, int(cols_floats), n, off.ctypes.data, new.ctypes.data, before.ctypes.data, int(bins),
+            int(width), int(step), tail_ptr, int(tail_floats), t_off.ctypes.data, win_ptr, int(win_cap),
+            n_win.ctypes.data))
+        return n_win
+
+    def follow_stream_log_dev(self, codes_ptr, n_rows, row_count, rows_in_log, keep, dim, log_ptr, log_floats, log_off):
+        """the code logs of score following for parallel streams (asr_follow_stream_log_dev): stream s owns row_count[s]
+        consecutive rows of the (n_rows, dim) code table at codes_ptr; where it brings rows, the last
+        min(rows_in_log[s], keep) rows of its log at float log_off[s] of the buffer at log_ptr move to the log's front
+        and the new rows are copied behind them.  -> rows_in_log int32 per stream after the call"""
+        count = np.ascontiguousarray(row_count, dtype=np.int32)
+        n = count.size
+        in_log = np.ascontiguousarray(rows_in_log, dtype=np.int32)
+        l_off = np.ascontiguousarray(log_off, dtype=np.int64)
+        if count.ndim != 1 or in_log.shape != (n,) or l_off.shape != (n,):
+            raise ValueError("follow_stream_log_dev: the per-stream tables differ in length")
+        self._check(self.lib.asr_follow_stream_log_dev(
+            self.ctx, codes_ptr, int(n_rows), n, count.ctypes.data, in_log.ctypes.data, int(keep), int(dim), log_ptr,
+            int(log_floats), l_off.ctypes.data))
+        return np.where(count > 0, np.minimum(in_log, int(keep)) + count, in_log).astype(np.int32)
 
     def dtw(self, a, b, want_dists=True):
         """cosine distance matrix + DTW of two code sequences, rows = a (utils/dtw_by_dist.py:5-34 on

@@ -40,6 +40,13 @@ a candidate, the share of windows at which it has the least cost, and the median
 position from the onset map interpolated at each window's centre; --dump_results writes them to
 following_<tag>_A2S.yaml.  A report, not a gate.
 
+--follow --bank is the same report for live streams, which have no finished recording to vote on: every test piece is
+one of as many parallel streams (piece_identification.live_follow_scores), pushed in blocks of --block_frames frames
+through a PieceTrackerBank, whose leaders of the round's last voiced frame (at most --locate_pieces) become the
+stream's candidates, and through a ScoreFollowerBank - a fixed number of library calls per round whatever the number
+of pieces.  A candidate that enters late is followed from --catch_up windows back (default 64).  best_share and
+median_error are taken over the windows at which the own piece occupies a slot, and occupied_share is their share.
+
 The microphone and the GUI of the live server, audio decoding (--real_audio) and MSMD loading are not part of this
 implementation.  sheet_audio_server.py is the S2A direction (sheet -> audio) of the same driver.
 """
@@ -50,8 +57,8 @@ import numpy as np
 import yaml
 
 from . import audio2sheet_align
-from .piece_identification import (EmbeddingDB, ScoreFollower, detect_performances, detect_scores, locate_scores,
-                                   rank_summary, track_scores)
+from .piece_identification import (EmbeddingDB, ScoreFollower, detect_performances, detect_scores, live_follow_scores,
+                                   locate_scores, rank_summary, track_scores)
 from .utils.data_pools import NO_AUGMENT, AudioScoreRetrievalPool
 
 # per direction: data-base flag, data-base file, data-base view, what a query finds (the reference's summary line)
@@ -98,8 +105,17 @@ def _arguments(argv, direction):
         p.add_argument("--follow", action="store_true",
                        help="follow every test piece's first performance through the scores of the vote's candidates")
         p.add_argument("--block_frames", type=int, default=20, help="frames pushed per block (--follow)")
+        p.add_argument("--bank", action="store_true",
+                       help="--follow for live streams: all test pieces in parallel, candidates from the running vote")
+        p.add_argument("--catch_up", type=int, default=64,
+                       help="windows of history a candidate that enters late is followed from (--follow --bank)")
     p.add_argument("--seed", type=int, default=23)
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if getattr(args, "bank", False) and not args.follow:
+        p.error("--bank goes with --follow")
+    if direction == "A2S" and not 0 <= args.catch_up <= 512:
+        p.error("--catch_up must lie in 0..512")
+    return args
 
 
 def result_file(param_file, direction):
@@ -260,6 +276,37 @@ def follow(engine, db, pool, names, n_candidates, n_pieces, step_spec, block_fra
     return out
 
 
+def follow_bank(engine, db, pool, names, n_candidates, n_pieces, step_spec, block_frames, running_frames, catch_up):
+    """every piece's first performance as one of len(names) parallel live streams (live_follow_scores): blocks of
+    block_frames frames go to the running vote, whose leaders (at most n_pieces) become the stream's candidates, and to
+    a ScoreFollowerBank -> follow's dict per piece, with best_share and median_error over the windows at which the own
+    piece occupies a slot, candidate = there is such a window, and occupied_share = their share of all windows"""
+    if block_frames < 1:
+        raise ValueError("block_frames must be >= 1")
+    specs = [np.ascontiguousarray(spec[0], dtype=np.float32) for spec in pool.specs]
+    win_w = int(pool.spec_dim[1])
+    levels = [spec.sum(axis=0).max() if spec.shape[1] else 0.0 for spec in specs]
+    ids = {name: i for i, name in db.id_to_name.items()}
+    _, followed = live_follow_scores(engine, db, specs, levels, block_frames=block_frames, n_slots=n_pieces,
+                                     top_k=n_pieces, n_candidates=n_candidates, running_frames=running_frames,
+                                     step_spec=step_spec, catch_up=catch_up, spec_shape=tuple(pool.spec_dim),
+                                     sheet_columns=pool_sheet_columns(pool, len(db)))
+    out = []
+    for name, o2c, res in zip(names, pool.o2c_maps, followed):
+        own = res.piece == ids.get(name, -2)                 # (windows, slots): at most one slot per window
+        at = np.flatnonzero(own.any(axis=1))
+        entry = dict(name=str(name), candidate=bool(len(at)), windows=int(len(res.frames)), best_share=0.0,
+                     median_error=None, occupied_share=float(len(at)) / len(res.frames) if len(res.frames) else 0.0)
+        if len(at):
+            slot = np.argmax(own[at], axis=1)
+            o2c = np.asarray(o2c[0], np.float64)
+            truth = np.interp(res.frames[at] + win_w // 2, o2c[:, 0], o2c[:, 1])
+            entry.update(best_share=float(np.mean(res.best[at] == slot)),
+                         median_error=float(np.median(np.abs(res.x[at, slot] - truth))))
+        out.append(entry)
+    return out
+
+
 def report_following(entries, res_file=None):
     for e in entries:
         if e["median_error"] is not None:
@@ -307,6 +354,10 @@ def run(argv, direction):
                                res_file=location_file(param_file, direction) if args.dump_results else None)
     if getattr(args, "follow", False):
         print("\nFollowing every test piece through the scores:")
+        if args.bank:
+            return report_following(follow_bank(engine, db, pool, data["names"], args.n_candidates, args.locate_pieces,
+                                                args.step_spec, args.block_frames, args.running_frames, args.catch_up),
+                                    res_file=following_file(param_file, direction) if args.dump_results else None)
         return report_following(follow(engine, db, pool, data["names"], args.n_candidates, args.locate_pieces,
                                        args.step_spec, args.block_frames),
                                 res_file=following_file(param_file, direction) if args.dump_results else None)

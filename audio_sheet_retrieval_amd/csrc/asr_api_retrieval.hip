@@ -1415,6 +1415,131 @@ int asr_track_stream_vote_dev(asr_ctx *ctx, const int32_t *idx_dev, int64_t n_ro
     return mark_main(ctx);
 }
 
+// ---- score following for parallel streams, state on the device (follow_stream_kernels.hip) ---------------------------
+int asr_follow_stream_windows_dev(asr_ctx *ctx, const float *cols_dev, int64_t cols_floats, int n_streams,
+                                  const int64_t *col_off, const int32_t *n_new, const int64_t *cols_before, int bins,
+                                  int width, int step, float *tail_dev, int64_t tail_floats, const int64_t *tail_off,
+                                  float *win_dev, int64_t win_cap, int32_t *n_win) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_streams < 1 || bins < 1 || width < 8 || width > 128 || step < 1 || cols_floats < 0 || tail_floats < 0 ||
+        win_cap < 0)
+        return fail(ctx, ASR_ERR_INVALID,
+                    "asr_follow_stream_windows_dev: bad sizes n_streams=%d bins=%d width=%d (8..128) step=%d (>= 1)",
+                    n_streams, bins, width, step);
+    if (!col_off || !n_new || !cols_before || !tail_dev || !tail_off || !n_win)
+        return fail(ctx, ASR_ERR_INVALID, "asr_follow_stream_windows_dev: NULL argument");
+    std::vector<asr::FollowStreamRec> recs(n_streams);
+    std::vector<int32_t> counts(n_streams);
+    int64_t total = 0, total_new = 0;
+    auto done = [&](int64_t T) { return T < width ? (int64_t)0 : (T - width) / step + 1; };
+    for (int s = 0; s < n_streams; ++s) {
+        if (n_new[s] < 0 || cols_before[s] < 0 || cols_before[s] > INT64_MAX / 4 || col_off[s] < 0 ||
+            col_off[s] > cols_floats || (int64_t)bins * n_new[s] > cols_floats - col_off[s])
+            return fail(ctx, ASR_ERR_INVALID,
+                        "asr_follow_stream_windows_dev: stream %d (%d x %d at %lld, %lld columns before) lies outside the "
+                        "%lld-float buffer", s, bins, n_new[s], (long long)col_off[s], (long long)cols_before[s],
+                        (long long)cols_floats);
+        const int64_t k0 = done(cols_before[s]), k1 = done(cols_before[s] + n_new[s]);
+        asr::FollowStreamRec &R = recs[s];
+        R.col_off = col_off[s]; R.tail_off = tail_off[s]; R.first = total; R.n_new = n_new[s];
+        R.n_win = (int32_t)(k1 - k0);                         // <= n_new: a window per new column at the most
+        R.c0 = k0 * step - cols_before[s] + (width - 1);      // >= 0 where n_win > 0: such a window ends in a new column
+        R.has_tail = cols_before[s] > 0 ? 1 : 0; R.pad = 0;
+        counts[s] = R.n_win;
+        total += R.n_win;
+        total_new += n_new[s];
+        if (total_new > INT32_MAX / 2)
+            return fail(ctx, ASR_ERR_INVALID, "asr_follow_stream_windows_dev: more than 2^30 - 1 columns");
+    }
+    if (track_slices_bad(tail_off, n_streams, (int64_t)bins * (width - 1), tail_floats))
+        return fail(ctx, ASR_ERR_INVALID,
+                    "asr_follow_stream_windows_dev: a tail (%d x %d) lies outside the %lld-float buffer or two tails overlap",
+                    bins, width - 1, (long long)tail_floats);
+    if (total > win_cap)
+        return fail(ctx, ASR_ERR_INVALID, "asr_follow_stream_windows_dev: %lld windows for a buffer of %lld",
+                    (long long)total, (long long)win_cap);
+    if ((total_new > 0 && !cols_dev) || (total > 0 && !win_dev))
+        return fail(ctx, ASR_ERR_INVALID, "asr_follow_stream_windows_dev: NULL argument");
+    memcpy(n_win, counts.data(), (size_t)n_streams * sizeof(int32_t));
+    if (total_new == 0) return ASR_OK;
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    int rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    rc = track_ws(ctx, recs.size() * sizeof(asr::FollowStreamRec));
+    if (rc != ASR_OK) return rc;
+    char *ws = (char *)ctx->vote_ws;
+    ASR_HIP(ctx, hipMemcpyAsync(ws, recs.data(), recs.size() * sizeof(asr::FollowStreamRec), hipMemcpyHostToDevice,
+                                ctx->stream));
+    asr::FollowStreamWinArgs a;
+    a.cols = cols_dev; a.tail = tail_dev; a.win = win_dev; a.recs = (const asr::FollowStreamRec *)ws;
+    a.n_streams = n_streams; a.total_win = total; a.bins = bins; a.width = width; a.step = step;
+    {   // bytes: the windows and the tails written
+        ProfScope ps(ctx, "follow_stream_windows", 0, 0.0,
+                     4.0 * ((double)total * bins * width + (double)n_streams * bins * (width - 1)));
+        ASR_HIP(ctx, asr::launch_follow_stream_windows(ctx->stream, a));
+    }
+    ASR_HIP(ctx, hipStreamSynchronize(ctx->stream));    // `recs` was read by the upload
+    return mark_main(ctx);
+}
+
+int asr_follow_stream_log_dev(asr_ctx *ctx, const float *codes_dev, int64_t n_rows, int n_streams,
+                              const int32_t *row_count, const int32_t *rows_in_log, int keep, int dim, float *log_dev,
+                              int64_t log_floats, const int64_t *log_off) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_streams < 1 || n_rows < 0 || n_rows > INT32_MAX || keep < 0 || dim < 1 || dim > 64 || log_floats < 0)
+        return fail(ctx, ASR_ERR_INVALID,
+                    "asr_follow_stream_log_dev: bad sizes n_rows=%lld n_streams=%d keep=%d (>= 0) dim=%d (1..64)",
+                    (long long)n_rows, n_streams, keep, dim);
+    if (!row_count || !rows_in_log || !log_dev || !log_off)
+        return fail(ctx, ASR_ERR_INVALID, "asr_follow_stream_log_dev: NULL argument");
+    std::vector<asr::FollowStreamLogRec> recs(n_streams);
+    std::vector<std::pair<int64_t, int64_t>> regions(n_streams);                   // (first float, floats)
+    int64_t row0 = 0;
+    for (int s = 0; s < n_streams; ++s) {
+        if (row_count[s] < 0 || rows_in_log[s] < 0 || row_count[s] > n_rows - row0)
+            return fail(ctx, ASR_ERR_INVALID, "asr_follow_stream_log_dev: stream %d: %d rows from row %lld of %lld, %d in the log",
+                        s, row_count[s], (long long)row0, (long long)n_rows, rows_in_log[s]);
+        const int64_t kept = std::min<int64_t>(rows_in_log[s], keep);
+        const int64_t need = std::max<int64_t>(rows_in_log[s], kept + row_count[s]) * dim;
+        if (log_off[s] < 0 || log_off[s] > log_floats || need > log_floats - log_off[s])
+            return fail(ctx, ASR_ERR_INVALID,
+                        "asr_follow_stream_log_dev: the log of stream %d (%lld floats at %lld) lies outside the %lld-float buffer",
+                        s, (long long)need, (long long)log_off[s], (long long)log_floats);
+        asr::FollowStreamLogRec &R = recs[s];
+        R.log_off = log_off[s]; R.src_row = row0; R.rows_in_log = rows_in_log[s]; R.kept = (int32_t)kept;
+        R.n_new = row_count[s]; R.pad = 0;
+        regions[s] = std::make_pair(log_off[s], need);
+        row0 += row_count[s];
+    }
+    if (row0 != n_rows)
+        return fail(ctx, ASR_ERR_INVALID, "asr_follow_stream_log_dev: the row counts add up to %lld, not n_rows=%lld",
+                    (long long)row0, (long long)n_rows);
+    std::sort(regions.begin(), regions.end());
+    for (int s = 1; s < n_streams; ++s)
+        if (regions[s].first - regions[s - 1].first < regions[s - 1].second)
+            return fail(ctx, ASR_ERR_INVALID, "asr_follow_stream_log_dev: two logs overlap (at floats %lld and %lld)",
+                        (long long)regions[s - 1].first, (long long)regions[s].first);
+    if (n_rows == 0) return ASR_OK;
+    if (!codes_dev) return fail(ctx, ASR_ERR_INVALID, "asr_follow_stream_log_dev: NULL argument");
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    int rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    rc = track_ws(ctx, recs.size() * sizeof(asr::FollowStreamLogRec));
+    if (rc != ASR_OK) return rc;
+    char *ws = (char *)ctx->vote_ws;
+    ASR_HIP(ctx, hipMemcpyAsync(ws, recs.data(), recs.size() * sizeof(asr::FollowStreamLogRec), hipMemcpyHostToDevice,
+                                ctx->stream));
+    asr::FollowStreamLogArgs a;
+    a.codes = codes_dev; a.log = log_dev; a.recs = (const asr::FollowStreamLogRec *)ws; a.n_streams = n_streams;
+    a.dim = dim; a.n_rows = n_rows;
+    {   // bytes: the new rows written (the kept rows move only where a log is full)
+        ProfScope ps(ctx, "follow_stream_log", 0, 0.0, 4.0 * (double)n_rows * dim);
+        ASR_HIP(ctx, asr::launch_follow_stream_log(ctx->stream, a));
+    }
+    ASR_HIP(ctx, hipStreamSynchronize(ctx->stream));    // `recs` was read by the upload
+    return mark_main(ctx);
+}
+
 int asr_topk(asr_ctx *ctx, const float *db, int64_t n_db, int64_t ld_db, const float *q, int64_t n_q, int64_t ld_q,
              int dim, int k, int64_t idx_offset, int32_t *idx, double *dist) {
     if (!ctx) return ASR_ERR_INVALID;

@@ -314,6 +314,27 @@ struct TrackStreamVoteArgs {
 };
 hipError_t launch_track_stream_vote(hipStream_t s, const TrackStreamVoteArgs &a, int grid, bool global_path);
 
+// ---- score following for parallel streams: the windows on the step grid and the code logs (follow_stream_kernels.hip) ----
+// windows: stream s brings n_new columns as a (bins, n_new) row-major block at float col_off of cols; its state is the
+// (bins, width - 1) block at tail_off of tail, counted as zeros and not read with has_tail == 0.  It completes n_win
+// windows, numbered first .. first + n_win - 1 in win; window i of them starts at column c0 + i * step of [tail | new].
+struct FollowStreamRec {
+    int64_t col_off, tail_off, first, c0;
+    int32_t n_new, n_win, has_tail, pad;
+};
+struct FollowStreamWinArgs {
+    const float *cols; float *tail; float *win; const FollowStreamRec *recs; int n_streams; int64_t total_win;
+    int bins, width, step;
+};
+hipError_t launch_follow_stream_windows(hipStream_t s, const FollowStreamWinArgs &a);   // windows, then the tails
+// log: the last `kept` of the rows_in_log rows (dim floats each) at float log_off of log move to its front, and the
+// n_new rows from row src_row of codes are copied behind them
+struct FollowStreamLogRec { int64_t log_off, src_row; int32_t rows_in_log, kept, n_new, pad; };
+struct FollowStreamLogArgs {
+    const float *codes; float *log; const FollowStreamLogRec *recs; int n_streams; int dim; int64_t n_rows;
+};
+hipError_t launch_follow_stream_log(hipStream_t s, const FollowStreamLogArgs &a);
+
 // autotuner self-check (ASR_TUNE_VERIFY=1): deterministic input pattern, max |a - b| as float bits
 hipError_t launch_fill_pattern(hipStream_t s, float *p, int64_t n);
 hipError_t launch_max_abs_diff(hipStream_t s, const float *a, const float *b, int64_t n, uint32_t *out_bits);

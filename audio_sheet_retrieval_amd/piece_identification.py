@@ -1328,3 +1328,429 @@ def follow_scores_host(engine, sheet_db, spectrograms, pieces, step_spec=2, spec
     alignment.follow_dtw_host on alignment.cosine_dists_host - what the device path is tested against"""
     return _follow(engine, sheet_db, spectrograms, pieces, step_spec, tuple(spec_shape), segments, sheet_columns,
                    max_windows, host=True)
+
+
+# ---- where in which score are many live streams now?  ScoreFollower for parallel streams, candidates from the vote ------
+def follow_slot_plan(slots, wanted, segments=None):
+    """The candidate policy of ScoreFollowerBank, a pure function: `slots` holds per slot a piece id or None, `wanted`
+    the pieces a stream is to be followed against (at most len(slots), no piece twice; with `segments` each must have
+    one).  A piece already in a slot keeps its slot (and its state); a slot whose piece is not wanted is freed; the
+    remaining wanted pieces, in the given order, take the free slots in ascending slot index; an empty `wanted` leaves
+    the slots as they are.  -> (the new slots, the indices of the newly taken ones)"""
+    slots = [None if p is None else int(p) for p in slots]
+    wanted = [int(p) for p in wanted]
+    if len(set(wanted)) != len(wanted):
+        raise ValueError("a piece is wanted twice: %r" % (wanted,))
+    if len(wanted) > len(slots):
+        raise ValueError("%d pieces wanted for %d slots" % (len(wanted), len(slots)))
+    if segments is not None:
+        for piece in wanted:
+            if piece not in segments:
+                raise ValueError("candidate %r is no piece of the data base with a segment" % (piece,))
+    if not wanted:
+        return slots, []
+    new = [p if p in wanted else None for p in slots]
+    free = [k for k, p in enumerate(new) if p is None]
+    taken = []
+    for piece in wanted:
+        if piece not in new:
+            k = free.pop(0)
+            new[k] = piece
+            taken.append(k)
+    return new, taken
+
+
+class BankFollowResult(object):
+    """Score following of one stream of a ScoreFollowerBank per query window: frames (n,) the first stream column of each
+    window; per window and slot (n, n_slots): piece (int32, -1: the slot is empty), cost (float64, +inf for an empty
+    slot) - the accumulated cost divided by the windows followed since `since`, so slots that entered at different
+    times compare -, row / start_row (int32, rows of the piece's segment where the best path so far ends / started; -1
+    for an empty slot), x / start_x (their strip coordinates; NaN for an empty slot), since (int64, the stream's window
+    index from which the slot follows its piece; -1 for an empty slot); best (n,) the occupied slot of least cost, the
+    lower slot on equal costs, -1 where no slot is occupied.  names: {piece id: name}."""
+
+    def __init__(self, frames, piece, cost, row, start_row, x, start_x, since, names=None, best=None):
+        self.frames, self.piece, self.cost, self.row, self.start_row = frames, piece, cost, row, start_row
+        self.x, self.start_x, self.since, self.names = x, start_x, since, names
+        if best is not None:                                # a slice of a larger result's
+            self.best = best
+            return
+        occupied = piece >= 0
+        least = np.argmin(np.where(occupied, cost, np.inf), axis=1) if piece.shape[0] else np.zeros(0, np.int64)
+        self.best = np.where(occupied.any(axis=1), least, -1).astype(np.int64)
+
+
+def _bank_follow_result(frames, n_slots, names):
+    """a BankFollowResult of len(frames) windows with every slot empty"""
+    n = len(frames)
+    return BankFollowResult(np.asarray(frames, np.int64), np.full((n, n_slots), -1, np.int32), np.full((n, n_slots), np.inf),
+                            np.full((n, n_slots), -1, np.int32), np.full((n, n_slots), -1, np.int32),
+                            np.full((n, n_slots), np.nan), np.full((n, n_slots), np.nan), np.full((n, n_slots), -1, np.int64),
+                            names)
+
+
+def _fill_bank_slot(res, k, piece, since, cost, start, pos, first, sheet_columns):
+    """slot k of `res` <- one piece's (cost, start, pos) over all its windows"""
+    res.piece[:, k], res.since[:, k], res.cost[:, k], res.row[:, k], res.start_row[:, k] = piece, since, cost, pos, start
+    res.x[:, k] = sheet_columns[first + np.asarray(pos, np.int64)]
+    res.start_x[:, k] = sheet_columns[first + np.asarray(start, np.int64)]
+
+
+def _concat_bank_results(parts, n_slots, names):
+    """the BankFollowResults of consecutive rounds of one stream as one"""
+    if not parts:
+        return _bank_follow_result(np.zeros(0, np.int64), n_slots, names)
+    cat = lambda name: np.concatenate([getattr(r, name) for r in parts])
+    return BankFollowResult(cat("frames"), cat("piece"), cat("cost"), cat("row"), cat("start_row"), cat("x"), cat("start_x"),
+                            cat("since"), names)
+
+
+def follow_bank_host(codes_per_stream, window_counts_per_round, candidate_schedule, db_codes, segments, n_slots=5,
+                     catch_up=64, sheet_columns=None, step_spec=2):
+    """ScoreFollowerBank restated in numpy.  codes_per_stream: per stream the (windows, dim) codes of all its windows;
+    window_counts_per_round: per round the windows every stream completes in it; candidate_schedule:
+    {round: {stream: pieces}}, the wishes recorded (set_candidates) before that round's push.  Slots follow
+    follow_slot_plan; a newly taken slot enters at the first round in which its stream completes a window, from
+    min(windows so far, catch_up) windows back (`since`); per slot occupancy the values are alignment.follow_dtw_host
+    on alignment.cosine_dists_host of the stream's window codes from `since` on against db_codes[segment], the
+    catch-up rows' outputs dropped.  -> (one BankFollowResult per stream over all rounds, frames = window index *
+    step_spec; per stream and slot None or (piece, since, pending, follow_dtw_host's state or None))"""
+    from . import alignment
+    n_streams = len(codes_per_stream)
+    db_codes = np.asarray(db_codes, np.float32)
+    if sheet_columns is None:
+        sheet_columns = np.zeros(len(db_codes), np.float64)
+    sheet_columns = np.asarray(sheet_columns, np.float64)
+    slots = [[None] * n_slots for _ in range(n_streams)]
+    info = [[None] * n_slots for _ in range(n_streams)]      # per occupied slot [since, pending, state]
+    done = [0] * n_streams
+    parts = [[] for _ in range(n_streams)]
+    for rnd, counts in enumerate(window_counts_per_round):
+        if len(counts) != n_streams:
+            raise ValueError("round %d: %d window counts for %d streams" % (rnd, len(counts), n_streams))
+        for s, wanted in dict(candidate_schedule.get(rnd, {})).items():
+            new, taken = follow_slot_plan(slots[s], wanted, segments)
+            for k in range(n_slots):
+                if new[k] is None:
+                    info[s][k] = None
+                elif k in taken:
+                    info[s][k] = [-1, True, None]
+            slots[s] = new
+        for s in range(n_streams):
+            m, W = int(counts[s]), done[s]
+            if m == 0:
+                continue
+            if W + m > len(codes_per_stream[s]):
+                raise ValueError("stream %d: %d windows scheduled, %d codes" % (s, W + m, len(codes_per_stream[s])))
+            res = _bank_follow_result(np.arange(W, W + m, dtype=np.int64) * step_spec, n_slots, None)
+            K = min(W, int(catch_up))
+            for k, piece in enumerate(slots[s]):
+                if piece is None:
+                    continue
+                first, n = segments[piece]
+                if info[s][k][1]:
+                    info[s][k] = [W - K, False, None]
+                    q0, drop = W - K, K
+                else:
+                    q0, drop = W, 0
+                d = alignment.cosine_dists_host(codes_per_stream[s][q0:W + m], db_codes[first:first + n])
+                cost, start, pos, info[s][k][2] = alignment.follow_dtw_host(d, info[s][k][2])
+                _fill_bank_slot(res, k, piece, info[s][k][0], cost[drop:], start[drop:], pos[drop:], first, sheet_columns)
+            parts[s].append(BankFollowResult(res.frames, res.piece, res.cost, res.row, res.start_row, res.x, res.start_x,
+                                             res.since, None))
+            done[s] = W + m
+    state = [[None if slots[s][k] is None else (slots[s][k],) + tuple(info[s][k]) for k in range(n_slots)]
+             for s in range(n_streams)]
+    return [_concat_bank_results(p, n_slots, None) for p in parts], state
+
+
+class ScoreFollowerBank(object):
+    """ScoreFollower for n_streams parallel streams in one object whose candidates may change while the streams run,
+    with every stream's state on the device: the last w - 1 columns of all streams in one buffer, the codes of their
+    last windows in another (a linear log per stream of catch_up + the per-round row limit rows, the query buffer of
+    the follow call) and per (stream, slot) an accumulated row and its path origins sized for the longest segment of
+    the data base.  set_candidates(stream, pieces) names the pieces a stream is followed against (for example
+    PieceTrackerBank's current leaders); follow_slot_plan assigns them to the stream's n_slots slots at the next push.
+    A newly taken slot is pending and enters at the first round in which its stream completes a window, catch_up
+    windows back (fewer when the stream is younger): the stream's window index `since`.  push(columns) takes one
+    (bins, n_i >= 0) block per stream - host arrays, or the DeviceArrays handle of AudioStream.push_dev, which it does
+    not free - and returns one BankFollowResult per stream for the windows the block completes (those at stream
+    columns k * step_spec, whatever the block cut).  Per window i an occupied slot's values are what
+    asr_dtw_subseq_batch_dev gives for the stream's windows since .. i against the slot's piece, the cost divided by
+    i - since + 1.  One round is one asr_follow_stream_windows_dev call, one tower call over the windows of all
+    streams, one asr_follow_stream_log_dev call and one asr_dtw_follow_batch_dev call over all occupied (stream, slot)
+    pairs with the download that call makes, whatever the number of streams; a stream without an occupied slot still
+    has its windows embedded and logged.  A round takes at most 1024 - catch_up columns per stream (the follow call's
+    limit of 1024 query rows) and max_windows columns in all; a larger push is cut along the columns into several
+    rounds, which changes no result.  The work buffers are allocated once and grown when a larger round arrives."""
+
+    def __init__(self, engine, sheet_db, n_streams, n_slots=5, step_spec=2, spec_shape=(92, 42), catch_up=64,
+                 segments=None, sheet_columns=None, max_windows=4096):
+        if step_spec < 1 or int(step_spec) != step_spec:
+            raise ValueError("step_spec must be an int >= 1")
+        if n_streams < 1 or n_slots < 1 or max_windows < 1:
+            raise ValueError("n_streams, n_slots and max_windows must be >= 1")
+        if catch_up < 0 or catch_up > FOLLOW_MAX_ROWS // 2 or int(catch_up) != catch_up:
+            raise ValueError("catch_up must be an int in 0..%d" % (FOLLOW_MAX_ROWS // 2))
+        self.engine, self.db, self.n_streams, self.n_slots = engine, sheet_db, int(n_streams), int(n_slots)
+        self.step_spec, self.spec_shape, self.catch_up = int(step_spec), tuple(spec_shape), int(catch_up)
+        self.max_windows = int(max_windows)
+        self.round_rows = FOLLOW_MAX_ROWS - self.catch_up    # columns (so at most that many windows) per stream and round
+        self.segments, self.sheet_columns = _score_tables(engine, sheet_db, segments, sheet_columns)
+        if not self.segments:
+            raise ValueError("the data base has no piece with a segment")
+        self.dim = int(np.asarray(sheet_db.codes).shape[1])
+        win_h, win_w = self.spec_shape
+        tail, self._log_rows = win_h * (win_w - 1), FOLLOW_MAX_ROWS
+        self._seg_max = max(n for _, n in self.segments.values())
+        self._tail_off = np.arange(self.n_streams, dtype=np.int64) * tail
+        self._log_off = np.arange(self.n_streams, dtype=np.int64) * (self._log_rows * self.dim)
+        self._tail_floats, self._log_floats = self.n_streams * tail, self.n_streams * self._log_rows * self.dim
+        self._state_len = self.n_streams * self.n_slots * self._seg_max
+        self._d_tail = engine.alloc(max(4, self._tail_floats * 4))
+        self._d_log = engine.alloc(self._log_floats * 4)
+        self._d_acc, self._d_org = engine.alloc(self._state_len * 8), engine.alloc(self._state_len * 4)
+        self._work = {}
+        #: a dict here receives the seconds per stage (windows / embed / log / follow; synchronises after every stage)
+        self.stages = None
+        self.reset()
+
+    def reset(self, streams=None):
+        """`streams` (default: all) start over: the next push is the first of a new recording, with every slot empty
+        and no wish recorded.  Only the host's counters are zeroed - the calls do not read the state of a new stream."""
+        which = range(self.n_streams) if streams is None else [int(s) for s in streams]
+        for s in which:
+            if not 0 <= s < self.n_streams:
+                raise ValueError("stream %d of %d" % (s, self.n_streams))
+        if streams is None:
+            self.n_columns, self.n_windows = [0] * self.n_streams, [0] * self.n_streams
+            self._in_log = [0] * self.n_streams             # valid rows at the front of the stream's log
+            self._slots = [[None] * self.n_slots for _ in range(self.n_streams)]
+            self._since = [[-1] * self.n_slots for _ in range(self.n_streams)]
+            self._pending = [[False] * self.n_slots for _ in range(self.n_streams)]
+            self._wish = [None] * self.n_streams
+        for s in which:
+            self.n_columns[s] = self.n_windows[s] = self._in_log[s] = 0
+            self._slots[s], self._since[s] = [None] * self.n_slots, [-1] * self.n_slots
+            self._pending[s], self._wish[s] = [False] * self.n_slots, None
+
+    def close(self):
+        for buf in [self._d_tail, self._d_log, self._d_acc, self._d_org] + list(self._work.values()):
+            if buf is not None:
+                buf.free()
+        self._d_tail = self._d_log = self._d_acc = self._d_org = None
+        self._work = {}
+
+    def set_candidates(self, stream, pieces):
+        """stream `stream` is to be followed against `pieces` (ids or names, at most n_slots, each with a segment) from
+        its next push on; only the last wish before a push counts, and an empty list leaves the slots as they are"""
+        stream = int(stream)
+        if not 0 <= stream < self.n_streams:
+            raise ValueError("stream %d of %d" % (stream, self.n_streams))
+        wanted = _follow_candidates(self.db, pieces, self.segments)
+        follow_slot_plan(self._slots[stream], wanted, self.segments)          # refuses what the push would refuse
+        self._wish[stream] = wanted
+
+    def slots(self, stream):
+        """per slot of `stream` the piece id or None, the recorded wish applied"""
+        wish = self._wish[int(stream)]
+        return follow_slot_plan(self._slots[int(stream)], wish)[0] if wish else list(self._slots[int(stream)])
+
+    def _state_off(self, s, k):
+        return (s * self.n_slots + k) * self._seg_max
+
+    def state(self):
+        """downloaded, for tests and checkpoints: per stream and slot None (empty) or (piece, since, pending, (acc, org,
+        rows consumed) or None while pending); a recorded wish is not applied before the next push"""
+        acc = self._d_acc.download((self._state_len,), np.float64)
+        org = self._d_org.download((self._state_len,), np.int32)
+        out = []
+        for s in range(self.n_streams):
+            row = []
+            for k, piece in enumerate(self._slots[s]):
+                if piece is None:
+                    row.append(None)
+                elif self._pending[s][k]:
+                    row.append((piece, -1, True, None))
+                else:
+                    o, n = self._state_off(s, k), self.segments[piece][1]
+                    row.append((piece, self._since[s][k], False,
+                                (acc[o:o + n].copy(), org[o:o + n].copy(), self.n_windows[s] - self._since[s][k])))
+            out.append(row)
+        return out
+
+    _buffer = PieceTrackerBank._buffer
+
+    def _apply_wishes(self):
+        for s, wanted in enumerate(self._wish):
+            if wanted:
+                new, taken = follow_slot_plan(self._slots[s], wanted, self.segments)
+                for k in range(self.n_slots):
+                    if new[k] is None or k in taken:
+                        self._since[s][k], self._pending[s][k] = -1, new[k] is not None
+                self._slots[s] = new
+            self._wish[s] = None
+
+    def _round(self, cols_ptr, cols_floats, col_off, n_new):
+        """one round of (bins, n_new[s]) blocks at float col_off[s] of the device buffer -> one BankFollowResult per
+        stream"""
+        import time
+        eng, db, dim = self.engine, self.db, self.dim
+        win_h, win_w = self.spec_shape
+        starts = [follow_window_plan(self.n_columns[s], int(n_new[s]), win_w, self.step_spec)[0]
+                  for s in range(self.n_streams)]
+        m = np.array([len(st) for st in starts], np.int32)
+        total = int(m.sum())
+        d_win = self._buffer("win", total * win_h * win_w * 4)
+
+        def timed(name, fn, *args):
+            if self.stages is None:
+                return fn(*args)
+            t0 = time.perf_counter()
+            out = fn(*args)
+            eng.sync()
+            self.stages[name] = self.stages.get(name, 0.0) + time.perf_counter() - t0
+            return out
+        n_win = timed("windows", eng.follow_stream_windows_dev, cols_ptr, cols_floats, col_off, n_new, self.n_columns,
+                      win_h, win_w, self.step_spec, self._d_tail.ptr, self._tail_floats, self._tail_off, d_win.ptr, total)
+        if not np.array_equal(n_win, m):
+            raise RuntimeError("the windows call completed %r windows, the plan %r" % (n_win.tolist(), m.tolist()))
+        # one result over the windows of all streams, filled pair by pair and cut into the streams' at the end
+        res = _bank_follow_result(np.concatenate(starts), self.n_slots, db.id_to_name)
+        w_at = np.concatenate([[0], np.cumsum(m)])
+        if total:
+            d_codes = self._buffer("codes", total * dim * 4)
+            if (eng.cfg.h2, eng.cfg.w2) != (win_h, win_w):
+                eng.set_input_size(2, win_h, win_w)
+            timed("embed", eng.embed_view2_dev, d_win.ptr, total, d_codes.ptr)
+            kept = np.minimum(self._in_log, self.catch_up)
+            in_log = timed("log", eng.follow_stream_log_dev, d_codes.ptr, total, m, self._in_log, self.catch_up, dim,
+                           self._d_log.ptr, self._log_floats, self._log_off)
+            pairs, q_row, n_q, before = [], [], [], []       # pairs: (stream, slot, catch-up rows whose outputs are dropped)
+            for s in range(self.n_streams):
+                if not m[s]:
+                    continue
+                K, W = int(kept[s]), self.n_windows[s]
+                for k, piece in enumerate(self._slots[s]):
+                    if piece is None:
+                        continue
+                    if self._pending[s][k]:                  # enters: from K windows back, a fresh state
+                        self._since[s][k], self._pending[s][k] = W - K, False
+                        pairs.append((s, k, K)), q_row.append(s * self._log_rows), n_q.append(K + int(m[s])), before.append(0)
+                    else:
+                        pairs.append((s, k, 0)), q_row.append(s * self._log_rows + K), n_q.append(int(m[s]))
+                        before.append(W - self._since[s][k])
+            if pairs:
+                seg = [self.segments[self._slots[s][k]] for s, k, _ in pairs]
+                out = timed("follow", eng.dtw_follow_batch_dev, self._d_log.ptr, self.n_streams * self._log_rows,
+                            db._d_codes.ptr, len(db), q_row, n_q, [f for f, _ in seg], [n for _, n in seg], before, dim,
+                            self._d_acc.ptr, self._d_org.ptr, self._state_len, [self._state_off(s, k) for s, k, _ in pairs])
+                first = np.zeros((total, self.n_slots), np.int64)
+                for (s, k, drop), (f, _), (cost, start, pos) in zip(pairs, seg, out):
+                    a, b = w_at[s], w_at[s + 1]
+                    res.piece[a:b, k], res.since[a:b, k], first[a:b, k] = self._slots[s][k], self._since[s][k], f
+                    res.cost[a:b, k], res.row[a:b, k], res.start_row[a:b, k] = cost[drop:], pos[drop:], start[drop:]
+                occupied = res.piece >= 0
+                res.x = np.where(occupied, self.sheet_columns[first + np.maximum(res.row, 0)], np.nan)
+                res.start_x = np.where(occupied, self.sheet_columns[first + np.maximum(res.start_row, 0)], np.nan)
+            self._in_log = [int(v) for v in in_log]
+        for s in range(self.n_streams):
+            self.n_columns[s] += int(n_new[s])
+            self.n_windows[s] += int(m[s])
+        res = BankFollowResult(res.frames, res.piece, res.cost, res.row, res.start_row, res.x, res.start_x, res.since)
+        cut = lambda x, s: x[w_at[s]:w_at[s + 1]]
+        return [BankFollowResult(cut(res.frames, s), cut(res.piece, s), cut(res.cost, s), cut(res.row, s), cut(res.start_row, s),
+                                 cut(res.x, s), cut(res.start_x, s), cut(res.since, s), db.id_to_name, cut(res.best, s))
+                for s in range(self.n_streams)]
+
+    def push(self, columns):
+        if self._d_tail is None:
+            raise ValueError("the ScoreFollowerBank is closed")
+        win_h, win_w = self.spec_shape
+        if _is_device(columns):
+            buf, offsets, shapes = columns
+            offsets, shapes = [int(o) for o in offsets], [tuple(int(v) for v in shp) for shp in shapes]
+            if len(offsets) != len(shapes):
+                raise ValueError("device handle: %d offsets for %d shapes" % (len(offsets), len(shapes)))
+        else:
+            cols = [np.ascontiguousarray(c, dtype=np.float32) for c in columns]
+            shapes = [c.shape for c in cols]
+        if len(shapes) != self.n_streams:
+            raise ValueError("%d blocks for %d streams" % (len(shapes), self.n_streams))
+        for s, shp in enumerate(shapes):
+            if len(shp) != 2 or shp[0] != win_h:
+                raise ValueError("stream %d: expected a (%d, n >= 0) block of columns, got shape %r" % (s, win_h, shp))
+        n_new = [int(shp[1]) for shp in shapes]
+        total = sum(n_new)
+        if not _is_device(columns):
+            offsets = [int(o) for o in np.concatenate([[0], np.cumsum([c.size for c in cols])[:-1]])]
+            buf = self._buffer("cols", total * win_h * 4)
+            if total:
+                buf.upload(np.concatenate([c.ravel() for c in cols]))
+        self._apply_wishes()
+        src_floats = buf.nbytes // 4
+        if total <= self.max_windows and max(n_new) <= self.round_rows:
+            return self._round(buf.ptr, src_floats, offsets, n_new)
+        # cut along the columns: every round takes the next columns of each stream, round_rows of one and max_windows in
+        # all; a column range of a row-major block is not one, so the gather call repacks it
+        parts, done = [[] for _ in shapes], [0] * self.n_streams
+        d_cut = self._buffer("cut", self.max_windows * win_h * 4)
+        while sum(done) < total:
+            room, take = self.max_windows, []
+            for s in range(self.n_streams):
+                take.append(min(n_new[s] - done[s], self.round_rows, room))
+                room -= take[-1]
+            cut_off = [int(o) for o in np.concatenate([[0], np.cumsum(take)[:-1]]) * win_h]
+            for s in range(self.n_streams):
+                if take[s]:
+                    self.engine.gather_windows_dev(buf.ptr, src_floats,
+                                                   _identity_desc(offsets[s], win_h, n_new[s], 0, [done[s]]), win_h, take[s],
+                                                   d_cut.offset(cut_off[s] * 4))
+                    done[s] += take[s]
+            for s, r in enumerate(self._round(d_cut.ptr, d_cut.nbytes // 4, cut_off, take)):
+                parts[s].append(r)
+        return [_concat_bank_results(p, self.n_slots, self.db.id_to_name) for p in parts]
+
+
+def live_follow_scores(engine, sheet_db, specs, levels, block_frames=20, n_slots=5, top_k=5, n_candidates=5,
+                       running_frames=100, step_spec=2, catch_up=64, spec_shape=(92, 42), segments=None,
+                       sheet_columns=None):
+    """Which piece is every live stream playing, and where in its score is it now?  All streams run in parallel through
+    one PieceTrackerBank and one ScoreFollowerBank.  `specs`: one (bins, frames) spectrogram per stream, pushed in
+    rounds of block_frames columns (a stream that has ended brings empty blocks) - or any iterable of rounds, each one
+    block per stream as host arrays or as the DeviceArrays handle of AudioStream.push_dev (not freed here).  levels:
+    per stream the normaliser of the music gate.  Per round: the tracker bank takes the blocks; per stream the leaders
+    of its last voiced frame of the round (at most n_slots of the top_k) go to set_candidates - nothing where the round
+    had no voiced frame -; the follower bank takes the same blocks.  -> (one TrackResult per stream, one
+    BankFollowResult per stream), the fields of the rounds concatenated."""
+    levels = np.ascontiguousarray(levels, dtype=np.float32)
+    n = int(levels.size)
+    if block_frames < 1:
+        raise ValueError("block_frames must be >= 1")
+    if isinstance(specs, (list, tuple)) and all(isinstance(x, np.ndarray) and x.ndim == 2 for x in specs):
+        whole = [np.ascontiguousarray(x, dtype=np.float32) for x in specs]
+        longest = max([x.shape[1] for x in whole] + [0])
+        rounds = ([np.ascontiguousarray(x[:, f:f + block_frames]) for x in whole] for f in range(0, longest, block_frames))
+    else:
+        rounds = iter(specs)
+    tracker = PieceTrackerBank(engine, sheet_db, levels, top_k, n_candidates, running_frames, spec_shape)
+    follower = None
+    tracks, follows = [[] for _ in range(n)], [[] for _ in range(n)]
+    try:
+        follower = ScoreFollowerBank(engine, sheet_db, n, n_slots, step_spec, spec_shape, catch_up, segments, sheet_columns)
+        for blocks in rounds:
+            tracked = tracker.push(blocks)
+            for s, r in enumerate(tracked):
+                if len(r.m_prob):
+                    tracks[s].append(r)
+                if len(r.frames):
+                    leaders = [int(p) for p in r.pieces[-1][:int(r.n_out[-1])] if int(p) in follower.segments]
+                    follower.set_candidates(s, leaders[:n_slots])
+            for s, r in enumerate(follower.push(blocks)):
+                follows[s].append(r)
+    finally:
+        tracker.close()
+        if follower is not None:
+            follower.close()
+    return ([_concat_track_results(p, sheet_db.id_to_name, top_k, n_candidates) for p in tracks],
+            [_concat_bank_results(p, n_slots, sheet_db.id_to_name) for p in follows])

@@ -496,6 +496,54 @@ int asr_dtw_follow_batch_dev(asr_ctx *ctx, const float *q_dev, int64_t q_rows, c
                              double *acc_dev, int32_t *org_dev, int64_t state_len, const int64_t *state_off,
                              double *cost, int32_t *start, int32_t *pos);
 
+/* ---- score following for n_streams parallel live streams, state on the device (follow_stream_kernels.hip) ------------
+ * What a session around asr_dtw_follow_batch_dev needs per round of new columns when the streams' state is to stay on
+ * the device: the query windows on the step grid cut from [tail | new block], and per stream a linear log of its last
+ * window codes, so that a candidate that enters late can be followed from `keep` windows back and entering and
+ * continuing pairs of one follow call address the same rows.  Between the two calls the caller runs asr_embed_view2_dev
+ * over win_dev; behind them asr_dtw_follow_batch_dev with q_dev = log_dev.  Both calls move floats only, use no atomics
+ * (every order comes from counts the host knows) and check every index against the sizes validated here.
+ *
+ * The contract of a session built on them (piece_identification.ScoreFollowerBank): per window i (counted over the
+ * stream's life) a slot that holds a piece since window `since` reports what asr_dtw_subseq_batch_dev gives for the
+ * stream's windows since .. i against that piece: end = row, start = start_row, and cost = A / (i - since + 1) - the
+ * accumulated cost already normalised by the rows consumed, which is what makes a late entrant comparable with slots
+ * that have followed for longer.
+ *
+ * asr_follow_stream_windows_dev: cols_dev, cols_floats, n_streams, col_off, n_new, bins, width, tail_dev, tail_floats,
+ *   tail_off as in asr_track_stream_gate_dev (the tail layout is the same; the tail counts as zeros and is not read when
+ *   cols_before[s] == 0).  cols_before[s]: columns of the stream before this call.  The windows of a stream are those
+ *   that begin at stream column k * step (follow_window_plan's rule, whatever the block cut): with
+ *   done(T) = T < width ? 0 : (T - width) / step + 1 the call writes windows done(cols_before) <= k <
+ *   done(cols_before + n_new) as (bins, width) row-major blocks to win_dev (room for win_cap windows), ordered by stream
+ *   and then by k; nothing is written past the last window.  n_win (host, n_streams): windows per stream.  A window
+ *   written by a call ends in a new column, so it never starts before the tail; with step > width the next unfinished
+ *   window may start beyond the stream's end.  Afterwards the tail of every stream with n_new[s] > 0 holds the last
+ *   width - 1 columns of [tail | new]; a stream with n_new[s] == 0 is left untouched.  ASR_ERR_INVALID before anything
+ *   is launched and with no state touched: width outside 8..128, bins < 1, n_streams < 1, step < 1, a negative n_new or
+ *   cols_before, a block outside cols_floats, a tail outside tail_floats, two tails that overlap, more windows than
+ *   win_cap.  Two launches whatever n_streams is: the windows (one workgroup per window, rows of width floats written
+ *   coalesced, 128 bits per lane where bins * width is a multiple of 4), and behind them the tails (one workgroup per
+ *   stream: a chunk's sources are read before a barrier and the chunk written after it).
+ *
+ * asr_follow_stream_log_dev: codes_dev = (n_rows x dim) float32, the new code rows of all streams (what the tower
+ *   wrote for win_dev); stream s owns row_count[s] >= 0 consecutive rows in stream order, sum(row_count) = n_rows.  Its
+ *   log starts at float log_off[s] of log_dev (log_floats floats) and holds rows_in_log[s] valid rows at its front.
+ *   For a stream with row_count[s] > 0 and kept = min(rows_in_log[s], keep): the last kept rows move to the front of
+ *   the log (in place, overlap-safe: chunk by chunk, sources read before a barrier) and the new rows are copied behind
+ *   them, so the log is [kept | new] and the caller sets rows_in_log = kept + row_count.  A stream with
+ *   row_count[s] == 0 is left untouched.  ASR_ERR_INVALID before anything is launched and with no state touched:
+ *   n_streams < 1, dim outside 1..64, keep < 0, a negative row_count or rows_in_log, sum(row_count) != n_rows, a log
+ *   that cannot hold max(rows_in_log, kept + row_count) rows inside log_floats, two logs that overlap.  One launch,
+ *   one workgroup per stream; 128 bits per lane where dim and the log's offset are multiples of 4. */
+int asr_follow_stream_windows_dev(asr_ctx *ctx, const float *cols_dev, int64_t cols_floats, int n_streams,
+                                  const int64_t *col_off, const int32_t *n_new, const int64_t *cols_before, int bins,
+                                  int width, int step, float *tail_dev, int64_t tail_floats, const int64_t *tail_off,
+                                  float *win_dev, int64_t win_cap, int32_t *n_win);
+int asr_follow_stream_log_dev(asr_ctx *ctx, const float *codes_dev, int64_t n_rows, int n_streams,
+                              const int32_t *row_count, const int32_t *rows_in_log, int keep, int dim, float *log_dev,
+                              int64_t log_floats, const int64_t *log_off);
+
 /* ---- training-pool batch assembly on the device ----------------------
  * AudioScoreRetrievalPool.__getitem__ (utils/data_pools.py:127-228): every sample is a window of one strip (unrolled
  * score image or spectrogram) of a pool that stays resident on the device, with the augmentations of
