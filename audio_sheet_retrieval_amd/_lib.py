@@ -43,7 +43,7 @@ EXPORTS = [
     "asr_seg_create", "asr_seg_set_window", "asr_seg_destroy", "asr_seg_predict_dev", "asr_systems_from_maps_dev",
     "asr_notes_from_map_dev", "asr_bars_from_map_dev",
     "asr_unroll_systems_dev", "asr_spectrogram_batch_dev", "asr_spectrogram_fft_batch_dev", "asr_resample_batch_dev", "asr_resize_pages_dev",
-    "asr_audio_stream_push_dev", "asr_skew_estimate_dev", "asr_deskew_pages_dev",
+    "asr_audio_stream_push_dev", "asr_audio_stream_push_fft_dev", "asr_skew_estimate_dev", "asr_deskew_pages_dev",
     "asr_track_stream_gate_dev", "asr_track_stream_vote_dev",
     "asr_follow_stream_windows_dev", "asr_follow_stream_log_dev",
     "asr_opt_state_size", "asr_get_opt_state", "asr_set_opt_state", "asr_debug_train_tensor", "asr_cca_train_debug",
@@ -245,6 +245,10 @@ def load_library(path=None):
                                               c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64,
                                               c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
                                               c_float, c_int, c_void_p, c_int64]),
+        "asr_audio_stream_push_fft_dev": (c_int, [c_void_p, c_void_p, c_int64] + [c_void_p] * 7 + [c_int, c_int, c_int,
+                                                  c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64,
+                                                  c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
+                                                  c_float, c_int, c_void_p, c_int64]),
         "asr_debug_tune_report": (c_int, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_float)]),
         "asr_comm_unique_id": (c_int, [c_void_p]),
         "asr_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),
@@ -891,18 +895,16 @@ class Engine(object):
             out_counts.ctypes.data, n, int(up), int(down), taps.ctypes.data, taps.shape[1], int(half),
             1 if round_int16 else 0, out_ptr, int(out_floats)))
 
-    def audio_stream_push_dev(self, blocks_ptr, blocks_floats, block_offsets, block_counts, samples_before, final,
-                              first_frames, n_new_frames, out_offsets, up, down, taps_phase_major, half, round_int16,
-                              state_ptr, state_floats, state_offsets, state_cap, frame_size, hop, window, fb_start,
-                              fb_len, fb_weights, out_ptr, out_floats, mul=1.0, add=1.0, transposed=True):
-        """one block of new input samples per stream -> the spectrogram frames those samples complete
-        (asr_audio_stream_push_dev): stream i gets block_counts[i] floats at block_offsets[i] of the buffer at blocks_ptr
+    def _audio_stream_push(self, fn, blocks_ptr, blocks_floats, block_offsets, block_counts, samples_before, final,
+                           first_frames, n_new_frames, out_offsets, up, down, taps_phase_major, half, round_int16,
+                           state_ptr, state_floats, state_offsets, state_cap, frame_size, hop, window, fb_start,
+                           fb_len, fb_weights, out_ptr, out_floats, mul, add, transposed):
+        """the argument marshalling asr_audio_stream_push_dev and asr_audio_stream_push_fft_dev (fn) share: stream i
+        gets block_counts[i] floats at block_offsets[i] of the buffer at blocks_ptr
         after samples_before[i] earlier ones, its n_new_frames[i] frames from frame first_frames[i] on
         (audio_frontend.audio_stream_plan) go to out_offsets[i] of the buffer at out_ptr, and its carried input samples
         live in state_cap floats at state_offsets[i] of the buffer at state_ptr.  taps_phase_major: float64 (up, taps per
-        phase), audio_frontend.resample_plan's, or None with up == down == 1 for the front-end's own rate.  Whatever the
-        cut into calls, the concatenated frames are bit-identical with resample_batch_dev + spectrogram_batch_dev on the
-        whole recording"""
+        phase), audio_frontend.resample_plan's, or None with up == down == 1 for the front-end's own rate."""
         i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
         block_offsets, block_counts, samples_before, first_frames, n_new_frames, out_offsets, state_offsets = map(
             i64, (block_offsets, block_counts, samples_before, first_frames, n_new_frames, out_offsets, state_offsets))
@@ -922,13 +924,40 @@ class Engine(object):
         fb_start = np.ascontiguousarray(fb_start, np.int32)
         fb_len = np.ascontiguousarray(fb_len, np.int32)
         fb_weights = np.ascontiguousarray(fb_weights, np.float32)
-        self._check(self.lib.asr_audio_stream_push_dev(
+        self._check(fn(
             self.ctx, blocks_ptr, int(blocks_floats), block_offsets.ctypes.data, block_counts.ctypes.data,
             samples_before.ctypes.data, final.ctypes.data, first_frames.ctypes.data, n_new_frames.ctypes.data,
             out_offsets.ctypes.data, n, int(up), int(down), taps_ptr, taps_per_phase, int(half), 1 if round_int16 else 0,
             state_ptr, int(state_floats), state_offsets.ctypes.data, int(state_cap), int(frame_size), hop,
             window.ctypes.data, fb_start.ctypes.data, fb_len.ctypes.data, fb_weights.ctypes.data, fb_start.size, mul, add,
             1 if transposed else 0, out_ptr, int(out_floats)))
+
+    def audio_stream_push_dev(self, blocks_ptr, blocks_floats, block_offsets, block_counts, samples_before, final,
+                              first_frames, n_new_frames, out_offsets, up, down, taps_phase_major, half, round_int16,
+                              state_ptr, state_floats, state_offsets, state_cap, frame_size, hop, window, fb_start,
+                              fb_len, fb_weights, out_ptr, out_floats, mul=1.0, add=1.0, transposed=True):
+        """one block of new input samples per stream -> the spectrogram frames those samples complete
+        (asr_audio_stream_push_dev; the arguments: _audio_stream_push).  Whatever the cut into calls, the concatenated
+        frames are bit-identical with resample_batch_dev + spectrogram_batch_dev on the whole recording"""
+        self._audio_stream_push(self.lib.asr_audio_stream_push_dev, blocks_ptr, blocks_floats, block_offsets,
+                                block_counts, samples_before, final, first_frames, n_new_frames, out_offsets, up, down,
+                                taps_phase_major, half, round_int16, state_ptr, state_floats, state_offsets, state_cap,
+                                frame_size, hop, window, fb_start, fb_len, fb_weights, out_ptr, out_floats, mul, add,
+                                transposed)
+
+    def audio_stream_push_fft_dev(self, blocks_ptr, blocks_floats, block_offsets, block_counts, samples_before, final,
+                                  first_frames, n_new_frames, out_offsets, up, down, taps_phase_major, half, round_int16,
+                                  state_ptr, state_floats, state_offsets, state_cap, frame_size, hop, window, fb_start,
+                                  fb_len, fb_weights, out_ptr, out_floats, mul=1.0, add=1.0, transposed=True):
+        """audio_stream_push_dev with the magnitudes from the real-input FFT (asr_audio_stream_push_fft_dev; frame_size
+        2048 only; same state, same plan).  Whatever the cut into calls and whatever the other streams, the concatenated
+        frames are bit-identical with resample_batch_dev + spectrogram_fft_batch_dev on the whole recording, in either
+        layout; not bit-identical with audio_stream_push_dev"""
+        self._audio_stream_push(self.lib.asr_audio_stream_push_fft_dev, blocks_ptr, blocks_floats, block_offsets,
+                                block_counts, samples_before, final, first_frames, n_new_frames, out_offsets, up, down,
+                                taps_phase_major, half, round_int16, state_ptr, state_floats, state_offsets, state_cap,
+                                frame_size, hop, window, fb_start, fb_len, fb_weights, out_ptr, out_floats, mul, add,
+                                transposed)
 
     def resize_pages_dev(self, pages_ptr, pages_bytes, page_offsets, heights, widths, out_offsets, out_heights,
                          out_widths, out_ptr, out_bytes):

@@ -16,7 +16,9 @@ semantic, unverified offline; it reproduces the reference's 92 bands); framing, 
 filterbank and logarithm run in one kernel per call (csrc/piece_vote_kernels.hip: spectrogram_kernel).
 `SpectrogramProcessor(engine, dft="fft")` takes the magnitudes from a real-input FFT instead of the direct DFT
 (asr_spectrogram_fft_batch_dev, csrc/spectrogram_fft_kernels.hip; `spectrogram_fft_host` restates its plan): the same
-spectrogram within float32 rounding and some 55 times faster, but not bit-identical with the default route.
+spectrogram within float32 rounding and some 55 times faster, but not bit-identical with the default route.  Its
+stream is `processor.stream(..., dft="fft")` (asr_audio_stream_push_fft_dev, csrc/audio_stream_fft_kernels.hip):
+bit-identical with that processor's `process`, and only given when asked for by name.
 """
 from __future__ import print_function
 
@@ -248,7 +250,8 @@ class SpectrogramProcessor(object):
         """dft: "direct" - the direct DFT of csrc/spectrogram_frame.h, the route every bit-parity statement of this
         class is about (process, process_many, the stream); "fft" - the magnitudes from a real-input FFT
         (asr_spectrogram_fft_batch_dev; frames of 2048 samples only): within float32 rounding of the same spectrogram and
-        closer to the float64 one, several times faster, but not bit-identical with "direct" and without a stream."""
+        closer to the float64 one, several times faster, but not bit-identical with "direct"; its stream is
+        stream(dft="fft"), a plain stream() is refused."""
         if dft not in ("direct", "fft"):
             raise ValueError('dft=%r: "direct" or "fft"' % (dft,))
         if dft == "fft" and frame_size != 2048:
@@ -414,9 +417,10 @@ class SpectrogramProcessor(object):
             dev.buf.free()
         return [flat[o:o + r * c].reshape(r, c).copy() for o, (r, c) in zip(dev.offsets, dev.shapes)]
 
-    def stream(self, n_streams=1, sample_rate=None, integer=False, window_scale=None):
-        """AudioStream(self, ...): spectrogram columns from audio that arrives block by block"""
-        return AudioStream(self, n_streams, sample_rate, integer, window_scale)
+    def stream(self, n_streams=1, sample_rate=None, integer=False, window_scale=None, dft=None):
+        """AudioStream(self, ...): spectrogram columns from audio that arrives block by block.  dft: None - the direct
+        stream of a "direct" processor; "fft" - the FFT stream of an "fft" processor, named explicitly (AudioStream)"""
+        return AudioStream(self, n_streams, sample_rate, integer, window_scale, dft)
 
 
 # ---- streamed audio: blocks of samples in, the spectrogram columns they complete out ----------------------------------------
@@ -547,14 +551,27 @@ class AudioStream(object):
     (None: the processor's); integer: they are 16-bit PCM values (read_audio's flag); window_scale: what read_audio
     returned (None: the processor's).  All streams share rate, integer flag and window scale: one push is one
     asr_audio_stream_push_dev call (csrc/audio_stream_kernels.hip).  The samples the next frames still read stay on the
-    device (audio_stream_state_len floats per stream); state and upload buffers are allocated once and reused."""
+    device (audio_stream_state_len floats per stream); state and upload buffers are allocated once and reused.
+    dft: which transform computes the frames, named explicitly.  None - the direct DFT, for a dft="direct" processor (a
+    "fft" processor is refused: it has to ask for its stream by name).  "fft" - the real-input FFT
+    (asr_audio_stream_push_fft_dev, csrc/audio_stream_fft_kernels.hip), for a dft="fft" processor only: the same plan,
+    state and methods, and the concatenated columns of a stream are bit-identical with
+    processor.process(recording, sample_rate, integer) of that same "fft" processor, whatever the cut into blocks and
+    whatever the other streams carry.  "direct" - the direct DFT, for a "direct" processor only."""
 
-    def __init__(self, processor, n_streams=1, sample_rate=None, integer=False, window_scale=None):
+    def __init__(self, processor, n_streams=1, sample_rate=None, integer=False, window_scale=None, dft=None):
         if n_streams < 1:
             raise ValueError("n_streams must be >= 1")
-        if processor.dft != "direct":
+        if dft not in (None, "direct", "fft"):
+            raise ValueError('dft=%r: None, "direct" or "fft"' % (dft,))
+        if dft is None and processor.dft != "direct":
             raise ValueError('AudioStream: the streamed front-end is bit-identical with the dft="direct" route and '
-                             'computes the direct DFT; this processor was built with dft=%r' % (processor.dft,))
+                             'computes the direct DFT; this processor was built with dft=%r (its FFT stream has to be '
+                             'asked for by name: dft="fft")' % (processor.dft,))
+        if dft is not None and dft != processor.dft:
+            raise ValueError('AudioStream: dft=%r for a processor built with dft=%r: a stream reproduces the bits of its '
+                             'own processor' % (dft, processor.dft))
+        self.dft = processor.dft
         self.processor, self.engine, self.n_streams = processor, processor.engine, int(n_streams)
         self.sample_rate = processor.sample_rate if sample_rate is None else sample_rate
         self.integer = bool(integer)
@@ -614,8 +631,9 @@ class AudioStream(object):
             d_blocks.upload(np.concatenate(blocks))
         d_out = self.engine.alloc(max(4, out_floats * 4)) if out_buf is None else self._buffer(out_buf, out_floats * 4)
         p = self.processor
+        call = self.engine.audio_stream_push_fft_dev if self.dft == "fft" else self.engine.audio_stream_push_dev
         try:
-            self.engine.audio_stream_push_dev(
+            call(
                 d_blocks.ptr, total_in, b_off, counts, self.n_samples, [1 if f else 0 for f in final], first, n_new, o_off,
                 self.up, self.down, self.taps, self.half, self.integer, self._d_state.ptr, self.state_floats,
                 self.state_offsets, self.state_cap, p.frame_size, p.hop, self.window, p.fb_start, p.fb_len, p.fb_w,

@@ -1,7 +1,8 @@
 // C-ABI layer of the UMC drivers' device stages: asr_resize_pages_dev (page scans of any resolution -> pages of the
 // networks' width), asr_unroll_systems_dev (page scans -> unrolled strips), asr_resample_batch_dev (recordings at any
 // rate -> recordings at the front-end's rate), asr_spectrogram_batch_dev (recordings -> spectrograms) and
-// asr_audio_stream_push_dev (blocks of streamed samples at any rate -> the spectrogram frames they complete);
+// asr_audio_stream_push_dev / asr_audio_stream_push_fft_dev (blocks of streamed samples at any rate -> the spectrogram
+// frames they complete, by the direct DFT / by the FFT; audio_stream_fft_kernels.hip);
 // include/asr_hip.h for the contract.  Kernels: page_resize_kernels.hip, umc_kernels.hip, resample_kernels.hip,
 // piece_vote_kernels.hip (spectrogram_batch_kernel), audio_stream_kernels.hip.  Every call checks every offset against the buffer sizes the
 // caller states before anything is launched, and returns after the work is done.
@@ -167,6 +168,22 @@ static const std::vector<float> &specfft_twiddles() {
     return table;
 }
 
+// the FFT routes' workspace (asr_spectrogram_fft_batch_dev, asr_audio_stream_push_fft_dev): the twiddle table in front,
+// then the per-call tables of the batched call; a (re)allocation uploads the table again, so whichever call comes first
+// in a context finds it on the device
+static int specfft_workspace(asr_ctx *ctx, size_t need) {
+    if (need <= ctx->specfft_ws_bytes) return ASR_OK;
+    const std::vector<float> &tw = specfft_twiddles();
+    ASR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->specfft_ws) ASR_HIP(ctx, hipFree(ctx->specfft_ws));
+    ctx->specfft_ws = nullptr; ctx->specfft_ws_bytes = 0;
+    const size_t bytes = need + need / 2;                           // growing recording tables do not reallocate each time
+    ASR_HIP(ctx, hipMalloc(&ctx->specfft_ws, bytes));
+    ctx->specfft_ws_bytes = bytes;
+    ASR_HIP(ctx, hipMemcpy(ctx->specfft_ws, tw.data(), tw.size() * 4, hipMemcpyHostToDevice));
+    return ASR_OK;
+}
+
 int asr_spectrogram_fft_batch_dev(asr_ctx *ctx, const float *samples_dev, int64_t samples_floats,
                                   const int64_t *sample_offsets, const int64_t *sample_counts, const int64_t *n_frames,
                                   const int64_t *out_offsets, int n_recordings, int frame_size, double hop,
@@ -222,15 +239,8 @@ int asr_spectrogram_fft_batch_dev(asr_ctx *ctx, const float *samples_dev, int64_
     const std::vector<float> &tw = specfft_twiddles();
     const size_t b_tw = tw.size() * 4, b_tab = n_tab * 8, b_win = (size_t)2048 * 4, b_i = (size_t)n_filters * 4,
                  b_w = (size_t)total_w * 4, b_call = b_tab + b_win + 3 * b_i + b_w, need = b_tw + b_call;
-    if (need > ctx->specfft_ws_bytes) {
-        ASR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->specfft_ws) ASR_HIP(ctx, hipFree(ctx->specfft_ws));
-        ctx->specfft_ws = nullptr; ctx->specfft_ws_bytes = 0;
-        const size_t bytes = need + need / 2;                       // growing recording tables do not reallocate each time
-        ASR_HIP(ctx, hipMalloc(&ctx->specfft_ws, bytes));
-        ctx->specfft_ws_bytes = bytes;
-        ASR_HIP(ctx, hipMemcpy(ctx->specfft_ws, tw.data(), b_tw, hipMemcpyHostToDevice));
-    }
+    rc = specfft_workspace(ctx, need);
+    if (rc != ASR_OK) return rc;
     std::vector<char> image(b_call);
     memcpy(image.data(), tab.data(), b_tab);
     memcpy(image.data() + b_tab, window, b_win);
@@ -371,36 +381,43 @@ struct StreamPlan {
 
 }  // namespace
 
-int asr_audio_stream_push_dev(asr_ctx *ctx, const float *blocks_dev, int64_t blocks_floats, const int64_t *block_offsets,
-                              const int64_t *block_counts, const int64_t *samples_before, const int32_t *final_flags,
-                              const int64_t *first_frames, const int64_t *n_new_frames, const int64_t *out_offsets,
-                              int n_streams, int up, int down, const double *taps_phase_major, int taps_per_phase,
-                              int half, int round_int16, float *state_dev, int64_t state_floats,
-                              const int64_t *state_offsets, int64_t state_cap, int frame_size, double hop,
-                              const float *window, const int32_t *fb_start, const int32_t *fb_len,
-                              const float *fb_weights, int n_filters, float mul, float add, int transposed,
-                              float *out_dev, int64_t out_floats) {
+// asr_audio_stream_push_dev (fft == false, who = "audio_stream_push") and asr_audio_stream_push_fft_dev (fft == true,
+// "audio_stream_push_fft"): the checks, the plan, the rows, the overlap test and the taps cache are one; the two differ in
+// the frame sizes and filters they take, in the LDS a frame needs and in the kernel that computes the frames
+#define STREAM_FAIL(code, fmt, ...) fail(ctx, code, "%s: " fmt, who, ##__VA_ARGS__)
+static int audio_stream_push(asr_ctx *ctx, bool fft, const char *who, const float *blocks_dev, int64_t blocks_floats,
+                             const int64_t *block_offsets, const int64_t *block_counts, const int64_t *samples_before,
+                             const int32_t *final_flags, const int64_t *first_frames, const int64_t *n_new_frames,
+                             const int64_t *out_offsets, int n_streams, int up, int down, const double *taps_phase_major,
+                             int taps_per_phase, int half, int round_int16, float *state_dev, int64_t state_floats,
+                             const int64_t *state_offsets, int64_t state_cap, int frame_size, double hop,
+                             const float *window, const int32_t *fb_start, const int32_t *fb_len,
+                             const float *fb_weights, int n_filters, float mul, float add, int transposed,
+                             float *out_dev, int64_t out_floats) {
     if (!ctx) return ASR_ERR_INVALID;
     if (n_streams < 0 || blocks_floats < 0 || state_floats < 0 || state_cap < 0 || out_floats < 0 || frame_size < 64 ||
         frame_size > 8192 || (frame_size & (frame_size - 1)) || !(hop > 0.0) || n_filters < 1 || n_filters > 4096)
-        return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: bad sizes (frame_size must be a power of two in [64, 8192])");
+        return STREAM_FAIL(ASR_ERR_INVALID, "bad sizes (frame_size must be a power of two in [64, 8192])");
+    if (fft && frame_size != 2048)
+        return STREAM_FAIL(ASR_ERR_INVALID, "frame_size %d (the FFT route has frames of 2048 samples; "
+                           "asr_audio_stream_push_dev takes the others)", frame_size);
     if (up < 1 || down < 1)
-        return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: ratio %d / %d (up and down must be at least 1)", up, down);
+        return STREAM_FAIL(ASR_ERR_INVALID, "ratio %d / %d (up and down must be at least 1)", up, down);
     const bool native = !taps_phase_major;
     if (native && (up != 1 || down != 1))
-        return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: ratio %d / %d without taps (only 1 / 1 is the front-end's "
+        return STREAM_FAIL(ASR_ERR_INVALID, "ratio %d / %d without taps (only 1 / 1 is the front-end's "
                     "own rate)", up, down);
     if (!native && (half < 0 || taps_per_phase < 1 || (int64_t)taps_per_phase * up < 2 * (int64_t)half + 1))
-        return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: %d taps per phase x %d phases do not hold the %lld taps of "
+        return STREAM_FAIL(ASR_ERR_INVALID, "%d taps per phase x %d phases do not hold the %lld taps of "
                     "half = %d", taps_per_phase, up, 2 * (long long)half + 1, half);
     if (!window || !fb_start || !fb_len || !fb_weights)
-        return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: NULL argument");
+        return STREAM_FAIL(ASR_ERR_INVALID, "NULL argument");
     std::vector<int32_t> off(n_filters);
     int64_t total_w = 0;
     int max_bin = 0;
     for (int f = 0; f < n_filters; ++f) {
         if (fb_start[f] < 0 || fb_len[f] < 0 || fb_start[f] + fb_len[f] > frame_size / 2)
-            return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: filter %d covers bins [%d, %d) outside [0, %d)", f,
+            return STREAM_FAIL(ASR_ERR_INVALID, "filter %d covers bins [%d, %d) outside [0, %d)", f,
                         fb_start[f], fb_start[f] + fb_len[f], frame_size / 2);
         off[f] = (int32_t)total_w;
         total_w += fb_len[f];
@@ -408,18 +425,20 @@ int asr_audio_stream_push_dev(asr_ctx *ctx, const float *blocks_dev, int64_t blo
     }
     const StreamPlan plan{up, down, native ? 0 : half, native ? 1 : taps_per_phase, frame_size, hop, native};
     const int64_t span64 = native ? 0 : ((int64_t)(frame_size - 1) * down + up - 1) / up + taps_per_phase;
+    // the FFT kernel never needs more than the direct one at the same span: it takes every ratio that one takes
     if (span64 > (int64_t)(asr::AUDIO_STREAM_MAX_LDS / 4) ||
-        asr::audio_stream_lds(frame_size, max_bin, (int)span64) > asr::AUDIO_STREAM_MAX_LDS)
-        return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: ratio %d / %d with %d taps per phase and frames of %d: the "
+        (fft ? asr::audio_stream_fft_lds((int)span64) : asr::audio_stream_lds(frame_size, max_bin, (int)span64)) >
+            asr::AUDIO_STREAM_MAX_LDS)
+        return STREAM_FAIL(ASR_ERR_INVALID, "ratio %d / %d with %d taps per phase and frames of %d: the "
                     "input span of a frame (%lld samples) does not fit %zu bytes of LDS", up, down, taps_per_phase,
                     frame_size, (long long)span64, asr::AUDIO_STREAM_MAX_LDS);
     if (state_cap < plan.state_len())
-        return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: a state of %lld floats per stream, %lld are needed",
+        return STREAM_FAIL(ASR_ERR_INVALID, "a state of %lld floats per stream, %lld are needed",
                     (long long)state_cap, (long long)plan.state_len());
     if (n_streams == 0) return ASR_OK;
     if (!block_offsets || !block_counts || !samples_before || !final_flags || !first_frames || !n_new_frames ||
         !out_offsets || !state_offsets)
-        return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: NULL argument");
+        return STREAM_FAIL(ASR_ERR_INVALID, "NULL argument");
     const int n = n_streams;
     const size_t b_first = ((size_t)n + 1) * 8, b_rows = (size_t)n * sizeof(asr::StreamRow), b_win = (size_t)frame_size * 4,
                  b_i = (size_t)n_filters * 4, b_w = (size_t)std::max<int64_t>(total_w, 1) * 4;
@@ -434,14 +453,14 @@ int asr_audio_stream_push_dev(asr_ctx *ctx, const float *blocks_dev, int64_t blo
     for (int i = 0; i < n; ++i) {
         const int64_t n0 = samples_before[i], cnt = block_counts[i];
         if (n0 < 0 || cnt < 0 || block_offsets[i] < 0 || cnt > blocks_floats || block_offsets[i] > blocks_floats - cnt)
-            return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: stream %d: block of %lld samples at %lld (after %lld) "
+            return STREAM_FAIL(ASR_ERR_INVALID, "stream %d: block of %lld samples at %lld (after %lld) "
                         "outside the %lld-float buffer", i, (long long)cnt, (long long)block_offsets[i], (long long)n0,
                         (long long)blocks_floats);
         if (n0 > max_count || cnt > max_count - n0)
-            return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: stream %d: %lld + %lld samples x %d overflow", i,
+            return STREAM_FAIL(ASR_ERR_INVALID, "stream %d: %lld + %lld samples x %d overflow", i,
                         (long long)n0, (long long)cnt, up);
         if (state_offsets[i] < 0 || state_cap > state_floats || state_offsets[i] > state_floats - state_cap)
-            return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: stream %d: state of %lld floats at %lld outside the "
+            return STREAM_FAIL(ASR_ERR_INVALID, "stream %d: state of %lld floats at %lld outside the "
                         "%lld-float buffer", i, (long long)state_cap, (long long)state_offsets[i], (long long)state_floats);
         ranges[i] = {state_offsets[i], i};
         const int64_t n1 = n0 + cnt;
@@ -449,13 +468,13 @@ int asr_audio_stream_push_dev(asr_ctx *ctx, const float *blocks_dev, int64_t blo
         const int64_t f1 = final_flags[i] ? std::max(f0, (int64_t)std::ceil((double)plan.length(n1) / hop))
                                           : plan.complete_frames(plan.final_outputs(n1));
         if (first_frames[i] != f0 || n_new_frames[i] != f1 - f0)
-            return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: stream %d: %lld new frames from frame %lld stated, %lld "
+            return STREAM_FAIL(ASR_ERR_INVALID, "stream %d: %lld new frames from frame %lld stated, %lld "
                         "+ %lld samples%s give %lld from %lld", i, (long long)n_new_frames[i], (long long)first_frames[i],
                         (long long)n0, (long long)cnt, final_flags[i] ? " (flushed)" : "", (long long)(f1 - f0),
                         (long long)f0);
         if (out_offsets[i] < 0 || (f1 - f0) > out_floats / n_filters ||
             out_offsets[i] > out_floats - (f1 - f0) * (int64_t)n_filters)
-            return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: stream %d: %lld frames at %lld outside the %lld-float "
+            return STREAM_FAIL(ASR_ERR_INVALID, "stream %d: %lld frames at %lld outside the %lld-float "
                         "output", i, (long long)(f1 - f0), (long long)out_offsets[i], (long long)out_floats);
         asr::StreamRow &r = rows[i];
         r.n0 = n0; r.n1 = n1;
@@ -465,7 +484,7 @@ int asr_audio_stream_push_dev(asr_ctx *ctx, const float *blocks_dev, int64_t blo
         r.y_len = plan.length(n1);
         r.block_off = block_offsets[i]; r.state_off = state_offsets[i]; r.out_off = out_offsets[i];
         if (r.keep1 < r.keep0 || r.n1 - r.keep1 > state_cap || r.n0 - r.keep0 > state_cap)
-            return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: stream %d: the state would hold samples %lld .. %lld "
+            return STREAM_FAIL(ASR_ERR_INVALID, "stream %d: the state would hold samples %lld .. %lld "
                         "(before: from %lld) in %lld floats", i, (long long)r.keep1, (long long)r.n1, (long long)r.keep0,
                         (long long)state_cap);
         moves = moves || cnt > 0 || r.keep1 != r.keep0;
@@ -476,14 +495,14 @@ int asr_audio_stream_push_dev(asr_ctx *ctx, const float *blocks_dev, int64_t blo
     std::sort(ranges.begin(), ranges.end());
     for (int i = 1; i < n; ++i)
         if (ranges[i].first < ranges[i - 1].first + state_cap)
-            return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: the states of streams %d and %d overlap (%lld floats at "
+            return STREAM_FAIL(ASR_ERR_INVALID, "the states of streams %d and %d overlap (%lld floats at "
                         "%lld and at %lld)", ranges[i - 1].second, ranges[i].second, (long long)state_cap,
                         (long long)ranges[i - 1].first, (long long)ranges[i].first);
     if (total > 0x7fffffffLL)
-        return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: %lld frames in one call", (long long)total);
+        return STREAM_FAIL(ASR_ERR_INVALID, "%lld frames in one call", (long long)total);
     if (total == 0 && !moves) return ASR_OK;
     if (!blocks_dev || !state_dev || (total && !out_dev))
-        return fail(ctx, ASR_ERR_INVALID, "audio_stream_push: NULL argument");
+        return STREAM_FAIL(ASR_ERR_INVALID, "NULL argument");
     char *t = tab.data() + b_first + b_rows;
     memcpy(t, window, b_win);
     memcpy(t + b_win, fb_start, b_i);
@@ -511,6 +530,10 @@ int asr_audio_stream_push_dev(asr_ctx *ctx, const float *blocks_dev, int64_t blo
         ASR_HIP(ctx, hipMemcpy(ctx->stream_taps, taps_phase_major, n_taps * 8, hipMemcpyHostToDevice));
         ctx->stream_taps_host.assign(taps_phase_major, taps_phase_major + n_taps);
     }
+    if (fft) {                                                      // the twiddle table, whichever FFT call came first
+        rc = specfft_workspace(ctx, specfft_twiddles().size() * 4);
+        if (rc != ASR_OK) return rc;
+    }
     char *d = (char *)ctx->stream_ws;
     const int64_t *d_first = (const int64_t *)d;
     const asr::StreamRow *d_rows = (const asr::StreamRow *)(d + b_first);
@@ -522,41 +545,85 @@ int asr_audio_stream_push_dev(asr_ctx *ctx, const float *blocks_dev, int64_t blo
     if (e == hipSuccess && total) {
         const asr::StreamResample r{up, down, plan.half, plan.T, (int)span64, round_int16 ? 1 : 0,
                                     native ? nullptr : ctx->stream_taps};
-        ProfScope ps(ctx, "audio_stream_frames", 0,
-                     (4.0 * frame_size * (double)max_bin + (native ? 0.0 : 2.0 * taps_per_phase * frame_size)) * (double)total,
-                     4.0 * (double)(native ? frame_size : span64) * (double)total);
-        // fewer frames than CUs: split a frame's filters over workgroups of about 192 DFT bins each (a lane then sums one
-        // bin, not three), balanced by the filters' bin counts, as long as every part of every frame still finds a CU
-        asr::StreamParts parts{};
-        const int64_t want = std::min<int64_t>({(int64_t)asr::STREAM_MAX_PARTS, (int64_t)(max_bin + 191) / 192,
-                                                (int64_t)ctx->num_cus / total, (int64_t)n_filters});
-        const char *env = getenv("ASR_STREAM_PARTS");                   // debug: force the number of parts (1 .. 8)
-        const int n_parts = (int)std::max<int64_t>(1, env ? std::min<int64_t>({(int64_t)atoi(env), (int64_t)asr::STREAM_MAX_PARTS,
-                                                                               (int64_t)n_filters}) : want);
-        parts.n = n_parts;
-        int f = 0;
-        for (int p = 0; p < n_parts; ++p) {
-            parts.f[p] = f;
-            const int64_t upto = total_w * (p + 1) / n_parts;           // weights (= bins read) up to the end of part p
-            while (f < n_filters && (p == n_parts - 1 || off[f] + fb_len[f] <= upto || f == parts.f[p])) ++f;
-            parts.k0[p] = parts.k1[p] = 0;
-            for (int q = parts.f[p]; q < f; ++q) {
-                if (q == parts.f[p] || fb_start[q] < parts.k0[p]) parts.k0[p] = fb_start[q];
-                parts.k1[p] = std::max(parts.k1[p], fb_start[q] + fb_len[q]);
+        if (fft) {
+            // 5 passes of 1024 complex values at about 8.5 FLOP per value, the post-pass, the filterbank, the resampler
+            ProfScope ps(ctx, "audio_stream_fft_frames", 0,
+                         (5.0 * 1024 * 8.5 + 1024 * 16.0 + 2.0 * total_w + (native ? 0.0 : 2.0 * taps_per_phase * frame_size)) *
+                             (double)total,
+                         4.0 * (double)(native ? frame_size : span64) * (double)total);
+            e = asr::launch_audio_stream_fft_frames(ctx->stream, blocks_dev, state_dev, d_first, d_rows, n, total, r,
+                                                    (const float *)ctx->specfft_ws, d_win, hop, d_start, d_len, d_off, d_w,
+                                                    n_filters, mul, add, out_dev, transposed);
+        } else {
+            ProfScope ps(ctx, "audio_stream_frames", 0,
+                         (4.0 * frame_size * (double)max_bin + (native ? 0.0 : 2.0 * taps_per_phase * frame_size)) * (double)total,
+                         4.0 * (double)(native ? frame_size : span64) * (double)total);
+            // fewer frames than CUs: split a frame's filters over workgroups of about 192 DFT bins each (a lane then sums one
+            // bin, not three), balanced by the filters' bin counts, as long as every part of every frame still finds a CU
+            asr::StreamParts parts{};
+            const int64_t want = std::min<int64_t>({(int64_t)asr::STREAM_MAX_PARTS, (int64_t)(max_bin + 191) / 192,
+                                                    (int64_t)ctx->num_cus / total, (int64_t)n_filters});
+            const char *env = getenv("ASR_STREAM_PARTS");                   // debug: force the number of parts (1 .. 8)
+            const int n_parts = (int)std::max<int64_t>(1, env ? std::min<int64_t>({(int64_t)atoi(env), (int64_t)asr::STREAM_MAX_PARTS,
+                                                                                   (int64_t)n_filters}) : want);
+            parts.n = n_parts;
+            int f = 0;
+            for (int p = 0; p < n_parts; ++p) {
+                parts.f[p] = f;
+                const int64_t upto = total_w * (p + 1) / n_parts;           // weights (= bins read) up to the end of part p
+                while (f < n_filters && (p == n_parts - 1 || off[f] + fb_len[f] <= upto || f == parts.f[p])) ++f;
+                parts.k0[p] = parts.k1[p] = 0;
+                for (int q = parts.f[p]; q < f; ++q) {
+                    if (q == parts.f[p] || fb_start[q] < parts.k0[p]) parts.k0[p] = fb_start[q];
+                    parts.k1[p] = std::max(parts.k1[p], fb_start[q] + fb_len[q]);
+                }
             }
+            parts.f[n_parts] = n_filters;
+            e = asr::launch_audio_stream_frames(ctx->stream, blocks_dev, state_dev, d_first, d_rows, n, total, r, parts, d_win,
+                                                frame_size, hop, max_bin, d_start, d_len, d_off, d_w, n_filters, mul, add,
+                                                out_dev, transposed);
         }
-        parts.f[n_parts] = n_filters;
-        e = asr::launch_audio_stream_frames(ctx->stream, blocks_dev, state_dev, d_first, d_rows, n, total, r, parts, d_win,
-                                            frame_size, hop, max_bin, d_start, d_len, d_off, d_w, n_filters, mul, add,
-                                            out_dev, transposed);
     }
     if (e == hipSuccess && moves) {
         ProfScope ps(ctx, "audio_stream_carry", 0, 0.0, 8.0 * (double)plan.state_len() * n);
         e = asr::launch_audio_stream_carry(ctx->stream, blocks_dev, state_dev, d_rows, n);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "audio_stream_push: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return STREAM_FAIL(ASR_ERR_HIP, "%s", hipGetErrorString(e));
     return mark_main(ctx);
+}
+#undef STREAM_FAIL
+
+int asr_audio_stream_push_dev(asr_ctx *ctx, const float *blocks_dev, int64_t blocks_floats, const int64_t *block_offsets,
+                              const int64_t *block_counts, const int64_t *samples_before, const int32_t *final_flags,
+                              const int64_t *first_frames, const int64_t *n_new_frames, const int64_t *out_offsets,
+                              int n_streams, int up, int down, const double *taps_phase_major, int taps_per_phase,
+                              int half, int round_int16, float *state_dev, int64_t state_floats,
+                              const int64_t *state_offsets, int64_t state_cap, int frame_size, double hop,
+                              const float *window, const int32_t *fb_start, const int32_t *fb_len,
+                              const float *fb_weights, int n_filters, float mul, float add, int transposed,
+                              float *out_dev, int64_t out_floats) {
+    return audio_stream_push(ctx, false, "audio_stream_push", blocks_dev, blocks_floats, block_offsets, block_counts,
+                             samples_before, final_flags, first_frames, n_new_frames, out_offsets, n_streams, up, down,
+                             taps_phase_major, taps_per_phase, half, round_int16, state_dev, state_floats, state_offsets,
+                             state_cap, frame_size, hop, window, fb_start, fb_len, fb_weights, n_filters, mul, add,
+                             transposed, out_dev, out_floats);
+}
+
+int asr_audio_stream_push_fft_dev(asr_ctx *ctx, const float *blocks_dev, int64_t blocks_floats,
+                                  const int64_t *block_offsets, const int64_t *block_counts,
+                                  const int64_t *samples_before, const int32_t *final_flags, const int64_t *first_frames,
+                                  const int64_t *n_new_frames, const int64_t *out_offsets, int n_streams, int up, int down,
+                                  const double *taps_phase_major, int taps_per_phase, int half, int round_int16,
+                                  float *state_dev, int64_t state_floats, const int64_t *state_offsets, int64_t state_cap,
+                                  int frame_size, double hop, const float *window, const int32_t *fb_start,
+                                  const int32_t *fb_len, const float *fb_weights, int n_filters, float mul, float add,
+                                  int transposed, float *out_dev, int64_t out_floats) {
+    return audio_stream_push(ctx, true, "audio_stream_push_fft", blocks_dev, blocks_floats, block_offsets, block_counts,
+                             samples_before, final_flags, first_frames, n_new_frames, out_offsets, n_streams, up, down,
+                             taps_phase_major, taps_per_phase, half, round_int16, state_dev, state_floats, state_offsets,
+                             state_cap, frame_size, hop, window, fb_start, fb_len, fb_weights, n_filters, mul, add,
+                             transposed, out_dev, out_floats);
 }
 
 int asr_resize_pages_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,

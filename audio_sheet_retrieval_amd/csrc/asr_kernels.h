@@ -409,6 +409,17 @@ hipError_t launch_audio_stream_frames(hipStream_t s, const float *blocks, const 
                                       const float *fb_w, int nf, float mul, float add, float *out, int transposed);
 hipError_t launch_audio_stream_carry(hipStream_t s, const float *blocks, float *state, const StreamRow *rows,
                                      int n_streams);
+// the same frames with the magnitudes from the real-input FFT (audio_stream_fft_kernels.hip; frame_size 2048 only): stage 1
+// as launch_audio_stream_frames, then the frame plan of launch_spectrogram_fft_batch (twiddles, window: as there) - per
+// frame bit-identical with it on the resampled recording.  One workgroup per frame, no split; the state is slid by
+// launch_audio_stream_carry.  Its LDS never exceeds audio_stream_lds at the same span.
+size_t audio_stream_fft_lds(int span);
+hipError_t launch_audio_stream_fft_frames(hipStream_t s, const float *blocks, const float *state,
+                                          const int64_t *frame_first, const StreamRow *rows, int n_streams,
+                                          int64_t total_frames, const StreamResample &r, const float *twiddles,
+                                          const float *window, double hop, const int32_t *fb_start, const int32_t *fb_len,
+                                          const int32_t *fb_off, const float *fb_w, int nf, float mul, float add,
+                                          float *out, int transposed);
 // score pages at another resolution (page_resize_kernels.hip): exact integer area resampling, one 64-thread workgroup
 // per tile of RESIZE_TILE_H x RESIZE_TILE_W output pixels of one page.  tile_first (n_pages + 1 running tile counts) and
 // the page table on the device.  A tile stages its source rows in RESIZE_LDS_BYTES of LDS, chunk by chunk; one row of a

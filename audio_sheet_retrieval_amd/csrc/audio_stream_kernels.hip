@@ -21,24 +21,18 @@
 //                               (into registers), then a barrier, then written.  It runs after the frame kernel on the
 //                               same stream.
 //
-// The sum of a resampled sample starts at 0.0 and runs over t = 0 .. T-1 in ascending order, one rounding per product and
-// one per sum.  This file is built with the default flags, as piece_vote_kernels.hip is (spectrogram_frame's
-// re * re + im * im and mul * s + add are contracted there, and the stream has to reproduce those bits), so the loop of
-// the sum alone is compiled under `#pragma clang fp contract(off)`.  (__dmul_rn / __dadd_rn would not do: this toolchain
-// defines them as plain `*` and `+`, which the default flags fuse into v_fmac_f64, and a float64 tap times a float32
-// sample is not exact in float64.)  Every index product is int64.
+// The staging and the resampling are audio_stream_stage.h's, shared with the FFT route of the stream
+// (audio_stream_fft_kernels.hip); the note on the flags of the resampler's sum is there.  This file is built with the
+// default flags, as piece_vote_kernels.hip is (spectrogram_frame's re * re + im * im and mul * s + add are contracted
+// there, and the stream has to reproduce those bits).
 //
 // LDS of the frame kernel, in floats: [ max(3 * frame_size, span) | frame_size | max_bin ].  The staged inputs (span) share
 // their place with the windowed frame and the twiddle table, which are written after the resampling is done.
 #include "asr_kernels.h"
+#include "audio_stream_stage.h"
 #include "spectrogram_frame.h"
 
 namespace asr {
-
-__device__ __forceinline__ float stream_input(const StreamRow &w, const float *st, const float *bl, int64_t j) {
-    if (j < w.keep0 || j >= w.n1) return 0.0f;                     // keep0 >= 0: also every index before the stream
-    return j < w.n0 ? st[j - w.keep0] : bl[j - w.n0];
-}
 
 template <bool UP1>
 __global__ __launch_bounds__(256) void audio_stream_frame_kernel(SpecArgs a, const float *__restrict__ blocks,
@@ -47,64 +41,18 @@ __global__ __launch_bounds__(256) void audio_stream_frame_kernel(SpecArgs a, con
                                                                  const StreamRow *__restrict__ rows, int n_streams,
                                                                  StreamResample r, StreamParts parts) {
     extern __shared__ __attribute__((aligned(16))) float sl[];
-    constexpr int PER = 4;
-    const int F = a.frame_size, T = r.taps_per_phase;
+    const int F = a.frame_size;
     const int head = 3 * F > r.span ? 3 * F : r.span;
     float *x = sl, *tc = sl + F, *ts = sl + 2 * F, *xs = sl, *ys = sl + head, *mag = ys + F;
     const int64_t g = blockIdx.x / parts.n;                         // the frame; the workgroup takes part blockIdx.x % n of it
     const int part = blockIdx.x % parts.n;
-    int lo = 0, hi = n_streams - 1;                                 // last s with frame_first[s] <= g
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (frame_first[mid] <= g) lo = mid; else hi = mid - 1;
-    }
+    const int lo = stream_of_frame(frame_first, n_streams, g);
     const StreamRow w = rows[lo];
     const int64_t col = g - frame_first[lo];
     const int64_t frame = w.first_frame + col;
     const int64_t start = (int64_t)((double)frame * a.hop);        // spectrogram_frame's
-    const float *st = state + w.state_off, *bl = blocks + w.block_off;
-    if (!r.taps) {                                                  // the front-end's own rate: y = x
-        for (int t = threadIdx.x; t < F; t += 256) ys[t] = stream_input(w, st, bl, start + t);
-    } else {
-        const int64_t base = (start * r.down + r.half) / r.up - (T - 1);   // first input the frame's first sample reads
-        for (int i = threadIdx.x; i < r.span; i += 256) xs[i] = stream_input(w, st, bl, base + i);
-        __syncthreads();
-        for (int t0 = 0; t0 < F; t0 += 256 * PER) {
-            int rel[PER];                                           // j0 - base of the lane's samples
-            const double *tp[PER];
-            double acc[PER];
-#pragma unroll
-            for (int k = 0; k < PER; ++k) {
-                // samples past the end of the frame are computed on its last one and not stored
-                const int t = min(t0 + (int)threadIdx.x + 256 * k, F - 1);
-                const int64_t c = (start + t) * r.down + r.half;
-                rel[k] = (int)(c / r.up - base);
-                tp[k] = UP1 ? r.taps : r.taps + (c % r.up) * T;
-                acc[k] = 0.0;
-            }
-            for (int t = 0; t < T; ++t) {
-#pragma clang fp contract(off)
-#pragma unroll
-                for (int k = 0; k < PER; ++k) {
-                    const double prod = tp[k][t] * (double)xs[rel[k] - t];
-                    acc[k] = acc[k] + prod;
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < PER; ++k) {
-                const int t = t0 + (int)threadIdx.x + 256 * k;
-                if (t >= F) continue;
-                double v = acc[k];
-                if (r.round_int16) {                                // np.clip(np.rint(v), -32768, 32767): a NaN stays one
-                    v = rint(v);
-                    v = v < -32768.0 ? -32768.0 : v;
-                    v = v > 32767.0 ? 32767.0 : v;
-                }
-                ys[t] = start + t < w.y_len ? (float)v : 0.0f;      // the recording ends at y_len: zeros from there on
-            }
-        }
-        __syncthreads();                                            // xs is read no more: the twiddles take its place
-    }
+    stream_resample_frame<UP1>(w, state + w.state_off, blocks + w.block_off, start, F, r, xs, ys);
+    // xs is read no more: the twiddles take its place
     spectrogram_twiddles(F, tc, ts);
     spectrogram_frame(a, ys, start, start + F, frame, a.out + w.out_off, col, w.n_new, x, tc, ts, mag, parts.f[part],
                       parts.f[part + 1], parts.k0[part], parts.k1[part]);

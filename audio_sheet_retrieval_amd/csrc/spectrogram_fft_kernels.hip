@@ -32,47 +32,12 @@
 // is decided at compile time, every frame runs the same instructions on its own 2048 samples and no sum crosses a frame,
 // so a recording's result cannot depend on the batch, its order or `transposed` with either setting;
 // -ffp-contract=off would only add roundings to the complex products.
+// The passes, the post-pass and the filterbank are in spectrogram_fft_frame.h, which the streamed route
+// (audio_stream_fft_kernels.hip) includes too.
 #include "asr_kernels.h"
+#include "spectrogram_fft_frame.h"      // the frame body: fft_lane_tables, fft_frame_magnitudes, fft_frame_filterbank
 
 namespace asr {
-
-namespace {
-
-constexpr int FFT_BUF = 1024 + 256;      // complex values per buffer: 1024 and the padding of i + (i >> 2)
-
-template <int SH> __device__ __forceinline__ int fft_pad(int i) { return SH ? i + (i >> SH) : i; }
-
-__device__ __forceinline__ float2 cmul(float2 a, float2 w) {
-    return make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x);
-}
-
-// one radix-4 pass of lane tid on v (in[tid + 256 k]); stride S = 1 << LOG_S; the results go to dst, value i at
-// fft_pad<PAD>(i)
-template <int LOG_S, int PAD>
-__device__ __forceinline__ void fft_pass(const float2 (&v)[4], const float2 *w, float2 *dst, int tid) {
-    constexpr int S = 1 << LOG_S;
-    const float2 apc = make_float2(v[0].x + v[2].x, v[0].y + v[2].y), amc = make_float2(v[0].x - v[2].x, v[0].y - v[2].y);
-    const float2 bpd = make_float2(v[1].x + v[3].x, v[1].y + v[3].y), bmd = make_float2(v[1].x - v[3].x, v[1].y - v[3].y);
-    float2 y0 = make_float2(apc.x + bpd.x, apc.y + bpd.y);
-    float2 y1 = make_float2(amc.x + bmd.y, amc.y - bmd.x);          // (v0 - v2) - i (v1 - v3)
-    float2 y2 = make_float2(apc.x - bpd.x, apc.y - bpd.y);
-    float2 y3 = make_float2(amc.x - bmd.y, amc.y + bmd.x);          // (v0 - v2) + i (v1 - v3)
-    if (S < 256) {
-        y1 = cmul(y1, w[0]); y2 = cmul(y2, w[1]); y3 = cmul(y3, w[2]);
-    }
-    const int base = (tid & (S - 1)) + 4 * S * (tid >> LOG_S);
-    dst[fft_pad<PAD>(base)] = y0;
-    dst[fft_pad<PAD>(base + S)] = y1;
-    dst[fft_pad<PAD>(base + 2 * S)] = y2;
-    dst[fft_pad<PAD>(base + 3 * S)] = y3;
-}
-
-template <int PAD> __device__ __forceinline__ void fft_read(float2 (&v)[4], const float2 *src, int tid) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = src[fft_pad<PAD>(tid + 256 * k)];
-}
-
-}  // namespace
 
 struct SpecFftArgs {
     const float *samples;                           // base of the concatenated recordings
@@ -90,20 +55,8 @@ __global__ __launch_bounds__(256) void spectrogram_fft_batch_kernel(SpecFftArgs 
     __shared__ float2 buf_a[FFT_BUF], buf_b[FFT_BUF];
     __shared__ float mag[1024];
     const int tid = threadIdx.x;
-    // what depends on the lane only: its window values, the twiddles of the four multiplying passes and of the post-pass
-    float2 win[4], w0[3], w1[3], w2[3], w3[3], wp[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        win[k] = a.window[tid + 256 * k];
-        wp[k] = a.tw[tid + 256 * k];
-    }
-#pragma unroll
-    for (int k = 1; k < 4; ++k) {
-        w0[k - 1] = a.tw[2 * tid * k];                  // S = 1:  p = tid,      2 S p k <= 1530
-        w1[k - 1] = a.tw[8 * (tid >> 2) * k];           // S = 4:  p = tid / 4
-        w2[k - 1] = a.tw[32 * (tid >> 4) * k];          // S = 16: p = tid / 16
-        w3[k - 1] = a.tw[128 * (tid >> 6) * k];         // S = 64: p = tid / 64
-    }
+    FftLane l;                                  // the lane's 8 window values and 16 twiddles, kept for all its frames
+    fft_lane_tables(l, a.tw, a.window, tid);
     for (int64_t g = blockIdx.x; g < a.total_frames; g += gridDim.x) {
         int lo = 0, hi = a.n_rec - 1;                               // last r with frame_first[r] <= g
         while (lo < hi) {
@@ -122,43 +75,13 @@ __global__ __launch_bounds__(256) void spectrogram_fft_batch_kernel(SpecFftArgs 
             const int64_t i = start + 2 * (tid + 256 * k);
             const float x0 = i < n_samples ? samples[i] : 0.0f;
             const float x1 = i + 1 < n_samples ? samples[i + 1] : 0.0f;
-            v[k] = make_float2(x0 * win[k].x, x1 * win[k].y);
+            v[k] = make_float2(x0 * l.win[k].x, x1 * l.win[k].y);
         }
-        fft_pass<0, 4>(v, w0, buf_a, tid);
-        __syncthreads();
-        fft_read<4>(v, buf_a, tid);
-        fft_pass<2, 2>(v, w1, buf_b, tid);
-        __syncthreads();
-        fft_read<2>(v, buf_b, tid);
-        fft_pass<4, 0>(v, w2, buf_a, tid);
-        __syncthreads();
-        fft_read<0>(v, buf_a, tid);
-        fft_pass<6, 0>(v, w3, buf_b, tid);
-        __syncthreads();
-        fft_read<0>(v, buf_b, tid);
-        fft_pass<8, 0>(v, w3, buf_a, tid);                          // p = 0: the twiddles are not used
-        __syncthreads();
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const int k = tid + 256 * m;
-            const float2 zk = buf_a[k], zn = buf_a[(1024 - k) & 1023];
-            const float2 s = make_float2(zk.x + zn.x, zk.y - zn.y);             // Z[k] + conj Z[N - k]
-            const float2 t = cmul(make_float2(zk.x - zn.x, zk.y + zn.y), wp[m]);    // W^k (Z[k] - conj Z[N - k])
-            const float re = s.x + t.y, im = s.y - t.x;                         // ... - i t
-            mag[k] = 0.5f * sqrtf(re * re + im * im);
-        }
-        __syncthreads();
-        for (int f = tid; f < a.nf; f += 256) {
-            const float *w = a.fb_w + a.fb_off[f];
-            const int b0 = a.fb_start[f];
-            float s = 0.0f;
-            for (int q = 0; q < a.fb_len[f]; ++q) s = fmaf(mag[b0 + q], w[q], s);
-            const float r = log10f(a.mul * s + a.add);
-            if (a.transposed) out[(int64_t)f * n_frames + frame] = r;
-            else out[frame * a.nf + f] = r;
-        }
+        fft_frame_magnitudes(v, l, buf_a, buf_b, mag, tid);
+        fft_frame_filterbank(mag, a.fb_start, a.fb_len, a.fb_off, a.fb_w, a.nf, a.mul, a.add, out, n_frames, frame,
+                             a.transposed, tid);
         // the next frame writes buf_a before its first barrier and mag after its fifth: buf_a was last read before the
-        // barrier above, mag is read here - no further barrier needed
+        // last barrier of fft_frame_magnitudes, mag is read here - no further barrier needed
     }
 }
 

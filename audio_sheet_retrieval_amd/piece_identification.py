@@ -878,7 +878,7 @@ def _concat_track_results(parts, id_to_name, top_k, n_candidates):
 
 def live_track_scores(engine, sheet_db, processor, recordings, sample_rates, block_samples, levels=None, top_k=5,
                       n_candidates=5, running_frames=100, spec_shape=(92, 42), integer=None, window_scales=None,
-                      batched=False):
+                      batched=False, dft=None):
     """The live server from the samples on: every recording (mono samples at sample_rates[i]) is cut into blocks of
     block_samples input samples (an int, or one per recording) and pushed block by block through an
     audio_frontend.AudioStream - all recordings of one (rate, integer, window scale) group as parallel streams of one
@@ -888,7 +888,9 @@ def live_track_scores(engine, sheet_db, processor, recordings, sample_rates, blo
     levels.  levels: per recording the normaliser of the music gate; None takes spec.sum(axis=0).max() of the finished
     spectrogram, as track_scores does - which means computing that spectrogram first: a real stream cannot, and must be
     given a level.  batched=True: the columns of a group stay on the device (AudioStream.push_dev / flush_dev) and one
-    PieceTrackerBank takes the place of the group's trackers - the same results, a fixed number of calls per round."""
+    PieceTrackerBank takes the place of the group's trackers - the same results, a fixed number of calls per round.
+    dft: AudioStream's argument, for either branch - None for a dft="direct" processor, "fft" for a dft="fft" processor,
+    whose streams compute the FFT and whose results equal track_scores on that processor's process_many."""
     from .audio_frontend import AudioStream
     recs = [np.ascontiguousarray(r, dtype=np.float32).ravel() for r in recordings]
     n = len(recs)
@@ -916,7 +918,7 @@ def live_track_scores(engine, sheet_db, processor, recordings, sample_rates, blo
         else:
             trackers = [PieceTracker(engine, sheet_db, levels[i], top_k, n_candidates, running_frames, spec_shape)
                         for i in sel]
-        stream = AudioStream(processor, len(sel), key[0], key[1], key[2])
+        stream = AudioStream(processor, len(sel), key[0], key[1], key[2], dft)
 
         def track_dev(handle):
             try:

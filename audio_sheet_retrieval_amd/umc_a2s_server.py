@@ -6,7 +6,7 @@ umc_a2s_server.py (:178-189):
         --train_split splits/all_split.yaml --config exp_configs/mutopia_full_aug.yaml \
         --init_sheet_db --full_eval --dump_results [--real_perf] [--n_candidates 25] [--estimate_UV] \
         --system_params system_params.pkl --bar_params bar_params.pkl [--device_post] [--resample] [--page_width 835]
-        [--deskew] [--live [--bank] [--block_ms 100] [--running_frames 100]]
+        [--deskew] [--live [--bank] [--live_dft direct|fft] [--block_ms 100] [--running_frames 100]]
 
 <dir> holds one folder per piece: sheet/*.png (the page scans), score_ppq.* (the synthesised recording) and, for
 --real_perf, 01_performance*.  The pages go through the two segmentation networks (their parameter pickles:
@@ -41,6 +41,9 @@ the first frame at which the piece leads and the share of voiced frames at which
 music gate is taken from the finished spectrogram, as --track of audio_sheet_server does; a microphone has to be given one.
 --bank (with --live) tracks all recordings of one sample rate with one piece_identification.PieceTrackerBank, whose
 state stays on the device (live_track_scores(batched=True)): the same printout and the same file.
+--live_dft fft (with --live; default direct) computes the streamed frames with the real-input FFT
+(asr_audio_stream_push_fft_dev): the processor is built with dft="fft" and its streams are asked for by that name, so the
+tracking equals track_scores on that processor's spectrograms.  --fast_dft stays a flag of the offline routes.
 """
 import argparse
 import os
@@ -90,12 +93,18 @@ def _arguments(argv, direction):
         p.add_argument("--bank", action="store_true",
                        help="--live with one PieceTrackerBank per sample rate in place of a PieceTracker per recording: "
                             "the trackers' state stays on the device (live_track_scores(batched=True))")
+        p.add_argument("--live_dft", choices=("direct", "fft"), default="direct",
+                       help="--live: the transform of the streamed front-end - the direct DFT, or the real-input FFT "
+                            "(asr_audio_stream_push_fft_dev; SpectrogramProcessor(dft=\"fft\").stream(dft=\"fft\"))")
         p.add_argument("--block_ms", type=float, default=100.0, help="milliseconds of audio per block (--live)")
         p.add_argument("--running_frames", type=int, default=100,
                        help="voiced frames in the history of the running vote (--live)")
     args = p.parse_args(argv)
     if args.fast_dft and getattr(args, "live", False):
-        p.error("--fast_dft with --live: the streamed front-end computes the direct DFT only")
+        p.error("--fast_dft with --live: the streamed front-end computes the direct DFT unless --live_dft fft asks for "
+                "its FFT")
+    if getattr(args, "live_dft", "direct") != "direct" and not args.live:
+        p.error("--live_dft needs --live: it chooses the transform of the streamed front-end")
     if getattr(args, "bank", False) and not args.live:
         p.error("--bank needs --live: it chooses how the streamed recordings are tracked")
     return args
@@ -107,9 +116,9 @@ def tracking_file(param_file, dset, real_perf=False):
 
 
 def live_track(engine, db, processor, piece_paths, names, audio_file, n_candidates, running_frames, block_ms,
-               batched=False):
+               batched=False, dft=None):
     """the recordings of `piece_paths`, streamed in blocks of block_ms milliseconds -> (names, first_lead, lead_share) as
-    audio_sheet_server.track"""
+    audio_sheet_server.track.  dft: live_track_scores' ("fft" with a dft="fft" processor)"""
     from .audio_frontend import read_audio
     recs, scales, rates, integer = [], [], [], []
     for piece_path in piece_paths:
@@ -121,7 +130,7 @@ def live_track(engine, db, processor, piece_paths, names, audio_file, n_candidat
     steps = [max(1, int(round(rate * block_ms / 1000.0))) for rate in rates]
     results = live_track_scores(engine, db, processor, recs, rates, steps, None, top_k=TRACK_TOP_K,
                                 n_candidates=n_candidates, running_frames=running_frames, integer=integer,
-                                window_scales=scales, batched=batched)
+                                window_scales=scales, batched=batched, dft=dft)
     ids = {name: i for i, name in db.id_to_name.items()}
     first_lead, lead_share = [], []
     for name, res in zip(names, results):
@@ -155,7 +164,8 @@ def run(argv, direction):
         dset = os.path.basename(args.data_dir)
         audio_file = "01_performance" if args.real_perf else "score_ppq"
         engine, param_file = audio2sheet_align.load_network(args.model, args.estimate_UV, args.train_split, args.config)
-        processor = SpectrogramProcessor(engine, dft="fft" if args.fast_dft else "direct")
+        live_fft = getattr(args, "live_dft", "direct") == "fft"
+        processor = SpectrogramProcessor(engine, dft="fft" if args.fast_dft or live_fft else "direct")
         if direction == "A2S":
             # a piece without the recording is left out of the ranks
             queried = []
@@ -187,7 +197,7 @@ def run(argv, direction):
                 names = [te_pieces[i] for i in queried]
                 return report_tracking(*live_track(engine, db, processor, [piece_paths[i] for i in queried], names,
                                                    audio_file, args.n_candidates, args.running_frames, args.block_ms,
-                                                   batched=args.bank),
+                                                   batched=args.bank, dft="fft" if live_fft else None),
                                        res_file=tracking_file(param_file, dset, args.real_perf) if args.dump_results
                                        else None)
             if not args.full_eval:

@@ -897,7 +897,8 @@ int asr_bars_from_map_dev(asr_ctx *ctx, const double *maps_dev, const int32_t *h
  *                more than asr_spectrogram_batch_dev's does on the same input (tests/test_gpu_spectrogram_fft.py)
  *     bit for bit  a recording's output does not depend on which other recordings are in the call, on their order or
  *                on `transposed` (the two layouts are exact transposes), and repeated calls agree.  It is NOT
- *                bit-identical with asr_spectrogram_batch_dev or asr_audio_stream_push_dev.
+ *                bit-identical with asr_spectrogram_batch_dev or asr_audio_stream_push_dev; the stream that reproduces
+ *                its bits is asr_audio_stream_push_fft_dev.
  *   Checked before anything is launched: everything asr_spectrogram_batch_dev checks, frame_size == 2048 (the
  *   reference's only value) and every filter inside bins 0 .. 1023.  A violation returns ASR_ERR_INVALID with a message
  *   and launches nothing.  n_recordings == 0 and recordings of zero samples or zero frames are valid and write nothing;
@@ -967,6 +968,23 @@ int asr_bars_from_map_dev(asr_ctx *ctx, const double *maps_dev, const int32_t *h
  *   message; a failing call touches no state and writes no output.  n_streams == 0 and all-empty blocks are valid and
  *   write nothing.  One workgroup per new frame resamples the frame's own samples (overlapping frames resample the
  *   samples they share once each), then one workgroup per stream slides the state.
+ * asr_audio_stream_push_fft_dev = asr_audio_stream_push_dev, same arguments, state and plan, with the magnitudes of a
+ *   frame taken from the real-input FFT of asr_spectrogram_fft_batch_dev instead of the direct DFT
+ *   (csrc/audio_stream_fft_kernels.hip): asr_resample_batch_dev followed by asr_spectrogram_fft_batch_dev for recordings
+ *   that arrive block by block.
+ *     property   the frames a call emits are bit-identical with the corresponding columns of asr_spectrogram_fft_batch_dev
+ *                on asr_resample_batch_dev of the whole recording (at the front-end's own rate: on the recording itself),
+ *                whatever the cut into calls, whatever the other streams of the call, and in both output layouts (the two
+ *                are exact transposes); before the flush the emitted frames are a prefix of that result.  They are NOT
+ *                bit-identical with asr_audio_stream_push_dev's.
+ *     state      as asr_audio_stream_push_dev: input samples, the same keep_from and the same bound on state_cap, slid by
+ *                the same kernel.  A stream's state does not record which of the two calls wrote it.
+ *   Checked before anything is launched: everything asr_audio_stream_push_dev checks, frame_size == 2048 and every filter
+ *   inside bins [0, 1024).  A frame needs no more LDS than the direct call's at the same ratio, so every ratio that call
+ *   takes (input rates from 4 to 192 kHz) is taken here.  A violation returns ASR_ERR_INVALID with a message that starts
+ *   with "audio_stream_push_fft:"; a failing call touches no state and writes no output.  The twiddle table is the
+ *   context's (asr_spectrogram_fft_batch_dev's); the call puts it on the device where no FFT call has done so before.
+ *   One workgroup per new frame: the filters of a frame are never split over workgroups (ASR_STREAM_PARTS does not apply).
  * asr_resize_pages_dev = what scripts/prepare_umc_data.py:17-22 does to a scan before the OMR networks see it (width
  *   835, height int(835.0 / W * H), cv2.resize), for n_pages pages of any sizes in one launch, between the upload and
  *   asr_seg_predict_dev.  OpenCV's fixed-point bilinear rule is not restated; the yardstick is this definition, exact
@@ -1045,6 +1063,15 @@ int asr_audio_stream_push_dev(asr_ctx *ctx, const float *blocks_dev, int64_t blo
                               const float *window, const int32_t *fb_start, const int32_t *fb_len,
                               const float *fb_weights, int n_filters, float mul, float add, int transposed,
                               float *out_dev, int64_t out_floats);
+int asr_audio_stream_push_fft_dev(asr_ctx *ctx, const float *blocks_dev, int64_t blocks_floats,
+                                  const int64_t *block_offsets, const int64_t *block_counts,
+                                  const int64_t *samples_before, const int32_t *final, const int64_t *first_frames,
+                                  const int64_t *n_new_frames, const int64_t *out_offsets, int n_streams, int up, int down,
+                                  const double *taps_phase_major, int taps_per_phase, int half, int round_int16,
+                                  float *state_dev, int64_t state_floats, const int64_t *state_offsets, int64_t state_cap,
+                                  int frame_size, double hop, const float *window, const int32_t *fb_start,
+                                  const int32_t *fb_len, const float *fb_weights, int n_filters, float mul, float add,
+                                  int transposed, float *out_dev, int64_t out_floats);
 int asr_resize_pages_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
                          const int32_t *heights, const int32_t *widths, int n_pages, const int64_t *out_offsets,
                          const int32_t *out_heights, const int32_t *out_widths, void *out_dev, int64_t out_bytes);
