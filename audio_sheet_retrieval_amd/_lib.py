@@ -45,6 +45,7 @@ EXPORTS = [
     "asr_unroll_systems_dev", "asr_spectrogram_batch_dev", "asr_spectrogram_fft_batch_dev", "asr_resample_batch_dev", "asr_resize_pages_dev",
     "asr_audio_stream_push_dev", "asr_audio_stream_push_fft_dev", "asr_skew_estimate_dev", "asr_deskew_pages_dev",
     "asr_track_stream_gate_dev", "asr_track_stream_vote_dev",
+    "asr_track_gate_running_dev", "asr_track_stream_gate_running_dev",
     "asr_follow_stream_windows_dev", "asr_follow_stream_log_dev",
     "asr_opt_state_size", "asr_get_opt_state", "asr_set_opt_state", "asr_debug_train_tensor", "asr_cca_train_debug",
     "asr_debug_train_candidate",
@@ -211,6 +212,11 @@ def load_library(path=None):
                                               c_int64, c_void_p, c_void_p, c_int64] + [c_void_p] * 3),
         "asr_track_stream_vote_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int,
                                               c_void_p, c_int64, c_int32, c_int, c_void_p, c_int64] + [c_void_p] * 4),
+        "asr_track_gate_running_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int] + [c_void_p] * 3 +
+                                       [c_int, c_int, ctypes.c_float] + [c_void_p] * 3),
+        "asr_track_stream_gate_running_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int] + [c_void_p] * 3 +
+                                              [c_int, ctypes.c_float, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p,
+                                               c_int64, c_void_p, c_void_p, c_int64] + [c_void_p] * 4),
         "asr_follow_stream_windows_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int] + [c_void_p] * 3 +
                                           [c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
         "asr_follow_stream_log_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int,
@@ -584,6 +590,48 @@ class Engine(object):
             int(running_frames), ids_ptr, int(n_db), int(n_pieces), int(top_k), hist_ptr, int(hist_len),
             None if h_off is None else h_off.ctypes.data, pieces.ctypes.data, counts.ctypes.data, n_out.ctypes.data))
         return pieces, counts, n_out
+
+    def track_gate_running_dev(self, src_ptr, src_floats, offsets, shapes, width, memory=0, floor=-np.inf):
+        """track_gate_dev at the level of what has been heard so far (asr_track_gate_running_dev): frame i is gated with
+        max(floor, the largest column sum of its last `memory` columns up to its own; memory 0: of all so far)
+        -> (m_prob float32, voiced bool, level float32), all per frame."""
+        n = len(shapes)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        bins = np.ascontiguousarray([s[0] for s in shapes], dtype=np.int32)
+        frames = np.ascontiguousarray([s[1] for s in shapes], dtype=np.int32)
+        if off.shape != (n,):
+            raise ValueError("track_gate_running_dev: %d offsets for %d recordings" % (off.size, n))
+        total = int(np.maximum(frames, 0).sum())
+        m_prob, voiced, level = np.empty(total, np.float32), np.empty(total, np.uint8), np.empty(total, np.float32)
+        self._check(self.lib.asr_track_gate_running_dev(
+            self.ctx, src_ptr, int(src_floats), n, off.ctypes.data, bins.ctypes.data, frames.ctypes.data, int(width),
+            int(memory), float(floor), m_prob.ctypes.data, voiced.ctypes.data, level.ctypes.data))
+        return m_prob, voiced.astype(bool), level
+
+    def track_stream_gate_running_dev(self, cols_ptr, cols_floats, col_off, n_new, frames_before, memory, floor, bins,
+                                      width, tail_ptr, tail_floats, tail_off, level_ptr, level_floats, level_off, win_ptr,
+                                      win_cap):
+        """track_stream_gate_dev at the level of what each stream has brought so far
+        (asr_track_stream_gate_running_dev): `memory` and `floor` take the place of the levels, and stream s carries its
+        level state - memory - 1 floats, or one with memory 0 - at float level_off[s] of the buffer at level_ptr, updated
+        in place.  -> (m_prob float32, voiced bool, n_voiced int32 per stream, level float32 per frame)."""
+        new = np.ascontiguousarray(n_new, dtype=np.int32)
+        n = new.size
+        off = np.ascontiguousarray(col_off, dtype=np.int64)
+        before = np.ascontiguousarray(frames_before, dtype=np.int64)
+        t_off = np.ascontiguousarray(tail_off, dtype=np.int64)
+        l_off = np.ascontiguousarray(level_off, dtype=np.int64)
+        if new.ndim != 1 or not (off.shape == before.shape == t_off.shape == l_off.shape == (n,)):
+            raise ValueError("track_stream_gate_running_dev: the per-stream tables differ in length")
+        total = int(np.maximum(new, 0).sum())
+        m_prob, voiced, n_voiced = np.empty(total, np.float32), np.empty(total, np.uint8), np.zeros(n, np.int32)
+        level = np.empty(total, np.float32)
+        self._check(self.lib.asr_track_stream_gate_running_dev(
+            self.ctx, cols_ptr, int(cols_floats), n, off.ctypes.data, new.ctypes.data, before.ctypes.data, int(memory),
+            float(floor), int(bins), int(width), tail_ptr, int(tail_floats), t_off.ctypes.data, level_ptr,
+            int(level_floats), l_off.ctypes.data, win_ptr, int(win_cap), m_prob.ctypes.data, voiced.ctypes.data,
+            n_voiced.ctypes.data, level.ctypes.data))
+        return m_prob, voiced.astype(bool), n_voiced, level
 
     def follow_stream_windows_dev(self, cols_ptr, cols_floats, col_off, n_new, cols_before, bins, width, step, tail_ptr,
                                   tail_floats, tail_off, win_ptr, win_cap):

@@ -57,8 +57,8 @@ import numpy as np
 import yaml
 
 from . import audio2sheet_align
-from .piece_identification import (EmbeddingDB, ScoreFollower, detect_performances, detect_scores, live_follow_scores,
-                                   locate_scores, rank_summary, track_scores)
+from .piece_identification import (EmbeddingDB, RunningLevel, ScoreFollower, detect_performances, detect_scores,
+                                   live_follow_scores, locate_scores, rank_summary, track_scores)
 from .utils.data_pools import NO_AUGMENT, AudioScoreRetrievalPool
 
 # per direction: data-base flag, data-base file, data-base view, what a query finds (the reference's summary line)
@@ -109,13 +109,48 @@ def _arguments(argv, direction):
                        help="--follow for live streams: all test pieces in parallel, candidates from the running vote")
         p.add_argument("--catch_up", type=int, default=64,
                        help="windows of history a candidate that enters late is followed from (--follow --bank)")
+        level_arguments(p, "--track, --follow --bank")
     p.add_argument("--seed", type=int, default=23)
     args = p.parse_args(argv)
     if getattr(args, "bank", False) and not args.follow:
         p.error("--bank goes with --follow")
+    if direction == "A2S":
+        check_level_arguments(p, args, args.track or (args.follow and args.bank),
+                              "--level running goes with --track or with --follow --bank")
     if direction == "A2S" and not 0 <= args.catch_up <= 512:
         p.error("--catch_up must lie in 0..512")
     return args
+
+
+def level_arguments(p, where):
+    """the music gate's level: of the finished recording (the reference's rule), or of what has been heard so far"""
+    p.add_argument("--level", choices=("recording", "running"), default="recording",
+                   help="level of the music gate (%s): the maximum column sum of the finished recording, or `running`: "
+                        "of the columns heard so far (piece_identification.RunningLevel) - what a microphone can know"
+                        % where)
+    p.add_argument("--level_memory", type=int, default=None,
+                   help="--level running: the maximum over the last N columns only (at least the window width)")
+    p.add_argument("--level_floor", type=float, default=None,
+                   help="--level running: a level below which the gate's divisor does not fall")
+
+
+def check_level_arguments(p, args, allowed, message):
+    if args.level != "running" and (args.level_memory is not None or args.level_floor is not None):
+        p.error("--level_memory and --level_floor go with --level running")
+    if args.level == "running":
+        if not allowed:
+            p.error(message)
+        try:
+            level_rule(args)
+        except ValueError as err:
+            p.error(str(err))
+
+
+def level_rule(args):
+    """None for --level recording, the RunningLevel of --level running"""
+    if getattr(args, "level", "recording") != "running":
+        return None
+    return RunningLevel(args.level_memory, args.level_floor)
 
 
 def result_file(param_file, direction):
@@ -146,13 +181,14 @@ def tracking_file(param_file, direction):
     return param_file.replace("params_", "tracking_").replace(".pkl", "_%s.yaml") % direction
 
 
-def track(engine, db, pool, names, n_candidates, running_frames):
+def track(engine, db, pool, names, n_candidates, running_frames, level=None):
     """the running vote over every piece's spectrogram -> (names, per piece the first frame at which its own piece
     leads the ranking (-1: never), per piece the share of its voiced frames at which it leads (0.0 without voiced
-    frames))"""
+    frames)).  level: track_scores' (None, or a RunningLevel)"""
     ids = {name: i for i, name in db.id_to_name.items()}
     results = track_scores(engine, db, [spec[0] for spec in pool.specs], top_k=TRACK_TOP_K, n_candidates=n_candidates,
-                           running_frames=running_frames, spec_shape=tuple(pool.spec_dim))
+                           running_frames=running_frames, spec_shape=tuple(pool.spec_dim),
+                           **({} if level is None else {"level": level}))
     first_lead, lead_share = [], []
     for name, res in zip(names, results):
         leads = (res.n_out > 0) & (res.pieces[:, 0] == ids.get(name, -2)) if len(res.frames) else np.zeros(0, bool)
@@ -161,10 +197,15 @@ def track(engine, db, pool, names, n_candidates, running_frames):
     return names, first_lead, lead_share
 
 
-def report_tracking(names, first_lead, lead_share, res_file=None):
+def report_tracking(names, first_lead, lead_share, res_file=None, level=None):
+    """level: the RunningLevel the gate used, named in the report and in the file; None: the recording's own"""
+    if level is not None:
+        print("music gate at the level of what has been heard so far: %r" % (level,))
     for name, first, share in zip(names, first_lead, lead_share):
         print("leads from frame %5d, at %.2f of the voiced frames  %s" % (first, share, name))
     results = {"first_lead": [int(f) for f in first_lead], "lead_share": [float(v) for v in lead_share]}
+    if level is not None:
+        results["level"] = repr(level)
     if res_file is not None:
         with open(res_file, "w") as fp:
             yaml.dump(results, fp, default_flow_style=False)
@@ -276,16 +317,18 @@ def follow(engine, db, pool, names, n_candidates, n_pieces, step_spec, block_fra
     return out
 
 
-def follow_bank(engine, db, pool, names, n_candidates, n_pieces, step_spec, block_frames, running_frames, catch_up):
+def follow_bank(engine, db, pool, names, n_candidates, n_pieces, step_spec, block_frames, running_frames, catch_up,
+                level=None):
     """every piece's first performance as one of len(names) parallel live streams (live_follow_scores): blocks of
     block_frames frames go to the running vote, whose leaders (at most n_pieces) become the stream's candidates, and to
     a ScoreFollowerBank -> follow's dict per piece, with best_share and median_error over the windows at which the own
-    piece occupies a slot, candidate = there is such a window, and occupied_share = their share of all windows"""
+    piece occupies a slot, candidate = there is such a window, and occupied_share = their share of all windows.
+    level: a RunningLevel for the vote's gate; None: every finished spectrogram's own maximum"""
     if block_frames < 1:
         raise ValueError("block_frames must be >= 1")
     specs = [np.ascontiguousarray(spec[0], dtype=np.float32) for spec in pool.specs]
     win_w = int(pool.spec_dim[1])
-    levels = [spec.sum(axis=0).max() if spec.shape[1] else 0.0 for spec in specs]
+    levels = level if level is not None else [spec.sum(axis=0).max() if spec.shape[1] else 0.0 for spec in specs]
     ids = {name: i for i, name in db.id_to_name.items()}
     _, followed = live_follow_scores(engine, db, specs, levels, block_frames=block_frames, n_slots=n_pieces,
                                      top_k=n_pieces, n_candidates=n_candidates, running_frames=running_frames,
@@ -307,7 +350,12 @@ def follow_bank(engine, db, pool, names, n_candidates, n_pieces, step_spec, bloc
     return out
 
 
-def report_following(entries, res_file=None):
+def report_following(entries, res_file=None, level=None):
+    """level: the RunningLevel the vote's gate used, named in the report and in every entry of the file"""
+    if level is not None:
+        print("music gate at the level of what has been heard so far: %r" % (level,))
+        for e in entries:
+            e["level"] = repr(level)
     for e in entries:
         if e["median_error"] is not None:
             print("own piece a candidate, least cost at %.2f of %5d windows, median off by %6.1f px  %s"
@@ -345,8 +393,10 @@ def run(argv, direction):
         db = EmbeddingDB.load(engine, d["db_file"])
     if getattr(args, "track", False):
         print("\nTracking every test piece:")
-        return report_tracking(*track(engine, db, pool, data["names"], args.n_candidates, args.running_frames),
-                               res_file=tracking_file(param_file, direction) if args.dump_results else None)
+        return report_tracking(*track(engine, db, pool, data["names"], args.n_candidates, args.running_frames,
+                                      level_rule(args)),
+                               res_file=tracking_file(param_file, direction) if args.dump_results else None,
+                               level=level_rule(args))
     if getattr(args, "locate", False):
         print("\nLocating an excerpt of every test piece:")
         return report_location(locate(engine, db, pool, data["names"], args.n_candidates, args.excerpt_frames,
@@ -356,8 +406,10 @@ def run(argv, direction):
         print("\nFollowing every test piece through the scores:")
         if args.bank:
             return report_following(follow_bank(engine, db, pool, data["names"], args.n_candidates, args.locate_pieces,
-                                                args.step_spec, args.block_frames, args.running_frames, args.catch_up),
-                                    res_file=following_file(param_file, direction) if args.dump_results else None)
+                                                args.step_spec, args.block_frames, args.running_frames, args.catch_up,
+                                                level_rule(args)),
+                                    res_file=following_file(param_file, direction) if args.dump_results else None,
+                                    level=level_rule(args))
         return report_following(follow(engine, db, pool, data["names"], args.n_candidates, args.locate_pieces,
                                        args.step_spec, args.block_frames),
                                 res_file=following_file(param_file, direction) if args.dump_results else None)

@@ -27,6 +27,7 @@ FLAGS = BASE_FLAGS + ["-I", INCLUDE] + EXTRA_FLAGS
 # multiply-adds there
 FILE_FLAGS = {"omr_post_kernels.hip": ["-ffp-contract=off"], "omr_detect_kernels.hip": ["-ffp-contract=off"],
               "track_kernels.hip": ["-ffp-contract=off"], "track_stream_kernels.hip": ["-ffp-contract=off"],
+              "track_level_kernels.hip": ["-ffp-contract=off"],
               "resample_kernels.hip": ["-ffp-contract=off"], "follow_stream_kernels.hip": ["-ffp-contract=off"]}
 
 

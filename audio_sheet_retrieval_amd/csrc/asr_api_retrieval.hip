@@ -1159,6 +1159,82 @@ int asr_track_gate_dev(asr_ctx *ctx, const float *src_dev, int64_t src_floats, i
     return mark_main(ctx);
 }
 
+// the running level's rule: memory 0 or width .. 2^20 (a shorter memory would not cover the columns of the mean), a
+// floor that is a number or -inf
+static bool track_running_bad(int memory, float floor, int width) {
+    return memory < 0 || (memory > 0 && memory < width) || memory > (1 << 20) || floor != floor || floor == INFINITY;
+}
+
+int asr_track_gate_running_dev(asr_ctx *ctx, const float *src_dev, int64_t src_floats, int n_rec, const int64_t *offsets,
+                               const int32_t *bins, const int32_t *frames, int width, int memory, float floor,
+                               float *m_prob, uint8_t *voiced, float *level) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_rec < 0 || src_floats < 0 || width < 8 || width > 128)
+        return fail(ctx, ASR_ERR_INVALID, "track_gate_running: bad sizes n_rec=%d width=%d (8..128)", n_rec, width);
+    if (track_running_bad(memory, floor, width))
+        return fail(ctx, ASR_ERR_INVALID, "track_gate_running: memory=%d (0, or width=%d..2^20) floor=%g (not NaN, not +inf)",
+                    memory, width, (double)floor);
+    if (n_rec == 0) return ASR_OK;
+    if (!src_dev || !offsets || !bins || !frames || !m_prob || !voiced)
+        return fail(ctx, ASR_ERR_INVALID, "track_gate_running: NULL argument");
+    std::vector<asr::TrackRec> recs(n_rec);
+    std::vector<asr::TrackLevelSeq> seqs(n_rec);
+    int64_t total = 0;
+    for (int r = 0; r < n_rec; ++r) {
+        if (bins[r] < 1 || frames[r] < 1 || offsets[r] < 0 || offsets[r] > src_floats ||
+            (int64_t)bins[r] * frames[r] > src_floats - offsets[r])
+            return fail(ctx, ASR_ERR_INVALID,
+                        "track_gate_running: recording %d (%d x %d at %lld) lies outside the %lld-float buffer", r, bins[r],
+                        frames[r], (long long)offsets[r], (long long)src_floats);
+        asr::TrackRec &R = recs[r];
+        R.off = offsets[r]; R.first = total; R.frame0 = 0; R.bins = bins[r]; R.frames = frames[r];
+        R.has_norm = 0; R.norm = 0.0f;
+        asr::TrackLevelSeq &Q = seqs[r];
+        Q.cs_first = Q.out_first = Q.sfx_first = total; Q.state_off = 0; Q.frames_before = 0;
+        Q.n_new = frames[r]; Q.n_hist = 0;
+        total += frames[r];
+        if (total > INT32_MAX / 2) return fail(ctx, ASR_ERR_INVALID, "track_gate_running: more than 2^30 - 1 frames");
+    }
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    int rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    // results (one download): m_prob | level per frame | voiced; then the two tables, the column sums, the suffix maxima
+    // and the (unused) carried maxima
+    const size_t T = (size_t)total, o_level = T * 4, o_voiced = 2 * T * 4, res_bytes = o_voiced + T;
+    const size_t o_recs = dtw_align(res_bytes), o_seqs = dtw_align(o_recs + recs.size() * sizeof(asr::TrackRec));
+    const size_t o_colsum = dtw_align(o_seqs + seqs.size() * sizeof(asr::TrackLevelSeq));
+    const size_t o_sfx = dtw_align(o_colsum + T * 4), o_last = dtw_align(o_sfx + (memory > 0 ? T * 4 : 0));
+    rc = track_ws(ctx, o_last + (size_t)n_rec * 4);
+    if (rc != ASR_OK) return rc;
+    char *ws = (char *)ctx->vote_ws;
+    ASR_HIP(ctx, hipMemcpyAsync(ws + o_recs, recs.data(), recs.size() * sizeof(asr::TrackRec), hipMemcpyHostToDevice,
+                                ctx->stream));
+    ASR_HIP(ctx, hipMemcpyAsync(ws + o_seqs, seqs.data(), seqs.size() * sizeof(asr::TrackLevelSeq), hipMemcpyHostToDevice,
+                                ctx->stream));
+    {
+        ProfScope ps(ctx, "track_gate_running", 0, 0.0, 4.0 * (double)src_floats);
+        asr::TrackGateArgs a;
+        a.src = src_dev; a.recs = (const asr::TrackRec *)(ws + o_recs); a.n_rec = n_rec; a.total_frames = total;
+        a.width = width;
+        a.colsum = (float *)(ws + o_colsum); a.level = nullptr;
+        a.m_prob = (float *)ws; a.voiced = (uint8_t *)(ws + o_voiced);
+        asr::TrackLevelArgs l;
+        l.colsum = a.colsum; l.seqs = (const asr::TrackLevelSeq *)(ws + o_seqs); l.n_seq = n_rec; l.memory = memory;
+        l.floor = floor; l.state = nullptr;
+        l.suffix = (float *)(ws + o_sfx); l.last = (float *)(ws + o_last); l.level = (float *)(ws + o_level);
+        ASR_HIP(ctx, asr::launch_track_colsum(ctx->stream, a));
+        ASR_HIP(ctx, asr::launch_track_level(ctx->stream, l));
+        ASR_HIP(ctx, asr::launch_track_gate_running(ctx->stream, a, l.level));
+    }
+    std::vector<char> host(res_bytes);
+    ASR_HIP(ctx, hipMemcpyAsync(host.data(), ws, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    ASR_HIP(ctx, hipStreamSynchronize(ctx->stream));    // (also: the tables were read by the uploads)
+    memcpy(m_prob, host.data(), T * 4);
+    if (level) memcpy(level, host.data() + o_level, T * 4);
+    memcpy(voiced, host.data() + o_voiced, T);
+    return mark_main(ctx);
+}
+
 int asr_track_vote_batch_dev(asr_ctx *ctx, const int32_t *idx_dev, int64_t n_rows, int n_rec, const int64_t *row_first,
                              const int64_t *row_count, const int64_t *emit_from, int n_candidates, int running_frames,
                              const int32_t *ids_dev, int64_t n_db, int32_t n_pieces, int top_k, int32_t *pieces,
@@ -1246,42 +1322,61 @@ static bool track_slices_bad(const int64_t *off, int n, int64_t len, int64_t tot
     return false;
 }
 
-int asr_track_stream_gate_dev(asr_ctx *ctx, const float *cols_dev, int64_t cols_floats, int n_streams,
-                              const int64_t *col_off, const int32_t *n_new, const int64_t *frames_before,
-                              const float *level, int bins, int width, float *tail_dev, int64_t tail_floats,
-                              const int64_t *tail_off, float *win_dev, int64_t win_cap, float *m_prob, uint8_t *voiced,
-                              int32_t *n_voiced) {
+// the level of what has been heard so far in place of a given one (track_level_kernels.hip): the rule, the streams'
+// carried column sums and the optional per-frame output
+struct TrackRunning {
+    int memory; float floor;
+    float *state_dev; int64_t state_floats; const int64_t *state_off;
+    float *level_out;
+};
+
+// asr_track_stream_gate_dev (level, run == NULL) and asr_track_stream_gate_running_dev (level == NULL, run)
+static int track_stream_gate(asr_ctx *ctx, const char *fn, const float *cols_dev, int64_t cols_floats, int n_streams,
+                             const int64_t *col_off, const int32_t *n_new, const int64_t *frames_before,
+                             const float *level, const TrackRunning *run, int bins, int width, float *tail_dev,
+                             int64_t tail_floats, const int64_t *tail_off, float *win_dev, int64_t win_cap,
+                             float *m_prob, uint8_t *voiced, int32_t *n_voiced) {
     if (!ctx) return ASR_ERR_INVALID;
     if (n_streams < 1 || bins < 1 || width < 8 || width > 128 || cols_floats < 0 || tail_floats < 0 || win_cap < 0)
-        return fail(ctx, ASR_ERR_INVALID, "asr_track_stream_gate_dev: bad sizes n_streams=%d bins=%d width=%d (8..128)",
+        return fail(ctx, ASR_ERR_INVALID, "%s: bad sizes n_streams=%d bins=%d width=%d (8..128)", fn,
                     n_streams, bins, width);
-    if (!col_off || !n_new || !frames_before || !level || !tail_dev || !tail_off || !n_voiced)
-        return fail(ctx, ASR_ERR_INVALID, "asr_track_stream_gate_dev: NULL argument");
+    if (!col_off || !n_new || !frames_before || (!level && !run) || !tail_dev || !tail_off || !n_voiced)
+        return fail(ctx, ASR_ERR_INVALID, "%s: NULL argument", fn);
+    const int64_t state_len = run ? (run->memory > 0 ? run->memory - 1 : 1) : 0;
+    if (run && track_running_bad(run->memory, run->floor, width))
+        return fail(ctx, ASR_ERR_INVALID, "%s: memory=%d (0, or width=%d..2^20) floor=%g (not NaN, not +inf)", fn,
+                    run->memory, width, (double)run->floor);
+    if (run && (!run->state_dev || !run->state_off || run->state_floats < 0))
+        return fail(ctx, ASR_ERR_INVALID, "%s: NULL argument", fn);
     std::vector<asr::TrackStreamRec> recs(n_streams);
     int64_t total = 0, total_ext = 0;
     for (int s = 0; s < n_streams; ++s) {
         if (n_new[s] < 0 || frames_before[s] < 0 || col_off[s] < 0 || col_off[s] > cols_floats ||
             (int64_t)bins * n_new[s] > cols_floats - col_off[s])
             return fail(ctx, ASR_ERR_INVALID,
-                        "asr_track_stream_gate_dev: stream %d (%d x %d at %lld, %lld frames before) lies outside the "
-                        "%lld-float buffer", s, bins, n_new[s], (long long)col_off[s], (long long)frames_before[s],
+                        "%s: stream %d (%d x %d at %lld, %lld frames before) lies outside the "
+                        "%lld-float buffer", fn, s, bins, n_new[s], (long long)col_off[s], (long long)frames_before[s],
                         (long long)cols_floats);
         asr::TrackStreamRec &R = recs[s];
         R.col_off = col_off[s]; R.tail_off = tail_off[s]; R.frames_before = frames_before[s];
-        R.first = total; R.ext_first = total_ext; R.n_new = n_new[s]; R.level = level[s];
+        R.first = total; R.ext_first = total_ext; R.n_new = n_new[s]; R.level = level ? level[s] : 0.0f;
         total += n_new[s];
         if (n_new[s] > 0) total_ext += (int64_t)(width - 1) + n_new[s];
-        if (total > INT32_MAX / 2) return fail(ctx, ASR_ERR_INVALID, "asr_track_stream_gate_dev: more than 2^30 - 1 frames");
+        if (total > INT32_MAX / 2) return fail(ctx, ASR_ERR_INVALID, "%s: more than 2^30 - 1 frames", fn);
     }
     if (track_slices_bad(tail_off, n_streams, (int64_t)bins * (width - 1), tail_floats))
         return fail(ctx, ASR_ERR_INVALID,
-                    "asr_track_stream_gate_dev: a tail (%d x %d) lies outside the %lld-float buffer or two tails overlap",
+                    "%s: a tail (%d x %d) lies outside the %lld-float buffer or two tails overlap", fn,
                     bins, width - 1, (long long)tail_floats);
+    if (run && track_slices_bad(run->state_off, n_streams, state_len, run->state_floats))
+        return fail(ctx, ASR_ERR_INVALID,
+                    "%s: a level state (%lld floats) lies outside the %lld-float buffer or two level states overlap", fn,
+                    (long long)state_len, (long long)run->state_floats);
     if (total > win_cap)
-        return fail(ctx, ASR_ERR_INVALID, "asr_track_stream_gate_dev: %lld new frames for %lld windows", (long long)total,
+        return fail(ctx, ASR_ERR_INVALID, "%s: %lld new frames for %lld windows", fn, (long long)total,
                     (long long)win_cap);
     if (total > 0 && (!cols_dev || !win_dev || !m_prob || !voiced))
-        return fail(ctx, ASR_ERR_INVALID, "asr_track_stream_gate_dev: NULL argument");
+        return fail(ctx, ASR_ERR_INVALID, "%s: NULL argument", fn);
     if (total == 0) {
         memset(n_voiced, 0, (size_t)n_streams * sizeof(int32_t));
         return ASR_OK;
@@ -1289,11 +1384,29 @@ int asr_track_stream_gate_dev(asr_ctx *ctx, const float *cols_dev, int64_t cols_
     ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
     int rc = join_views(ctx);
     if (rc != ASR_OK) return rc;
-    // results (one download): m_prob | n_voiced | voiced; then the stream table, the column sums and the window slots
-    const size_t T = (size_t)total, o_nv = T * 4, o_voiced = o_nv + (size_t)n_streams * 4, res_bytes = o_voiced + T;
+    // results (one download): m_prob | n_voiced | voiced (| level per frame); then the stream table, the column sums and
+    // the window slots (and the level's sequence table, suffix maxima and carried maxima)
+    const size_t T = (size_t)total, o_nv = T * 4, o_voiced = o_nv + (size_t)n_streams * 4;
+    const size_t o_lvl = dtw_align(o_voiced + T), res_bytes = run ? o_lvl + T * 4 : o_voiced + T;
     const size_t o_recs = dtw_align(res_bytes), o_colsum = dtw_align(o_recs + recs.size() * sizeof(asr::TrackStreamRec));
     const size_t o_slot = dtw_align(o_colsum + (size_t)total_ext * 4);
-    rc = track_ws(ctx, o_slot + (T + 1) * 4);
+    size_t need = o_slot + (T + 1) * 4, o_seqs = 0, o_sfx = 0, o_last = 0;
+    std::vector<asr::TrackLevelSeq> seqs;
+    if (run) {
+        seqs.resize(n_streams);
+        int64_t sfx = 0;
+        for (int s = 0; s < n_streams; ++s) {
+            asr::TrackLevelSeq &Q = seqs[s];
+            Q.cs_first = recs[s].ext_first + (width - 1); Q.out_first = recs[s].first; Q.sfx_first = sfx;
+            Q.state_off = run->state_off[s]; Q.frames_before = frames_before[s]; Q.n_new = n_new[s];
+            Q.n_hist = (int32_t)std::min<int64_t>(frames_before[s], state_len);
+            if (n_new[s] > 0 && run->memory > 0) sfx += (int64_t)Q.n_hist + n_new[s];
+        }
+        o_seqs = dtw_align(need); o_sfx = dtw_align(o_seqs + seqs.size() * sizeof(asr::TrackLevelSeq));
+        o_last = dtw_align(o_sfx + (size_t)sfx * 4);
+        need = o_last + (size_t)n_streams * 4;
+    }
+    rc = track_ws(ctx, need);
     if (rc != ASR_OK) return rc;
     char *ws = (char *)ctx->vote_ws;
     ASR_HIP(ctx, hipMemcpyAsync(ws + o_recs, recs.data(), recs.size() * sizeof(asr::TrackStreamRec), hipMemcpyHostToDevice,
@@ -1303,22 +1416,58 @@ int asr_track_stream_gate_dev(asr_ctx *ctx, const float *cols_dev, int64_t cols_
     a.total_frames = total; a.total_ext = total_ext; a.bins = bins; a.width = width;
     a.colsum = (float *)(ws + o_colsum); a.slot = (int32_t *)(ws + o_slot); a.win = win_dev;
     a.m_prob = (float *)ws; a.voiced = (uint8_t *)(ws + o_voiced); a.n_voiced = (int32_t *)(ws + o_nv);
-    {
+    asr::TrackLevelArgs l;
+    if (!run) {
         ProfScope ps(ctx, "track_stream_gate", 0, 0.0, 4.0 * (double)total_ext * bins);
         ASR_HIP(ctx, asr::launch_track_stream_gate(ctx->stream, a));
+    } else {
+        ASR_HIP(ctx, hipMemcpyAsync(ws + o_seqs, seqs.data(), seqs.size() * sizeof(asr::TrackLevelSeq),
+                                    hipMemcpyHostToDevice, ctx->stream));
+        l.colsum = a.colsum; l.seqs = (const asr::TrackLevelSeq *)(ws + o_seqs); l.n_seq = n_streams;
+        l.memory = run->memory; l.floor = run->floor; l.state = run->state_dev;
+        l.suffix = (float *)(ws + o_sfx); l.last = (float *)(ws + o_last); l.level = (float *)(ws + o_lvl);
+        ProfScope ps(ctx, "track_stream_gate_running", 0, 0.0, 4.0 * (double)total_ext * bins);
+        ASR_HIP(ctx, asr::launch_track_stream_colsum(ctx->stream, a));
+        ASR_HIP(ctx, asr::launch_track_level(ctx->stream, l));
+        ASR_HIP(ctx, asr::launch_track_stream_gate_running(ctx->stream, a, l.level));
     }
     {   // bytes: every new frame voiced
         ProfScope ps(ctx, "track_stream_windows", 0, 0.0, 4.0 * (double)total * bins * width);
         ASR_HIP(ctx, asr::launch_track_stream_windows(ctx->stream, a));
     }
+    if (run) ASR_HIP(ctx, asr::launch_track_level_state(ctx->stream, l));  // behind every reader of the carried values
     std::vector<char> host(res_bytes);
     ASR_HIP(ctx, hipMemcpyAsync(host.data(), ws, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
     ASR_HIP(ctx, hipStreamSynchronize(ctx->stream));    // (also: `recs` was read by the upload)
     memcpy(m_prob, host.data(), T * 4);
     memcpy(n_voiced, host.data() + o_nv, (size_t)n_streams * 4);
     memcpy(voiced, host.data() + o_voiced, T);
+    if (run && run->level_out) memcpy(run->level_out, host.data() + o_lvl, T * 4);
     return mark_main(ctx);
 }
+
+int asr_track_stream_gate_dev(asr_ctx *ctx, const float *cols_dev, int64_t cols_floats, int n_streams,
+                              const int64_t *col_off, const int32_t *n_new, const int64_t *frames_before,
+                              const float *level, int bins, int width, float *tail_dev, int64_t tail_floats,
+                              const int64_t *tail_off, float *win_dev, int64_t win_cap, float *m_prob, uint8_t *voiced,
+                              int32_t *n_voiced) {
+    return track_stream_gate(ctx, "asr_track_stream_gate_dev", cols_dev, cols_floats, n_streams, col_off, n_new,
+                             frames_before, level, nullptr, bins, width, tail_dev, tail_floats, tail_off, win_dev, win_cap,
+                             m_prob, voiced, n_voiced);
+}
+
+int asr_track_stream_gate_running_dev(asr_ctx *ctx, const float *cols_dev, int64_t cols_floats, int n_streams,
+                                      const int64_t *col_off, const int32_t *n_new, const int64_t *frames_before,
+                                      int memory, float floor, int bins, int width, float *tail_dev, int64_t tail_floats,
+                                      const int64_t *tail_off, float *level_dev, int64_t level_floats,
+                                      const int64_t *level_off, float *win_dev, int64_t win_cap, float *m_prob,
+                                      uint8_t *voiced, int32_t *n_voiced, float *level) {
+    const TrackRunning run = {memory, floor, level_dev, level_floats, level_off, level};
+    return track_stream_gate(ctx, "asr_track_stream_gate_running_dev", cols_dev, cols_floats, n_streams, col_off, n_new,
+                             frames_before, nullptr, &run, bins, width, tail_dev, tail_floats, tail_off, win_dev, win_cap,
+                             m_prob, voiced, n_voiced);
+}
+
 
 int asr_track_stream_vote_dev(asr_ctx *ctx, const int32_t *idx_dev, int64_t n_rows, int n_streams,
                               const int32_t *row_count, const int64_t *voiced_before, int n_candidates,

@@ -264,6 +264,7 @@ struct TrackGateArgs {
     float *m_prob; uint8_t *voiced;     // total_frames each
 };
 hipError_t launch_track_gate(hipStream_t s, const TrackGateArgs &a);
+hipError_t launch_track_colsum(hipStream_t s, const TrackGateArgs &a);                  // its first launch alone
 // sliding vote: one wave per segment = frames f0 .. f0 + n - 1 of a recording whose frame f is row row0 + f of the
 // (rows x n_candidates) top-k index table; frame f0 + i writes output row out0 + i.  n_pieces <= TRACK_LDS_PIECES keeps
 // the counters in LDS (16 KiB), larger ones use hist_ws (grid * n_pieces int32, zeroed by the launcher).
@@ -296,6 +297,7 @@ struct TrackStreamGateArgs {
     float *m_prob; uint8_t *voiced; int32_t *n_voiced;
 };
 hipError_t launch_track_stream_gate(hipStream_t s, const TrackStreamGateArgs &a);       // column sums, gate, slots
+hipError_t launch_track_stream_colsum(hipStream_t s, const TrackStreamGateArgs &a);     // its first launch alone
 hipError_t launch_track_stream_windows(hipStream_t s, const TrackStreamGateArgs &a);    // windows, then the tails
 // vote: one wave per segment = voiced frames v0 .. v0 + n - 1 (counted over the stream's life) of a stream with vb
 // voiced frames before this call, whose new rows start at row row0 of idx; frame v >= vb is row row0 + v - vb (its
@@ -313,6 +315,31 @@ struct TrackStreamVoteArgs {
     int32_t *hist_ws;
 };
 hipError_t launch_track_stream_vote(hipStream_t s, const TrackStreamVoteArgs &a, int grid, bool global_path);
+
+// ---- the gate at the level of what has been heard so far (track_level_kernels.hip) ----
+// level of new frame k of sequence q (a recording, or a stream's round) = fmaxf(floor, max of the last `memory` column
+// sums up to its own; memory == 0: of all).  A sequence is ext = [its n_hist carried values in frame order | its n_new
+// new column sums, colsum[cs_first ..]]: with memory > 0 the carried values are the last n_hist = min(frames_before,
+// memory - 1) column sums, frame f in slot f mod (memory - 1) of the ring at state_off of `state`; with memory == 0 the
+// one float there, the maximum so far (n_hist = frames_before > 0).  out_first = its first entry in `level`, sfx_first =
+// its first entry in `suffix` (n_hist + n_new floats per sequence, memory > 0 only), which holds per ext entry the
+// maximum from it to the end of its block of `memory` entries.  last (n_seq): the maximum that memory == 0 carries on.
+// All pointers on the device; state may be NULL where every n_hist is 0.
+struct TrackLevelSeq {
+    int64_t cs_first, out_first, sfx_first, state_off, frames_before;
+    int32_t n_new, n_hist;
+};
+struct TrackLevelArgs {
+    const float *colsum; const TrackLevelSeq *seqs; int n_seq; int memory; float floor;
+    float *state;
+    float *suffix, *last;               // workspace
+    float *level;                       // per new frame
+};
+hipError_t launch_track_level(hipStream_t s, const TrackLevelArgs &a);                  // (suffix maxima,) levels
+hipError_t launch_track_level_state(hipStream_t s, const TrackLevelArgs &a);            // behind them: the carried state
+// the two gates with TrackLevelArgs::level per frame in place of the recording's / the stream's level
+hipError_t launch_track_gate_running(hipStream_t s, const TrackGateArgs &a, const float *frame_level);
+hipError_t launch_track_stream_gate_running(hipStream_t s, const TrackStreamGateArgs &a, const float *frame_level);
 
 // ---- score following for parallel streams: the windows on the step grid and the code logs (follow_stream_kernels.hip) ----
 // windows: stream s brings n_new columns as a (bins, n_new) row-major block at float col_off of cols; its state is the

@@ -30,18 +30,6 @@ namespace asr {
 
 namespace {
 
-constexpr int GATE_THREADS = 256;
-
-// recording of concatenated frame g: the last r with recs[r].first <= g
-__device__ __forceinline__ int track_rec_of(const TrackRec *__restrict__ recs, int n_rec, int64_t g) {
-    int lo = 0, hi = n_rec - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (recs[mid].first <= g) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(GATE_THREADS) void track_colsum_kernel(TrackGateArgs a) {
     const int64_t g = (int64_t)blockIdx.x * GATE_THREADS + threadIdx.x;
     if (g >= a.total_frames) return;
@@ -84,14 +72,7 @@ __global__ __launch_bounds__(GATE_THREADS) void track_gate_kernel(TrackGateArgs 
     const int64_t g = (int64_t)blockIdx.x * GATE_THREADS + threadIdx.x;
     if (g >= a.total_frames) return;
     const int ri = track_rec_of(a.recs, a.n_rec, g);
-    const TrackRec R = a.recs[ri];
-    const int w = a.width;
-    const int64_t c0 = g - R.first - (w - 1);                  // first column of the window (negative: zeros)
-    const float *cs = a.colsum + R.first;
-    auto elem = [&](int j) { const int64_t c = c0 + j; return c >= 0 ? cs[c] : 0.0f; };
-    const float m = track_music_prob(elem, w, a.level[ri]);
-    a.m_prob[g] = m;
-    a.voiced[g] = (m > 0.5f && R.frame0 + (g - R.first) >= (int64_t)w) ? 1 : 0;
+    track_gate_frame(a, a.recs[ri], g, a.level[ri]);
 }
 
 // ---- sliding vote ----------------------------------------------------------------------------------------------------
@@ -133,6 +114,12 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_vote_kernel(TrackVoteArgs
 }
 
 }  // namespace
+
+hipError_t launch_track_colsum(hipStream_t s, const TrackGateArgs &a) {
+    if (a.total_frames <= 0 || a.n_rec <= 0) return hipSuccess;
+    track_colsum_kernel<<<(int)((a.total_frames + GATE_THREADS - 1) / GATE_THREADS), GATE_THREADS, 0, s>>>(a);
+    return hipGetLastError();
+}
 
 hipError_t launch_track_gate(hipStream_t s, const TrackGateArgs &a) {
     if (a.total_frames <= 0 || a.n_rec <= 0) return hipSuccess;

@@ -1,6 +1,7 @@
-// Device functions of the running piece vote that track_kernels.hip (whole recordings) and track_stream_kernels.hip
-// (streams with carried device state) share: the gate's arithmetic and the vote histogram with its top-k selection.
-// Both files are compiled without contraction; every float operation here has a fixed order.
+// Device functions of the running piece vote that track_kernels.hip (whole recordings), track_stream_kernels.hip
+// (streams with carried device state) and track_level_kernels.hip (both, with the level of what has been heard so far)
+// share: the gate's arithmetic, the gate of a frame and of a round of streams, and the vote histogram with its top-k
+// selection.  All three files are compiled without contraction; every float operation here has a fixed order.
 #pragma once
 #include "asr_kernels.h"
 
@@ -28,6 +29,93 @@ __device__ __forceinline__ float track_music_prob(Elem elem, int w, float level)
     m = __fdiv_rn(m, __fmul_rn(level, 0.15f));
     if (m == m) m = fminf(fmaxf(m, 0.0f), 1.0f);
     return m;
+}
+
+// ---- the gate of one frame, at a level the caller chooses (the recording's, the stream's, or the frame's own) ----------
+constexpr int GATE_THREADS = 256;
+constexpr int SGATE_THREADS = 256;
+
+// recording of concatenated frame g: the last r with recs[r].first <= g
+__device__ __forceinline__ int track_rec_of(const TrackRec *__restrict__ recs, int n_rec, int64_t g) {
+    int lo = 0, hi = n_rec - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (recs[mid].first <= g) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// m_prob and voiced of concatenated frame g of recording R from the last w column sums (zeros before its start)
+__device__ __forceinline__ void track_gate_frame(const TrackGateArgs &a, const TrackRec &R, int64_t g, float level) {
+    const int w = a.width;
+    const int64_t c0 = g - R.first - (w - 1);                  // first column of the window (negative: zeros)
+    const float *cs = a.colsum + R.first;
+    auto elem = [&](int j) { const int64_t c = c0 + j; return c >= 0 ? cs[c] : 0.0f; };
+    const float m = track_music_prob(elem, w, level);
+    a.m_prob[g] = m;
+    a.voiced[g] = (m > 0.5f && R.frame0 + (g - R.first) >= (int64_t)w) ? 1 : 0;
+}
+
+// stream of concatenated frame g / column sum x: the last s with first (ext_first) <= the index; streams without new
+// columns share their successor's value and are never the last
+__device__ __forceinline__ int stream_of_frame(const TrackStreamRec *__restrict__ recs, int n, int64_t g) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (recs[mid].first <= g) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+__device__ __forceinline__ int stream_of_ext(const TrackStreamRec *__restrict__ recs, int n, int64_t x) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (recs[mid].ext_first <= x) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// One workgroup of SGATE_THREADS: per new frame g of every stream m_prob and voiced from the w column sums that end at
+// it, at level_of(R, g), and in the same pass the exclusive running count of the voiced frames (ballot + popcount per
+// wave, the wave totals through LDS, a carry from chunk to chunk): the window a voiced frame writes, in stream and frame
+// order.  n_voiced per stream is the difference of two counts.  s_wave: SGATE_THREADS / 64 ints of LDS.
+template <typename Level>
+__device__ __forceinline__ void track_stream_gate_stage(const TrackStreamGateArgs &a, int *s_wave, Level level_of) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int w = a.width;
+    int carry = 0;                                            // voiced frames before this chunk (the same in every thread)
+    for (int64_t base = 0; base < a.total_frames; base += SGATE_THREADS) {
+        const int64_t g = base + tid;
+        int v = 0;
+        if (g < a.total_frames) {
+            const TrackStreamRec R = a.recs[stream_of_frame(a.recs, a.n_streams, g)];
+            const int64_t i = g - R.first;                    // window of frame i: column sums i .. i + w - 1
+            const float *cs = a.colsum + R.ext_first + i;
+            auto elem = [&](int j) { return cs[j]; };
+            const float m = track_music_prob(elem, w, level_of(R, g));
+            v = (m > 0.5f && R.frames_before + i >= (int64_t)w) ? 1 : 0;
+            a.m_prob[g] = m;
+            a.voiced[g] = (uint8_t)v;
+        }
+        const unsigned long long bal = __ballot(v);
+        if (lane == 0) s_wave[wave] = __popcll(bal);
+        __syncthreads();
+        int before = __popcll(bal & ((1ull << lane) - 1ull)), total = 0;
+        for (int k = 0; k < SGATE_THREADS / 64; ++k) {
+            const int c = s_wave[k];
+            if (k < wave) before += c;
+            total += c;
+        }
+        if (g < a.total_frames) a.slot[g] = carry + before;
+        carry += total;
+        __syncthreads();                                      // s_wave is rewritten by the next chunk
+    }
+    if (tid == 0) a.slot[a.total_frames] = carry;
+    __syncthreads();
+    for (int s = tid; s < a.n_streams; s += SGATE_THREADS) {
+        const TrackStreamRec R = a.recs[s];
+        a.n_voiced[s] = a.slot[R.first + R.n_new] - a.slot[R.first];
+    }
 }
 
 template <bool GLOBAL>

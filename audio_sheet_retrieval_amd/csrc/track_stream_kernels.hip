@@ -37,27 +37,7 @@ namespace asr {
 
 namespace {
 
-constexpr int SGATE_THREADS = 256;
 constexpr int TAIL_THREADS = 256;
-
-// stream of concatenated frame g / column sum x: the last s with first (ext_first) <= the index; streams without new
-// columns share their successor's value and are never the last
-__device__ __forceinline__ int stream_of_frame(const TrackStreamRec *__restrict__ recs, int n, int64_t g) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (recs[mid].first <= g) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-__device__ __forceinline__ int stream_of_ext(const TrackStreamRec *__restrict__ recs, int n, int64_t x) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (recs[mid].ext_first <= x) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 // element (row b, column c) of [tail | new] of stream R; the tail counts as zeros while the stream has no frames
 __device__ __forceinline__ float ext_elem(const TrackStreamGateArgs &a, const TrackStreamRec &R, int b, int64_t c) {
@@ -79,41 +59,7 @@ __global__ __launch_bounds__(SGATE_THREADS) void track_stream_colsum_kernel(Trac
 
 __global__ __launch_bounds__(SGATE_THREADS) void track_stream_gate_kernel(TrackStreamGateArgs a) {
     __shared__ int s_wave[SGATE_THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int w = a.width;
-    int carry = 0;                                            // voiced frames before this chunk (the same in every thread)
-    for (int64_t base = 0; base < a.total_frames; base += SGATE_THREADS) {
-        const int64_t g = base + tid;
-        int v = 0;
-        if (g < a.total_frames) {
-            const TrackStreamRec R = a.recs[stream_of_frame(a.recs, a.n_streams, g)];
-            const int64_t i = g - R.first;                    // window of frame i: column sums i .. i + w - 1
-            const float *cs = a.colsum + R.ext_first + i;
-            auto elem = [&](int j) { return cs[j]; };
-            const float m = track_music_prob(elem, w, R.level);
-            v = (m > 0.5f && R.frames_before + i >= (int64_t)w) ? 1 : 0;
-            a.m_prob[g] = m;
-            a.voiced[g] = (uint8_t)v;
-        }
-        const unsigned long long bal = __ballot(v);
-        if (lane == 0) s_wave[wave] = __popcll(bal);
-        __syncthreads();
-        int before = __popcll(bal & ((1ull << lane) - 1ull)), total = 0;
-        for (int k = 0; k < SGATE_THREADS / 64; ++k) {
-            const int c = s_wave[k];
-            if (k < wave) before += c;
-            total += c;
-        }
-        if (g < a.total_frames) a.slot[g] = carry + before;
-        carry += total;
-        __syncthreads();                                      // s_wave is rewritten by the next chunk
-    }
-    if (tid == 0) a.slot[a.total_frames] = carry;
-    __syncthreads();
-    for (int s = tid; s < a.n_streams; s += SGATE_THREADS) {
-        const TrackStreamRec R = a.recs[s];
-        a.n_voiced[s] = a.slot[R.first + R.n_new] - a.slot[R.first];
-    }
+    track_stream_gate_stage(a, s_wave, [](const TrackStreamRec &R, int64_t) { return R.level; });
 }
 
 __global__ __launch_bounds__(SGATE_THREADS) void track_stream_window_kernel(TrackStreamGateArgs a) {
@@ -210,6 +156,12 @@ __global__ __launch_bounds__(SGATE_THREADS) void track_stream_ring_kernel(TrackS
 }
 
 }  // namespace
+
+hipError_t launch_track_stream_colsum(hipStream_t s, const TrackStreamGateArgs &a) {
+    if (a.total_frames <= 0 || a.n_streams <= 0) return hipSuccess;
+    track_stream_colsum_kernel<<<(int)((a.total_ext + SGATE_THREADS - 1) / SGATE_THREADS), SGATE_THREADS, 0, s>>>(a);
+    return hipGetLastError();
+}
 
 hipError_t launch_track_stream_gate(hipStream_t s, const TrackStreamGateArgs &a) {
     if (a.total_frames <= 0 || a.n_streams <= 0) return hipSuccess;

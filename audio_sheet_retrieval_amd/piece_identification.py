@@ -486,18 +486,89 @@ def _history_lengths(n_before, n_new, n_candidates, running_frames):
     return np.minimum(n_before + 1 + np.arange(n_new, dtype=np.int64), running_frames) * n_candidates
 
 
+class RunningLevel(object):
+    """The music gate's level from what has been heard so far, for streams whose end nobody has heard: frame i is gated
+    with max(floor, the largest column sum of the last `memory` columns up to its own) in place of
+    spec.sum(axis=0).max() of the finished spectrogram (_detect_music, :527) - the reference's rule on the columns so
+    far.  memory: None (or 0) for every column so far, else a number of columns between the window width and 2^20 - one
+    loud bang then does not deafen the gate for the rest of a session.  floor: None, or a level below which the
+    divisor does not fall (a quiet room is not music).  Pass it where a level is expected: track_gate_host,
+    track_score_host, track_scores, PieceTrackerBank, live_track_scores, live_follow_scores."""
+    MAX_MEMORY = 1 << 20
+
+    def __init__(self, memory=None, floor=None):
+        if memory is not None:
+            if isinstance(memory, bool) or int(memory) != memory or memory < 0 or memory > self.MAX_MEMORY:
+                raise ValueError("memory must be None or an int in 0..2^20, got %r" % (memory,))
+        if floor is not None and (np.isnan(floor) or floor == np.inf):
+            raise ValueError("floor must be None or a number below +inf, got %r" % (floor,))
+        self.memory = int(memory) if memory else None
+        self.floor = None if floor is None or floor == -np.inf else float(np.float32(floor))
+
+    @property
+    def memory_arg(self):
+        """the C calls' `memory`: 0 = unbounded"""
+        return self.memory or 0
+
+    @property
+    def floor_arg(self):
+        """the C calls' `floor`: -inf = none"""
+        return -np.inf if self.floor is None else self.floor
+
+    def check_width(self, width):
+        """a memory shorter than the window would let the mean read columns the level does not cover"""
+        if self.memory is not None and self.memory < width:
+            raise ValueError("RunningLevel: memory=%d is shorter than the window of %d columns" % (self.memory, width))
+
+    def state_floats(self):
+        """floats of carried state per stream (asr_track_stream_gate_running_dev)"""
+        return self.memory - 1 if self.memory else 1
+
+    def levels(self, column_sums):
+        """the level of every frame from the float32 column sums of the recording so far (max is exact: no order of
+        evaluation changes a bit)"""
+        c = np.ascontiguousarray(column_sums, dtype=np.float32)
+        if self.memory is None:
+            m = np.maximum.accumulate(c) if c.size else c.copy()
+        else:
+            m, span = c.copy(), 1                           # m[i] = max of the last `span` sums up to i
+            while span < self.memory:
+                step = min(span, self.memory - span)
+                m[step:] = np.maximum(m[step:], m[:-step].copy())
+                span += step
+        return m if self.floor is None else np.maximum(np.float32(self.floor), m)
+
+    def __repr__(self):
+        return "RunningLevel(memory=%r, floor=%r)" % (self.memory, self.floor)
+
+
+_BANK_HINT = ("a RunningLevel keeps its state on the device: use PieceTrackerBank(engine, sheet_db, RunningLevel(...), "
+              "n_streams=1) (live_track_scores: batched=True)")
+
+
 def track_gate_host(spectrogram, width, level=None):
     """the loop's gate, line by line (:92, :110-117, _detect_music :524-528) -> (m_prob (T,) float32, voiced (T,) bool).
-    level: stands in for spec.sum(axis=0).max() (a stream does not know it)."""
+    level: stands in for spec.sum(axis=0).max() (a stream does not know it) - a number, or a RunningLevel: then frame i
+    takes the maximum over the columns heard so far (its last `memory` ones), np.maximum.accumulate or a sliding
+    maximum of spec.sum(axis=0)."""
     spec = np.ascontiguousarray(spectrogram, dtype=np.float32)
     T = spec.shape[1]
     m_probs, voiced = np.zeros(T, np.float32), np.zeros(T, bool)
     running_spec = np.zeros((spec.shape[0], width), dtype=np.float32)
-    norm = spec.sum(axis=0).max() if level is None else np.float32(level)
+    norms = None
+    if isinstance(level, RunningLevel):
+        level.check_width(width)
+        # c_j: the rows added one after the other, as running_spec.sum(axis=0) adds them below (numpy sums the only
+        # column of a (bins, 1) array pairwise instead, hence the column of zeros)
+        norms = level.levels(np.hstack((spec, np.zeros((spec.shape[0], 1), np.float32))).sum(axis=0)[:T])
+    else:
+        norm = spec.sum(axis=0).max() if level is None else np.float32(level)
     with np.errstate(invalid="ignore", divide="ignore"):
         for i_frame in range(T):
             running_spec = np.hstack((running_spec[:, 1::], spec[:, i_frame:i_frame + 1]))
             music_prob = running_spec.sum(axis=0).mean()
+            if norms is not None:
+                norm = norms[i_frame]
             music_prob /= (norm * 0.15)
             m_prob = np.clip(music_prob, 0.0, 1.0)
             m_probs[i_frame] = m_prob
@@ -574,16 +645,21 @@ def _track_lookup(engine, db, src_ptr, src_floats, desc, win_shape, n_candidates
 
 
 def track_scores(engine, sheet_db, spectrograms, top_k=5, n_candidates=5, running_frames=100, spec_shape=(92, 42),
-                 max_windows=4096, return_idx=False, stages=None):
+                 max_windows=4096, return_idx=False, stages=None, level=None):
     """The running vote of the reference's live server (AudioSheetServer.run, :83-211) over every frame of a list of
     recordings, in one pass: one asr_track_gate_dev call for all frames; the windows of the voiced frames only are cut,
     embedded and looked up max_windows at a time; one asr_track_vote_batch_dev call slides the vote over the last
     running_frames voiced frames of every recording.  -> one TrackResult per recording, equal to track_score_host's.
     `spectrograms`: (spec_shape[0], frames) host arrays or a DeviceArrays handle.  return_idx: keep the top-k index
     table.  stages: a dict that receives the seconds per stage (gate / gather / embed / topk / vote; synchronises
-    after every stage)."""
+    after every stage).  level: None - every recording's own spec.sum(axis=0).max() - or a RunningLevel: the causal gate
+    of a finished recording (one asr_track_gate_running_dev call), what a live session at that rule computes."""
     import time
     _track_check(top_k, n_candidates, running_frames, max_windows)
+    if level is not None and not isinstance(level, RunningLevel):
+        raise ValueError("level: None or a RunningLevel, got %r" % (level,))
+    if level is not None:
+        level.check_width(spec_shape[1])
     if n_candidates > len(sheet_db):
         raise ValueError("n_candidates=%d for a data base of %d codes" % (n_candidates, len(sheet_db)))
     win_h, win_w = spec_shape
@@ -602,7 +678,11 @@ def track_scores(engine, sheet_db, spectrograms, top_k=5, n_candidates=5, runnin
             return []
         src_floats = dev.buf.nbytes // 4
         t0 = time.perf_counter()
-        m_prob, voiced, _ = engine.track_gate_dev(dev.buf.ptr, src_floats, dev.offsets, dev.shapes, win_w)
+        if level is None:
+            m_prob, voiced, _ = engine.track_gate_dev(dev.buf.ptr, src_floats, dev.offsets, dev.shapes, win_w)
+        else:
+            m_prob, voiced, _ = engine.track_gate_running_dev(dev.buf.ptr, src_floats, dev.offsets, dev.shapes, win_w,
+                                                              level.memory_arg, level.floor_arg)
         if stages is not None:
             stages["gate"] = stages.get("gate", 0.0) + time.perf_counter() - t0
         first = np.concatenate([[0], np.cumsum([T for _, T in dev.shapes])])
@@ -646,10 +726,10 @@ def track_scores(engine, sheet_db, spectrograms, top_k=5, n_candidates=5, runnin
 
 
 def track_score(engine, sheet_db, spectrogram, top_k=5, n_candidates=5, running_frames=100, spec_shape=(92, 42),
-                max_windows=4096, return_idx=False):
+                max_windows=4096, return_idx=False, level=None):
     """track_scores for one recording -> its TrackResult"""
     return track_scores(engine, sheet_db, [spectrogram], top_k, n_candidates, running_frames, spec_shape, max_windows,
-                        return_idx)[0]
+                        return_idx, level=level)[0]
 
 
 class PieceTracker(object):
@@ -662,6 +742,8 @@ class PieceTracker(object):
 
     def __init__(self, engine, sheet_db, level, top_k=5, n_candidates=5, running_frames=100, spec_shape=(92, 42)):
         _track_check(top_k, n_candidates, running_frames)
+        if isinstance(level, RunningLevel):
+            raise ValueError("PieceTracker: " + _BANK_HINT)
         if n_candidates > len(sheet_db):
             raise ValueError("n_candidates=%d for a data base of %d codes" % (n_candidates, len(sheet_db)))
         self.engine, self.db, self.level = engine, sheet_db, np.float32(level)
@@ -718,17 +800,33 @@ class PieceTrackerBank(object):
     asr_track_stream_gate_dev call, one tower and one top-k call over the voiced windows of all streams, one
     asr_track_stream_vote_dev call and one download of the new index rows, whatever the number of streams; a round of
     more than max_windows new frames is cut along the frames into several, which changes no result.  The work buffers
-    (windows, codes, index rows, distances) are allocated once and grown when a larger round arrives."""
+    (windows, codes, index rows, distances) are allocated once and grown when a larger round arrives.
+    `levels` may be one RunningLevel for all streams, with n_streams=N: no level is known beforehand, every frame is
+    gated at the level of what its stream has brought so far (asr_track_stream_gate_running_dev), the carried column
+    sums are a third device buffer, and the results per stream equal track_scores(..., level=that RunningLevel) on the
+    stream's columns."""
 
     def __init__(self, engine, sheet_db, levels, top_k=5, n_candidates=5, running_frames=100, spec_shape=(92, 42),
-                 max_windows=4096):
+                 max_windows=4096, n_streams=None):
         _track_check(top_k, n_candidates, running_frames, max_windows)
         if n_candidates > len(sheet_db):
             raise ValueError("n_candidates=%d for a data base of %d codes" % (n_candidates, len(sheet_db)))
-        self.levels = np.ascontiguousarray(levels, dtype=np.float32)
-        if self.levels.ndim != 1 or self.levels.size < 1:
-            raise ValueError("levels: expected one gate level per stream (at least one), got shape %r" % (self.levels.shape,))
-        self.engine, self.db, self.n_streams = engine, sheet_db, int(self.levels.size)
+        self.running = levels if isinstance(levels, RunningLevel) else None
+        if self.running is not None:
+            if n_streams is None or int(n_streams) != n_streams or n_streams < 1:
+                raise ValueError("a RunningLevel needs n_streams=<number of streams, at least one>, got %r" % (n_streams,))
+            self.running.check_width(spec_shape[1])
+            self.levels = None
+            self.n_streams = int(n_streams)
+        else:
+            if n_streams is not None:
+                raise ValueError("n_streams goes with a RunningLevel; given levels, there is one stream per level")
+            self.levels = np.ascontiguousarray(levels, dtype=np.float32)
+            if self.levels.ndim != 1 or self.levels.size < 1:
+                raise ValueError("levels: expected one gate level per stream (at least one), got shape %r" %
+                                 (self.levels.shape,))
+            self.n_streams = int(self.levels.size)
+        self.engine, self.db = engine, sheet_db
         self.top_k, self.n_candidates, self.running_frames = int(top_k), int(n_candidates), int(running_frames)
         self.spec_shape, self.max_windows = tuple(spec_shape), int(max_windows)
         self.n_frames = [0] * self.n_streams                # frames pushed so far, per stream
@@ -740,6 +838,12 @@ class PieceTrackerBank(object):
         self._tail_floats, self._hist_len = self.n_streams * tail, self.n_streams * ring
         self._d_tail = engine.alloc(max(4, self._tail_floats * 4))                      # running_spec[:, 1:] (:92) per stream
         self._d_hist = engine.alloc(self._hist_len * 4) if ring else None
+        self._d_level = None
+        if self.running is not None:                        # the carried column sums (or the one maximum) per stream
+            per = self.running.state_floats()
+            self._level_off = np.arange(self.n_streams, dtype=np.int64) * per
+            self._level_floats = self.n_streams * per
+            self._d_level = engine.alloc(self._level_floats * 4)
         self._work = {}
         #: a dict here receives the seconds per stage (gate / embed / topk / vote / rows; synchronises after every stage)
         self.stages = None
@@ -769,9 +873,15 @@ class PieceTrackerBank(object):
             eng.sync()
             self.stages[name] = self.stages.get(name, 0.0) + time.perf_counter() - t0
             return out
-        m_prob, voiced, n_voiced = timed("gate", eng.track_stream_gate_dev, cols_ptr, cols_floats, col_off, n_new,
-                                         self.n_frames, self.levels, win_h, win_w, self._d_tail.ptr, self._tail_floats,
-                                         self._tail_off, d_win.ptr, total)
+        if self.running is None:
+            m_prob, voiced, n_voiced = timed("gate", eng.track_stream_gate_dev, cols_ptr, cols_floats, col_off, n_new,
+                                             self.n_frames, self.levels, win_h, win_w, self._d_tail.ptr,
+                                             self._tail_floats, self._tail_off, d_win.ptr, total)
+        else:
+            m_prob, voiced, n_voiced, _ = timed(
+                "gate", eng.track_stream_gate_running_dev, cols_ptr, cols_floats, col_off, n_new, self.n_frames,
+                self.running.memory_arg, self.running.floor_arg, win_h, win_w, self._d_tail.ptr, self._tail_floats,
+                self._tail_off, self._d_level.ptr, self._level_floats, self._level_off, d_win.ptr, total)
         m = int(n_voiced.sum())
         pieces = counts = np.zeros((0, self.top_k), np.int32)
         n_out, idx = np.zeros(0, np.int32), np.zeros((0, C), np.int32)
@@ -857,10 +967,10 @@ class PieceTrackerBank(object):
             self.n_frames[s], self.n_voiced[s] = 0, 0
 
     def close(self):
-        for buf in [self._d_tail, self._d_hist] + list(self._work.values()):
+        for buf in [self._d_tail, self._d_hist, self._d_level] + list(self._work.values()):
             if buf is not None:
                 buf.free()
-        self._d_tail = self._d_hist = None
+        self._d_tail = self._d_hist = self._d_level = None
         self._work = {}
 
 
@@ -887,11 +997,16 @@ def live_track_scores(engine, sheet_db, processor, recordings, sample_rates, blo
     within the recording; idx included); equal to track_scores on processor.process_many(recordings, ...) at the same
     levels.  levels: per recording the normaliser of the music gate; None takes spec.sum(axis=0).max() of the finished
     spectrogram, as track_scores does - which means computing that spectrogram first: a real stream cannot, and must be
-    given a level.  batched=True: the columns of a group stay on the device (AudioStream.push_dev / flush_dev) and one
+    given a level - or a RunningLevel, with batched=True: then no spectrogram is computed beforehand, every frame is gated
+    at the level of what its stream has brought so far, and the results equal track_scores(..., level=that RunningLevel)
+    on process_many's spectrograms.  batched=True: the columns of a group stay on the device (AudioStream.push_dev / flush_dev) and one
     PieceTrackerBank takes the place of the group's trackers - the same results, a fixed number of calls per round.
     dft: AudioStream's argument, for either branch - None for a dft="direct" processor, "fft" for a dft="fft" processor,
     whose streams compute the FFT and whose results equal track_scores on that processor's process_many."""
     from .audio_frontend import AudioStream
+    running = levels if isinstance(levels, RunningLevel) else None
+    if running is not None and not batched:
+        raise ValueError("live_track_scores(batched=False): " + _BANK_HINT)
     recs = [np.ascontiguousarray(r, dtype=np.float32).ravel() for r in recordings]
     n = len(recs)
     rates = list(sample_rates)
@@ -906,13 +1021,16 @@ def live_track_scores(engine, sheet_db, processor, recordings, sample_rates, blo
     if levels is None:
         levels = [spec.sum(axis=0).max() if spec.shape[1] else 0.0
                   for spec in processor.process_many(recs, scales, rates, flags)]
-    if len(levels) != n:
+    if running is None and len(levels) != n:
         raise ValueError("%d levels for %d recordings" % (len(levels), n))
     parts = [[] for _ in recs]
     for key in sorted(set(zip(rates, flags, scales))):
         sel = [i for i in range(n) if (rates[i], flags[i], scales[i]) == key]
         bank, trackers = None, []
-        if batched:
+        if running is not None:
+            bank = PieceTrackerBank(engine, sheet_db, running, top_k, n_candidates, running_frames, spec_shape,
+                                    n_streams=len(sel))
+        elif batched:
             bank = PieceTrackerBank(engine, sheet_db, [levels[i] for i in sel], top_k, n_candidates, running_frames,
                                     spec_shape)
         else:
@@ -1721,21 +1839,34 @@ def live_follow_scores(engine, sheet_db, specs, levels, block_frames=20, n_slots
     one PieceTrackerBank and one ScoreFollowerBank.  `specs`: one (bins, frames) spectrogram per stream, pushed in
     rounds of block_frames columns (a stream that has ended brings empty blocks) - or any iterable of rounds, each one
     block per stream as host arrays or as the DeviceArrays handle of AudioStream.push_dev (not freed here).  levels:
-    per stream the normaliser of the music gate.  Per round: the tracker bank takes the blocks; per stream the leaders
+    per stream the normaliser of the music gate, or one RunningLevel for all streams (the number of streams is then
+    taken from `specs`: its length, or that of its first round).  Per round: the tracker bank takes the blocks; per stream the leaders
     of its last voiced frame of the round (at most n_slots of the top_k) go to set_candidates - nothing where the round
     had no voiced frame -; the follower bank takes the same blocks.  -> (one TrackResult per stream, one
     BankFollowResult per stream), the fields of the rounds concatenated."""
-    levels = np.ascontiguousarray(levels, dtype=np.float32)
-    n = int(levels.size)
+    running = levels if isinstance(levels, RunningLevel) else None
+    if running is None:
+        levels = np.ascontiguousarray(levels, dtype=np.float32)
+        n = int(levels.size)
     if block_frames < 1:
         raise ValueError("block_frames must be >= 1")
     if isinstance(specs, (list, tuple)) and all(isinstance(x, np.ndarray) and x.ndim == 2 for x in specs):
         whole = [np.ascontiguousarray(x, dtype=np.float32) for x in specs]
         longest = max([x.shape[1] for x in whole] + [0])
         rounds = ([np.ascontiguousarray(x[:, f:f + block_frames]) for x in whole] for f in range(0, longest, block_frames))
+        if running is not None:
+            n = len(whole)
     else:
         rounds = iter(specs)
-    tracker = PieceTrackerBank(engine, sheet_db, levels, top_k, n_candidates, running_frames, spec_shape)
+        if running is not None:
+            import itertools
+            first = next(rounds, None)
+            if first is None:
+                raise ValueError("live_follow_scores: no rounds, so no number of streams for the RunningLevel")
+            n = len(first[2]) if _is_device(first) else len(first)
+            rounds = itertools.chain([first], rounds)
+    tracker = PieceTrackerBank(engine, sheet_db, levels, top_k, n_candidates, running_frames, spec_shape,
+                               n_streams=n if running is not None else None)
     follower = None
     tracks, follows = [[] for _ in range(n)], [[] for _ in range(n)]
     try:

@@ -6,7 +6,8 @@ umc_a2s_server.py (:178-189):
         --train_split splits/all_split.yaml --config exp_configs/mutopia_full_aug.yaml \
         --init_sheet_db --full_eval --dump_results [--real_perf] [--n_candidates 25] [--estimate_UV] \
         --system_params system_params.pkl --bar_params bar_params.pkl [--device_post] [--resample] [--page_width 835]
-        [--deskew] [--live [--bank] [--live_dft direct|fft] [--block_ms 100] [--running_frames 100]]
+        [--deskew] [--live [--bank] [--live_dft direct|fft] [--block_ms 100] [--running_frames 100]
+                   [--level running [--level_memory N] [--level_floor F]]]
 
 <dir> holds one folder per piece: sheet/*.png (the page scans), score_ppq.* (the synthesised recording) and, for
 --real_perf, 01_performance*.  The pages go through the two segmentation networks (their parameter pickles:
@@ -41,6 +42,9 @@ the first frame at which the piece leads and the share of voiced frames at which
 music gate is taken from the finished spectrogram, as --track of audio_sheet_server does; a microphone has to be given one.
 --bank (with --live) tracks all recordings of one sample rate with one piece_identification.PieceTrackerBank, whose
 state stays on the device (live_track_scores(batched=True)): the same printout and the same file.
+--level running (with --live --bank; default recording) gates every frame at the level of what its stream has brought
+so far (piece_identification.RunningLevel; --level_memory N: of its last N columns, --level_floor F: never below F): no
+spectrogram is computed beforehand - what a microphone can do.  The report and the file name the rule.
 --live_dft fft (with --live; default direct) computes the streamed frames with the real-input FFT
 (asr_audio_stream_push_fft_dev): the processor is built with dft="fft" and its streams are asked for by that name, so the
 tracking equals track_scores on that processor's spectrograms.  --fast_dft stays a flag of the offline routes.
@@ -52,7 +56,8 @@ import numpy as np
 
 from . import audio2sheet_align
 from .audio_frontend import SpectrogramProcessor
-from .audio_sheet_server import TRACK_TOP_K, common_arguments, report_ranks, report_tracking
+from .audio_sheet_server import (TRACK_TOP_K, check_level_arguments, common_arguments, level_arguments, level_rule,
+                                 report_ranks, report_tracking)
 from .piece_identification import EmbeddingDB, detect_performances, detect_scores, live_track_scores
 from .sheet_utils import umc
 
@@ -99,6 +104,7 @@ def _arguments(argv, direction):
         p.add_argument("--block_ms", type=float, default=100.0, help="milliseconds of audio per block (--live)")
         p.add_argument("--running_frames", type=int, default=100,
                        help="voiced frames in the history of the running vote (--live)")
+        level_arguments(p, "--live --bank")
     args = p.parse_args(argv)
     if args.fast_dft and getattr(args, "live", False):
         p.error("--fast_dft with --live: the streamed front-end computes the direct DFT unless --live_dft fft asks for "
@@ -107,6 +113,10 @@ def _arguments(argv, direction):
         p.error("--live_dft needs --live: it chooses the transform of the streamed front-end")
     if getattr(args, "bank", False) and not args.live:
         p.error("--bank needs --live: it chooses how the streamed recordings are tracked")
+    if direction == "A2S":
+        check_level_arguments(p, args, args.live and args.bank,
+                              "--level running needs --live --bank: the running level's state lives on the device, in "
+                              "the PieceTrackerBank")
     return args
 
 
@@ -116,9 +126,10 @@ def tracking_file(param_file, dset, real_perf=False):
 
 
 def live_track(engine, db, processor, piece_paths, names, audio_file, n_candidates, running_frames, block_ms,
-               batched=False, dft=None):
+               batched=False, dft=None, level=None):
     """the recordings of `piece_paths`, streamed in blocks of block_ms milliseconds -> (names, first_lead, lead_share) as
-    audio_sheet_server.track.  dft: live_track_scores' ("fft" with a dft="fft" processor)"""
+    audio_sheet_server.track.  dft: live_track_scores' ("fft" with a dft="fft" processor); level: None - the finished
+    spectrogram's maximum, computed beforehand - or a RunningLevel (batched only)"""
     from .audio_frontend import read_audio
     recs, scales, rates, integer = [], [], [], []
     for piece_path in piece_paths:
@@ -128,7 +139,7 @@ def live_track(engine, db, processor, piece_paths, names, audio_file, n_candidat
         rates.append(rate)
         integer.append(is_int)
     steps = [max(1, int(round(rate * block_ms / 1000.0))) for rate in rates]
-    results = live_track_scores(engine, db, processor, recs, rates, steps, None, top_k=TRACK_TOP_K,
+    results = live_track_scores(engine, db, processor, recs, rates, steps, level, top_k=TRACK_TOP_K,
                                 n_candidates=n_candidates, running_frames=running_frames, integer=integer,
                                 window_scales=scales, batched=batched, dft=dft)
     ids = {name: i for i, name in db.id_to_name.items()}
@@ -197,9 +208,10 @@ def run(argv, direction):
                 names = [te_pieces[i] for i in queried]
                 return report_tracking(*live_track(engine, db, processor, [piece_paths[i] for i in queried], names,
                                                    audio_file, args.n_candidates, args.running_frames, args.block_ms,
-                                                   batched=args.bank, dft="fft" if live_fft else None),
+                                                   batched=args.bank, dft="fft" if live_fft else None,
+                                                   level=level_rule(args)),
                                        res_file=tracking_file(param_file, dset, args.real_perf) if args.dump_results
-                                       else None)
+                                       else None, level=level_rule(args))
             if not args.full_eval:
                 return []
             print("\nRunning full evaluation:")

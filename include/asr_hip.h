@@ -376,6 +376,65 @@ int asr_track_stream_vote_dev(asr_ctx *ctx, const int32_t *idx_dev, int64_t n_ro
                               int32_t *hist_dev, int64_t hist_len, const int64_t *hist_off, int32_t *pieces,
                               int32_t *counts, int32_t *n_out);
 
+/* ---- the music gate at the level of what has been heard so far (track_level_kernels.hip) ----------------------------
+ * _detect_music (:524-528) divides by spec.sum(axis=0).max() of the finished spectrogram; the reference's microphone
+ * branch (spec=None) cannot run it, and a live stream has no such number.  The causal rule is the reference's own rule
+ * applied to what has been heard, optionally with a bounded memory so that one loud bang does not deafen the gate for
+ * the rest of a session.
+ *
+ * Inputs, for a stream or recording with columns 0, 1, ...: c_j = the float32 sum of column j over the bins, added row
+ *   after row (what the two gate calls above compute); width = w; memory = L: 0 (unbounded) or w <= L <= 2^20; floor =
+ *   F: a float32, or -inf for none.
+ * Rule, per frame i:
+ *     level_i  = fmaxf(F, max{ c_j : max(0, i - L + 1) <= j <= i })            (L == 0: 0 <= j <= i)
+ *     m_prob_i = the gate of asr_track_gate_dev - the eight-accumulator mean of the w column sums that end at i (zeros
+ *                before column 0) divided by float32(w), divided by float32(level_i * float32(0.15)), clipped to
+ *                [0, 1], NaN stays NaN - the same device function, at level_i
+ *     voiced_i = m_prob_i > 0.5 and i >= w                                     (i: the stream position)
+ * Consequences:
+ *   - With F = -inf and L == 0, (m_prob_i, voiced_i) is the last entry of asr_track_gate_dev on columns 0 .. i.
+ *   - With F = -inf and L >= w, m_prob_i is the last m_prob entry of asr_track_gate_dev on columns
+ *     max(0, i - L + 1) .. i.  This needs L >= w - the mean would otherwise read columns the level does not cover - so
+ *     0 < L < w is rejected.
+ *   - A silent prefix gives 0 / 0 = NaN and is unvoiced, as there.
+ *   - Inputs must be finite: a non-finite column sum leaves the results unspecified (nothing faults).  max is exact on
+ *     finite values, so no scan order, no cut into blocks and no neighbour in the batch changes a bit.
+ *
+ * asr_track_gate_running_dev: whole recordings - the causal gate of finished recordings, which is how one evaluates
+ *   offline what a live session will do.  Arguments as in asr_track_gate_dev without norm and frame0; level (host,
+ *   sum(frames) floats, may be NULL) receives level_i per frame.  ASR_ERR_INVALID as there, and for memory negative, in
+ *   1 .. width - 1 or above 2^20, and for floor NaN or +inf.  Four launches whatever n_rec is (three with memory == 0):
+ *   the column sums; with memory > 0 per recording the maxima from every column to the end of its block of L columns;
+ *   per recording the maxima from the start of the block, combined per frame with the former (van Herk / Gil-Werman:
+ *   level_i = fmaxf(F, fmaxf(suffix[i - L + 1], prefix[i])), no frame rescans its window); the gate.  Both maxima are
+ *   segmented workgroup scans, one workgroup per recording.
+ *
+ * asr_track_stream_gate_running_dev: asr_track_stream_gate_dev in every respect - blocks, tails, windows in stream and
+ *   frame order, m_prob, voiced, n_voiced, validation, nothing launched and no state touched on error - except that
+ *   the `level` array is replaced by memory and floor, and that a stream carries a level state at float level_off[s]
+ *   of level_dev (level_floats floats), updated in place:
+ *     L == 0: one float, the maximum column sum so far;
+ *     L > 0 : L - 1 floats, a ring with c_f in slot f mod (L - 1), valid for the last min(frames_before, L - 1) frames.
+ *   With frames_before[s] == 0 the state is not read and need not be initialised; a stream with n_new[s] == 0 leaves
+ *   it untouched.  level (host, sum(n_new) floats, may be NULL): level_i per new frame.  Per frame the results are
+ *   those of asr_track_gate_running_dev on the stream's columns so far, whatever the cut into blocks and whatever the
+ *   other streams bring.  Further ASR_ERR_INVALID cases: memory negative, in 1 .. width - 1 or above 2^20; floor NaN or
+ *   +inf; a level state outside level_floats; two level states that overlap.  Seven launches whatever n_streams is
+ *   (six with memory == 0): the column sums, the suffix maxima over [valid ring entries in frame order | new column
+ *   sums] (memory > 0), the prefix maxima and levels, the gate with the window numbering, the windows, the tails, and
+ *   behind every reader of the old state the level states (one workgroup per stream: its last min(n_new, L - 1) column
+ *   sums to their slots - with fewer old and new entries coexist in the ring).  Work per call is O(state + new
+ *   frames) per stream. */
+int asr_track_gate_running_dev(asr_ctx *ctx, const float *src_dev, int64_t src_floats, int n_rec, const int64_t *offsets,
+                               const int32_t *bins, const int32_t *frames, int width, int memory, float floor,
+                               float *m_prob, uint8_t *voiced, float *level);
+int asr_track_stream_gate_running_dev(asr_ctx *ctx, const float *cols_dev, int64_t cols_floats, int n_streams,
+                                      const int64_t *col_off, const int32_t *n_new, const int64_t *frames_before,
+                                      int memory, float floor, int bins, int width, float *tail_dev, int64_t tail_floats,
+                                      const int64_t *tail_off, float *level_dev, int64_t level_floats,
+                                      const int64_t *level_off, float *win_dev, int64_t win_cap, float *m_prob,
+                                      uint8_t *voiced, int32_t *n_voiced, float *level);
+
 /* ---- audio front-end -------------------------------------------------
  * The madmom chain the reference feeds its spectrogram tower with (tutorials/Embedding Tutorial.ipynb cell 28,
  * msmd.midi_parser.processor; audio_sheet_server.py:632,678 `processor.process(audio_file).T`):

@@ -16,7 +16,15 @@ the kernel times of the two new calls from the library's profile scopes (track_s
 numbering, track_stream_windows = window assembly + tail slide, track_stream_vote = votes + ring write-back).  The
 window scope's bytes written (twice: every float is read once and written once) are set against the rate of a
 device-to-device copy timed in the same process.  Prints one
-JSON line."""
+JSON line.
+
+    python tools/bench_live_track.py --level [--out profiles/r28_live_level.json]
+
+measures instead what the gate at the level of what has been heard so far costs: three banks - the fixed level (the
+route above, the baseline), RunningLevel() and RunningLevel(memory=--level_memory) - get the same device columns and
+alternate sample by sample in one process.  Per setting the whole round and, in samples of their own with a
+synchronisation after every stage, the bank's `gate` stage; medians of --reps samples of --rounds rounds with their
+ranges.  The streams are pushed until the history and the level's ring are full before anything is timed."""
 import argparse
 import json
 import os
@@ -156,6 +164,73 @@ def case(eng, db, pid, n_streams, n_cols, args, kw):
         d_cols.free()
 
 
+def level_case(eng, db, pid, n_streams, n_cols, args, kw):
+    """one round of n_cols columns on n_streams streams at the three level rules -> the row of the result"""
+    rng = np.random.default_rng(28 * n_streams + n_cols)
+    warm = max(WIDTH + args.running_frames + 20, args.level_memory + 50)
+    T = warm + 2 * (args.reps + 1) * args.rounds * n_cols
+    specs = [(3.0 * rng.random((BINS, T)) ** 2).astype(np.float32) for _ in range(n_streams)]
+    rules = {"fixed": None, "running": pid.RunningLevel(), "running_memory": pid.RunningLevel(memory=args.level_memory)}
+    banks = {}
+    d_cols = eng.alloc(n_streams * BINS * max(warm, n_cols) * 4)
+    at = [0]
+
+    def blocks(n):
+        out = [np.ascontiguousarray(s[:, at[0]:at[0] + n]) for s in specs]
+        at[0] += n
+        return out
+
+    def handle(blks):
+        d_cols.upload(np.concatenate([b.ravel() for b in blks]))
+        sizes = [b.size for b in blks]
+        return pid.DeviceArrays(d_cols, [int(o) for o in np.concatenate([[0], np.cumsum(sizes)[:-1]])], [b.shape for b in blks])
+
+    try:
+        for name, rule in rules.items():
+            banks[name] = (pid.PieceTrackerBank(eng, db, [s.sum(axis=0).max() for s in specs], **kw) if rule is None else
+                           pid.PieceTrackerBank(eng, db, rule, n_streams=n_streams, **kw))
+        first = blocks(warm)
+        for bank in banks.values():
+            bank.push(handle(first))
+            assert all(v >= args.running_frames for v in bank.n_voiced), bank.n_voiced   # steady state: history full
+
+        def sample(stage):
+            """every bank over the same args.rounds rounds, one bank after the other -> seconds per round and bank"""
+            per_round = [blocks(n_cols) for _ in range(args.rounds)]
+            out = {}
+            for name, bank in banks.items():
+                bank.stages = {} if stage else None
+                t = 0.0
+                for blks in per_round:
+                    h = handle(blks)                                 # the columns are on the device already: not timed
+                    eng.sync()
+                    t0 = time.perf_counter()
+                    res = bank.push(h)
+                    t += time.perf_counter() - t0
+                    assert all(r.voiced.all() for r in res)          # gate open: the same work behind every gate
+                out[name] = (bank.stages["gate"] if stage else t) / args.rounds
+                bank.stages = None
+            return out
+
+        times = {"round": {k: [] for k in banks}, "gate": {k: [] for k in banks}}
+        for rep in range(args.reps + 1):
+            for what, stage in (("round", False), ("gate", True)):
+                for name, t in sample(stage).items():
+                    if rep:
+                        times[what][name].append(t)
+        row = {"streams": n_streams, "columns": n_cols,
+               "settings": {k: {"round": _stat(times["round"][k]), "gate_stage": _stat(times["gate"][k])} for k in banks}}
+        for what, key in (("round", "round"), ("gate", "gate_stage")):
+            base = float(np.median(times[what]["fixed"]))
+            row[key + "_over_fixed"] = {k: float(np.median(times[what][k]) / base) for k in banks if k != "fixed"}
+        _note("%r" % (row,))
+        return row
+    finally:
+        for bank in banks.values():
+            bank.close()
+        d_cols.free()
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--streams", type=int, nargs="+", default=[1, 16])
@@ -168,6 +243,9 @@ def main():
     p.add_argument("--n_candidates", type=int, default=25)
     p.add_argument("--top_k", type=int, default=7)
     p.add_argument("--out", default=None)
+    p.add_argument("--level", action="store_true",
+                   help="measure the gate at the level of what has been heard so far against the fixed level")
+    p.add_argument("--level_memory", type=int, default=1200, help="--level: the bounded memory (a minute at 20 fps)")
     args = p.parse_args()
     from audio_sheet_retrieval_amd import _lib, piece_identification as pid
     eng = _lib.Engine("mutopia_ccal_cont")
@@ -181,8 +259,13 @@ def main():
     res = {"tool": "bench_live_track", "db_entries": args.db, "pieces": args.pieces, "reps": args.reps,
            "rounds_per_sample": args.rounds, "bins": BINS, "width": WIDTH}
     res.update(kw)
-    res["cases"] = [case(eng, db, pid, n, c, args, kw) for n in args.streams for c in args.columns]
-    res["copy_gb_per_s"] = copy_rate(eng)
+    if args.level:
+        res["tool"], res["level_memory"] = "bench_live_track --level", args.level_memory
+        res["cases"] = [level_case(eng, db, pid, n, c, args, kw) for n in sorted(args.streams, reverse=True)
+                        for c in args.columns]
+    else:
+        res["cases"] = [case(eng, db, pid, n, c, args, kw) for n in args.streams for c in args.columns]
+        res["copy_gb_per_s"] = copy_rate(eng)
     db.close()
     eng.close()
     for row in res["cases"]:
