@@ -44,6 +44,7 @@ EXPORTS = [
     "asr_notes_from_map_dev", "asr_bars_from_map_dev",
     "asr_unroll_systems_dev", "asr_spectrogram_batch_dev", "asr_spectrogram_fft_batch_dev", "asr_resample_batch_dev", "asr_resize_pages_dev",
     "asr_audio_stream_push_dev", "asr_audio_stream_push_fft_dev", "asr_skew_estimate_dev", "asr_deskew_pages_dev",
+    "asr_flatten_pages_dev",
     "asr_track_stream_gate_dev", "asr_track_stream_vote_dev",
     "asr_track_gate_running_dev", "asr_track_stream_gate_running_dev",
     "asr_follow_stream_windows_dev", "asr_follow_stream_log_dev",
@@ -247,6 +248,8 @@ def load_library(path=None):
                                           c_void_p, c_void_p]),
         "asr_deskew_pages_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                          c_int, c_void_p, c_int64]),
+        "asr_flatten_pages_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                          c_int, c_void_p, c_int64, c_void_p]),
         "asr_audio_stream_push_dev": (c_int, [c_void_p, c_void_p, c_int64] + [c_void_p] * 7 + [c_int, c_int, c_int,
                                               c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64,
                                               c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
@@ -1057,6 +1060,23 @@ class Engine(object):
         self._check(self.lib.asr_deskew_pages_dev(
             self.ctx, pages_ptr, int(pages_bytes), page_offsets.ctypes.data, heights.ctypes.data, widths.ctypes.data, n,
             slopes.ctypes.data, int(fill), out_ptr, int(out_bytes)))
+
+    def flatten_pages_dev(self, pages_ptr, pages_bytes, page_offsets, heights, widths, radii, out_ptr, out_bytes, floor=64,
+                          background_ptr=None):
+        """every uint8 page divided by the grey closing of its paper by a (2 * radii[i] + 1)-square, where that is at
+        least `floor`, in two launches (asr_flatten_pages_dev): the result of page i goes to byte page_offsets[i] of the
+        buffer at out_ptr, in the shape of the page, and the closing itself to the same place of the buffer at
+        background_ptr, if one is given.  Byte for byte sheet_utils.omr.flatten_page_host / page_background_host per page"""
+        page_offsets = np.ascontiguousarray(page_offsets, dtype=np.int64)
+        heights = np.ascontiguousarray(heights, dtype=np.int32)
+        widths = np.ascontiguousarray(widths, dtype=np.int32)
+        radii = np.ascontiguousarray(radii, dtype=np.int32)
+        n = heights.size
+        if not (page_offsets.size == widths.size == radii.size == n):
+            raise ValueError("flatten_pages_dev: the per-page tables differ in length")
+        self._check(self.lib.asr_flatten_pages_dev(
+            self.ctx, pages_ptr, int(pages_bytes), page_offsets.ctypes.data, heights.ctypes.data, widths.ctypes.data, n,
+            radii.ctypes.data, int(floor), out_ptr, int(out_bytes), background_ptr))
 
     def unroll_systems_dev(self, pages_ptr, pages_bytes, page_offsets, heights, widths, systems, system_height,
                            strip_offsets, strip_widths, strips_ptr, strips_floats):

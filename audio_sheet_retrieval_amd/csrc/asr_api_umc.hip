@@ -10,6 +10,7 @@
 // spectrogram_fft_kernels.hip.
 // asr_skew_estimate_dev / asr_deskew_pages_dev (the slope of a scan's staves and its correction, before the resize):
 // page_deskew_kernels.hip.
+// asr_flatten_pages_dev (a scan divided by the grey closing of its paper, before the deskew): page_flatten_kernels.hip.
 #include "asr_ctx.h"
 
 int asr_unroll_systems_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
@@ -869,5 +870,111 @@ int asr_deskew_pages_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_byte
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "deskew_pages: %s", hipGetErrorString(e));
+    return mark_main(ctx);
+}
+
+int asr_flatten_pages_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
+                          const int32_t *heights, const int32_t *widths, int n_pages, const int32_t *radii, int floor,
+                          void *out_dev, int64_t out_bytes, void *background_dev) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_pages < 0 || pages_bytes < 0 || out_bytes < 0) return fail(ctx, ASR_ERR_INVALID, "flatten_pages: bad sizes");
+    if (floor < 0 || floor > 255) return fail(ctx, ASR_ERR_INVALID, "flatten_pages: floor %d outside [0, 255]", floor);
+    if (n_pages == 0) return ASR_OK;
+    if (!page_offsets || !heights || !widths || !radii || !pages_dev || !out_dev)
+        return fail(ctx, ASR_ERR_INVALID, "flatten_pages: NULL argument");
+    static_assert(asr::FLATTEN_MAX_DIM == asr::SKEW_MAX_DIM, "skew_check_pages checks the dimensions of both stages");
+    int rc = skew_check_pages(ctx, "flatten_pages", pages_bytes, page_offsets, heights, widths, n_pages);
+    if (rc != ASR_OK) return rc;
+    const char *in0 = (const char *)pages_dev, *out0 = (const char *)out_dev, *bg0 = (const char *)background_dev;
+    if (in0 < out0 + out_bytes && out0 < in0 + pages_bytes)
+        return fail(ctx, ASR_ERR_INVALID, "flatten_pages: the output buffer overlaps the pages");
+    if (bg0 && bg0 < in0 + pages_bytes && in0 < bg0 + out_bytes)
+        return fail(ctx, ASR_ERR_INVALID, "flatten_pages: the background buffer overlaps the pages");
+    if (bg0 && bg0 < out0 + out_bytes && out0 < bg0 + out_bytes)
+        return fail(ctx, ASR_ERR_INVALID, "flatten_pages: the background buffer overlaps the output");
+    // chunks of whole pages whose D fit ASR_OMR_BUDGET_MB (at least one page each)
+    const char *env = getenv("ASR_OMR_BUDGET_MB");
+    const size_t budget = (size_t)std::max<int64_t>(env && *env ? atoll(env) : 4096, 1) << 20;
+    struct Chunk { int first, n, max_r; size_t d_bytes; int64_t tiles_d, tiles_p; size_t first_at; };
+    std::vector<Chunk> chunks;
+    std::vector<asr::FlattenPage> table(n_pages);
+    std::vector<int64_t> first_d, first_p;                         // per chunk: n + 1 running tile counts, of D and of the page
+    double bytes_d = 0.0, bytes_p = 0.0;
+    constexpr int T = asr::FLATTEN_TILE;
+    for (int p = 0; p < n_pages; ++p) {
+        const int64_t h = heights[p], w = widths[p], r = radii[p];
+        if (r < 1 || r > asr::FLATTEN_MAX_RADIUS)
+            return fail(ctx, ASR_ERR_INVALID, "flatten_pages: page %d: radius %d outside [1, %d]", p, radii[p],
+                        asr::FLATTEN_MAX_RADIUS);
+        if (h * w > out_bytes || page_offsets[p] > out_bytes - h * w)
+            return fail(ctx, ASR_ERR_INVALID, "flatten_pages: output %d (%lld x %lld at %lld) outside the %lld-byte buffer", p,
+                        (long long)h, (long long)w, (long long)page_offsets[p], (long long)out_bytes);
+        const int64_t dh = h + 2 * r, dw = w + 2 * r;
+        const size_t d_bytes = (size_t)(dh * dw);
+        if (chunks.empty() || chunks.back().d_bytes + d_bytes > budget) {
+            if (!chunks.empty()) {
+                first_d.push_back(chunks.back().tiles_d);
+                first_p.push_back(chunks.back().tiles_p);
+            }
+            chunks.push_back({p, 0, 0, 0, 0, 0, first_d.size()});
+        }
+        Chunk &c = chunks.back();
+        asr::FlattenPage &e = table[p];
+        e.off = page_offsets[p];
+        e.d = (int64_t)c.d_bytes;
+        e.h = (int32_t)h; e.w = (int32_t)w; e.r = (int32_t)r;
+        e.tiles_x_d = (int32_t)((dw + T - 1) / T);
+        e.tiles_x_p = (int32_t)((w + T - 1) / T);
+        e.pad = 0;
+        first_d.push_back(c.tiles_d);
+        first_p.push_back(c.tiles_p);
+        c.n += 1;
+        c.max_r = std::max(c.max_r, (int)r);
+        c.d_bytes += d_bytes;
+        c.tiles_d += (int64_t)e.tiles_x_d * ((dh + T - 1) / T);
+        c.tiles_p += (int64_t)e.tiles_x_p * ((h + T - 1) / T);
+        bytes_d += (double)(h * w) + (double)d_bytes;
+        bytes_p += (double)d_bytes + (double)(h * w) * (background_dev ? 3.0 : 2.0);
+    }
+    first_d.push_back(chunks.back().tiles_d);
+    first_p.push_back(chunks.back().tiles_p);
+    size_t max_d = 0;
+    for (const Chunk &c : chunks) {
+        if (c.tiles_d > 0x7fffffffLL)
+            return fail(ctx, ASR_ERR_INVALID, "flatten_pages: %lld tiles in one chunk", (long long)c.tiles_d);
+        max_d = std::max(max_d, c.d_bytes);
+    }
+    // workspace: running tile counts of D | of the pages | page table (one upload) | D of one chunk
+    const size_t b_first = first_d.size() * sizeof(int64_t), b_table = table.size() * sizeof(asr::FlattenPage);
+    const size_t o_table = 2 * b_first, o_d = skew_align(o_table + b_table), total = o_d + max_d;
+    std::vector<char> blob(o_table + b_table);
+    memcpy(blob.data(), first_d.data(), b_first);
+    memcpy(blob.data() + b_first, first_p.data(), b_first);
+    memcpy(blob.data() + o_table, table.data(), b_table);
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    rc = skew_ws_reserve(ctx, total);
+    if (rc != ASR_OK) return rc;
+    char *ws = (char *)ctx->skew_ws;
+    uint8_t *d_ws = (uint8_t *)(ws + o_d);
+    hipError_t e = hipMemcpyAsync(ws, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream);
+    for (size_t i = 0; i < chunks.size() && e == hipSuccess; ++i) {
+        const Chunk &c = chunks[i];
+        const asr::FlattenPage *d_table = (const asr::FlattenPage *)(ws + o_table) + c.first;
+        {
+            ProfScope ps(ctx, "flatten_dilate", 0, 0.0, bytes_d / chunks.size());
+            e = asr::launch_flatten_dilate(ctx->stream, (const uint8_t *)pages_dev, (const int64_t *)ws + c.first_at, d_table,
+                                           c.n, c.tiles_d, c.max_r, d_ws);
+        }
+        if (e == hipSuccess) {
+            ProfScope ps(ctx, "flatten_erode", 0, 0.0, bytes_p / chunks.size());
+            e = asr::launch_flatten_erode(ctx->stream, (const uint8_t *)pages_dev, d_ws,
+                                          (const int64_t *)(ws + b_first) + c.first_at, d_table, c.n, c.tiles_p, c.max_r,
+                                          floor, (uint8_t *)out_dev, (uint8_t *)background_dev);
+        }
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "flatten_pages: %s", hipGetErrorString(e));
     return mark_main(ctx);
 }

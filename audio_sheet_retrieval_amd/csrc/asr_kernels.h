@@ -502,6 +502,28 @@ struct DeskewPage {
 };
 hipError_t launch_deskew_pages(hipStream_t s, const uint8_t *pages, uint8_t *out, const int64_t *tile_first,
                                const DeskewPage *table, int n_pages, int64_t total_tiles, int fill);
+// paper of scanned pages (page_flatten_kernels.hip; include/asr_hip.h carries the definition).  Two launches: the dilate
+// writes D, (h + 2r) x (w + 2r) bytes per page, to workspace; the erode reads it and writes the background and the divided
+// page.  One 256-thread workgroup per tile of FLATTEN_TILE x FLATTEN_TILE results, its source with the halo of 2r in LDS.
+constexpr int FLATTEN_TILE = 64;
+constexpr int FLATTEN_THREADS = 256;
+constexpr int FLATTEN_MAX_RADIUS = 127;
+constexpr int FLATTEN_MAX_DIM = 16384;
+struct FlattenPage {
+    int64_t off;            // byte offset of the page in the source buffer, of its result and of its background
+    int64_t d;              // byte offset of the page's D in the workspace of its chunk
+    int32_t h, w;
+    int32_t r;              // radius
+    int32_t tiles_x_d;      // column tiles of D: ceil((w + 2r) / FLATTEN_TILE)
+    int32_t tiles_x_p;      // column tiles of the page: ceil(w / FLATTEN_TILE)
+    int32_t pad;
+};
+size_t flatten_lds_bytes(int radius);       // dynamic LDS of a workgroup at this radius (grows with it)
+hipError_t launch_flatten_dilate(hipStream_t s, const uint8_t *pages, const int64_t *tile_first, const FlattenPage *table,
+                                 int n_pages, int64_t total_tiles, int max_radius, uint8_t *dws);
+hipError_t launch_flatten_erode(hipStream_t s, const uint8_t *pages, const uint8_t *dws, const int64_t *tile_first,
+                                const FlattenPage *table, int n_pages, int64_t total_tiles, int max_radius, int floor_,
+                                uint8_t *out, uint8_t *background);
 // batch assembly of the training pool: desc_dev holds n x 9 doubles (see piece_vote_kernels.hip)
 hipError_t launch_gather_windows(hipStream_t s, const float *src, const double *desc_dev, int n, int out_h, int out_w,
                                  float *out);

@@ -444,6 +444,47 @@ def deskew_page_host(page, max_slope=64, fill=255):
     return shear_page_host(page, k, fill), k
 
 
+FLATTEN_TILE = 64           # results per side of a workgroup's tile of flatten_pass_kernel (csrc/asr_kernels.h)
+MAX_RADIUS = 127            # the largest radius of asr_flatten_pages_dev
+FLATTEN_FLOOR = 64          # the default floor: a background darker than this is not paper
+
+
+def flatten_radius(width):
+    """the default radius of asr_flatten_pages_dev for a page of this width: wider than a note head, thinner than
+    anything a shadow does - 13 at 835 columns, 39 at 2480"""
+    return min(MAX_RADIUS, max(1, (int(width) + 32) // 64))
+
+
+def _flatten_arguments(radius, floor, who):
+    radius, floor = int(radius), int(floor)
+    if not 1 <= radius <= MAX_RADIUS or not 0 <= floor <= 255:
+        raise ValueError("%s: radius %d (1 .. %d) / floor %d (0 .. 255)" % (who, radius, MAX_RADIUS, floor))
+    return radius, floor
+
+
+def page_background_host(page, radius):
+    """the background B of asr_flatten_pages_dev on the host (the definition in include/asr_hip.h): the grey closing of
+    a uint8 page by a (2 * radius + 1)-square - the maximum over the page's radius-neighbourhood, where the outside is
+    absent, then the minimum of that.  The device returns the same bytes."""
+    page = _uint8_page(page, "page_background_host")
+    r, _ = _flatten_arguments(radius, 0, "page_background_host")
+    size = 2 * r + 1
+    D = ndimage.maximum_filter(np.pad(page, r, mode="constant", constant_values=0), size=size, mode="constant", cval=0)
+    B = ndimage.minimum_filter(D, size=size, mode="constant", cval=255)
+    return np.ascontiguousarray(B[r:r + page.shape[0], r:r + page.shape[1]])
+
+
+def flatten_page_host(page, radius=None, floor=FLATTEN_FLOOR):
+    """asr_flatten_pages_dev on the host: the page divided by its background (page_background_host; radius None:
+    flatten_radius of its width), 255 * P / B rounded with a half going up, where B >= max(floor, 1); the page itself
+    elsewhere.  White paper (B == 255) is reproduced byte for byte.  The device returns the same bytes."""
+    page = _uint8_page(page, "flatten_page_host")
+    r, floor = _flatten_arguments(flatten_radius(page.shape[1]) if radius is None else radius, floor, "flatten_page_host")
+    B = page_background_host(page, r).astype(np.int64)
+    P = page.astype(np.int64)
+    return np.where(B >= max(floor, 1), (510 * P + B) // (2 * np.maximum(B, 1)), P).astype(np.uint8)
+
+
 class DevicePages(object):
     """uint8 pages back to back in one device buffer, as asr_seg_predict_dev (IN_U8_RAW) and asr_unroll_systems_dev
     read them: uploaded once, used by both networks and by the unroll."""
@@ -518,6 +559,35 @@ class DevicePages(object):
             raise
         return res
 
+    def flattened(self, radius=None, floor=FLATTEN_FLOOR):
+        """a new DevicePages on the same engine: every page divided by the grey closing of its paper, in the shape it has
+        (asr_flatten_pages_dev; radius None: flatten_radius of each page's width, a number: that radius for all pages, a
+        sequence: one per page).  The result carries the radii as .radii (int32); nothing is uploaded or downloaded.
+        This object stays valid; free both."""
+        if radius is None:
+            radii = [flatten_radius(w) for w in self.widths]
+        elif np.ndim(radius) == 0:
+            radii = [int(radius)] * len(self)
+        else:
+            radii = radius
+        radii = np.ascontiguousarray(radii, dtype=np.int32)
+        if radii.shape != (len(self),):
+            raise ValueError("%d radii for %d pages" % (radii.size, len(self)))
+        res = DevicePages.__new__(DevicePages)
+        res.engine = self.engine
+        res.heights, res.widths, res.sizes, res.offsets = self.heights.copy(), self.widths.copy(), self.sizes.copy(), \
+            self.offsets.copy()
+        res.nbytes = self.nbytes
+        res.radii = radii
+        res.buf = self.engine.alloc(max(res.nbytes, 4))
+        try:
+            self.engine.flatten_pages_dev(self.buf.ptr, self.nbytes, self.offsets, self.heights, self.widths, radii,
+                                          res.buf.ptr, res.nbytes, floor)
+        except Exception:
+            res.buf.free()
+            raise
+        return res
+
     def download_page(self, i):
         """page i as a uint8 array on the host"""
         return self.engine.raw_download(self.buf.ptr + int(self.offsets[i]), (int(self.heights[i]), int(self.widths[i])),
@@ -545,6 +615,16 @@ def deskew_pages_dev(engine, pages, max_slope=64, slopes=None, fill=255):
     raw = DevicePages(engine, pages)
     try:
         return raw.deskewed(max_slope, slopes, fill)
+    finally:
+        raw.free()
+
+
+def flatten_pages_dev(engine, pages, radius=None, floor=FLATTEN_FLOOR):
+    """host pages (2-D uint8 arrays of any sizes) -> a DevicePages holding them with the paper taken out
+    (DevicePages.flattened), with the radii as .radii: one upload of the raw pages.  Free it when done."""
+    raw = DevicePages(engine, pages)
+    try:
+        return raw.flattened(radius, floor)
     finally:
         raw.free()
 

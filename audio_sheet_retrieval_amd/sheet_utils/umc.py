@@ -123,20 +123,25 @@ def load_umc_sheets(data_dir, require_performance=False, omr=None, system_params
 
 
 def load_umc_scans(data_dir, require_performance=False, omr=None, system_params=None, bar_params=None, device=0,
-                   return_device=False, device_post=False, page_width=PAGE_WIDTH, deskew=True, max_slope=64):
-    """load_umc_sheets for flat-bed scans: pages of any resolution whose staves need not be horizontal.  The raw pages
-    are uploaded once; with deskew the slope of every page is estimated among -max_slope .. max_slope (in 1/1024 pixel
-    per pixel) and the page sheared by it on the device (DevicePages.deskewed: asr_skew_estimate_dev,
-    asr_deskew_pages_dev), then the pages are reduced to page_width columns (DevicePages.resized; None: left at their
-    size) - the area resize after the shear takes the interpolation blur away again.  Everything downstream reads the
-    result on the device, as in load_umc_sheets; the return values are the same."""
+                   return_device=False, device_post=False, page_width=PAGE_WIDTH, deskew=True, max_slope=64, flatten=False,
+                   flatten_radius=None, flatten_floor=64):
+    """load_umc_sheets for flat-bed scans: pages of any resolution whose staves need not be horizontal and whose paper
+    need not be white.  The raw pages are uploaded once; with flatten (off by default) every page is first divided by
+    the grey closing of its paper on the device (DevicePages.flattened: asr_flatten_pages_dev; flatten_radius None: by
+    each page's width, flatten_floor: a background darker than this is left alone) - before the deskew, whose shear
+    fills the corners with white and whose score should read ink, not shadow; with deskew the slope of every page is
+    estimated among -max_slope .. max_slope (in 1/1024 pixel per pixel) and the page sheared by it on the device
+    (DevicePages.deskewed: asr_skew_estimate_dev, asr_deskew_pages_dev), then the pages are reduced to page_width columns
+    (DevicePages.resized; None: left at their size) - the area resize after the shear takes the interpolation blur away
+    again.  Everything downstream reads the result on the device, as in load_umc_sheets; the return values are the
+    same."""
     return _load_sheets(data_dir, require_performance, omr, system_params, bar_params, device, return_device, device_post,
-                        page_width, deskew, max_slope)
+                        page_width, deskew, max_slope, (flatten_radius, flatten_floor) if flatten else None)
 
 
 def _load_sheets(data_dir, require_performance, omr, system_params, bar_params, device, return_device, device_post,
-                 page_width, deskew, max_slope):
-    """the body of load_umc_sheets / load_umc_scans"""
+                 page_width, deskew, max_slope, flatten=None):
+    """the body of load_umc_sheets / load_umc_scans.  flatten: None, or (radius, floor) of DevicePages.flattened"""
     if omr is None:
         omr = build_recognizer(system_params, bar_params, device=device)
 
@@ -164,10 +169,12 @@ def _load_sheets(data_dir, require_performance, omr, system_params, bar_params, 
     # every page of every piece: one call per network (prepare_image on the device)
     all_pages = [I for _, _, pages in jobs for I in pages]
     dev_pages = None
-    if (page_width is not None or deskew) and all_pages:
+    if (page_width is not None or deskew or flatten is not None) and all_pages:
         from audio_sheet_retrieval_amd.sheet_utils.omr import _engine
         engine = omr.system_detector.engine or _engine(omr.system_detector.device)
-        dev_pages = DevicePages(engine, all_pages)              # upload raw, then deskew, then resize
+        dev_pages = DevicePages(engine, all_pages)              # upload raw, then flatten, then deskew, then resize
+        if flatten is not None:
+            dev_pages = _next_stage(dev_pages, lambda pages: pages.flattened(*flatten))
         if deskew:
             dev_pages = _next_stage(dev_pages, lambda pages: pages.deskewed(max_slope))
         if page_width is not None:

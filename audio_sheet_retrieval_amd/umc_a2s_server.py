@@ -6,7 +6,7 @@ umc_a2s_server.py (:178-189):
         --train_split splits/all_split.yaml --config exp_configs/mutopia_full_aug.yaml \
         --init_sheet_db --full_eval --dump_results [--real_perf] [--n_candidates 25] [--estimate_UV] \
         --system_params system_params.pkl --bar_params bar_params.pkl [--device_post] [--resample] [--page_width 835]
-        [--deskew] [--live [--bank] [--live_dft direct|fft] [--block_ms 100] [--running_frames 100]
+        [--deskew] [--flatten] [--live [--bank] [--live_dft direct|fft] [--block_ms 100] [--running_frames 100]
                    [--level running [--level_memory N] [--level_floor F]]]
 
 <dir> holds one folder per piece: sheet/*.png (the page scans), score_ppq.* (the synthesised recording) and, for
@@ -31,7 +31,10 @@ and the spectrogram launch (asr_resample_batch_dev).  The pages are taken at the
 them to W columns on the device, between the upload and the first network (asr_resize_pages_dev: exact area
 resampling, the shape rule of the reference's scripts/prepare_umc_data.py).  --deskew (off by default; with or without
 --page_width) takes flat-bed scans whose staves are not horizontal: the slope of every page is estimated and the page
-sheared by it on the device, between the upload and the resize (sheet_utils/umc.load_umc_scans).
+sheared by it on the device, between the upload and the resize (sheet_utils/umc.load_umc_scans).  --flatten (off by
+default; with or without --deskew and --page_width) takes scans whose paper is not white - a spine shadow, a gradient,
+yellowed paper: every page is divided by the grey closing of its paper on the device, right after the upload
+(asr_flatten_pages_dev).
 
 --live (A2S only, off by default) runs the reference's default mode, the running vote of AudioSheetServer.run, on the
 recordings as a sound card would deliver them: every queried piece's recording is read at its own rate
@@ -89,6 +92,10 @@ def _arguments(argv, direction):
     p.add_argument("--deskew", action="store_true",
                    help="estimate the slope of every page's staves and straighten the page on the device, before the "
                         "resize (asr_skew_estimate_dev, asr_deskew_pages_dev; sheet_utils/umc.load_umc_scans)")
+    p.add_argument("--flatten", action="store_true",
+                   help="divide every page by the grey closing of its paper on the device, before the deskew and the "
+                        "resize: shadows, gradients, yellowed paper (asr_flatten_pages_dev; "
+                        "sheet_utils/umc.load_umc_scans)")
     p.add_argument("--fast_dft", action="store_true",
                    help="compute the spectrograms' magnitudes with an FFT (asr_spectrogram_fft_batch_dev; "
                         "SpectrogramProcessor(dft=\"fft\")): the same spectrograms to float32 rounding, not bit for bit")
@@ -163,10 +170,11 @@ def run(argv, direction):
     if args.data_dir is None:
         raise SystemExit("--data_dir: the directory of pieces is required")
     omr = umc.build_recognizer(args.system_params, args.bar_params)
-    if args.deskew:
+    if args.deskew or args.flatten:
         te_pieces, piece_paths, _, strips = umc.load_umc_scans(args.data_dir, require_performance=True, omr=omr,
                                                                return_device=True, device_post=args.device_post,
-                                                               page_width=args.page_width, deskew=True)
+                                                               page_width=args.page_width, deskew=args.deskew,
+                                                               flatten=args.flatten)
     else:
         te_pieces, piece_paths, _, strips = umc.load_umc_sheets(args.data_dir, require_performance=True, omr=omr,
                                                                return_device=True, device_post=args.device_post,

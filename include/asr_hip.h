@@ -1092,7 +1092,29 @@ int asr_bars_from_map_dev(asr_ctx *ctx, const double *maps_dev, const int32_t *h
  *   are.
  *   Both: rows at any alignment.  Before anything is launched: 1 <= H, W <= 16384, 0 <= max_slope <= 128,
  *   |slopes[p]| <= 128, 0 <= fill <= 255, and every page inside the buffers.  A violation returns ASR_ERR_INVALID with a
- *   message and writes nothing.  n_pages == 0 is valid and writes nothing. */
+ *   message and writes nothing.  n_pages == 0 is valid and writes nothing.
+ * asr_flatten_pages_dev = taking the paper out of a scan - a spine shadow, a gradient, yellowed paper - between the upload
+ *   and the deskew.  The reference has no such stage; the yardstick is this definition, all in integers, which
+ *   sheet_utils/omr.page_background_host / flatten_page_host restate in numpy / scipy and the device reproduces exactly.
+ *   A page P is H x W uint8, dark ink on light paper, in the layout of asr_resize_pages_dev; a radius r is 1 .. 127, a
+ *   floor f 0 .. 255.
+ *     dilate  D(y', x') = max { P[y][x] : |y - y'| <= r, |x - x'| <= r, (y, x) inside the page }
+ *             for y' in [-r, H-1+r], x' in [-r, W-1+r]  (the page's r-neighbourhood; every such window meets the page)
+ *     erode   B[y][x]   = min { D(y', x') : |y' - y| <= r, |x' - x| <= r }      for (y, x) inside the page
+ *     result  out[y][x] = (510 * P + B) / (2 * B)  if B >= max(f, 1)   (integer division: 255 * P / B, a half goes up)
+ *                         P                        otherwise           (not paper: a black scanner border stays)
+ *   B is the grey closing of the page by a (2r+1)-square on an unbounded plane where the outside is absent: B >= P, so
+ *   out <= 255; where B == 255 the result is P; a page without ink that is monotone along each axis gives B == P (hence
+ *   the extended grid of D: with windows merely clipped to the page a shadow at a border would stay).  The passes are row
+ *   max, column max, then row min and column min - not a row closing followed by a column closing.
+ *   Page p goes to the same byte offset of out_dev (out_bytes = its size), which must not overlap pages_dev;
+ *   background_dev, unless NULL, receives B in the same layout and must overlap neither.  Bytes that belong to no page are
+ *   left as they are.  radii: host int32[n_pages] (sheet_utils/omr.flatten_radius: min(127, max(1, (W + 32) / 64))).
+ *   Rows at any alignment; two launches per call whatever n_pages is; D is workspace of the context, and batches whose D
+ *   exceed ASR_OMR_BUDGET_MB (default 4096) run in chunks of whole pages with identical results.  Before anything is
+ *   launched: 1 <= H, W <= 16384, 1 <= radii[p] <= 127, 0 <= floor <= 255, every page inside the buffers, and the
+ *   overlaps above.  A violation returns ASR_ERR_INVALID with a message that starts with "flatten_pages:" and writes
+ *   nothing.  n_pages == 0 is valid and writes nothing. */
 int asr_unroll_systems_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
                            const int32_t *heights, const int32_t *widths, int n_pages, const int32_t *systems,
                            int n_systems, int system_height, const int64_t *strip_offsets, const int32_t *strip_widths,
@@ -1140,6 +1162,9 @@ int asr_skew_estimate_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_byt
 int asr_deskew_pages_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
                          const int32_t *heights, const int32_t *widths, int n_pages, const int32_t *slopes, int fill,
                          void *out_dev, int64_t out_bytes);
+int asr_flatten_pages_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
+                          const int32_t *heights, const int32_t *widths, int n_pages, const int32_t *radii, int floor,
+                          void *out_dev, int64_t out_bytes, void *background_dev);
 
 /* ---- device memory (plain pointers; library-owned allocations) ---------- */
 int asr_dev_alloc(asr_ctx *ctx, size_t bytes, void **dptr);
