@@ -357,13 +357,15 @@ TRAINABLE = [i for i in range(90) if i % 5 in (0, 1, 2)]      # W, beta, gamma o
 
 
 def loss_and_grads(x_prepared, z, params, gamma=0.7, l2=1e-5, r=(1e-3, 1e-3, 1e-3), alpha=1.0, routing=None, ties="all",
-                   diag=None, weight=1.0, symmetric=False):
+                   diag=None, weight=1.0, symmetric=False, keep=None, towers_backward=True):
     """Returns loss (incl. the L2 penalty), corr, gradients for TRAINABLE (54
     arrays, same order), and the parameter list after the running-stat side
     effects (BN EMA, CCALayer values).  routing = (tower 1's, tower 2's) dicts for
     tower_forward_train: the pooling selection a device made, imposed on this evaluation.  ties: the max-pool gradient
     rule at windows with equal maxima (maxpool2_bwd_nhwc; "all" = Theano's CPU MaxPoolGrad).  diag: a dict that receives
-    route_check's (gap, flips) per (tower, block) when a routing is imposed."""
+    route_check's (gap, flips) per (tower, block) when a routing is imposed.  keep: a dict that receives what a caller
+    needs to run tower_backward itself (per tower: H, statistics, cache, last shape, and the dH of this evaluation);
+    towers_backward=False stops after the CCALayer stage - the gradients come back as None."""
     dtype = params[0].dtype
     d1, d2 = ({}, {}) if diag is not None else (None, None)
     H1, st1, c1, ls1 = tower_forward_train(x_prepared, params[0:45], routing[0] if routing else None, d1)
@@ -379,6 +381,13 @@ def loss_and_grads(x_prepared, z, params, gamma=0.7, l2=1e-5, r=(1e-3, 1e-3, 1e-
     dout1 = length_norm_bwd(out1, dlv1)
     dout2 = length_norm_bwd(out2, dlv2)
     dH1, dH2 = cca_train_bwd(cca_cache, dout1, dout2)
+    if keep is not None:
+        keep.update(H=(H1, H2), stats=(st1, st2), cache=(c1, c2), last_shape=(ls1, ls2), dH=(dH1, dH2))
+    if not towers_backward:
+        pen = dtype.type(0)
+        for pi in TRAINABLE:
+            pen = pen + (params[pi] * params[pi]).sum(dtype=dtype)
+        return loss + dtype.type(l2) * pen, corr, None, None, (lv1, lv2)
     g1 = tower_backward(params[0:45], c1, ls1, dH1.astype(dtype), ties)
     g2 = tower_backward(params[45:90], c2, ls2, dH2.astype(dtype), ties)
     grads = g1 + g2

@@ -32,22 +32,33 @@ def device_routing(eng, params, B, hw1, hw2):
     pool_ties="all" the SET of window elements the device found equal to the maximum (asr_debug_train_tensor kind 10,
     boolean (B, h/2, w/2, c, 4)), under "first" the window index of the one selected element (from kind 9, its raw value).
     The two exports have to agree: the selected element is the first member of the set."""
+    return routing_from_exports(lambda kind, view, index: eng.debug_train_tensor(kind, view=view, index=index, batch=B),
+                                params, B, hw1, hw2, eng.pool_ties)
+
+
+def routing_from_exports(export, params, B, hw1, hw2, ties):
+    """device_routing on exported tensors: export(kind, view, index) is the flat asr_debug_train_tensor array, or None
+    for "zsel" where the device keeps none (ASR_TRAIN_ZSEL=0) - the selection then comes from the tie sets alone, whose
+    first member is the first maximum."""
     from oracle import train as otrain
     routing = ({}, {})
     for t, (h, w) in enumerate((hw1, hw2)):
         for blk in range(8):
             c = params[45 * t + 5 * blk].shape[0]
             if blk in (1, 3, 5, 7):
-                z = eng.debug_train_tensor("z", view=t + 1, index=blk, batch=B).reshape(B, h, w, c)
-                zsel = eng.debug_train_tensor("zsel", view=t + 1, index=blk, batch=B).reshape(B, h // 2, w // 2, c)
-                first = otrain.routing_from_selected(z, zsel)
-                bits = eng.debug_train_tensor("pool_mask", view=t + 1, index=blk, batch=B).reshape(B, h // 2, w // 2, c)
+                z = export("z", t + 1, blk).reshape(B, h, w, c)
+                zsel = export("zsel", t + 1, blk)
+                bits = export("pool_mask", t + 1, blk).reshape(B, h // 2, w // 2, c)
                 sets = otrain.routing_from_tie_sets(bits)
-                # the stored value belongs to a member of the set (equal raw values share their window index: compare values)
-                zwin = otrain._windows(z)
-                zfirst = np.take_along_axis(zwin, sets.argmax(axis=-1)[..., None], axis=-1)[..., 0]
-                assert np.array_equal(zfirst, zsel), "zsel is not the first element of the device's tie set"
-                routing[t][blk] = sets if eng.pool_ties == "all" else first
+                first = sets.argmax(axis=-1)
+                if zsel is not None:
+                    zsel = zsel.reshape(B, h // 2, w // 2, c)
+                    first = otrain.routing_from_selected(z, zsel)
+                    # the stored value belongs to a member of the set (equal raw values share their window index: compare values)
+                    zwin = otrain._windows(z)
+                    zfirst = np.take_along_axis(zwin, sets.argmax(axis=-1)[..., None], axis=-1)[..., 0]
+                    assert np.array_equal(zfirst, zsel), "zsel is not the first element of the device's tie set"
+                routing[t][blk] = sets if ties == "all" else first
                 h, w = h // 2, w // 2
     return routing
 
