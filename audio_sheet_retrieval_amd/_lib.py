@@ -44,7 +44,7 @@ EXPORTS = [
     "asr_notes_from_map_dev", "asr_bars_from_map_dev",
     "asr_unroll_systems_dev", "asr_spectrogram_batch_dev", "asr_spectrogram_fft_batch_dev", "asr_resample_batch_dev", "asr_resize_pages_dev",
     "asr_audio_stream_push_dev", "asr_audio_stream_push_fft_dev", "asr_skew_estimate_dev", "asr_deskew_pages_dev",
-    "asr_flatten_pages_dev",
+    "asr_flatten_pages_dev", "asr_score_map_dev",
     "asr_track_stream_gate_dev", "asr_track_stream_vote_dev",
     "asr_track_gate_running_dev", "asr_track_stream_gate_running_dev",
     "asr_follow_stream_windows_dev", "asr_follow_stream_log_dev",
@@ -250,6 +250,9 @@ def load_library(path=None):
                                          c_int, c_void_p, c_int64]),
         "asr_flatten_pages_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                           c_int, c_void_p, c_int64, c_void_p]),
+        "asr_score_map_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_int, c_int, c_double, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]),
         "asr_audio_stream_push_dev": (c_int, [c_void_p, c_void_p, c_int64] + [c_void_p] * 7 + [c_int, c_int, c_int,
                                               c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64,
                                               c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
@@ -1094,6 +1097,37 @@ class Engine(object):
             self.ctx, pages_ptr, int(pages_bytes), page_offsets.ctypes.data, heights.ctypes.data, widths.ctypes.data,
             heights.size, systems.ctypes.data, systems.shape[0], int(system_height), strip_offsets.ctypes.data,
             strip_widths.ctypes.data, strip_widths.size, strips_ptr, int(strips_floats)))
+
+    def score_map_dev(self, maps_ptr, heights, widths, page_in_piece, systems, system_index, n_pieces, threshold=0.5,
+                      min_rows=60, tol=10, max_lines=64):
+        """the measures of every piece in strip coordinates from the bar network's float64 maps, which lie back to back
+        on the device, and the table unroll_systems_dev takes, in three launches (asr_score_map_dev).  page_in_piece:
+        (n_pages,) the page's index within its piece; system_index: (n_systems,) the system's index on its page.  ->
+        (measures (n, 8) int32 rows of x0, x1, page, system, col0, col1, row0, row1, piece_first (n_pieces + 1,) int32).
+        Integer for integer sheet_utils.omr.score_map_host.  ValueError when a system has more than max_lines interior
+        bar lines."""
+        heights, widths = self._map_tables("score_map_dev", heights, widths)
+        page_in_piece = np.ascontiguousarray(page_in_piece, dtype=np.int32)
+        systems = np.ascontiguousarray(systems, dtype=np.int32).reshape(-1, 8)
+        system_index = np.ascontiguousarray(system_index, dtype=np.int32)
+        if page_in_piece.shape != heights.shape or system_index.shape != (systems.shape[0],):
+            raise ValueError("score_map_dev: the per-page / per-system tables differ in length")
+        n_pieces, max_lines = int(n_pieces), int(max_lines)
+        if n_pieces < 0 or max_lines < 0:
+            raise ValueError("score_map_dev: n_pieces %d / max_lines %d" % (n_pieces, max_lines))
+        measures = np.zeros((systems.shape[0] * (max_lines + 1), 8), np.int32)
+        piece_first = np.zeros(n_pieces + 1, np.int32)
+        n, over = c_int32(0), c_int32(-1)
+        self._check(self.lib.asr_score_map_dev(
+            self.ctx, maps_ptr, int((heights.astype(np.int64) * widths).sum()), heights.ctypes.data, widths.ctypes.data,
+            heights.size, page_in_piece.ctypes.data, systems.ctypes.data, system_index.ctypes.data, systems.shape[0],
+            n_pieces, float(threshold), int(min_rows), int(tol), max_lines, measures.ctypes.data, piece_first.ctypes.data,
+            byref(n), byref(over)))
+        if over.value >= 0:
+            page, _, _, c0, c1 = systems[over.value, :5]
+            raise ValueError("score_map_dev: system %d (page %d, columns %d:%d) has more than max_lines = %d interior bar "
+                             "lines" % (over.value, page, c0, c1, max_lines))
+        return measures[:n.value].copy(), piece_first
 
     def systems_from_maps_dev(self, pages_ptr, in_mode, page_offsets, heights, widths, system_maps_ptr,
                               bar_maps_ptr=None, max_systems=None, system_seg=None, bar_seg=None):

@@ -11,6 +11,8 @@
 // asr_skew_estimate_dev / asr_deskew_pages_dev (the slope of a scan's staves and its correction, before the resize):
 // page_deskew_kernels.hip.
 // asr_flatten_pages_dev (a scan divided by the grey closing of its paper, before the deskew): page_flatten_kernels.hip.
+// asr_score_map_dev (the bar network's maps and the unroll table -> the measures of every piece in strip coordinates):
+// score_map_kernels.hip.
 #include "asr_ctx.h"
 
 int asr_unroll_systems_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
@@ -976,5 +978,114 @@ int asr_flatten_pages_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_byt
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "flatten_pages: %s", hipGetErrorString(e));
+    return mark_main(ctx);
+}
+
+int asr_score_map_dev(asr_ctx *ctx, const double *maps_dev, int64_t maps_doubles, const int32_t *heights,
+                      const int32_t *widths, int n_pages, const int32_t *page_in_piece, const int32_t *systems,
+                      const int32_t *system_index, int n_systems, int n_pieces, double threshold, int min_rows, int tol,
+                      int max_lines, int32_t *measures, int32_t *piece_first, int32_t *n_measures,
+                      int32_t *overflow_system) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_pages < 0 || n_systems < 0 || n_pieces < 0 || maps_doubles < 0)
+        return fail(ctx, ASR_ERR_INVALID, "score_map: bad sizes");
+    if (min_rows < 1 || tol < 0 || max_lines < 0 || threshold != threshold)
+        return fail(ctx, ASR_ERR_INVALID, "score_map: min_rows %d (>= 1) / tol %d (>= 0) / max_lines %d (>= 0) / threshold %g",
+                    min_rows, tol, max_lines, threshold);
+    if (!piece_first || !n_measures || !overflow_system) return fail(ctx, ASR_ERR_INVALID, "score_map: NULL argument");
+    if (n_systems == 0) {
+        for (int q = 0; q <= n_pieces; ++q) piece_first[q] = 0;
+        *n_measures = 0;
+        *overflow_system = -1;
+        return ASR_OK;
+    }
+    if (!maps_dev || !heights || !widths || !page_in_piece || !systems || !system_index || !measures)
+        return fail(ctx, ASR_ERR_INVALID, "score_map: NULL argument");
+    std::vector<int64_t> map_off((size_t)n_pages + 1, 0);
+    for (int p = 0; p < n_pages; ++p) {
+        if (heights[p] < 0 || widths[p] < 0)
+            return fail(ctx, ASR_ERR_INVALID, "score_map: page %d is %d x %d", p, heights[p], widths[p]);
+        map_off[p + 1] = map_off[p] + (int64_t)heights[p] * widths[p];
+        if (map_off[p + 1] > maps_doubles)
+            return fail(ctx, ASR_ERR_INVALID, "score_map: map %d (%d x %d at %lld) outside the %lld-double buffer", p,
+                        heights[p], widths[p], (long long)map_off[p], (long long)maps_doubles);
+    }
+    // workspace: system table (one upload) | flags | n_lines | lines | piece_count | sys_first | piece_first | header | rows
+    std::vector<asr::ScoreSystem> table(n_systems);
+    int64_t chunks = 0;
+    double elements = 0.0;
+    for (int i = 0; i < n_systems; ++i) {
+        const int32_t *t = systems + (size_t)i * 8;
+        const int32_t page = t[0], r0 = t[1], r1 = t[2], c0 = t[3], c1 = t[4], piece = t[6], x0 = t[7];
+        if (page < 0 || page >= n_pages || piece < 0 || piece >= n_pieces)
+            return fail(ctx, ASR_ERR_INVALID, "score_map: system %d names page %d / piece %d", i, page, piece);
+        if (i > 0 && piece < systems[(size_t)(i - 1) * 8 + 6])
+            return fail(ctx, ASR_ERR_INVALID, "score_map: system %d of piece %d follows one of piece %d", i, piece,
+                        systems[(size_t)(i - 1) * 8 + 6]);
+        if (r0 < 0 || r1 <= r0 || r1 > heights[page] || c0 < 0 || c1 <= c0 || c1 > widths[page])
+            return fail(ctx, ASR_ERR_INVALID, "score_map: system %d rows [%d, %d), columns [%d, %d) do not fit page %d "
+                        "(%d x %d)", i, r0, r1, c0, c1, page, heights[page], widths[page]);
+        if (x0 < 0 || (int64_t)x0 + (c1 - c0) > 0x7fffffffLL)
+            return fail(ctx, ASR_ERR_INVALID, "score_map: system %d at strip column %d", i, x0);
+        asr::ScoreSystem &s = table[i];
+        s.map = map_off[page] + (int64_t)r0 * widths[page] + c0;
+        s.chunk_first = chunks;
+        s.stride = widths[page];
+        s.rows = r1 - r0; s.width = c1 - c0;
+        s.r0 = r0; s.r1 = r1; s.c0 = c0;
+        s.page = page_in_piece[page]; s.system = system_index[i];
+        s.piece = piece; s.x0 = x0;
+        chunks += (s.width + asr::SCORE_MAP_CHUNK - 1) / asr::SCORE_MAP_CHUNK;
+        elements += (double)s.rows * s.width;
+    }
+    const int64_t cap_rows = (int64_t)n_systems * ((int64_t)max_lines + 1);
+    if (chunks > 0x7fffffffLL || cap_rows * 8 > 0x7fffffffLL)
+        return fail(ctx, ASR_ERR_INVALID, "score_map: %lld column chunks / %lld rows in one call", (long long)chunks,
+                    (long long)cap_rows);
+    const size_t b_table = table.size() * sizeof(asr::ScoreSystem);
+    const size_t o_flags = skew_align(b_table), o_nlines = skew_align(o_flags + (size_t)chunks * 8),
+                 o_lines = skew_align(o_nlines + (size_t)n_systems * 4),
+                 o_pcount = skew_align(o_lines + (size_t)n_systems * (size_t)std::max(max_lines, 1) * 4),
+                 o_sfirst = skew_align(o_pcount + (size_t)std::max(n_pieces, 1) * 4),
+                 o_pfirst = skew_align(o_sfirst + (size_t)n_systems * 4),
+                 o_header = o_pfirst + ((size_t)n_pieces + 1) * 4, o_rows = skew_align(o_header + 8),
+                 total = o_rows + (size_t)cap_rows * 32;
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    int rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    rc = skew_ws_reserve(ctx, total);
+    if (rc != ASR_OK) return rc;
+    char *ws = (char *)ctx->skew_ws;
+    const asr::ScoreSystem *d_table = (const asr::ScoreSystem *)ws;
+    unsigned long long *d_flags = (unsigned long long *)(ws + o_flags);
+    int32_t *d_nlines = (int32_t *)(ws + o_nlines), *d_lines = (int32_t *)(ws + o_lines);
+    int32_t *d_pfirst = (int32_t *)(ws + o_pfirst), *d_header = (int32_t *)(ws + o_header);
+    hipError_t e = hipMemcpyAsync(ws, table.data(), b_table, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        ProfScope ps(ctx, "score_map_counts", 0, 0.0, 8.0 * elements);
+        e = asr::launch_score_map_counts(ctx->stream, maps_dev, d_table, n_systems, chunks, threshold, min_rows, d_flags);
+    }
+    if (e == hipSuccess) {
+        ProfScope ps(ctx, "score_map_lines", 0, 0.0, 8.0 * (double)chunks);
+        e = asr::launch_score_map_lines(ctx->stream, d_table, n_systems, d_flags, tol, max_lines, d_nlines, d_lines);
+    }
+    if (e == hipSuccess) {
+        ProfScope ps(ctx, "score_map_table", 0, 0.0, 32.0 * (double)n_systems);
+        e = asr::launch_score_map_table(ctx->stream, d_table, n_systems, n_pieces, max_lines, d_nlines, d_lines,
+                                        (int32_t *)(ws + o_pcount), d_pfirst, d_header, (int32_t *)(ws + o_sfirst),
+                                        (int32_t *)(ws + o_rows));
+    }
+    std::vector<int32_t> head((size_t)n_pieces + 3);                       // piece_first (n + 1) | header (2): adjacent
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(head.data(), d_pfirst, head.size() * 4, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess && head[(size_t)n_pieces + 2] < 0 && head[(size_t)n_pieces + 1] > 0) {
+        e = hipMemcpyAsync(measures, ws + o_rows, (size_t)head[(size_t)n_pieces + 1] * 32, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    }
+    if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "score_map: %s", hipGetErrorString(e));
+    memcpy(piece_first, head.data(), ((size_t)n_pieces + 1) * 4);
+    *n_measures = head[(size_t)n_pieces + 1];
+    *overflow_system = head[(size_t)n_pieces + 2];
     return mark_main(ctx);
 }

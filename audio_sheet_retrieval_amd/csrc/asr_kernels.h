@@ -524,6 +524,29 @@ hipError_t launch_flatten_dilate(hipStream_t s, const uint8_t *pages, const int6
 hipError_t launch_flatten_erode(hipStream_t s, const uint8_t *pages, const uint8_t *dws, const int64_t *tile_first,
                                 const FlattenPage *table, int n_pages, int64_t total_tiles, int max_radius, int floor_,
                                 uint8_t *out, uint8_t *background);
+// measures of the pieces in strip coordinates (score_map_kernels.hip; include/asr_hip.h carries the definition).  Three
+// launches: the flags of SCORE_MAP_CHUNK columns per workgroup as one 64-bit word, the interior lines per system, the table.
+constexpr int SCORE_MAP_CHUNK = 64;         // columns of a workgroup of the count kernel: one lane each
+constexpr int SCORE_MAP_THREADS = 256;      // its threads: the band's rows go round its four waves
+struct ScoreSystem {
+    int64_t map;            // offset (doubles) of map[r0][c0] of the system's page
+    int64_t chunk_first;    // the system's first flag word; it has ceil(width / SCORE_MAP_CHUNK)
+    int32_t stride;         // the page's width
+    int32_t rows, width;    // r1 - r0, c1 - c0
+    int32_t r0, r1, c0;
+    int32_t page, system;   // the page within its piece, the system on its page
+    int32_t piece;
+    int32_t x0;             // strip column of c0
+};
+// flags: one uint64 per chunk; n_lines: int32 per system; lines: max_lines int32 per system (page columns, ascending);
+// piece_count, sys_first: n_pieces / n_systems int32 of workspace; header: total measures, first overflowing system or -1
+hipError_t launch_score_map_counts(hipStream_t s, const double *maps, const ScoreSystem *table, int n_systems,
+                                   int64_t total_chunks, double threshold, int min_rows, unsigned long long *flags);
+hipError_t launch_score_map_lines(hipStream_t s, const ScoreSystem *table, int n_systems, const unsigned long long *flags,
+                                  int tol, int max_lines, int32_t *n_lines, int32_t *lines);
+hipError_t launch_score_map_table(hipStream_t s, const ScoreSystem *table, int n_systems, int n_pieces, int max_lines,
+                                  const int32_t *n_lines, const int32_t *lines, int32_t *piece_count, int32_t *piece_first,
+                                  int32_t *header, int32_t *sys_first, int32_t *measures);
 // batch assembly of the training pool: desc_dev holds n x 9 doubles (see piece_vote_kernels.hip)
 hipError_t launch_gather_windows(hipStream_t s, const float *src, const double *desc_dev, int n, int out_h, int out_w,
                                  float *out);

@@ -280,13 +280,14 @@ def unwrap_systems(page, systems, system_height=SYSTEM_HEIGHT):
     return unwrapped_sheet
 
 
-def unroll_rows(page_shape, systems, system_height=SYSTEM_HEIGHT):
+def unroll_rows(page_shape, systems, system_height=SYSTEM_HEIGHT, with_index=False):
     """The integer rules of unwrap_systems without the copy: one (r0, r1, c0, c1, pad) per kept system - rows
     r0..r1-1, columns c0..c1-1 of the page, `pad` edge rows below them - in order; skipped systems print the
-    reference's message.  Slices resolve as numpy resolves page[r0:r1, c0:c1] on a page of page_shape."""
+    reference's message.  Slices resolve as numpy resolves page[r0:r1, c0:c1] on a page of page_shape.
+    with_index: (r0, r1, c0, c1, pad, i) with i the system's index in `systems` (the score map names a system by it)."""
     h, w = page_shape
     rows = []
-    for system in systems:
+    for i_system, system in enumerate(systems):
         r0 = int(np.mean([system[0, 0], system[2, 0]])) - system_height // 2
         r1 = r0 + system_height
         c0 = int(system[0, 1])
@@ -305,7 +306,7 @@ def unroll_rows(page_shape, systems, system_height=SYSTEM_HEIGHT):
             continue
         if n_cols == 0:
             continue                         # an empty slice adds no column
-        rows.append((r0, r1, c0, c1, to_pad))
+        rows.append((r0, r1, c0, c1, to_pad, i_system) if with_index else (r0, r1, c0, c1, to_pad))
     return rows
 
 
@@ -639,7 +640,7 @@ def unroll_systems_dev(dev_pages, page_rows, piece_of_page, n_pieces, system_hei
         if rows is None:
             continue
         q = int(piece_of_page[p])
-        for r0, r1, c0, c1, pad in rows:
+        for r0, r1, c0, c1, pad in (row[:5] for row in rows):
             table.append((p, r0, r1, c0, c1, pad, q, widths[q]))
             widths[q] += c1 - c0
     if widths.size and widths.max() > np.iinfo(np.int32).max:
@@ -657,6 +658,138 @@ def unroll_systems_dev(dev_pages, page_rows, piece_of_page, n_pieces, system_hei
         strips.free()
         raise
     return strips, [int(o) for o in offsets], [(system_height, int(w)) for w in widths]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the score map: measures in strip coordinates (asr_score_map_dev; the definition is in include/asr_hip.h)
+
+SCORE_MAP_THRESHOLD = 0.5    # a map value above this is bar line
+SCORE_MAP_MIN_ROWS = 60      # a column with this many such rows in a system's band belongs to a bar line
+SCORE_MAP_MAX_LINES = 64     # the default capacity: interior bar lines of one system
+
+
+def strip_bar_counts_host(bar_map, r0, r1, c0, c1, threshold=SCORE_MAP_THRESHOLD):
+    """count[c - c0] = the rows r in [r0, r1) with bar_map[r, c] > threshold, for the page columns c in [c0, c1):
+    int64 (c1 - c0,).  A NaN is not above."""
+    band = np.asarray(bar_map)[r0:r1, c0:c1]
+    with np.errstate(invalid="ignore"):
+        return (band > threshold).sum(axis=0).astype(np.int64)
+
+
+def strip_bar_lines_host(counts, c0, min_rows=SCORE_MAP_MIN_ROWS, tol=10):
+    """the boundaries B of a system whose columns c0 .. c0 + len(counts) - 1 have these counts: a bar line is a maximal
+    run of columns with count >= min_rows, at (first + last) // 2; it is interior when it lies more than tol from c0
+    and from c1 - 1.  -> int64 [c0, the interior lines ascending, c1]."""
+    flag = np.asarray(counts) >= min_rows
+    c1 = c0 + flag.size
+    edge = np.diff(np.concatenate([[0], flag.astype(np.int8), [0]]))
+    first, last = np.flatnonzero(edge == 1), np.flatnonzero(edge == -1) - 1
+    b = c0 + (first + last) // 2
+    b = b[(b - c0 > tol) & ((c1 - 1) - b > tol)]
+    return np.concatenate([[c0], b, [c1]]).astype(np.int64)
+
+
+def _score_map_systems(page_rows, piece_of_page, n_pieces, page_in_piece=None):
+    """the table asr_unroll_systems_dev takes, (n, 8) int32, the systems' indices on their pages and the pages' indices
+    within their pieces, from unroll_rows(..., with_index=True) per page (None: a page that is not unrolled)"""
+    table, index, widths = [], [], np.zeros(n_pieces, np.int64)
+    first_page = {}
+    auto = np.zeros(len(page_rows), np.int32)
+    for p, rows in enumerate(page_rows):
+        if rows is None:
+            continue
+        q = int(piece_of_page[p])
+        auto[p] = p - first_page.setdefault(q, p)
+        for row in rows:
+            if len(row) != 6:
+                raise ValueError("the score map takes unroll_rows(..., with_index=True)")
+            r0, r1, c0, c1, pad, i = row
+            table.append((p, r0, r1, c0, c1, pad, q, widths[q]))
+            index.append(i)
+            widths[q] += c1 - c0
+    if widths.size and widths.max() > np.iinfo(np.int32).max:
+        raise ValueError("a strip of %d columns is too wide" % widths.max())
+    if page_in_piece is None:
+        page_in_piece = auto
+    return (np.asarray(table, np.int32).reshape(-1, 8), np.asarray(index, np.int32),
+            np.ascontiguousarray(page_in_piece, np.int32), widths)
+
+
+def score_map_host(bar_maps, page_rows, piece_of_page, n_pieces, threshold=SCORE_MAP_THRESHOLD,
+                   min_rows=SCORE_MAP_MIN_ROWS, tol=None, max_lines=None, page_in_piece=None, counts=None):
+    """asr_score_map_dev on the host (the definition in include/asr_hip.h).  bar_maps[p]: the bar network's map of page
+    p (2-D; not read for a page whose page_rows[p] is None); page_rows[p]: unroll_rows(..., with_index=True) of page p;
+    piece_of_page[p]: its piece (the pages of a piece in order; page_in_piece overrides the index counted from the
+    piece's first unrolled page).  counts: instead of the maps, strip_bar_counts_host of every kept system in the
+    table's order.  -> (measures (n, 8) int32 rows of x0, x1, page, system, col0, col1, row0, row1, the pieces back to
+    back; piece_first (n_pieces + 1,) int32).  ValueError when a system has more than max_lines interior lines."""
+    tol = BAR_MISSING_TOL if tol is None else tol
+    table, index, page_in_piece, _ = _score_map_systems(page_rows, piece_of_page, n_pieces, page_in_piece)
+    out, per_piece = [], np.zeros(n_pieces, np.int64)
+    for i, (p, r0, r1, c0, c1, _, q, x0) in enumerate(table.tolist()):
+        cnt = strip_bar_counts_host(bar_maps[p], r0, r1, c0, c1, threshold) if counts is None else np.asarray(counts[i])
+        if cnt.shape != (c1 - c0,):
+            raise ValueError("system %d: %d counts for columns %d:%d" % (i, cnt.size, c0, c1))
+        B = strip_bar_lines_host(cnt, c0, min_rows, tol)
+        if max_lines is not None and B.size - 2 > max_lines:
+            raise ValueError("score_map_host: system %d (page %d, columns %d:%d) has more than max_lines = %d interior "
+                             "bar lines" % (i, p, c0, c1, max_lines))
+        for j in range(B.size - 1):
+            out.append((x0 + B[j] - c0, x0 + B[j + 1] - c0, page_in_piece[p], index[i], B[j], B[j + 1], r0, r1))
+        per_piece[q] += B.size - 1
+    piece_first = np.concatenate([[0], np.cumsum(per_piece)]).astype(np.int32)
+    return np.asarray(out, np.int32).reshape(-1, 8), piece_first
+
+
+class DeviceMaps(object):
+    """float64 probability maps of pages back to back in one device buffer, as asr_seg_predict_dev writes them: what
+    detect_systems_keep_bars_dev hands on to score_map_dev.  Free it when done."""
+
+    def __init__(self, engine, buf, heights, widths):
+        self.engine, self.buf = engine, buf
+        self.heights, self.widths, self.sizes, self.offsets = _map_table(heights, widths)
+
+    def __len__(self):
+        return len(self.sizes)
+
+    def free(self):
+        if self.buf is not None:
+            self.buf.free()
+        self.buf = None
+
+    def download_page(self, i):
+        """map i as a float64 array on the host"""
+        return _download_at(self.engine, self.buf, int(self.offsets[i]) * 8,
+                            int(self.sizes[i])).reshape(int(self.heights[i]), int(self.widths[i]))
+
+    def download(self):
+        """all maps as float64 arrays on the host"""
+        return [self.download_page(i) for i in range(len(self))]
+
+
+def upload_maps(engine, maps):
+    """2-D float64 arrays -> a DeviceMaps holding them"""
+    flat = [np.ascontiguousarray(m, dtype=np.float64) for m in maps]
+    for m in flat:
+        if m.ndim != 2:
+            raise ValueError("maps are 2-D, got shape %s" % (m.shape,))
+    host = np.concatenate([m.ravel() for m in flat]) if flat else np.zeros(0, np.float64)
+    buf = engine.alloc(max(host.nbytes, 8)).upload(host)
+    return DeviceMaps(engine, buf, [m.shape[0] for m in flat], [m.shape[1] for m in flat])
+
+
+def score_map_dev(dev_maps, page_rows, piece_of_page, n_pieces, threshold=SCORE_MAP_THRESHOLD,
+                  min_rows=SCORE_MAP_MIN_ROWS, tol=None, max_lines=SCORE_MAP_MAX_LINES, page_in_piece=None):
+    """score_map_host for all pages of all pieces in one device call (asr_score_map_dev: three launches) on the bar
+    network's maps where they are (a DeviceMaps): the same integers.  page_rows as unroll_systems_dev takes them, from
+    unroll_rows(..., with_index=True).  -> (measures (n, 8) int32, piece_first (n_pieces + 1,) int32); ValueError when a
+    system has more than max_lines interior bar lines."""
+    tol = BAR_MISSING_TOL if tol is None else tol
+    if len(page_rows) != len(dev_maps):
+        raise ValueError("%d pages of rows for %d maps" % (len(page_rows), len(dev_maps)))
+    table, index, page_in_piece, _ = _score_map_systems(page_rows, piece_of_page, n_pieces, page_in_piece)
+    return dev_maps.engine.score_map_dev(c_void_p(dev_maps.buf.ptr), dev_maps.heights, dev_maps.widths, page_in_piece,
+                                         table, index, n_pieces, threshold, min_rows, tol, max_lines)
 
 
 def pairwise_sum(a):
@@ -1089,12 +1222,24 @@ class OpticalMusicRecognizer(object):
         systems_from_maps on the host, their maps alone downloaded; self.last_fallback_pages lists their indices.
         The device restates np.histogram's bin rule as numpy >= 2 computes it (checked with 2.2.6); under numpy 1.x
         the equality with detect_systems_pages is not established."""
+        return self._detect_systems_dev(pages, in_mode, dev_pages, False)[0]
+
+    def detect_systems_keep_bars_dev(self, pages, in_mode=IN_U8_RAW, dev_pages=None):
+        """detect_systems_pages_dev that hands the bar network's maps on instead of freeing them: -> (what
+        detect_systems_pages_dev returns, a DeviceMaps of the bar maps of all pages - also of those the host decided -
+        or None without pages).  The score map (score_map_dev) reads them once the unroll rows are known, so the bar
+        network runs once.  The caller frees the DeviceMaps."""
+        if self.bar_detector is None:
+            raise ValueError("detect_systems_keep_bars_dev needs a bar network")
+        return self._detect_systems_dev(pages, in_mode, dev_pages, True)
+
+    def _detect_systems_dev(self, pages, in_mode, dev_pages, keep_bar_maps):
         if dev_pages is not None and (in_mode != IN_U8_RAW or len(dev_pages) != len(pages)):
             raise ValueError("dev_pages goes with the same number of raw uint8 pages (in_mode=IN_U8_RAW)")
         self.last_fallback_pages = []
         self.last_label_passes = 0
         if len(pages) == 0:
-            return []
+            return [], None
         sysd, bard = self.system_detector, self.bar_detector
         eng = sysd.engine
         if bard is not None and bard.engine is not eng:
@@ -1137,7 +1282,10 @@ class OpticalMusicRecognizer(object):
                         out.append(systems_from_maps(img, sp, bp))
                     except Exception as e:
                         out.append(e)
-            return out
+            kept = None
+            if keep_bar_maps:
+                kept, bar_out = DeviceMaps(eng, bar_out, hs, ws), None
+            return out, kept
         finally:
             for b in (sys_out, bar_out, x_sys, x_bar):
                 if b is not None:

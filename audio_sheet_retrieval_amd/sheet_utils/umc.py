@@ -13,7 +13,7 @@ import numpy as np
 from audio_sheet_retrieval_amd.sheet_utils import bar_detector, note_detector, system_detector
 from audio_sheet_retrieval_amd.sheet_utils.omr import (IN_U8_RAW, PAGE_WIDTH, SYSTEM_HEIGHT, DevicePages,
                                                        OpticalMusicRecognizer, SegmentationNetwork, imread_gray,
-                                                       unroll_rows, unroll_systems_dev, unwrap_systems)
+                                                       score_map_dev, unroll_rows, unroll_systems_dev, unwrap_systems)
 
 OKBLUE, ENDC = "\033[94m", "\033[0m"       # utils/plotting.BColors
 
@@ -117,14 +117,16 @@ def load_umc_sheets(data_dir, require_performance=False, omr=None, system_params
     of scripts/prepare_umc_data.py); the networks, the unrolling rules and the unroll see the resized pages.  On the
     host route they are downloaded once for unwrap_systems; with return_device a resized page comes to the host only
     where the post-processing reads it there (device_post=False: every page; device_post=True: a page the device does
-    not decide).  None: the pages are taken as they are."""
+    not decide).  None: the pages are taken as they are.
+    The score map (bars and pages for strip positions) is an option of load_umc_scans, which with deskew=False and
+    page_width=None is this function."""
     return _load_sheets(data_dir, require_performance, omr, system_params, bar_params, device, return_device, device_post,
                         page_width, False, 0)
 
 
 def load_umc_scans(data_dir, require_performance=False, omr=None, system_params=None, bar_params=None, device=0,
                    return_device=False, device_post=False, page_width=PAGE_WIDTH, deskew=True, max_slope=64, flatten=False,
-                   flatten_radius=None, flatten_floor=64):
+                   flatten_radius=None, flatten_floor=64, score_map=False):
     """load_umc_sheets for flat-bed scans: pages of any resolution whose staves need not be horizontal and whose paper
     need not be white.  The raw pages are uploaded once; with flatten (off by default) every page is first divided by
     the grey closing of its paper on the device (DevicePages.flattened: asr_flatten_pages_dev; flatten_radius None: by
@@ -134,16 +136,26 @@ def load_umc_scans(data_dir, require_performance=False, omr=None, system_params=
     (DevicePages.deskewed: asr_skew_estimate_dev, asr_deskew_pages_dev), then the pages are reduced to page_width columns
     (DevicePages.resized; None: left at their size) - the area resize after the shear takes the interpolation blur away
     again.  Everything downstream reads the result on the device, as in load_umc_sheets; the return values are the
-    same."""
+    same.  With deskew=False and page_width=None (and no flatten) this is load_umc_sheets.
+    score_map=True (with return_device=True and a bar network; ValueError otherwise): one more value is returned, the
+    score_map.ScoreMap of the kept pieces - their measures in strip coordinates, built on the device from the bar
+    network's maps in the pass that unrolls the pages (asr_score_map_dev).  The bar network runs once: the systems are
+    then detected by the device post-processing whatever device_post says (the same integers), which hands its bar maps
+    on.  Page coordinates in the map are those of the pages the networks saw, after flatten, deskew and resize."""
     return _load_sheets(data_dir, require_performance, omr, system_params, bar_params, device, return_device, device_post,
-                        page_width, deskew, max_slope, (flatten_radius, flatten_floor) if flatten else None)
+                        page_width, deskew, max_slope, (flatten_radius, flatten_floor) if flatten else None,
+                        score_map=score_map)
 
 
 def _load_sheets(data_dir, require_performance, omr, system_params, bar_params, device, return_device, device_post,
-                 page_width, deskew, max_slope, flatten=None):
+                 page_width, deskew, max_slope, flatten=None, score_map=False):
     """the body of load_umc_sheets / load_umc_scans.  flatten: None, or (radius, floor) of DevicePages.flattened"""
+    if score_map and not return_device:
+        raise ValueError("score_map=True needs return_device=True: the map is built where the bar maps are")
     if omr is None:
         omr = build_recognizer(system_params, bar_params, device=device)
+    if score_map and omr.bar_detector is None:
+        raise ValueError("score_map=True needs a bar network")
 
     piece_names = []
     unwrapped_sheets = []
@@ -180,7 +192,7 @@ def _load_sheets(data_dir, require_performance, omr, system_params, bar_params, 
         if page_width is not None:
             dev_pages = _next_stage(dev_pages, lambda pages: pages.resized(page_width))
     if return_device:
-        return _unroll_on_device(omr, jobs, all_pages, device_post=device_post, dev_pages=dev_pages)
+        return _unroll_on_device(omr, jobs, all_pages, device_post=device_post, dev_pages=dev_pages, score_map=score_map)
     detect = omr.detect_systems_pages_dev if device_post else omr.detect_systems_pages
     if dev_pages is not None:
         try:
@@ -218,9 +230,10 @@ def _load_sheets(data_dir, require_performance, omr, system_params, bar_params, 
     return piece_names, piece_paths, unwrapped_sheets
 
 
-def _unroll_on_device(omr, jobs, all_pages, device_post=False, dev_pages=None):
+def _unroll_on_device(omr, jobs, all_pages, device_post=False, dev_pages=None, score_map=False):
     """the second half of load_umc_sheets with the pages resident on the device.  dev_pages: the resized pages, where
-    load_umc_sheets resized them (freed here); otherwise all_pages are uploaded"""
+    load_umc_sheets resized them (freed here); otherwise all_pages are uploaded.  score_map: the bar maps stay on the
+    device until the unroll rows are known, and the ScoreMap of the kept pieces is returned as a fifth value"""
     from audio_sheet_retrieval_amd.piece_identification import DeviceArrays
     from audio_sheet_retrieval_amd.sheet_utils.omr import _engine
     if dev_pages is None:
@@ -228,9 +241,14 @@ def _unroll_on_device(omr, jobs, all_pages, device_post=False, dev_pages=None):
         dev_pages = DevicePages(engine, all_pages)
     else:
         all_pages = _PagesOnDevice(dev_pages)
+    bar_maps = None
     try:
-        detect = omr.detect_systems_pages_dev if device_post else omr.detect_systems_pages
-        results = detect(all_pages, in_mode=IN_U8_RAW, dev_pages=dev_pages) if all_pages else []
+        if score_map:
+            results, bar_maps = omr.detect_systems_keep_bars_dev(all_pages, in_mode=IN_U8_RAW, dev_pages=dev_pages) \
+                if all_pages else ([], None)
+        else:
+            detect = omr.detect_systems_pages_dev if device_post else omr.detect_systems_pages
+            results = detect(all_pages, in_mode=IN_U8_RAW, dev_pages=dev_pages) if all_pages else []
         piece_names, piece_paths = [], []
         kept_pages = 0
         k = 0
@@ -245,7 +263,7 @@ def _unroll_on_device(omr, jobs, all_pages, device_post=False, dev_pages=None):
                     system_problem = True
                 else:                       # the reference unrolls the good pages of a piece it drops, too: messages
                     page_shape = (int(dev_pages.heights[k]), int(dev_pages.widths[k]))
-                    page_rows[k] = unroll_rows(page_shape, results[k], SYSTEM_HEIGHT)
+                    page_rows[k] = unroll_rows(page_shape, results[k], SYSTEM_HEIGHT, with_index=score_map)
                 k += 1
             if system_problem:
                 page_rows[first:k] = [None] * (k - first)
@@ -254,10 +272,23 @@ def _unroll_on_device(omr, jobs, all_pages, device_post=False, dev_pages=None):
                 piece_names.append(piece_name)
                 piece_paths.append(piece_dir)
         buf, offsets, shapes = unroll_systems_dev(dev_pages, page_rows, piece_of_page, len(piece_names), SYSTEM_HEIGHT)
+        if score_map:
+            from audio_sheet_retrieval_amd.score_map import ScoreMap
+            try:
+                measures, piece_first = score_map_dev(bar_maps, page_rows, piece_of_page, len(piece_names)) \
+                    if bar_maps is not None else (np.zeros((0, 8), np.int32), np.zeros(1, np.int32))
+                the_map = ScoreMap.from_table(piece_names, measures, piece_first, [c for _, c in shapes])
+            except Exception:
+                buf.free()
+                raise
     finally:
         dev_pages.free()
+        if bar_maps is not None:
+            bar_maps.free()
     total = sum(r * c for r, c in shapes)
     flat = buf.download((total,), np.float32) if total else np.zeros(0, np.float32)
     unwrapped_sheets = [flat[o:o + r * c].reshape(r, c).astype(np.uint8) for o, (r, c) in zip(offsets, shapes)]
     print("%d pieces covering %d pages of sheet music." % (len(piece_names), kept_pages))
+    if score_map:
+        return piece_names, piece_paths, unwrapped_sheets, DeviceArrays(buf, offsets, shapes), the_map
     return piece_names, piece_paths, unwrapped_sheets, DeviceArrays(buf, offsets, shapes)

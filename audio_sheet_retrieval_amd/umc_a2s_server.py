@@ -8,6 +8,7 @@ umc_a2s_server.py (:178-189):
         --system_params system_params.pkl --bar_params bar_params.pkl [--device_post] [--resample] [--page_width 835]
         [--deskew] [--flatten] [--live [--bank] [--live_dft direct|fft] [--block_ms 100] [--running_frames 100]
                    [--level running [--level_memory N] [--level_floor F]]]
+        [--locate [--excerpt_frames 400] [--locate_pieces 5] [--step_spec 2] [--seed 23]]
 
 <dir> holds one folder per piece: sheet/*.png (the page scans), score_ppq.* (the synthesised recording) and, for
 --real_perf, 01_performance*.  The pages go through the two segmentation networks (their parameter pickles:
@@ -51,6 +52,17 @@ spectrogram is computed beforehand - what a microphone can do.  The report and t
 --live_dft fft (with --live; default direct) computes the streamed frames with the real-input FFT
 (asr_audio_stream_push_fft_dev): the processor is built with dft="fft" and its streams are asked for by that name, so the
 tracking equals track_scores on that processor's spectrograms.  --fast_dft stays a flag of the offline routes.
+
+--locate (A2S only, off by default) answers "where in which scan?" in bars and pages: a seeded excerpt of
+--excerpt_frames frames of every recording is located in the data base of the scans (piece_identification.locate_scores,
+--locate_pieces candidates, a query window every --step_spec frames, as audio_sheet_server --locate), and the score map
+(score_map.ScoreMap: the measures of every piece in strip coordinates, built on the device from the bar network's maps
+while the pages are unrolled - asr_score_map_dev) turns the strip coordinates into bars, pages and systems.  Per
+recording it prints the least-cost candidate, the rank of the recording's own piece among the candidates and the bars
+the excerpt covers; --dump_results writes umc_location_<tag>_<dset>_A2S[_real].yaml.  Bars are counted from 1 in the
+report, pages and systems from 0.  With --init_sheet_db the map is written next to the data-base file
+(umc_sheet_db_file_score_map.npz); a run without it loads the map from there.  Building the map detects the systems by
+the device post-processing (--device_post's route: the same systems), which keeps the bar maps for it.
 """
 import argparse
 import os
@@ -61,7 +73,8 @@ from . import audio2sheet_align
 from .audio_frontend import SpectrogramProcessor
 from .audio_sheet_server import (TRACK_TOP_K, check_level_arguments, common_arguments, level_arguments, level_rule,
                                  report_ranks, report_tracking)
-from .piece_identification import EmbeddingDB, detect_performances, detect_scores, live_track_scores
+from .piece_identification import EmbeddingDB, detect_performances, detect_scores, live_track_scores, locate_scores
+from .score_map import ScoreMap
 from .sheet_utils import umc
 
 # per direction: data-base flag, data-base file, data-base view
@@ -112,7 +125,16 @@ def _arguments(argv, direction):
         p.add_argument("--running_frames", type=int, default=100,
                        help="voiced frames in the history of the running vote (--live)")
         level_arguments(p, "--live --bank")
+        p.add_argument("--locate", action="store_true",
+                       help="locate a seeded excerpt of every recording in the scans and report bars and pages "
+                            "(locate_scores, score_map.ScoreMap)")
+        p.add_argument("--excerpt_frames", type=int, default=400, help="frames of the excerpt (--locate)")
+        p.add_argument("--locate_pieces", type=int, default=5, help="candidates of the vote that are aligned (--locate)")
+        p.add_argument("--step_spec", type=int, default=2, help="frames between the query windows (--locate)")
+        p.add_argument("--seed", type=int, default=23, help="seed of the excerpts (--locate)")
     args = p.parse_args(argv)
+    if getattr(args, "locate", False) and getattr(args, "live", False):
+        p.error("--locate and --live are two modes: choose one")
     if args.fast_dft and getattr(args, "live", False):
         p.error("--fast_dft with --live: the streamed front-end computes the direct DFT unless --live_dft fft asks for "
                 "its FFT")
@@ -158,6 +180,70 @@ def live_track(engine, db, processor, piece_paths, names, audio_file, n_candidat
     return names, first_lead, lead_share
 
 
+def location_file(param_file, dset, real_perf=False):
+    """result_file's name with umc_location_ in place of umc_retrieval_"""
+    return result_file(param_file, dset, "A2S", real_perf).replace("umc_retrieval_", "umc_location_", 1)
+
+
+def locate(engine, db, score_map, specs, names, n_candidates, excerpt_frames, n_pieces, step_spec, seed,
+           spec_shape=(92, 42)):
+    """a seeded excerpt of every spectrogram (host arrays, one per name) located in the data base of the scans -> one
+    dict per recording: name; candidate, cost (the least-cost candidate); own_rank (the rank by cost of the recording's
+    own piece among the candidates, 0: not among them); first_bar / last_bar (from 1) and start_page, start_system,
+    end_page, end_system (from 0) of the candidate's path through its score"""
+    rng = np.random.RandomState(seed)
+    excerpts = []
+    for spec in specs:
+        n = min(int(excerpt_frames), spec.shape[1])
+        f0 = int(rng.randint(0, spec.shape[1] - n + 1))
+        excerpts.append(np.ascontiguousarray(spec[:, f0:f0 + n]))
+    found = locate_scores(engine, db, excerpts, n_pieces=n_pieces, step_spec=step_spec, n_candidates=n_candidates,
+                          spec_shape=spec_shape)
+    out = []
+    for name, cands in zip(names, found):
+        entry = dict(name=str(name), candidate=None, cost=None, own_rank=0, first_bar=None, last_bar=None,
+                     start_page=None, start_system=None, end_page=None, end_system=None)
+        for rank, cand in enumerate(cands):
+            if cand["name"] == name:
+                entry["own_rank"] = rank + 1
+                break
+        if cands:
+            best = cands[0]
+            ann = score_map.annotate(best)
+            start, end = ann["start_x"], ann["end_x"]
+            entry.update(candidate=str(best["name"]), cost=float(best["cost"]),
+                         first_bar=int(start["bar"]) + 1, last_bar=int(end["bar"]) + 1,
+                         start_page=int(start["page"]), start_system=int(start["system"]),
+                         end_page=int(end["page"]), end_system=int(end["system"]))
+        out.append(entry)
+    return out
+
+
+def report_location(entries, res_file=None):
+    import yaml
+    for e in entries:
+        if e["candidate"] is None:
+            print("no candidate                                                          %s" % e["name"])
+            continue
+        own = "%02d" % e["own_rank"] if e["own_rank"] else "--"
+        print("own piece at rank %s; bars %3d - %3d (page %d system %d - page %d system %d) of %s  <- %s"
+              % (own, e["first_bar"], e["last_bar"], e["start_page"], e["start_system"], e["end_page"], e["end_system"],
+                 e["candidate"], e["name"]))
+    print("own piece first by cost: %d of %d" % (sum(e["own_rank"] == 1 for e in entries), len(entries)))
+    if res_file is not None:
+        with open(res_file, "w") as fp:
+            yaml.dump(entries, fp, default_flow_style=False)
+        print("location of %d recordings written to %s" % (len(entries), res_file))
+    return entries
+
+
+def _download_arrays(dev):
+    """the arrays of a piece_identification.DeviceArrays on the host, in one copy"""
+    total = sum(r * c for r, c in dev.shapes)
+    flat = dev.buf.download((total,), np.float32) if total else np.zeros(0, np.float32)
+    return [flat[o:o + r * c].reshape(r, c) for o, (r, c) in zip(dev.offsets, dev.shapes)]
+
+
 def result_file(param_file, dset, direction, real_perf=False):
     """the reference's dump name (:270-274): a tag-less params.pkl gives params_<dset>_<direction>.yaml"""
     ret_dir = direction + ("_real" if real_perf else "")
@@ -170,15 +256,17 @@ def run(argv, direction):
     if args.data_dir is None:
         raise SystemExit("--data_dir: the directory of pieces is required")
     omr = umc.build_recognizer(args.system_params, args.bar_params)
-    if args.deskew or args.flatten:
-        te_pieces, piece_paths, _, strips = umc.load_umc_scans(args.data_dir, require_performance=True, omr=omr,
-                                                               return_device=True, device_post=args.device_post,
-                                                               page_width=args.page_width, deskew=args.deskew,
-                                                               flatten=args.flatten)
+    locating = getattr(args, "locate", False)
+    build_map = locating and args.init_db                   # otherwise --locate loads the map the data base was saved with
+    if args.deskew or args.flatten or build_map:           # (neither flag: load_umc_scans is load_umc_sheets with the map)
+        loaded = umc.load_umc_scans(args.data_dir, require_performance=True, omr=omr, return_device=True,
+                                    device_post=args.device_post, page_width=args.page_width, deskew=args.deskew,
+                                    flatten=args.flatten, score_map=build_map)
     else:
-        te_pieces, piece_paths, _, strips = umc.load_umc_sheets(args.data_dir, require_performance=True, omr=omr,
-                                                               return_device=True, device_post=args.device_post,
-                                                               page_width=args.page_width)
+        loaded = umc.load_umc_sheets(args.data_dir, require_performance=True, omr=omr, return_device=True,
+                                     device_post=args.device_post, page_width=args.page_width)
+    te_pieces, piece_paths, _, strips = loaded[:4]
+    score_map = loaded[4] if build_map else None
     try:
         dset = os.path.basename(args.data_dir)
         audio_file = "01_performance" if args.real_perf else "score_ppq"
@@ -209,8 +297,18 @@ def run(argv, direction):
                 print("%d %s of %d pieces collected" % (len(db), "sheet snippet codes" if direction == "A2S" else
                                                         "audio excerpts", len(te_pieces)))
                 db.save(d["db_file"])
+                if score_map is not None:
+                    score_map.save(ScoreMap.path_for(d["db_file"]))
             else:
                 db = EmbeddingDB.load(engine, d["db_file"])
+                if locating:
+                    score_map = ScoreMap.load(ScoreMap.path_for(d["db_file"]))
+            if locating:
+                print("\nLocating an excerpt of every recording:")
+                names = [te_pieces[i] for i in queried]
+                return report_location(locate(engine, db, score_map, _download_arrays(specs), names, args.n_candidates,
+                                              args.excerpt_frames, args.locate_pieces, args.step_spec, args.seed),
+                                       location_file(param_file, dset, args.real_perf) if args.dump_results else None)
             if getattr(args, "live", False):
                 print("\nStreaming every recording through the running vote:")
                 names = [te_pieces[i] for i in queried]

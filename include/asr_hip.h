@@ -1114,7 +1114,43 @@ int asr_bars_from_map_dev(asr_ctx *ctx, const double *maps_dev, const int32_t *h
  *   exceed ASR_OMR_BUDGET_MB (default 4096) run in chunks of whole pages with identical results.  Before anything is
  *   launched: 1 <= H, W <= 16384, 1 <= radii[p] <= 127, 0 <= floor <= 255, every page inside the buffers, and the
  *   overlaps above.  A violation returns ASR_ERR_INVALID with a message that starts with "flatten_pages:" and writes
- *   nothing.  n_pages == 0 is valid and writes nothing. */
+ *   nothing.  n_pages == 0 is valid and writes nothing.
+ * asr_score_map_dev = the measures of every piece in strip coordinates: the way back from a column x of an unrolled strip
+ *   to a bar, a page, a staff system and a page position.  The reference has no such stage (its detect_bars gives blobs on
+ *   a page, its alignment raises for a system without a bar and knows nothing of strips); the yardstick is this
+ *   definition, all in integers after one comparison, which sheet_utils/omr.strip_bar_counts_host / strip_bar_lines_host
+ *   / score_map_host restate in numpy and the device reproduces exactly.
+ *   Inputs: the bar network's float64 maps of all pages back to back on the device (page p of H x W at the sum of the
+ *   sizes before it, as asr_seg_predict_dev writes and asr_bars_from_map_dev reads them; maps_doubles = their total);
+ *   `systems`, the table asr_unroll_systems_dev takes - host int32[n_systems * 8]: page, r0, r1, c0, c1, pad, piece,
+ *   strip x0 - with the pieces in non-decreasing order; system_index: host int32[n_systems], the system's index among
+ *   its page's detected systems; page_in_piece: host int32[n_pages], the page's index within its piece.
+ *     count     count[c] = #{ r in [r0, r1) : map[r][c] > threshold }  for c in [c0, c1)     (a NaN is not above)
+ *     lines     a bar line is a maximal run of consecutive columns with count >= min_rows; its column is
+ *               b = (first + last) / 2 (integer division)
+ *     interior  a line is interior when b - c0 > tol and (c1 - 1) - b > tol; the others merge into the system's edges
+ *     bounds    B = c0, the interior lines in ascending order, c1
+ *     measures  measure j of a system covers page columns B[j] .. B[j+1] - 1; a system without an interior line is one
+ *               measure.  The measures of a piece are numbered from 0 in the table's order (the systems of a page, then
+ *               the pages of the piece).  One int32 row of 8 per measure:
+ *                 x0, x1 (strip columns, half open: strip x0 + B[j] - c0, strip x0 + B[j+1] - c0), page (within its
+ *                 piece), system (on its page), col0 = B[j], col1 = B[j+1], row0 = r0, row1 = r1
+ *   Outputs (host): measures int32[n_systems * (max_lines + 1) * 8], of which the first *n_measures rows are written, the
+ *   pieces back to back; piece_first int32[n_pieces + 1], the first row of every piece and the total (a piece without a
+ *   kept system has none); *overflow_system = -1, or the first system with more than max_lines interior lines - then no
+ *   row is written and *n_measures is 0 (the call still returns ASR_OK: the caller names the system).
+ *   Three launches whatever n_pages and n_systems are (score_map_kernels.hip): the counts and the flags of 64 columns per
+ *   workgroup, lanes along the columns; the runs, their centres and the interior lines in column order by a scan, one
+ *   wave per system; the numbering by a scan over the systems that restarts at every piece.  No atomics: the table is
+ *   deterministic.  Every element of every band is read once.  Before anything is launched: every page inside
+ *   maps_doubles, every system inside its page (0 <= r0 < r1 <= H, 0 <= c0 < c1 <= W), 1 <= min_rows, 0 <= tol,
+ *   0 <= max_lines, pieces in [0, n_pieces) and in order, threshold not a NaN.  A violation returns ASR_ERR_INVALID with a
+ *   message that starts with "score_map:" and writes nothing.  n_systems == 0 is valid: piece_first is all 0. */
+int asr_score_map_dev(asr_ctx *ctx, const double *maps_dev, int64_t maps_doubles, const int32_t *heights,
+                      const int32_t *widths, int n_pages, const int32_t *page_in_piece, const int32_t *systems,
+                      const int32_t *system_index, int n_systems, int n_pieces, double threshold, int min_rows, int tol,
+                      int max_lines, int32_t *measures, int32_t *piece_first, int32_t *n_measures,
+                      int32_t *overflow_system);
 int asr_unroll_systems_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
                            const int32_t *heights, const int32_t *widths, int n_pages, const int32_t *systems,
                            int n_systems, int system_height, const int64_t *strip_offsets, const int32_t *strip_widths,
