@@ -39,6 +39,7 @@ namespace asr {
 
 typedef float floatx4q __attribute__((ext_vector_type(4)));
 typedef float float2q __attribute__((ext_vector_type(2)));
+typedef unsigned uint2q __attribute__((ext_vector_type(2)));
 
 struct Wino4Args {
     const float *in, *wpk, *bnp;
@@ -297,10 +298,19 @@ __global__ __launch_bounds__(64 * WAVES, 1) void conv3x3_wino4g(Wino4Args a) {
 // SLICE < C_out (96 output channels): blockIdx.y picks SLICE of them, so a workgroup stays at one wave per SIMD with
 // the two 72-register weight sets; the workgroups (x, 0) and (x, 1) walk the same M-tiles at the same time on the same
 // XCD (gridDim.x is a multiple of 8), the second reads its patches from L2.
-// PW = 2 (two n-tiles at most, so that the workgroup stays at four waves): TWO producer waves.  One producer needs
-// ~3600 cycles per (M-tile, channel block) item whatever the number of output channels, a consumer 72 MFMAs = 2304;
-// with three consumers the two sides are balanced, with two (24 output channels) the producer is the critical path
-// (24 -> 24 at 80x100: 0.76 ms against 0.66 for the F(2x2) global-A kernel - round 2 did not select it).  The
+// What bounds a step (round 31: -DASR_WINO4_ABL builds of the sheet tower's pooled 48 -> 48 block on 40x50 maps, timed by
+// the benchmark's per-layer survey, i.e. inside the step, where the default build takes 0.47 - 0.49 ms; stand-alone
+// timings such as the tuner's, which DESIGN.md quotes, are lower): not the producer's arithmetic.  Without the input
+// transform the layer takes the same time, without the LDS writes of V too; without the patch LOADS it is 14 % faster
+// and a producer that does nothing adds only 2 % to that; no weight loads -8 %, no output stores -4 %.  With an idle
+// producer a step still lasts about twice its 72 MFMAs = 2304 cycles.  The consumers set the step, and the producer's
+// 36 gathers per item cost them time on the memory path the four waves share - so what counts in the producer is
+// WHEN its loads are issued (see the item loop), not how many instructions it runs.  (The model this header carried
+// before, from rounds 2 and 3 - ~3600 producer cycles per item against 2304, "balanced with three consumers" - was
+// never measured and is superseded.)
+// PW = 2 (two n-tiles at most, so that the workgroup stays at four waves): TWO producer waves.  With two consumers
+// (24 output channels) this form loses to the F(2x2) global-A kernel: 24 -> 24 at 80x100 0.76 ms against 0.66, round 2
+// did not select it, and round 31's tuner times 0.70 - 0.72 ms against 0.53 on the sheet tower's conv4.  The
 // producers take alternate steps of the flattened (M-tile, channel block) sequence - producer p owns V buffer p - so
 // each has two step times per item; every wave still passes one workgroup barrier per step.
 // RAW (training step, un-pooled blocks): the output is the raw convolution z, and the consumers also gather the
@@ -363,7 +373,13 @@ __global__ __launch_bounds__(64 * (PW + (SLICE + 15) / 16), 1) void conv3x3_wino
         // tensors below 4 GiB only): every load is "uniform base + channel block (scalar) + lane offset" - no vector
         // address arithmetic per load
         unsigned poff[6][6];
-        unsigned oy_m = 0, ox_m = 0;
+        // the border of an M-tile, formed once per M-tile: keep[i][j] is all ones where patch pixel (i, j) of this
+        // lane's tile lies inside the image (and the tile exists), zero elsewhere - the loads of those pixels read
+        // clamped addresses, and the AND on the float bits puts +0.0f in their place (a kept value keeps its bits).
+        // `interior` (wave-uniform): every lane keeps every pixel, the M-tile needs no AND.  Needs a run of 16 tiles
+        // without a first or last tile column, i.e. at least 18 tile columns: none of the models' maps has them.
+        unsigned keep[6][6];
+        bool interior = false;
         auto setup = [&](int mtile) {
             int img, tty, ttx;
             bool tvalid;
@@ -371,7 +387,7 @@ __global__ __launch_bounds__(64 * (PW + (SLICE + 15) / 16), 1) void conv3x3_wino
             const int py = 4 * tty, px = 4 * ttx;
             const unsigned ib = ((unsigned)img * a.H * a.W * CIN + 2 * g) * 4u;
             unsigned rowb[6], colb[6];
-            oy_m = 0; ox_m = 0;
+            unsigned oy_m = 0, ox_m = 0;
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
                 const int y = py - 1 + i, x = px - 1 + i;
@@ -381,10 +397,14 @@ __global__ __launch_bounds__(64 * (PW + (SLICE + 15) / 16), 1) void conv3x3_wino
                 colb[i] = (unsigned)(min(max(x, 0), a.W - 1) * CIN) * 4u;
             }
             if (!tvalid) oy_m = 0;
+            interior = __builtin_amdgcn_ballot_w64(oy_m != 0x3fu || ox_m != 0x3fu) == 0;
 #pragma unroll
             for (int i = 0; i < 6; ++i)
 #pragma unroll
-                for (int j = 0; j < 6; ++j) poff[i][j] = ib + rowb[i] + colb[j];
+                for (int j = 0; j < 6; ++j) {
+                    poff[i][j] = ib + rowb[i] + colb[j];
+                    keep[i][j] = 0u - (((oy_m >> i) & (ox_m >> j)) & 1u);
+                }
         };
         float2q nxt[6][6];
         auto load = [&](int t) {
@@ -405,21 +425,42 @@ __global__ __launch_bounds__(64 * (PW + (SLICE + 15) / 16), 1) void conv3x3_wino
         while (t >= NB) { t -= NB; mt += mt_stride; }
         if (mt < mt_end) { setup(mt); load(t); }
         for (int step = wave; step < n_steps; step += PW) {
+            // nxt is consumed before the next item's loads are issued into it, and nothing copies it.  A border M-tile:
+            // the AND with the M-tile's masks writes dp, then FIRST columns of the first transform pass run, then the
+            // loads, then the rest.  Where the loads stand is measured, not derived (round 31): issued right behind
+            // the AND - some 70 instructions after the barrier, on the heels of the consumers' weight loads - the
+            // layer is 7 - 9 % slower than with the old select pass (220 instructions) in front of them; behind both
+            // passes it is as fast as that; behind three to six columns 3 - 5 % faster.  Three, four and five columns
+            // measured the same (conv6 0.444 / 0.443 / 0.444 ms, surveys of one box): four is an arbitrary pick among
+            // them, one step away from the slow edge.  An interior M-tile: the whole first pass reads nxt itself.
+            constexpr int FIRST = 4;
             float2q dp[6][6];
-            const unsigned oy = oy_m, ox = ox_m;
-            const bool interior = __builtin_amdgcn_ballot_w64(oy != 0x3fu || ox != 0x3fu) == 0;
-            if (interior) {
+            const bool inner = interior;                      // of THIS item's M-tile (setup below may replace it)
+            if (inner) {
 #pragma unroll
-                for (int i = 0; i < 6; ++i)
+                for (int j = 0; j < 6; ++j) {
 #pragma unroll
-                    for (int j = 0; j < 6; ++j) dp[i][j] = nxt[i][j];
+                    for (int i = 0; i < 6; ++i) dp[i][j] = nxt[i][j];
+                    if (!(ASR_WINO4_ABL & 8)) in6(dp[0][j], dp[1][j], dp[2][j], dp[3][j], dp[4][j], dp[5][j]);
+                }
             } else {
 #pragma unroll
                 for (int i = 0; i < 6; ++i)
 #pragma unroll
-                    for (int j = 0; j < 6; ++j) dp[i][j] = (((oy >> i) & (ox >> j)) & 1u) ? nxt[i][j] : float2q{0.f, 0.f};
+                    for (int j = 0; j < 6; ++j)
+                        dp[i][j] = __builtin_bit_cast(float2q, __builtin_bit_cast(uint2q, nxt[i][j]) & uint2q{keep[i][j], keep[i][j]});
+                if (!(ASR_WINO4_ABL & 8)) {
+#pragma unroll
+                for (int j = 0; j < FIRST; ++j) in6(dp[0][j], dp[1][j], dp[2][j], dp[3][j], dp[4][j], dp[5][j]);
+                }
             }
-            // this producer's next item is requested before the current one is transformed
+            // Empty statements that make dp opaque: their only purpose is to pin the loads where they stand (without
+            // them the compiler sinks the columns above below the loads).  No test sees a compiler that reorders them
+            // all the same - results do not change; tools/wino4s_isa_table.py does: the border block must read
+            // "and 72 pk 48" in front of the block with the 36 loads.
+#pragma unroll
+            for (int p = 0; p < 36; ++p) asm volatile("" : "+v"(dp[p / 6][p % 6]));
+            // this producer's next item is requested
             {
                 int tn = t + PW, mtn = mt;
                 while (tn >= NB) { tn -= NB; mtn += mt_stride; }
@@ -430,8 +471,10 @@ __global__ __launch_bounds__(64 * (PW + (SLICE + 15) / 16), 1) void conv3x3_wino
                 t = tn; mt = mtn;
             }
             if (!(ASR_WINO4_ABL & 8)) {
+            if (!inner) {
 #pragma unroll
-            for (int j = 0; j < 6; ++j) in6(dp[0][j], dp[1][j], dp[2][j], dp[3][j], dp[4][j], dp[5][j]);
+            for (int j = FIRST; j < 6; ++j) in6(dp[0][j], dp[1][j], dp[2][j], dp[3][j], dp[4][j], dp[5][j]);
+            }
 #pragma unroll
             for (int i = 0; i < 6; ++i) in6(dp[i][0], dp[i][1], dp[i][2], dp[i][3], dp[i][4], dp[i][5]);
             }
