@@ -44,7 +44,7 @@ EXPORTS = [
     "asr_notes_from_map_dev", "asr_bars_from_map_dev",
     "asr_unroll_systems_dev", "asr_spectrogram_batch_dev", "asr_spectrogram_fft_batch_dev", "asr_resample_batch_dev", "asr_resize_pages_dev",
     "asr_audio_stream_push_dev", "asr_audio_stream_push_fft_dev", "asr_skew_estimate_dev", "asr_deskew_pages_dev",
-    "asr_flatten_pages_dev", "asr_score_map_dev",
+    "asr_flatten_pages_dev", "asr_score_map_dev", "asr_crop_estimate_dev", "asr_crop_pages_dev",
     "asr_track_stream_gate_dev", "asr_track_stream_vote_dev",
     "asr_track_gate_running_dev", "asr_track_stream_gate_running_dev",
     "asr_follow_stream_windows_dev", "asr_follow_stream_log_dev",
@@ -250,6 +250,10 @@ def load_library(path=None):
                                          c_int, c_void_p, c_int64]),
         "asr_flatten_pages_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                           c_int, c_void_p, c_int64, c_void_p]),
+        "asr_crop_estimate_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+        "asr_crop_pages_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                       c_void_p, c_int64]),
         "asr_score_map_dev": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                       c_int, c_int, c_double, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                       c_void_p]),
@@ -1080,6 +1084,48 @@ class Engine(object):
         self._check(self.lib.asr_flatten_pages_dev(
             self.ctx, pages_ptr, int(pages_bytes), page_offsets.ctypes.data, heights.ctypes.data, widths.ctypes.data, n,
             radii.ctypes.data, int(floor), out_ptr, int(out_bytes), background_ptr))
+
+    def crop_estimate_dev(self, pages_ptr, pages_bytes, page_offsets, heights, widths, margins, floor=64, share=512,
+                          return_counts=False):
+        """the paper's rectangle inside a scanner's black border, for every uint8 page in two launches
+        (asr_crop_estimate_dev; the pages as resize_pages_dev reads them; margins: int32 per page).
+        -> rects int32 (n, 4): r0 r1 c0 c1, status int32 (n,): 1 where the page is undecided and the rect is the whole
+        page; with return_counts also the row counts and the column counts, int32, the pages back to back.  The integers
+        of sheet_utils.omr.crop_rect_host / crop_counts_host per page"""
+        page_offsets = np.ascontiguousarray(page_offsets, dtype=np.int64)
+        heights = np.ascontiguousarray(heights, dtype=np.int32)
+        widths = np.ascontiguousarray(widths, dtype=np.int32)
+        margins = np.ascontiguousarray(margins, dtype=np.int32)
+        n = heights.size
+        if not (page_offsets.size == widths.size == margins.size == n):
+            raise ValueError("crop_estimate_dev: the per-page tables differ in length")
+        rects = np.zeros((n, 4), np.int32)
+        status = np.zeros(n, np.int32)
+        rows = np.zeros(max(int(heights.astype(np.int64).clip(0).sum()), 1), np.int32) if return_counts else None
+        cols = np.zeros(max(int(widths.astype(np.int64).clip(0).sum()), 1), np.int32) if return_counts else None
+        self._check(self.lib.asr_crop_estimate_dev(
+            self.ctx, pages_ptr, int(pages_bytes), page_offsets.ctypes.data, heights.ctypes.data, widths.ctypes.data, n,
+            int(floor), int(share), margins.ctypes.data, rects.ctypes.data, status.ctypes.data,
+            rows.ctypes.data if return_counts else None, cols.ctypes.data if return_counts else None))
+        if return_counts:
+            return rects, status, rows[:int(heights.astype(np.int64).sum())], cols[:int(widths.astype(np.int64).sum())]
+        return rects, status
+
+    def crop_pages_dev(self, pages_ptr, pages_bytes, page_offsets, heights, widths, rects, out_offsets, out_ptr, out_bytes):
+        """rows r0 .. r1 - 1 x columns c0 .. c1 - 1 of every uint8 page (rects: int32 (n, 4)) copied in one launch
+        (asr_crop_pages_dev): the rect of page i goes to byte out_offsets[i] of the buffer at out_ptr, its rows back to
+        back.  Byte for byte page[r0:r1, c0:c1]"""
+        page_offsets = np.ascontiguousarray(page_offsets, dtype=np.int64)
+        heights = np.ascontiguousarray(heights, dtype=np.int32)
+        widths = np.ascontiguousarray(widths, dtype=np.int32)
+        rects = np.ascontiguousarray(rects, dtype=np.int32)
+        out_offsets = np.ascontiguousarray(out_offsets, dtype=np.int64)
+        n = heights.size
+        if not (page_offsets.size == widths.size == out_offsets.size == n and rects.size == 4 * n):
+            raise ValueError("crop_pages_dev: the per-page tables differ in length")
+        self._check(self.lib.asr_crop_pages_dev(
+            self.ctx, pages_ptr, int(pages_bytes), page_offsets.ctypes.data, heights.ctypes.data, widths.ctypes.data, n,
+            rects.ctypes.data, out_offsets.ctypes.data, out_ptr, int(out_bytes)))
 
     def unroll_systems_dev(self, pages_ptr, pages_bytes, page_offsets, heights, widths, systems, system_height,
                            strip_offsets, strip_widths, strips_ptr, strips_floats):

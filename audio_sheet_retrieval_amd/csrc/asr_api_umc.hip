@@ -11,6 +11,8 @@
 // asr_skew_estimate_dev / asr_deskew_pages_dev (the slope of a scan's staves and its correction, before the resize):
 // page_deskew_kernels.hip.
 // asr_flatten_pages_dev (a scan divided by the grey closing of its paper, before the deskew): page_flatten_kernels.hip.
+// asr_crop_estimate_dev / asr_crop_pages_dev (the paper's rectangle inside a scanner's black border and its copy, before
+// the flatten): page_crop_kernels.hip.
 // asr_score_map_dev (the bar network's maps and the unroll table -> the measures of every piece in strip coordinates):
 // score_map_kernels.hip.
 #include "asr_ctx.h"
@@ -978,6 +980,137 @@ int asr_flatten_pages_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_byt
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "flatten_pages: %s", hipGetErrorString(e));
+    return mark_main(ctx);
+}
+
+int asr_crop_estimate_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
+                          const int32_t *heights, const int32_t *widths, int n_pages, int floor, int share,
+                          const int32_t *margins, int32_t *rects, int32_t *status, int32_t *row_counts,
+                          int32_t *col_counts) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_pages < 0 || pages_bytes < 0) return fail(ctx, ASR_ERR_INVALID, "crop_pages: bad sizes");
+    if (floor < 0 || floor > 255) return fail(ctx, ASR_ERR_INVALID, "crop_pages: floor %d outside [0, 255]", floor);
+    if (share < 1 || share > 1024) return fail(ctx, ASR_ERR_INVALID, "crop_pages: share %d outside [1, 1024]", share);
+    if (n_pages == 0) return ASR_OK;
+    if (!page_offsets || !heights || !widths || !margins || !rects || !status || !pages_dev)
+        return fail(ctx, ASR_ERR_INVALID, "crop_pages: NULL argument");
+    static_assert(asr::CROP_MAX_DIM == asr::SKEW_MAX_DIM, "skew_check_pages checks the dimensions of this stage too");
+    int rc = skew_check_pages(ctx, "crop_pages", pages_bytes, page_offsets, heights, widths, n_pages);
+    if (rc != ASR_OK) return rc;
+    const size_t b_first = ((size_t)n_pages + 1) * sizeof(int64_t);
+    std::vector<char> tab(b_first + (size_t)n_pages * sizeof(asr::CropPage));     // tile_first (n + 1) | page table
+    int64_t *first = (int64_t *)tab.data();
+    asr::CropPage *table = (asr::CropPage *)(tab.data() + b_first);
+    int64_t tiles = 0, sum_h = 0, sum_w = 0;
+    double bytes = 0.0;
+    for (int p = 0; p < n_pages; ++p) {
+        const int64_t h = heights[p], w = widths[p];
+        if (margins[p] < 0) return fail(ctx, ASR_ERR_INVALID, "crop_pages: page %d: margin %d is negative", p, margins[p]);
+        asr::CropPage &r = table[p];
+        r.off = page_offsets[p];
+        r.row_at = sum_h; r.col_at = sum_w;
+        r.h = (int32_t)h; r.w = (int32_t)w;
+        r.tiles_x = (int32_t)((w + asr::CROP_TILE_W - 1) / asr::CROP_TILE_W);
+        r.margin = margins[p];
+        first[p] = tiles;
+        tiles += (int64_t)r.tiles_x * ((h + asr::CROP_TILE_H - 1) / asr::CROP_TILE_H);
+        sum_h += h; sum_w += w;
+        bytes += 0.75 * (double)(h * w);
+    }
+    first[n_pages] = tiles;
+    if (tiles > 0x7fffffffLL) return fail(ctx, ASR_ERR_INVALID, "crop_pages: %lld tiles in one call", (long long)tiles);
+    // workspace: running tile counts | page table (one upload) | rects | status | row counts | column counts
+    const size_t o_rects = skew_align(tab.size()), o_status = o_rects + (size_t)n_pages * 4 * sizeof(int32_t),
+                 o_rows = skew_align(o_status + (size_t)n_pages * sizeof(int32_t)),
+                 o_cols = o_rows + (size_t)sum_h * sizeof(int32_t), total = o_cols + (size_t)sum_w * sizeof(int32_t);
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    rc = skew_ws_reserve(ctx, total);
+    if (rc != ASR_OK) return rc;
+    char *ws = (char *)ctx->skew_ws;
+    const asr::CropPage *d_table = (const asr::CropPage *)(ws + b_first);
+    int32_t *d_rects = (int32_t *)(ws + o_rects), *d_status = (int32_t *)(ws + o_status);
+    int32_t *d_rows = (int32_t *)(ws + o_rows), *d_cols = (int32_t *)(ws + o_cols);
+    hipError_t e = hipMemcpyAsync(ws, tab.data(), tab.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_rows, 0, total - o_rows, ctx->stream);
+    if (e == hipSuccess) {
+        ProfScope ps(ctx, "crop_counts", 0, 0.0, bytes);
+        e = asr::launch_crop_counts(ctx->stream, (const uint8_t *)pages_dev, (const int64_t *)ws, d_table, n_pages, tiles,
+                                    floor, d_rows, d_cols);
+    }
+    if (e == hipSuccess) {
+        ProfScope ps(ctx, "crop_rects", 0, 0.0, (double)(total - o_rows));
+        e = asr::launch_crop_rects(ctx->stream, d_table, n_pages, share, d_rows, d_cols, d_rects, d_status);
+    }
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(rects, d_rects, (size_t)n_pages * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(status, d_status, (size_t)n_pages * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && row_counts)
+        e = hipMemcpyAsync(row_counts, d_rows, (size_t)sum_h * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && col_counts)
+        e = hipMemcpyAsync(col_counts, d_cols, (size_t)sum_w * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "crop_pages: %s", hipGetErrorString(e));
+    return mark_main(ctx);
+}
+
+int asr_crop_pages_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
+                       const int32_t *heights, const int32_t *widths, int n_pages, const int32_t *rects,
+                       const int64_t *out_offsets, void *out_dev, int64_t out_bytes) {
+    if (!ctx) return ASR_ERR_INVALID;
+    if (n_pages < 0 || pages_bytes < 0 || out_bytes < 0) return fail(ctx, ASR_ERR_INVALID, "crop_pages: bad sizes");
+    if (n_pages == 0) return ASR_OK;
+    if (!page_offsets || !heights || !widths || !rects || !out_offsets || !pages_dev || !out_dev)
+        return fail(ctx, ASR_ERR_INVALID, "crop_pages: NULL argument");
+    int rc = skew_check_pages(ctx, "crop_pages", pages_bytes, page_offsets, heights, widths, n_pages);
+    if (rc != ASR_OK) return rc;
+    const char *in0 = (const char *)pages_dev, *out0 = (const char *)out_dev;
+    if (in0 < out0 + out_bytes && out0 < in0 + pages_bytes)
+        return fail(ctx, ASR_ERR_INVALID, "crop_pages: the output buffer overlaps the pages");
+    const size_t b_first = ((size_t)n_pages + 1) * sizeof(int64_t);
+    std::vector<char> tab(b_first + (size_t)n_pages * sizeof(asr::CropCopy));     // tile_first (n + 1) | rect table
+    int64_t *first = (int64_t *)tab.data();
+    asr::CropCopy *table = (asr::CropCopy *)(tab.data() + b_first);
+    int64_t tiles = 0;
+    double bytes = 0.0;
+    for (int p = 0; p < n_pages; ++p) {
+        const int64_t h = heights[p], w = widths[p];
+        const int64_t r0 = rects[4 * p], r1 = rects[4 * p + 1], c0 = rects[4 * p + 2], c1 = rects[4 * p + 3];
+        if (r0 < 0 || r0 >= r1 || r1 > h || c0 < 0 || c0 >= c1 || c1 > w)
+            return fail(ctx, ASR_ERR_INVALID, "crop_pages: page %d: rect rows [%lld, %lld) columns [%lld, %lld) of a "
+                        "%lld x %lld page (0 <= r0 < r1 <= H, 0 <= c0 < c1 <= W)", p, (long long)r0, (long long)r1,
+                        (long long)c0, (long long)c1, (long long)h, (long long)w);
+        const int64_t ch = r1 - r0, cw = c1 - c0;
+        if (out_offsets[p] < 0 || ch * cw > out_bytes || out_offsets[p] > out_bytes - ch * cw)
+            return fail(ctx, ASR_ERR_INVALID, "crop_pages: output %d (%lld x %lld at %lld) outside the %lld-byte buffer", p,
+                        (long long)ch, (long long)cw, (long long)out_offsets[p], (long long)out_bytes);
+        asr::CropCopy &r = table[p];
+        r.src = page_offsets[p] + r0 * w + c0;
+        r.dst = out_offsets[p];
+        r.stride = (int32_t)w;
+        r.h = (int32_t)ch; r.w = (int32_t)cw;
+        r.pad = 0;
+        first[p] = tiles;
+        tiles += (ch + asr::CROP_COPY_ROWS - 1) / asr::CROP_COPY_ROWS;
+        bytes += 2.0 * (double)(ch * cw);
+    }
+    first[n_pages] = tiles;
+    if (tiles > 0x7fffffffLL) return fail(ctx, ASR_ERR_INVALID, "crop_pages: %lld tiles in one call", (long long)tiles);
+    ASR_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    rc = join_views(ctx);
+    if (rc != ASR_OK) return rc;
+    rc = skew_ws_reserve(ctx, tab.size());
+    if (rc != ASR_OK) return rc;
+    hipError_t e = hipMemcpyAsync(ctx->skew_ws, tab.data(), tab.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        ProfScope ps(ctx, "crop_copy", 0, 0.0, bytes);
+        e = asr::launch_crop_copy(ctx->stream, (const uint8_t *)pages_dev, (uint8_t *)out_dev, (const int64_t *)ctx->skew_ws,
+                                  (const asr::CropCopy *)((const char *)ctx->skew_ws + b_first), n_pages, tiles);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(ctx, ASR_ERR_HIP, "crop_pages: %s", hipGetErrorString(e));
     return mark_main(ctx);
 }
 

@@ -271,7 +271,7 @@ struct asr_ctx {
     size_t specfft_ws_bytes = 0;              // is allocated), then per call the recording tables, window and filters
     void *resize_ws = nullptr;                // asr_resize_pages_dev: running tile counts + page table
     size_t resize_ws_bytes = 0;
-    void *skew_ws = nullptr;                  // asr_skew_estimate_dev / asr_deskew_pages_dev: tables, profiles, scores; asr_flatten_pages_dev: tables, D
+    void *skew_ws = nullptr;                  // asr_skew_estimate_dev / asr_deskew_pages_dev: tables, profiles, scores; asr_flatten_pages_dev: tables, D; asr_crop_estimate_dev / asr_crop_pages_dev: tables, rects, counts
     size_t skew_ws_bytes = 0;
     void *stream_ws = nullptr;                // asr_audio_stream_push_dev: running frame counts, stream rows, window, filters
     size_t stream_ws_bytes = 0;

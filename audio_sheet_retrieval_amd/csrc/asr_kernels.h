@@ -547,6 +547,35 @@ hipError_t launch_score_map_lines(hipStream_t s, const ScoreSystem *table, int n
 hipError_t launch_score_map_table(hipStream_t s, const ScoreSystem *table, int n_systems, int n_pieces, int max_lines,
                                   const int32_t *n_lines, const int32_t *lines, int32_t *piece_count, int32_t *piece_first,
                                   int32_t *header, int32_t *sys_first, int32_t *measures);
+// scanner borders of scanned pages (page_crop_kernels.hip; include/asr_hip.h carries the definition).  The estimate is two
+// launches - the counts of dark pixels per row and per column (integer atomics on zeroed workspace), then the runs and the
+// rect, one workgroup per page - and the copy is one.  One 256-thread workgroup per tile of CROP_TILE_H rows x CROP_TILE_W
+// columns of a page (counts), or per CROP_COPY_ROWS rows of a rect (copy).
+constexpr int CROP_THREADS = 256;
+constexpr int CROP_TILE_W = 1024;                      // a wave reads 256 columns of a row, four per lane
+constexpr int CROP_TILE_H = 64;
+constexpr int CROP_COPY_ROWS = 8;
+constexpr int CROP_MAX_DIM = 16384;
+struct CropPage {
+    int64_t off;            // byte offset of the page in the source buffer
+    int64_t row_at, col_at; // the page's first entry in the row counts / in the column counts
+    int32_t h, w;
+    int32_t tiles_x;        // column tiles: ceil(w / CROP_TILE_W)
+    int32_t margin;
+};
+struct CropCopy {
+    int64_t src;            // byte offset of the rect's first byte in the source buffer
+    int64_t dst;            // byte offset of the result in the output buffer
+    int32_t stride;         // the page's width
+    int32_t h, w;           // of the rect
+    int32_t pad;
+};
+hipError_t launch_crop_counts(hipStream_t s, const uint8_t *pages, const int64_t *tile_first, const CropPage *table,
+                              int n_pages, int64_t total_tiles, int floor_, int32_t *row_counts, int32_t *col_counts);
+hipError_t launch_crop_rects(hipStream_t s, const CropPage *table, int n_pages, int share, const int32_t *row_counts,
+                             const int32_t *col_counts, int32_t *rects, int32_t *status);
+hipError_t launch_crop_copy(hipStream_t s, const uint8_t *pages, uint8_t *out, const int64_t *tile_first,
+                            const CropCopy *table, int n_pages, int64_t total_tiles);
 // batch assembly of the training pool: desc_dev holds n x 9 doubles (see piece_vote_kernels.hip)
 hipError_t launch_gather_windows(hipStream_t s, const float *src, const double *desc_dev, int n, int out_h, int out_w,
                                  float *out);

@@ -486,6 +486,72 @@ def flatten_page_host(page, radius=None, floor=FLATTEN_FLOOR):
     return np.where(B >= max(floor, 1), (510 * P + B) // (2 * np.maximum(B, 1)), P).astype(np.uint8)
 
 
+CROP_FLOOR = 64             # the default floor of the crop: the flatten's "not paper" level
+CROP_SHARE = 512            # the default share, in 1/1024: a border row is dark over half of its band
+
+
+def crop_margin(width):
+    """the default margin of asr_crop_estimate_dev for a page of this width: what is cut beyond a border that was found,
+    the corner residue of a slightly tilted frame - 13 at 835 columns, 39 at 2480 (the rule of flatten_radius)"""
+    return (int(width) + 32) // 64
+
+
+def _crop_arguments(floor, share, who):
+    floor, share = int(floor), int(share)
+    if not 0 <= floor <= 255 or not 1 <= share <= 1024:
+        raise ValueError("%s: floor %d (0 .. 255) / share %d (1 .. 1024)" % (who, floor, share))
+    return floor, share
+
+
+def crop_counts_host(page, floor=CROP_FLOOR):
+    """asr_crop_estimate_dev's counts on the host (the definition in include/asr_hip.h) -> (row counts int32 (H,), column
+    counts int32 (W,)): the pixels below `floor` of every row over the central band of the columns [W / 4, W - W / 4),
+    and of every column over the central band of the rows.  The device returns the same integers."""
+    page = _uint8_page(page, "crop_counts_host")
+    floor, _ = _crop_arguments(floor, 1, "crop_counts_host")
+    h, w = page.shape
+    dark = page < floor
+    return (dark[:, w // 4:w - w // 4].sum(axis=1).astype(np.int32),
+            dark[h // 4:h - h // 4, :].sum(axis=0).astype(np.int32))
+
+
+def _edge_run(border):
+    """the length of the run of True that starts at index 0"""
+    stops = np.flatnonzero(~border)
+    return int(stops[0]) if stops.size else int(border.size)
+
+
+def crop_rect_host(page, floor=CROP_FLOOR, share=CROP_SHARE, margin=None):
+    """asr_crop_estimate_dev on the host -> ((r0, r1, c0, c1), status): the paper's rectangle inside a scanner's black
+    border.  A row is a border row where 1024 * its count >= share * the band's width, a column likewise; the runs of
+    border rows / columns that touch the four edges are cut off, and `margin` more (None: crop_margin of the width) on
+    every side where a run was found.  Status 1 and the whole page where that leaves nothing.  The device returns the
+    same integers."""
+    page = _uint8_page(page, "crop_rect_host")
+    floor, share = _crop_arguments(floor, share, "crop_rect_host")
+    h, w = page.shape
+    margin = crop_margin(w) if margin is None else int(margin)
+    if margin < 0:
+        raise ValueError("crop_rect_host: margin %d is negative" % margin)
+    rows, cols = crop_counts_host(page, floor)
+    border_rows = 1024 * rows.astype(np.int64) >= share * (w - w // 4 - w // 4)
+    border_cols = 1024 * cols.astype(np.int64) >= share * (h - h // 4 - h // 4)
+    top, bottom = _edge_run(border_rows), _edge_run(border_rows[::-1])
+    left, right = _edge_run(border_cols), _edge_run(border_cols[::-1])
+    r0, r1 = top + (margin if top else 0), h - bottom - (margin if bottom else 0)
+    c0, c1 = left + (margin if left else 0), w - right - (margin if right else 0)
+    if top + bottom >= h or left + right >= w or r1 - r0 < 1 or c1 - c0 < 1:
+        return (0, h, 0, w), 1
+    return (r0, r1, c0, c1), 0
+
+
+def crop_page_host(page, floor=CROP_FLOOR, share=CROP_SHARE, margin=None):
+    """asr_crop_estimate_dev + asr_crop_pages_dev on the host: the page cut to crop_rect_host's rectangle.  The device
+    returns the same bytes."""
+    (r0, r1, c0, c1), _ = crop_rect_host(page, floor, share, margin)
+    return np.ascontiguousarray(np.asarray(page)[r0:r1, c0:c1])
+
+
 class DevicePages(object):
     """uint8 pages back to back in one device buffer, as asr_seg_predict_dev (IN_U8_RAW) and asr_unroll_systems_dev
     read them: uploaded once, used by both networks and by the unroll."""
@@ -589,6 +655,49 @@ class DevicePages(object):
             raise
         return res
 
+    def cropped(self, floor=CROP_FLOOR, share=CROP_SHARE, margin=None, rects=None):
+        """a new DevicePages on the same engine: every page cut to the paper inside a scanner's black border
+        (asr_crop_estimate_dev - the rects come to the host, they are the new shapes - then asr_crop_pages_dev; margin
+        None: crop_margin of each page's width, a number: that margin for all pages, a sequence: one per page; with
+        `rects`, (n, 4) rows of r0 r1 c0 c1, those are applied and nothing is estimated).  The result carries the rects
+        as .rects (int32 (n, 4), in this object's coordinates) and .crop_status (int32; 1: undecided, the page is
+        whole; all 0 with `rects`); the pages themselves are neither uploaded nor downloaded.  This object stays valid;
+        free both."""
+        n = len(self)
+        if rects is None:
+            if margin is None:
+                margins = [crop_margin(w) for w in self.widths]
+            elif np.ndim(margin) == 0:
+                margins = [int(margin)] * n
+            else:
+                margins = margin
+            margins = np.ascontiguousarray(margins, dtype=np.int32)
+            if margins.shape != (n,):
+                raise ValueError("%d margins for %d pages" % (margins.size, n))
+            rects, status = self.engine.crop_estimate_dev(self.buf.ptr, self.nbytes, self.offsets, self.heights,
+                                                          self.widths, margins, floor, share)
+        else:
+            rects = np.ascontiguousarray(rects, dtype=np.int32)
+            if rects.shape != (n, 4):
+                raise ValueError("rects of shape %s for %d pages" % (rects.shape, n))
+            status = np.zeros(n, np.int32)
+        res = DevicePages.__new__(DevicePages)
+        res.engine = self.engine
+        res.heights = (rects[:, 1] - rects[:, 0]).astype(np.int32)
+        res.widths = (rects[:, 3] - rects[:, 2]).astype(np.int32)
+        res.sizes = res.heights.astype(np.int64).clip(0) * res.widths.astype(np.int64).clip(0)
+        res.offsets = np.concatenate([[0], np.cumsum(res.sizes)[:-1]]).astype(np.int64)
+        res.nbytes = int(res.sizes.sum())
+        res.rects, res.crop_status = rects, status
+        res.buf = self.engine.alloc(max(res.nbytes, 4))
+        try:
+            self.engine.crop_pages_dev(self.buf.ptr, self.nbytes, self.offsets, self.heights, self.widths, rects,
+                                       res.offsets, res.buf.ptr, res.nbytes)
+        except Exception:
+            res.buf.free()
+            raise
+        return res
+
     def download_page(self, i):
         """page i as a uint8 array on the host"""
         return self.engine.raw_download(self.buf.ptr + int(self.offsets[i]), (int(self.heights[i]), int(self.widths[i])),
@@ -626,6 +735,17 @@ def flatten_pages_dev(engine, pages, radius=None, floor=FLATTEN_FLOOR):
     raw = DevicePages(engine, pages)
     try:
         return raw.flattened(radius, floor)
+    finally:
+        raw.free()
+
+
+def crop_pages_dev(engine, pages, floor=CROP_FLOOR, share=CROP_SHARE, margin=None, rects=None):
+    """host pages (2-D uint8 arrays of any sizes) -> a DevicePages holding them cut to their paper
+    (DevicePages.cropped), with the rects as .rects and the statuses as .crop_status: one upload of the raw pages.  Free
+    it when done."""
+    raw = DevicePages(engine, pages)
+    try:
+        return raw.cropped(floor, share, margin, rects)
     finally:
         raw.free()
 

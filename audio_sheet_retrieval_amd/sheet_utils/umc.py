@@ -100,6 +100,23 @@ def _next_stage(dev_pages, stage):
         dev_pages.free()
 
 
+_CROPPED_STRIPS = []        # the class of _strips_with_crop, made once (piece_identification is imported late)
+
+
+def _strips_with_crop(strips, rects, status):
+    """the DeviceArrays `strips` as a DeviceArrays - the same three fields, a tuple of three as before - that also
+    carries the crop of every raw page as .crop_rects (int32 (n_pages, 4): r0 r1 c0 c1) and .crop_status"""
+    if not _CROPPED_STRIPS:
+        from audio_sheet_retrieval_amd.piece_identification import DeviceArrays
+
+        class CroppedStrips(DeviceArrays):
+            pass                                                # no __slots__: instances take attributes
+        _CROPPED_STRIPS.append(CroppedStrips)
+    res = _CROPPED_STRIPS[0](*strips)
+    res.crop_rects, res.crop_status = rects, status
+    return res
+
+
 def load_umc_sheets(data_dir, require_performance=False, omr=None, system_params=None, bar_params=None, device=0,
                     return_device=False, device_post=False, page_width=None):
     """ load unwarpped sheets
@@ -126,9 +143,17 @@ def load_umc_sheets(data_dir, require_performance=False, omr=None, system_params
 
 def load_umc_scans(data_dir, require_performance=False, omr=None, system_params=None, bar_params=None, device=0,
                    return_device=False, device_post=False, page_width=PAGE_WIDTH, deskew=True, max_slope=64, flatten=False,
-                   flatten_radius=None, flatten_floor=64, score_map=False):
-    """load_umc_sheets for flat-bed scans: pages of any resolution whose staves need not be horizontal and whose paper
-    need not be white.  The raw pages are uploaded once; with flatten (off by default) every page is first divided by
+                   flatten_radius=None, flatten_floor=64, score_map=False, crop=False, crop_floor=64, crop_share=512,
+                   crop_margin=None):
+    """load_umc_sheets for flat-bed scans: pages of any resolution whose staves need not be horizontal, whose paper
+    need not be white and need not fill the scanner's glass.  The raw pages are uploaded once; with crop (off by
+    default) every page is first cut to the paper inside the scanner's black frame on the device (DevicePages.cropped:
+    asr_crop_estimate_dev, asr_crop_pages_dev; crop_floor: a pixel below this is dark, crop_share: a border row or
+    column is dark over this many 1/1024 of its central band, crop_margin None: by each page's width) - before
+    everything else, so that the resize scales the paper, not the frame, to page_width; with return_device=True the
+    returned strips then carry the rects as .crop_rects (int32 (n_pages, 4): r0 r1 c0 c1 in the pixels of the raw scans,
+    every page of every piece that was read, in reading order) and .crop_status (1: undecided, the page was left whole).
+    With flatten (off by default) every page is then divided by
     the grey closing of its paper on the device (DevicePages.flattened: asr_flatten_pages_dev; flatten_radius None: by
     each page's width, flatten_floor: a background darker than this is left alone) - before the deskew, whose shear
     fills the corners with white and whose score should read ink, not shadow; with deskew the slope of every page is
@@ -136,20 +161,21 @@ def load_umc_scans(data_dir, require_performance=False, omr=None, system_params=
     (DevicePages.deskewed: asr_skew_estimate_dev, asr_deskew_pages_dev), then the pages are reduced to page_width columns
     (DevicePages.resized; None: left at their size) - the area resize after the shear takes the interpolation blur away
     again.  Everything downstream reads the result on the device, as in load_umc_sheets; the return values are the
-    same.  With deskew=False and page_width=None (and no flatten) this is load_umc_sheets.
+    same.  With deskew=False and page_width=None (and no flatten, no crop) this is load_umc_sheets.
     score_map=True (with return_device=True and a bar network; ValueError otherwise): one more value is returned, the
     score_map.ScoreMap of the kept pieces - their measures in strip coordinates, built on the device from the bar
     network's maps in the pass that unrolls the pages (asr_score_map_dev).  The bar network runs once: the systems are
     then detected by the device post-processing whatever device_post says (the same integers), which hands its bar maps
-    on.  Page coordinates in the map are those of the pages the networks saw, after flatten, deskew and resize."""
+    on.  Page coordinates in the map are those of the pages the networks saw, after crop, flatten, deskew and resize."""
     return _load_sheets(data_dir, require_performance, omr, system_params, bar_params, device, return_device, device_post,
                         page_width, deskew, max_slope, (flatten_radius, flatten_floor) if flatten else None,
-                        score_map=score_map)
+                        score_map=score_map, crop=(crop_floor, crop_share, crop_margin) if crop else None)
 
 
 def _load_sheets(data_dir, require_performance, omr, system_params, bar_params, device, return_device, device_post,
-                 page_width, deskew, max_slope, flatten=None, score_map=False):
-    """the body of load_umc_sheets / load_umc_scans.  flatten: None, or (radius, floor) of DevicePages.flattened"""
+                 page_width, deskew, max_slope, flatten=None, score_map=False, crop=None):
+    """the body of load_umc_sheets / load_umc_scans.  flatten: None, or (radius, floor) of DevicePages.flattened; crop:
+    None, or (floor, share, margin) of DevicePages.cropped"""
     if score_map and not return_device:
         raise ValueError("score_map=True needs return_device=True: the map is built where the bar maps are")
     if omr is None:
@@ -181,10 +207,14 @@ def _load_sheets(data_dir, require_performance, omr, system_params, bar_params, 
     # every page of every piece: one call per network (prepare_image on the device)
     all_pages = [I for _, _, pages in jobs for I in pages]
     dev_pages = None
-    if (page_width is not None or deskew or flatten is not None) and all_pages:
+    cropped = None                                              # (rects, status) of the raw pages
+    if (page_width is not None or deskew or flatten is not None or crop is not None) and all_pages:
         from audio_sheet_retrieval_amd.sheet_utils.omr import _engine
         engine = omr.system_detector.engine or _engine(omr.system_detector.device)
-        dev_pages = DevicePages(engine, all_pages)              # upload raw, then flatten, then deskew, then resize
+        dev_pages = DevicePages(engine, all_pages)              # upload raw, then crop, flatten, deskew, resize
+        if crop is not None:
+            dev_pages = _next_stage(dev_pages, lambda pages: pages.cropped(*crop))
+            cropped = (dev_pages.rects, dev_pages.crop_status)
         if flatten is not None:
             dev_pages = _next_stage(dev_pages, lambda pages: pages.flattened(*flatten))
         if deskew:
@@ -192,7 +222,11 @@ def _load_sheets(data_dir, require_performance, omr, system_params, bar_params, 
         if page_width is not None:
             dev_pages = _next_stage(dev_pages, lambda pages: pages.resized(page_width))
     if return_device:
-        return _unroll_on_device(omr, jobs, all_pages, device_post=device_post, dev_pages=dev_pages, score_map=score_map)
+        res = _unroll_on_device(omr, jobs, all_pages, device_post=device_post, dev_pages=dev_pages, score_map=score_map)
+        if crop is not None:
+            rects, status = cropped if cropped is not None else (np.zeros((0, 4), np.int32), np.zeros(0, np.int32))
+            res = res[:3] + (_strips_with_crop(res[3], rects, status),) + res[4:]
+        return res
     detect = omr.detect_systems_pages_dev if device_post else omr.detect_systems_pages
     if dev_pages is not None:
         try:

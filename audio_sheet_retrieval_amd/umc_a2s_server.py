@@ -6,7 +6,7 @@ umc_a2s_server.py (:178-189):
         --train_split splits/all_split.yaml --config exp_configs/mutopia_full_aug.yaml \
         --init_sheet_db --full_eval --dump_results [--real_perf] [--n_candidates 25] [--estimate_UV] \
         --system_params system_params.pkl --bar_params bar_params.pkl [--device_post] [--resample] [--page_width 835]
-        [--deskew] [--flatten] [--live [--bank] [--live_dft direct|fft] [--block_ms 100] [--running_frames 100]
+        [--deskew] [--flatten] [--crop] [--live [--bank] [--live_dft direct|fft] [--block_ms 100] [--running_frames 100]
                    [--level running [--level_memory N] [--level_floor F]]]
         [--locate [--excerpt_frames 400] [--locate_pieces 5] [--step_spec 2] [--seed 23]]
 
@@ -35,7 +35,9 @@ resampling, the shape rule of the reference's scripts/prepare_umc_data.py).  --d
 sheared by it on the device, between the upload and the resize (sheet_utils/umc.load_umc_scans).  --flatten (off by
 default; with or without --deskew and --page_width) takes scans whose paper is not white - a spine shadow, a gradient,
 yellowed paper: every page is divided by the grey closing of its paper on the device, right after the upload
-(asr_flatten_pages_dev).
+(asr_flatten_pages_dev).  --crop (off by default; with or without the other three) takes scans of pages smaller than the
+scanner's glass: the black frame around the paper is found and cut off on the device, before everything else, so that
+--page_width scales the paper and not the frame (asr_crop_estimate_dev, asr_crop_pages_dev).
 
 --live (A2S only, off by default) runs the reference's default mode, the running vote of AudioSheetServer.run, on the
 recordings as a sound card would deliver them: every queried piece's recording is read at its own rate
@@ -108,6 +110,10 @@ def _arguments(argv, direction):
     p.add_argument("--flatten", action="store_true",
                    help="divide every page by the grey closing of its paper on the device, before the deskew and the "
                         "resize: shadows, gradients, yellowed paper (asr_flatten_pages_dev; "
+                        "sheet_utils/umc.load_umc_scans)")
+    p.add_argument("--crop", action="store_true",
+                   help="cut every page to the paper inside the scanner's black frame on the device, before the flatten, "
+                        "the deskew and the resize (asr_crop_estimate_dev, asr_crop_pages_dev; "
                         "sheet_utils/umc.load_umc_scans)")
     p.add_argument("--fast_dft", action="store_true",
                    help="compute the spectrograms' magnitudes with an FFT (asr_spectrogram_fft_batch_dev; "
@@ -258,10 +264,10 @@ def run(argv, direction):
     omr = umc.build_recognizer(args.system_params, args.bar_params)
     locating = getattr(args, "locate", False)
     build_map = locating and args.init_db                   # otherwise --locate loads the map the data base was saved with
-    if args.deskew or args.flatten or build_map:           # (neither flag: load_umc_scans is load_umc_sheets with the map)
+    if args.deskew or args.flatten or args.crop or build_map:  # (no flag: load_umc_scans is load_umc_sheets with the map)
         loaded = umc.load_umc_scans(args.data_dir, require_performance=True, omr=omr, return_device=True,
                                     device_post=args.device_post, page_width=args.page_width, deskew=args.deskew,
-                                    flatten=args.flatten, score_map=build_map)
+                                    flatten=args.flatten, score_map=build_map, crop=args.crop)
     else:
         loaded = umc.load_umc_sheets(args.data_dir, require_performance=True, omr=omr, return_device=True,
                                      device_post=args.device_post, page_width=args.page_width)

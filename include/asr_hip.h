@@ -1115,6 +1115,38 @@ int asr_bars_from_map_dev(asr_ctx *ctx, const double *maps_dev, const int32_t *h
  *   launched: 1 <= H, W <= 16384, 1 <= radii[p] <= 127, 0 <= floor <= 255, every page inside the buffers, and the
  *   overlaps above.  A violation returns ASR_ERR_INVALID with a message that starts with "flatten_pages:" and writes
  *   nothing.  n_pages == 0 is valid and writes nothing.
+ * asr_crop_estimate_dev / asr_crop_pages_dev = taking a flat-bed scanner's black frame off a scan of a page smaller than
+ *   the glass, between the upload and the flatten.  The reference has no such stage; the yardstick is this definition, all
+ *   in integers, which sheet_utils/omr.crop_counts_host / crop_rect_host / crop_page_host restate in numpy and the device
+ *   reproduces exactly.  A page is H x W uint8, dark ink on light paper, in the layout of asr_resize_pages_dev; floor is
+ *   0 .. 255 (a grey level), share 1 .. 1024 (in 1/1024), margins[p] >= 0 (pixels; host int32[n_pages];
+ *   sheet_utils/omr.crop_margin: (W + 32) / 64).
+ *     dark       dark(y, x) = page[y][x] < floor                          (floor 0: nothing is dark)
+ *     bands      columns cb0 = W / 4, cb1 = W - W / 4; rows rb0 = H / 4, rb1 = H - H / 4   (integer divisions; non-empty)
+ *     counts     rowcount[r] = #{ x in [cb0, cb1) : dark(r, x) },  colcount[c] = #{ y in [rb0, rb1) : dark(y, c) }
+ *                (each axis over the central band of the other: the frame of the other two sides and the corners never
+ *                enter a count)
+ *     border     row r: 1024 * rowcount[r] >= share * (cb1 - cb0);  column c: 1024 * colcount[c] >= share * (rb1 - rb0)
+ *     runs       top = the length of the maximal run of border rows that starts at row 0, bottom = of the one that ends at
+ *                row H - 1; left, right the same for columns.  Only a run that touches the edge counts.
+ *     rect       r0 = top + (top ? margin : 0), r1 = H - bottom - (bottom ? margin : 0); c0, c1 the same.  Status 0.
+ *     undecided  top + bottom >= H, or left + right >= W, or r1 - r0 < 1, or c1 - c0 < 1: the rect is the whole page
+ *                (0, H, 0, W) and the status is 1 - an all-dark page, a margin larger than the paper.
+ *     result     out = page[r0:r1, c0:c1]
+ *   A page without a dark edge is returned as it is; an axis-aligned frame of any widths up to a quarter of the page is
+ *   removed exactly.
+ *   asr_crop_estimate_dev writes rects (host int32[n_pages * 4]: r0 r1 c0 c1), status (host int32[n_pages]) and, unless
+ *   NULL, row_counts / col_counts (host int32, the pages' rows / columns back to back: sum of H / sum of W entries).  Two
+ *   launches whatever n_pages is: the counts - the three quarters of every page that lie in a band are read once, 4 bytes
+ *   per lane, and the tiles' partial counts are added with int32 atomics to zeroed workspace of the context, so the
+ *   counts do not depend on the order - then the runs and the rule, one wave per page and side.
+ *   asr_crop_pages_dev copies rows [r0, r1) x columns [c0, c1) of page p to byte out_offsets[p] of out_dev (out_bytes its
+ *   size), rows of c1 - c0 bytes back to back, in one launch; out_dev must not overlap pages_dev; bytes that belong to no
+ *   output page are left as they are.  The rects are the caller's: the estimate's, or any other.
+ *   Both: rows at any alignment on both sides.  Before anything is launched: 1 <= H, W <= 16384, the ranges above,
+ *   0 <= r0 < r1 <= H and 0 <= c0 < c1 <= W, every page and every output inside its buffer, and the overlap above.  A
+ *   violation returns ASR_ERR_INVALID with a message that starts with "crop_pages:" and writes nothing.  n_pages == 0 is
+ *   valid and writes nothing.
  * asr_score_map_dev = the measures of every piece in strip coordinates: the way back from a column x of an unrolled strip
  *   to a bar, a page, a staff system and a page position.  The reference has no such stage (its detect_bars gives blobs on
  *   a page, its alignment raises for a system without a bar and knows nothing of strips); the yardstick is this
@@ -1201,6 +1233,13 @@ int asr_deskew_pages_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_byte
 int asr_flatten_pages_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
                           const int32_t *heights, const int32_t *widths, int n_pages, const int32_t *radii, int floor,
                           void *out_dev, int64_t out_bytes, void *background_dev);
+int asr_crop_estimate_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
+                          const int32_t *heights, const int32_t *widths, int n_pages, int floor, int share,
+                          const int32_t *margins, int32_t *rects, int32_t *status, int32_t *row_counts,
+                          int32_t *col_counts);
+int asr_crop_pages_dev(asr_ctx *ctx, const void *pages_dev, int64_t pages_bytes, const int64_t *page_offsets,
+                       const int32_t *heights, const int32_t *widths, int n_pages, const int32_t *rects,
+                       const int64_t *out_offsets, void *out_dev, int64_t out_bytes);
 
 /* ---- device memory (plain pointers; library-owned allocations) ---------- */
 int asr_dev_alloc(asr_ctx *ctx, size_t bytes, void **dptr);
