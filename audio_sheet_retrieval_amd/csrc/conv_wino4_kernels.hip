@@ -31,7 +31,7 @@
 
 #ifndef ASR_WINO4_ABL
 #define ASR_WINO4_ABL 0      // timing experiments only (wrong results): 2 = no input loads after the first block;
-                             // conv3x3_wino4s also: 4 = no weight loads after the first, 8 = no input transform,
+                             // conv3x3_wino4s also: 4 = no weight loads after the first (streamed builds), 8 = no input transform,
                              // 16 = no LDS writes of V, 32 = no output stores
 #endif
 
@@ -69,6 +69,45 @@ typedef int int4q __attribute__((ext_vector_type(4)));
 // conv3x3_wino's LDS-DMA: with the buffer builtins inside a function template the host pass emits no kernel stub.
 __device__ __forceinline__ void buffer_store_q(float v, unsigned voff, int4q rsrc, unsigned soff) {
     asm volatile("buffer_store_dword %0, %1, %2, %3 offen" ::"v"(v), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
+}
+
+// ---- conv3x3_wino4s, non-RAW consumers: accumulators in architectural VGPRs, B operands in AGPRs.  The compiler
+// allocates an MFMA's C/D to the accumulator file and its B operand to VGPRs; the other way round needs inline
+// assembly, and what the compiler does around an instruction it knows - count its memory operation, pad its hazards -
+// has to be placed by hand (see the three places marked [wait] / [hazard] in the consumer).
+// four B operands from a scalar base + a 32-bit lane offset, straight into AGPRs.  The destination counts as written when
+// the statement ends: every reader has to stand behind a wino4_wait_weights that names it.
+__device__ __forceinline__ floatx4q wino4_load_weights(const char *base, unsigned voff) {
+    floatx4q d;
+    asm volatile("global_load_dwordx4 %0, %1, %2" : "=a"(d) : "v"(voff), "s"(base));
+    return d;
+}
+// [wait] at most N vector-memory operations issued after the loads of w[0..17] are still in flight, so those loads have
+// landed (gfx9 retires vmcnt in issue order, stores included).  Naming the 18 registers read-write keeps every reader
+// behind the wait.
+template <int N> __device__ __forceinline__ void wino4_wait_weights(floatx4q *w) {
+    static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit field");
+    asm volatile("s_waitcnt vmcnt(%18)"
+                 : "+a"(w[0]), "+a"(w[1]), "+a"(w[2]), "+a"(w[3]), "+a"(w[4]), "+a"(w[5]), "+a"(w[6]), "+a"(w[7]), "+a"(w[8]),
+                   "+a"(w[9]), "+a"(w[10]), "+a"(w[11]), "+a"(w[12]), "+a"(w[13]), "+a"(w[14]), "+a"(w[15]), "+a"(w[16]),
+                   "+a"(w[17])
+                 : "n"(N));
+}
+// acc (VGPRs) += A (VGPR) x B (AGPR); the _zero form starts from the inline zero C operand
+__device__ __forceinline__ void wino4_mfma(floatx4q &acc, float a, float b) {
+    asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "a"(b));
+}
+__device__ __forceinline__ void wino4_mfma_zero(floatx4q &acc, float a, float b) {
+    asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "a"(b));
+}
+// [hazard] an 8-pass fp32 MFMA's result may be read by a vector ALU instruction 10 wait states after it at the earliest
+// (4-, 8-, 16-pass: 4, 10, 18); the compiler pads that for an MFMA it knows.  Once per M-tile, between the last step and
+// the output transform: 16 states in front of anything that reads the first 18 accumulators, 16 more for the rest.
+__device__ __forceinline__ void wino4_settle(floatx4q *c) {
+    asm volatile("s_nop 15"
+                 : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(c[4]), "+v"(c[5]), "+v"(c[6]), "+v"(c[7]), "+v"(c[8]),
+                   "+v"(c[9]), "+v"(c[10]), "+v"(c[11]), "+v"(c[12]), "+v"(c[13]), "+v"(c[14]), "+v"(c[15]), "+v"(c[16]),
+                   "+v"(c[17]));
 }
 
 template <typename T> __device__ __forceinline__ T splatq(float c);
@@ -290,9 +329,14 @@ __global__ __launch_bounds__(64 * WAVES, 1) void conv3x3_wino4g(Wino4Args a) {
 //              (36 x 16 x 8 floats); it never issues an MFMA and the consumers never issue a transform instruction -
 //              the vector work that the fp32 MFMA cannot overlap inside one wave runs on another SIMD;
 //   consumers: read V as A operands (one conflict-free ds_read_b64 per position = two k-steps), multiply by their
-//              n-tile's transformed weights - kept entirely in registers when they fit (C_in = 24: 216 values),
-//              otherwise streamed from global memory (L2-resident, 331 KiB per layer at 48 -> 48) one channel block
-//              ahead into a ping-pong register set - and run the output transform / BN / ELU / pool of their n-tile.
+//              n-tile's transformed weights - streamed from global memory (L2-resident, 331 KiB per layer at
+//              48 -> 48) one channel block ahead into a ping-pong register set of 2 x 72 - and run the output
+//              transform / BN / ELU / pool of their n-tile.  Non-RAW builds swap the register classes the compiler
+//              would pick (inline assembly, see wino4_mfma): the 144 accumulators live in VGPRs, where the epilogue
+//              reads them without a copy each, and the weights are loaded straight into AGPRs, which nothing else
+//              needs - so at C_in = 24 all 216 values of a lane stay resident there for the workgroup's life and
+//              the M-tile loop has no weight load at all (as VGPRs, beside 144 accumulator AGPRs, they spilled,
+//              and that earlier form was removed).  RAW builds: compiler-allocated, accumulators in AGPRs.
 // One workgroup barrier per (M-tile, channel block) step hands a V buffer over.  The input transform is paid once per
 // M-tile, three of the four SIMDs run MFMAs only, and there are 1.78x fewer of them than in F(2x2,3x3).
 // SLICE < C_out (96 output channels): blockIdx.y picks SLICE of them, so a workgroup stays at one wave per SIMD with
@@ -525,11 +569,33 @@ __global__ __launch_bounds__(64 * (PW + (SLICE + 15) / 16), 1) void conv3x3_wino
     // loads, and have the whole step to arrive from L2.  Measured alternatives (conv6, 0.404 ms with 72 dword loads
     // after the barrier): the same loads before the barrier 0.440; in three bursts between the MFMA groups 0.473; one
     // register set reloaded in place after each group 0.449 - vector-memory instructions issued between MFMAs cost
-    // more than they hide
-    floatx4q bw[2][18];
+    // more than they hide.
+    // Non-RAW builds keep these sets in AGPRs and the accumulators in VGPRs (wino4_load_weights / wino4_mfma): the
+    // epilogue reads the accumulators where they are, without a v_accvgpr_read each.  RESIDENT (C_in = 24): the lane's
+    // weights of the whole layer, 54 float4 = 216 AGPRs, are loaded once per workgroup - no weight load, no ping-pong
+    // and no channel-block pointer inside the M-tile loop.  (In VGPRs, next to 144 accumulator AGPRs, they spilled.)
+    constexpr bool RESIDENT = !RAW && CIN == 24;
+    static_assert(RAW || RESIDENT || (NB & 1) == 0, "the streamed sets alternate over an even number of steps");
+    constexpr int NSETS = RESIDENT ? NB : 2;
+    floatx4q bw[NSETS * 18];                                  // set s: bw[18 s] ... bw[18 s + 17]
+    if constexpr (RAW) {
 #pragma unroll
-    for (int j = 0; j < 18; ++j)
-        bw[0][j] = *reinterpret_cast<const floatx4q *>(reinterpret_cast<const char *>(wl) + (size_t)j * (wstep * 16) + wlane);
+        for (int j = 0; j < 18; ++j)
+            bw[j] = *reinterpret_cast<const floatx4q *>(reinterpret_cast<const char *>(wl) + (size_t)j * (wstep * 16) + wlane);
+    } else {
+        // channel block t's 18 row groups follow block t - 1's: one run of 18 NB float4 per lane
+#pragma unroll
+        for (int j = 0; j < (RESIDENT ? NSETS : 1) * 18; ++j)
+            bw[j] = wino4_load_weights(reinterpret_cast<const char *>(wl) + (size_t)j * (wstep * 16), wlane);
+        if constexpr (RESIDENT) {                             // [wait] all of them, before the M-tile loop
+#pragma unroll
+            for (int s = 0; s < NSETS; ++s) wino4_wait_weights<0>(bw + 18 * s);
+        }
+    }
+    // streamed, non-RAW: the M-tile before this one ended in a branch-free epilogue, i.e. exactly FAST_STORES buffer
+    // stores were issued after the loads of the set its first step reads
+    constexpr int FAST_STORES = POOL ? 16 : 64;
+    bool after_fast = false;
     int step = 0;
     for (; mt < mt_end; mt += mt_stride) {
         unsigned my_off;
@@ -551,14 +617,16 @@ __global__ __launch_bounds__(64 * (PW + (SLICE + 15) / 16), 1) void conv3x3_wino
                 epi_mode = __builtin_amdgcn_ballot_w64(!wino4_rows_full(my_ext, POOL)) == 0 ? 1 : (wino4_general_form(POOL) ? 2 : 0);
         }
         // byte offsets of this lane in row groups 0, 2, 4 ... 16 of a channel block (the odd ones are an immediate
-        // offset away); opaque, so that the weight loads - which do not depend on the M-tile - are neither hoisted out
-        // of this loop (a layer's B operands do not fit the register file; it spilled them) nor folded into 64-bit
-        // vector pointers
+        // offset away, or a second scalar base); opaque, so that the weight loads - which do not depend on the M-tile -
+        // are neither hoisted out of this loop (a layer's B operands do not fit the register file; it spilled them) nor
+        // folded into 64-bit vector pointers
         unsigned voff[9];
+        if constexpr (!RESIDENT) {
 #pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            voff[k] = wlane + (unsigned)k * (2 * wstep * 16);
-            asm volatile("" : "+v"(voff[k]));
+            for (int k = 0; k < 9; ++k) {
+                voff[k] = wlane + (unsigned)k * (2 * wstep * 16);
+                asm volatile("" : "+v"(voff[k]));
+            }
         }
         floatx4q acc[36];
         // one step: 72 MFMAs on V buffer vb in three groups of 12 positions; the A operands of group g + 1 are read
@@ -574,18 +642,30 @@ __global__ __launch_bounds__(64 * (PW + (SLICE + 15) / 16), 1) void conv3x3_wino
             const char *wnb = reinterpret_cast<const char *>(wn);
 #pragma unroll
             for (int k = 0; k < 9; ++k) {
-                unsigned vo = voff[k];
-                asm volatile("" : "+v"(vo));
-                bw[SET][2 * k] = *reinterpret_cast<const floatx4q *>(wnb + vo);
-                bw[SET][2 * k + 1] = *reinterpret_cast<const floatx4q *>(wnb + (wstep * 16) + vo);
+                if constexpr (RAW) {
+                    unsigned vo = voff[k];
+                    asm volatile("" : "+v"(vo));
+                    bw[18 * SET + 2 * k] = *reinterpret_cast<const floatx4q *>(wnb + vo);
+                    bw[18 * SET + 2 * k + 1] = *reinterpret_cast<const floatx4q *>(wnb + (wstep * 16) + vo);
+                } else {                                      // (the odd row group: a second scalar base)
+                    bw[18 * SET + 2 * k] = wino4_load_weights(wnb, voff[k]);
+                    bw[18 * SET + 2 * k + 1] = wino4_load_weights(wnb + (wstep * 16), voff[k]);
+                }
             }
         };
-        auto run_step = [&](const float *vb, const float *wn, auto cur_c, auto first) {
+        // cur_c: the register set this step multiplies by (RESIDENT: the channel block).  WAIT (streamed, non-RAW): how
+        // many vector-memory operations may stay in flight once the step's own 18 loads are issued
+        auto run_step = [&](const float *vb, const float *wn, auto cur_c, auto first, auto wait_c) {
             constexpr bool FIRST = decltype(first)::value;
             constexpr int CUR = decltype(cur_c)::value;
-            using NXT = std::integral_constant<int, CUR ^ 1>;
             __syncthreads();                                  // V of this step is in buffer (step & 1)
-            reload(wn, NXT{});
+            if constexpr (!RESIDENT) {
+                reload(wn, std::integral_constant<int, CUR ^ 1>{});
+                // [wait] set CUR was requested one step ago.  Behind it stand this step's 18 loads and, in the first
+                // step of an M-tile, the stores of the epilogue before it: 18 covers every case (it drains the stores
+                // too), 18 + FAST_STORES lets the stores of a branch-free epilogue, whose count is static, stay in flight
+                if constexpr (!RAW) wino4_wait_weights<decltype(wait_c)::value>(bw + 18 * CUR);
+            }
             __builtin_amdgcn_sched_barrier(0);
             float2q dp[2][12];
 #pragma unroll
@@ -597,44 +677,72 @@ __global__ __launch_bounds__(64 * (PW + (SLICE + 15) / 16), 1) void conv3x3_wino
                     for (int i = 0; i < 12; ++i)
                         dp[(grp + 1) & 1][i] = *reinterpret_cast<const float2q *>(vb + ((grp + 1) * 12 + i) * 128);
                 }
+                // [hazard] the A operands come from ds_read_b64 alone: the compiler sees those registers and waits on
+                // lgkmcnt in front of the statement that reads them.  Should it ever put a register move in between, a
+                // vector ALU write needs two wait states before an MFMA reads it as A or B
+                if constexpr (!RAW) asm volatile("s_nop 1");
 #pragma unroll
                 for (int c = 0; c < 2; ++c)
 #pragma unroll
                     for (int i = 0; i < 12; ++i) {
                         const int p = grp * 12 + i;
-                        if (FIRST && c == 0)
-                            acc[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(dp[grp & 1][i][c], bw[CUR][(c * 36 + p) >> 2][(c * 36 + p) & 3],
-                                                                          floatx4q{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                        else
-                            acc[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(dp[grp & 1][i][c], bw[CUR][(c * 36 + p) >> 2][(c * 36 + p) & 3], acc[p],
-                                                                          0, 0,
-                                                                          0);
+                        const int q = c * 36 + p;
+                        if constexpr (RAW) {
+                            if (FIRST && c == 0)
+                                acc[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(dp[grp & 1][i][c], bw[18 * CUR + (q >> 2)][q & 3],
+                                                                              floatx4q{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+                            else
+                                acc[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(dp[grp & 1][i][c], bw[18 * CUR + (q >> 2)][q & 3], acc[p],
+                                                                              0, 0, 0);
+                        } else {
+                            if (FIRST && c == 0) wino4_mfma_zero(acc[p], dp[grp & 1][i][c], bw[18 * CUR + (q >> 2)][q & 3]);
+                            else wino4_mfma(acc[p], dp[grp & 1][i][c], bw[18 * CUR + (q >> 2)][q & 3]);
+                        }
                     }
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
         using C0 = std::integral_constant<int, 0>;
         using C1 = std::integral_constant<int, 1>;
+        using C2 = std::integral_constant<int, 2>;
+        using W18 = std::integral_constant<int, 18>;
+        using WFAST = std::integral_constant<int, (18 + FAST_STORES < 63 ? 18 + FAST_STORES : 63)>;
         auto wblock = [&](int t) {                            // the channel block after step t's, as a SCALAR pointer
             unsigned blk = (unsigned)(((t + 1) % NB) * 72) * wstep;
             asm volatile("" : "+s"(blk));                     // (a constant here would be folded into the lane offsets)
             return wl + blk;
         };
-        run_step(vlane + (step & 1) * VB, wblock(0), C0{}, std::true_type{});
-        ++step;
+        if constexpr (RESIDENT) {
+            static_assert(!RESIDENT || NB == 3, "one step per resident set");
+            run_step(vlane + (step & 1) * VB, wl, C0{}, std::true_type{}, W18{});
+            ++step;
+            run_step(vlane + (step & 1) * VB, wl, C1{}, std::false_type{}, W18{});
+            ++step;
+            run_step(vlane + (step & 1) * VB, wl, C2{}, std::false_type{}, W18{});
+            ++step;
+        } else {
+            if (!RAW && after_fast) run_step(vlane + (step & 1) * VB, wblock(0), C0{}, std::true_type{}, WFAST{});
+            else run_step(vlane + (step & 1) * VB, wblock(0), C0{}, std::true_type{}, W18{});
+            after_fast = false;
+            ++step;
 #pragma unroll 1
-        for (int t = 1; t + 1 < NB; t += 2) {
-            run_step(vlane + (step & 1) * VB, wblock(t), C1{}, std::false_type{});
-            ++step;
-            run_step(vlane + (step & 1) * VB, wblock(t + 1), C0{}, std::false_type{});
-            ++step;
-        }
-        if constexpr ((NB & 1) == 0) {                        // an odd last step fills set 0 for the next M-tile
-            run_step(vlane + (step & 1) * VB, wblock(NB - 1), C1{}, std::false_type{});
-            ++step;
-        } else {                                              // the last step filled set 1: 72 moves per M-tile
+            for (int t = 1; t + 1 < NB; t += 2) {
+                run_step(vlane + (step & 1) * VB, wblock(t), C1{}, std::false_type{}, W18{});
+                ++step;
+                run_step(vlane + (step & 1) * VB, wblock(t + 1), C0{}, std::false_type{}, W18{});
+                ++step;
+            }
+            if constexpr ((NB & 1) == 0) {                    // an odd last step fills set 0 for the next M-tile
+                run_step(vlane + (step & 1) * VB, wblock(NB - 1), C1{}, std::false_type{}, W18{});
+                ++step;
+            } else {                                          // (RAW only) the last step filled set 1: 72 moves per M-tile
 #pragma unroll
-            for (int j = 0; j < 18; ++j) bw[0][j] = bw[1][j];
+                for (int j = 0; j < 18; ++j) bw[j] = bw[18 + j];
+            }
+        }
+        if constexpr (!RAW) {                                 // [hazard] MFMA results -> the vector ALU
+            wino4_settle(acc);
+            wino4_settle(acc + 18);
         }
 
         // ---- output transform Y = A^T M A for the lane's four tiles at once (float4 = tiles r = 0..3), BN + ELU
@@ -696,9 +804,10 @@ __global__ __launch_bounds__(64 * (PW + (SLICE + 15) / 16), 1) void conv3x3_wino
                     }
             }
         };
-        if (epi_mode == 1) { fast_epilogue(std::false_type{}); continue; }
+        // (a build without the stores, -DASR_WINO4_ABL=32, has none to count)
+        if (epi_mode == 1) { fast_epilogue(std::false_type{}); after_fast = !(ASR_WINO4_ABL & 32); continue; }
         if constexpr (!RAW && wino4_general_form(POOL)) {
-            if (epi_mode == 2) { fast_epilogue(std::true_type{}); continue; }
+            if (epi_mode == 2) { fast_epilogue(std::true_type{}); after_fast = !(ASR_WINO4_ABL & 32); continue; }
         }
         if (POOL) {
 #pragma unroll

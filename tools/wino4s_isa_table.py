@@ -20,7 +20,16 @@ layout order, with their instructions by class:
     salu    scalar instructions without branches, waits and barriers
 and how the block ends (branch targets), so that an item's path - border or interior - can be followed by hand: the
 transform is the block with the 144 packed instructions, an item's loads the block with the 36 global loads.  Then
-VGPRs / AGPRs / scratch bytes / LDS of EVERY conv3x3_wino4s instantiation, one per line.  Counts are static.
+VGPRs / AGPRs / scratch bytes / LDS of EVERY conv3x3_wino4s instantiation, one per line, and for each of them the CONSUMER's
+register classes:
+    steps     steps (72 MFMAs each) in the basic blocks that hold at least one whole step
+    accvgpr   v_accvgpr_* in those blocks (0 with the accumulators in VGPRs and the B operands loaded into AGPRs)
+    loads>a   global / buffer loads with an AGPR destination per step (18 streamed, 0 with resident weights),
+    loads>v   and those with a VGPR destination (the RAW builds' 18)
+    epilogue  v_accvgpr_* / vector ALU instructions in the blocks that store outputs (the epilogues; what a consumer pays
+              per M-tile is one of them: guarded, rows-full or general)
+    all       v_accvgpr_* of the whole kernel
+Counts are static.
 """
 import collections
 import os
@@ -79,6 +88,21 @@ def registers(text):
     return out
 
 
+def consumer_classes(body):
+    """(step blocks, v_accvgpr in them, loads into AGPRs / VGPRs per step block, v_accvgpr / VALU in the storing
+    blocks, v_accvgpr in all) of one kernel"""
+    blocks = [ins for _, ins in blocks_of(body)]
+    acc = lambda ins: sum(s.startswith("v_accvgpr") for s in ins)
+    steps = [ins for ins in blocks if sum(s.startswith("v_mfma") for s in ins) >= 72]
+    loads = [s for ins in steps for s in ins if s.startswith(("global_load", "buffer_load"))]
+    to_a = sum(s.split()[1].startswith("a") for s in loads)
+    stores = [ins for ins in blocks if any(s.startswith(("buffer_store_dword", "global_store_dword")) for s in ins)]
+    n = max(sum(s.startswith("v_mfma") for ins in steps for s in ins) // 72, 1)      # (a block may hold several steps)
+    return (n,sum(acc(ins) for ins in steps), to_a // n, (len(loads) - to_a) // n, sum(acc(ins) for ins in stores),
+            sum(classify(s.split()[0]) in ("mov", "and", "bits", "pk", "valu") for ins in stores for s in ins),
+            sum(acc(ins) for ins in blocks))
+
+
 def main():
     funcs, meta, names = kernels(sys.argv[1])
     regs = registers(open(sys.argv[1]).read())
@@ -103,6 +127,11 @@ def main():
     for mangled in sorted(funcs, key=lambda k: names[k]):
         if "conv3x3_wino4s<" in names[mangled] and mangled in regs:
             print("    %-48s %3d / %3d / %d / %d" % ((names[mangled].split("(")[0].replace("void asr::conv3x3_", ""),) + regs[mangled]))
+    print("consumer register classes: steps / accvgpr in them / loads>a / loads>v per step / epilogue accvgpr / epilogue valu / accvgpr in all")
+    for mangled in sorted(funcs, key=lambda k: names[k]):
+        if "conv3x3_wino4s<" in names[mangled] and mangled in regs:
+            print("    %-48s %d / %d / %d / %d / %d / %d / %d" % ((names[mangled].split("(")[0].replace("void asr::conv3x3_", ""),) +
+                                                                 consumer_classes(funcs[mangled])))
 
 
 if __name__ == "__main__":
